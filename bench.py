@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of forward + NMS for RFBNet-300 (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --train [--gpus N]          data-parallel TRAINING step (BASELINE configs[3]), see below
+
+A plain run sets up, warms up (W steps), times K steps, writes the outputs of the last timed step if --dump-outputs is
+given, and prints one JSON line; `ms_per_step` is the wall time of the K timed steps / K.  Everything else the
+benchmark measures (roofline, stage rooflines, other configurations, CPU baseline: "Extra objects" below) runs only
+with --full.
 
 `--gpus N` with N > 1 and no torchrun environment (no WORLD_SIZE): bench.py launches its own N ranks through
 torch.distributed.run on 127.0.0.1, one per GPU, over RCCL (backend 'nccl'); it never prints a 1-GPU number for an
@@ -21,7 +26,14 @@ ranks with no data-path collective (inference).  `--scaling weak` (default): eve
 --batch images; `--scaling strong`: ONE batch of --batch images is split over the ranks, the
 reference's DataParallel scatter (train.py:296-297).  value = all images / max-over-ranks time.
 
-Extra objects on the JSON line (N=1, rank 0):
+--dump-outputs DIR: after the timed steps, what a caller of the timed path receives from its last step, as DIR/<name>.npy
+(float32; float64 for the training loss), at most 64 MB in all; inputs and weights are seeded, so two builds run with the
+same arguments can be compared file by file.  Inference: detections [B, classes, cap, 5] (x1 y1 x2 y2 score; rows past
+a class's count zeroed), detection_counts [B, classes], and fixed samples of the per-prior decoded boxes and fused scores.
+--train: loss [1] and a fixed sample of the parameters after the last SGD update.  A tensor above its element budget is
+replaced by the elements at sorted indices drawn without replacement by numpy's default_rng(0) (same sample every run).
+
+Extra objects on the JSON line (--full, N=1, rank 0; null otherwise):
   roofline      dominant kernel = the conv kernel with the most accumulated time of its own, from HIP events recorded on
                 the launch stream around every conv launch.  The timed region replays a hipGraph, inside which no
                 per-launch events exist, so the same K steps run once more as eager launches right after it
@@ -423,6 +435,42 @@ def log(msg):
 
 _T0 = time.perf_counter()
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000          # --dump-outputs: every file together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each (name, tensor, max_elements) -> out_dir/<name>.npy, float32 (float64 stays float64).  A tensor
+    with more elements than its max is replaced by a fixed sample: the flattened elements at sorted indices drawn without
+    replacement by np.random.default_rng(DUMP_SAMPLE_SEED) -- the same indices for the same shape on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    total, shapes = 0, {}
+    for name, t, max_elems in arrays:
+        t = t.detach()
+        if t.numel() > max_elems:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(t.numel(), max_elems, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        arr = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        total += arr.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit('bench.py --dump-outputs: %s would take the files past %d bytes' % (name, DUMP_LIMIT_BYTES))
+        np.save(os.path.join(out_dir, name + '.npy'), arr)
+        shapes[name] = list(arr.shape)
+    log('outputs written to %s: %s (%.1f MB)' % (out_dir, shapes, total / 1e6))
+
+
+def inference_outputs(pipe):
+    """What DetectionPipeline.run hands its caller (out_dets, out_count), plus samples of the per-prior boxes / scores it
+    also leaves on the device, for --dump-outputs."""
+    post = pipe.post
+    if int(post.overflow.item()):
+        raise SystemExit('bench.py --dump-outputs: postprocess output capacity %d exceeded' % post.cap)
+    dets = post.out_dets.clone()
+    rows = torch.arange(dets.shape[2], device=dets.device)
+    dets[rows.view(1, 1, -1) >= post.out_count.unsqueeze(-1)] = 0.0      # only rows [0, count) are part of the result
+    return [('detections', dets, 1 << 23), ('detection_counts', post.out_count, 1 << 23),
+            ('boxes', pipe.boxes, 1 << 20), ('scores', pipe.scores, 1 << 20)]
+
 
 def make_pipeline(size, num_fg, phase, setting, batch, dtype, dev):
     from ctdet.pipeline import DetectionPipeline
@@ -475,10 +523,11 @@ def quick_config(size, num_fg, phase, setting, batch, dtype, dev, steps=5, warmu
     return res
 
 
-def train_config(size, num_fg, phase, setting, batch, dev, steps=4, warmup=2, rank=0, world=1):
+def train_config(size, num_fg, phase, setting, batch, dev, steps=4, warmup=2, rank=0, world=1, after_timed=None):
     """One data-parallel training step (train.py:222-229 on this rank's image shard): forward with batch-statistics
     BatchNorm, MultiBoxLoss_combined, HIP backward with the bucketed gradient all-reduce issued from inside it, SGD.
-    Returns local timings; for world > 1 also the step without the all-reduce and the all-reduce alone."""
+    Returns local timings; for world > 1 also the step without the all-reduce and the all-reduce alone.
+    after_timed(net, loss): called right after the timed steps, before any further step changes the parameters."""
     import torch.distributed as tdist
     from ctdet import synth, dist as cdist
     from models.RFB_Net_vgg import build_net as bn
@@ -523,6 +572,8 @@ def train_config(size, num_fg, phase, setting, batch, dev, steps=4, warmup=2, ra
         return (time.perf_counter() - t0) / n, tf / n, tl / n, tb / n, float(loss)
     timed(warmup, False)
     dt, _, _, _, loss = timed(steps, False)              # the timed K steps: no host synchronisation inside
+    if after_timed is not None:
+        after_timed(net, loss)
     _, tf, tl, tb, _ = timed(max(2, steps // 2), True)   # stage split from HIP events, one sync per step
     res = {'ms_per_step': dt * 1e3, 'fwd_ms': tf, 'loss_ms': tl, 'bwd_ms': tb, 'loss': loss, 'batch': batch,
            'grad_bytes': int(trt.arena.numel()) * 4}
@@ -620,10 +671,17 @@ def main():
     ap.add_argument('--share-devices', action='store_true',
                     help='allow more ranks than GPUs (rehearsal of the N-rank path on a smaller box; gloo, since RCCL '
                          'refuses two ranks on one device); the line is marked devices_shared')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need (N=1 inference): conv roofline and stage rooflines '
+                         '(extra eager passes), the other configurations, the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step to DIR/<name>.npy (see the module docstring)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: leave out the roofline passes')
+    ap.add_argument('--no-other-configs', action='store_true', help='with --full: leave out the other configurations')
     a = ap.parse_args()
+    if (a.steps is not None and a.steps < 1) or (a.warmup is not None and a.warmup < 0):
+        raise SystemExit('bench.py: --steps must be >= 1 and --warmup >= 0')
     dflt = (512, 8, 60, 2, 5, 2) if a.train else (300, 32, 20, 1, 20, 5)
     explicit_workload = any(v is not None for v in (a.size, a.batch, a.classes, a.phase))
     for name, v in zip(('size', 'batch', 'classes', 'phase', 'steps', 'warmup'), dflt):
@@ -692,7 +750,12 @@ def main():
 
     if a.train:
         log('training step: building net + training runtime')
-        r = train_config(a.size, num_fg, a.phase, a.setting, batch, dev, a.steps, a.warmup, rank, world)
+
+        def dump_train(net, loss):
+            params = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+            dump_outputs(a.dump_outputs, [('loss', torch.tensor([loss], dtype=torch.float64), 1), ('parameters', params, 1 << 20)])
+        r = train_config(a.size, num_fg, a.phase, a.setting, batch, dev, a.steps, a.warmup, rank, world,
+                         after_timed=dump_train if a.dump_outputs and rank == 0 else None)
         dt = cdist.max_over_ranks(r['ms_per_step'] * 1e-3, dev)
         ms_rank = per_rank(round(r['ms_per_step'], 3))
         if rank == 0:
@@ -745,7 +808,7 @@ def main():
         pipe.run(x)
     torch.cuda.synchronize(dev)
     log('timed region')
-    want_roof = not a.no_roofline and rank == 0 and world == 1      # N > 1 runs only report throughput
+    want_roof = a.full and not a.no_roofline and rank == 0 and world == 1      # N > 1 runs only report throughput
     graph_mode = bool(pipe.use_graph)
     if want_roof and not graph_mode:
         pipe.rt.event_log = []          # HIP events around every conv launch of the timed region
@@ -761,6 +824,8 @@ def main():
     ms_rank = per_rank(round(dt_local / a.steps * 1e3, 3))
 
     log('timed region done: %.2f ms/step' % (dt / a.steps * 1e3))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, inference_outputs(pipe))
     graph_mode = pipe._graph is not None            # False if the capture failed and the steps were launched eagerly
     workload = {'size': a.size, 'batch': batch, 'phase': a.phase, 'classes': a.classes}
     roof = None
@@ -848,7 +913,7 @@ def main():
                          '(tools/tune_convs.py) with a parity test at that shape, or set CTDET_BENCH_ALLOW_LIVE_TUNE=1'
                          % (len(live_tuned), ', '.join(live_tuned[:3])))
     other = None
-    if rank == 0 and world == 1 and not a.no_other_configs and a.dtype == 'f32' and not explicit_workload:
+    if a.full and rank == 0 and world == 1 and not a.no_other_configs and a.dtype == 'f32' and not explicit_workload:
         del pipe
         torch.cuda.empty_cache()
         other = {}
@@ -886,7 +951,7 @@ def main():
                           'step': 'forward (batch-stat BN) + MultiBoxLoss_combined + HIP backward + SGD, one GPU '
                                   '(no all-reduce); `bench.py --train --gpus N` times the data-parallel form'}
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         log('cpu baseline (oracle on host cores)')
         cpu = cpu_baseline(a.size, num_fg)
         log('cpu baseline done')

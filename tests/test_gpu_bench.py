@@ -20,7 +20,7 @@ def _run(*args):
 
 
 def test_bench_line_contract():
-    d = _run('--steps', '3', '--warmup', '4', '--batch', '4', '--no-cpu-baseline', '--no-other-configs')
+    d = _run('--full', '--steps', '3', '--warmup', '4', '--batch', '4', '--no-cpu-baseline', '--no-other-configs')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in d, k
@@ -62,9 +62,35 @@ def test_bench_line_contract():
 
 
 def test_bench_phase2_reports_the_attention_stage():
-    d = _run('--steps', '2', '--warmup', '4', '--batch', '2', '--phase', '2', '--classes', '60', '--no-cpu-baseline',
+    d = _run('--full', '--steps', '2', '--warmup', '4', '--batch', '2', '--phase', '2', '--classes', '60', '--no-cpu-baseline',
              '--no-other-configs')
     st = d['roofline']['stages']
     assert st['ctx_attn_kernel']['bound'] == 'mfma' and 0 < st['ctx_attn_kernel']['frac'] < 1
     assert st['ctx_attn_kernel.hbm']['bound'] == 'hbm'
     assert st['ctx_attn_kernel']['piece_products'] == 6          # bf16x3 unless CTDET_ATTN_H2=1 (opt-in: DESIGN.md section 8 item 9)
+
+
+def test_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """Without --full the line carries the headline fields only (no roofline, other configurations or CPU baseline);
+    --dump-outputs writes what the timed path returned at its last step, and a second run with the same arguments
+    writes the same arrays."""
+    import numpy as np
+    d = _run('--steps', '3', '--warmup', '3', '--batch', '4', '--dump-outputs', str(tmp_path / 'a'))
+    _run('--steps', '3', '--warmup', '3', '--batch', '4', '--dump-outputs', str(tmp_path / 'b'))
+    assert d['steps'] == 3 and d['warmup'] == 3 and d['ms_per_step'] > 0 and d['launch_mode'] == 'hipGraph replay'
+    assert abs(d['value'] - 4 / (d['ms_per_step'] * 1e-3)) < 0.02 * d['value']
+    assert d['roofline'] is None and d['cpu_baseline'] is None and d['other_configs'] is None
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['boxes.npy', 'detection_counts.npy', 'detections.npy', 'scores.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64e6
+    out = {f[:-4]: np.load(tmp_path / 'a' / f) for f in files}
+    assert all(v.dtype == np.float32 for v in out.values())
+    dets, cnt = out['detections'], out['detection_counts']
+    assert dets.shape[:2] == cnt.shape == (4, 20) and dets.shape[3] == 5
+    assert int(cnt.sum()) == d['config']['detections_per_batch'] > 0
+    for b in range(4):
+        for c in range(20):
+            k = int(cnt[b, c])
+            assert not dets[b, c, k:].any() and (np.diff(dets[b, c, :k, 4]) <= 0).all()      # rows in descending score order
+    for f in files:
+        assert np.array_equal(out[f[:-4]], np.load(tmp_path / 'b' / f)), f

@@ -6,7 +6,7 @@ i=0
 for rep in 1 2; do
   for v in "$@"; do
     tag=$(echo "$v" | tr ' =/' '___')
-    env $v python bench.py --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > "$out/ab_${tag}_$rep.json" 2> "$out/ab_${tag}_$rep.err"
+    env $v python bench.py --full --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > "$out/ab_${tag}_$rep.json" 2> "$out/ab_${tag}_$rep.err"
     python - "$out/ab_${tag}_$rep.json" "$v" <<'PY'
 import sys, json
 try:

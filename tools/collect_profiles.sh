@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 run_set() {   # name, workload (size,batch,phase,classes), extra bench args...
   local name=$1 wl=$2; shift 2
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${name}_stats" -o bench -- \
-      python "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs "$@" > "$O/${name}_bench.json.log" 2> "$O/${name}_bench.err"
+      python "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs "$@" > "$O/${name}_bench.json.log" 2> "$O/${name}_bench.err"
   for C in FETCH_SIZE WRITE_SIZE; do
     CTDET_GRAPH=0 timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$O/${name}_pmc_$C" -o p -- \
         python "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-roofline "$@" > /dev/null 2>&1
@@ -22,7 +22,7 @@ run_set() {   # name, workload (size,batch,phase,classes), extra bench args...
   python "$R/tools/prof_summary.py" --stats "$(ls $O/${name}_stats/*kernel_stats.csv | head -1)" \
       --fetch "$(ls $O/${name}_pmc_FETCH_SIZE/*counter_collection.csv | head -1)" \
       --write "$(ls $O/${name}_pmc_WRITE_SIZE/*counter_collection.csv | head -1)" \
-      --tag "${TAG}_${name}" --workload "$wl" --cmd "python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs $*" \
+      --tag "${TAG}_${name}" --workload "$wl" --cmd "python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs $*" \
       --out "$O/condensed" > /dev/null
 }
 run_set rfb300 300,32,1,20
@@ -30,7 +30,7 @@ run_set rfb300ctx 300,32,2,60 --phase 2 --classes 60
 run_set rfb512 512,32,1,20 --size 512
 [ -n "${QUICK:-}" ] || { run_set bf16_512b16 512,16,1,20 --size 512 --batch 16 --dtype bf16; }
 cd "$R"
-python bench.py --steps 20 --warmup 5 > "$O/bench_full.json.log" 2> "$O/bench_full.err"
+python bench.py --full --steps 20 --warmup 5 > "$O/bench_full.json.log" 2> "$O/bench_full.err"
 CTDET_STREAMS=1 timeout 600 python tools/layer_report.py > "$O/layer_report.txt" 2>&1
 CTDET_STREAMS=1 timeout 600 python tools/layer_report.py --size 512 > "$O/layer_report_512.txt" 2>&1
 cd /tmp

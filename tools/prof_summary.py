@@ -13,7 +13,7 @@ ap.add_argument('--stats', required=True)
 ap.add_argument('--fetch')
 ap.add_argument('--write')
 ap.add_argument('--tag', default='r01')
-ap.add_argument('--cmd', default='python bench.py --steps 20 --warmup 5 --no-cpu-baseline')
+ap.add_argument('--cmd', default='python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline')
 ap.add_argument('--workload', default='300,32,1,20', help='size,batch,phase,classes of the profiled bench run')
 ap.add_argument('--out', default=None, help='output directory (default: profiles/)')
 a = ap.parse_args()
