@@ -30,6 +30,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
+from .wino_forms import FORMS, geometry_ok
 
 # CTDET_TUNE_TABLE: another table file (A/B measurements of a re-tuned table against the committed one)
 TUNE_TABLE = os.environ.get('CTDET_TUNE_TABLE') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'conv_tune_gfx950.json')
@@ -344,31 +345,16 @@ class Plan:
 
 
 # ======================================================================================
-WINO = -1          # ConvStep.rt['config'] value selecting the Winograd F(2x2,3x3) kernel
-WINO4 = -2         # ... the Winograd F(4x4,3x3) kernel
-WINOX = -3         # ... F(2x2,3x3) on the bf16 matrix pipe (bf16x3), two accumulators (csrc/ct_wino_x3.hip)
-WINO4S = -6        # ... F(4x4,3x3) as transform / bf16x3 GEMM / transform kernels, two accumulators (csrc/ct_wino4s.hip)
-WINO4F = -8        # ... F(4x4,3x3) fused on bf16x3, one 64-cout block per workgroup (csrc/ct_wino4f.hip): the narrow layers on big maps
-WINO4H = -9        # ... the three-kernel form on the f16x2 operand form (two binary16 pieces, three products; csrc/ct_f16x2.h)
-WINO4FH = -10      # ... the fused kernel on the f16x2 operand form
-# st.rt['wino'] values: 2, 4 = the fp32-MFMA kernels' tile sizes; 23 = F(2x2,3x3) on bf16x3 (two accumulators, eight waves)
-# 44 = F(4x4,3x3) in the three-kernel form with the GEMMs on bf16x3 (two accumulators); 46 = F(4x4,3x3) fused on bf16x3
-# (codes 24 and 45, the one-accumulator variants of 23 and 44, existed in rounds 4-5: never selected, removed in round 6)
-# 47 = the three-kernel form with its GEMMs on f16x2 (two binary16 pieces, three products, two accumulators)
-# 48 = the fused F(4x4,3x3) kernel on f16x2
-WINO_TILE = {WINO: 2, WINO4: 4, WINOX: 23, WINO4S: 44, WINO4F: 46, WINO4H: 47, WINO4FH: 48}
-WINO_NAME = {2: 'wino', 4: 'wino4', 23: 'winox', 44: 'wino4s', 46: 'wino4f', 47: 'wino4h', 48: 'wino4fh'}
-WINOX_TILES = (23,)
-WINOX_VARIANT = {23: 1}               # the `variant` argument of ct_conv2d_wino_x3_fwd
-WINO4S_TILES = (44, 47)
-WINO4S_VARIANT = {44: 1, 47: 3}       # the `variant` argument of ct_conv2d_wino4s_fwd
-WINO4H_TILES = (47,)                         # ... whose weights come from ct_conv_pack_weights_wino4s_h2
-WINO4F_TILES = (46, 48)
-WINO4F_VARIANT = {46: 1, 48: 2}              # the `variant` argument of ct_conv2d_wino4f_pool_fwd_v
-WINO4FH_TILES = (48,)                        # ... whose weights come from ct_conv_pack_weights_wino4f_h2 and which needs desc.in_absmax
-H2_TILES = (47, 48)                          # the f16x2 operand form: consumers of a maximum of |input| (ct_conv_desc.in_absmax)
-TRACK_TILES = (44, 47, 48)               # kernels that fold max |output| into ct_conv_desc.out_absmax (+ the 'valu' image layer)
-F4_TILES = (4, 44, 46, 47, 48)           # every variant with F(4x4,3x3)'s rounding (accuracy policies treat them alike)
+# ConvStep.rt['config'] values selecting a Winograd kernel, and the st.rt['wino'] codes they select (wino_forms.FORMS)
+WINO, WINO4, WINOX, WINO4S, WINO4F, WINO4H, WINO4FH = (FORMS[c].config for c in (2, 4, 23, 44, 46, 47, 48))
+WINO_TILE = {f.config: c for c, f in FORMS.items()}
+WINO_NAME = {c: f.name for c, f in FORMS.items()}
+WINO4S_TILES = tuple(c for c, f in FORMS.items() if f.split)
+WINO4F_TILES = tuple(c for c, f in FORMS.items() if f.ok == 'wino4f_ok')
+H2_TILES = tuple(c for c, f in FORMS.items() if f.h2)
+F4_TILES = tuple(c for c, f in FORMS.items() if f.f4)
+# bf16x3 tile -> the same kernel on the f16x2 operand form (csrc/ct_f16x2.h: two binary16 pieces, three products)
+H2_OF_TILE = {f.plain: c for c, f in FORMS.items() if f.h2}
 
 
 class HipBackend:
@@ -426,7 +412,8 @@ class HipBackend:
         """(Re)size the pool to what the given conv steps need, per key; called once the schedule is known."""
         need = {}
         for st in steps:
-            if st.rt.get('wino') in WINO4S_TILES:
+            f = FORMS.get(st.rt.get('wino'))
+            if f is not None and f.split:
                 k = st.rt.get('ws_key', 0)
                 need[k] = max(need.get(k, 0), st.rt.get('ws4s_bytes', 0))
         for k in list(self.ws_pool):
@@ -530,41 +517,21 @@ class HipBackend:
         tile = int(tile or 2)
         # the three-kernel form also takes dilated 3x3 layers (pad = dilation: tiles on the sub-lattices), which the fused
         # kernels do not
-        if not (rt.get('wino_ok') or (tile in WINO4S_TILES and rt.get('wino4s_ok'))):
+        if not geometry_ok(rt, tile):
             raise _lib.CtdetError('%s: geometry has no Winograd path' % st.name)
         rt['x3'] = None
-        if tile not in (2, 4) + WINOX_TILES + WINO4S_TILES + WINO4F_TILES:
+        f = FORMS.get(tile)
+        if f is None:
             raise _lib.CtdetError('%s: Winograd tile %r (2, 4, 23, 44, 46, 47 or 48)' % (st.name, tile))
-        if tile not in WINO4S_TILES:
+        if not f.split:
             rt.pop('ws4s_bytes', None)
-        if tile in WINO4S_TILES:
-            if not rt.get('wino4s_ok'):
-                raise _lib.CtdetError('%s: geometry has no three-kernel Winograd path (cin %% 16)' % st.name)
-            if tile in WINO4H_TILES:
-                if 'U4H' not in rt:
-                    rt['U4H'] = self.alloc((self.lib.ct_conv_wino4s_h2_packed_bytes(st.cin, st.cout),), torch.uint8)
-            elif 'U4S' not in rt:
-                rt['U4S'] = self.alloc((self.lib.ct_conv_wino4s_packed_bytes(st.cin, st.cout),), torch.uint8)
+        if not rt.get(f.ok):
+            raise _lib.CtdetError('%s: geometry has no %s' % (st.name, f.path))
+        if f.key not in rt:
+            rt[f.key] = f.alloc(self.lib, self.alloc, st.cin, st.cout)
+        if f.split:
             rt['ws4s_bytes'] = self.lib.ct_conv_wino4s_workspace_bytes(C.byref(rt['desc']))
             self.ws_reserve(rt.get('ws_key', 0), rt['ws4s_bytes'])
-        elif tile in WINO4F_TILES:
-            if not rt.get('wino4f_ok'):
-                raise _lib.CtdetError('%s: geometry has no fused F(4x4,3x3) bf16x3 path (cin %% 16)' % st.name)
-            if tile in WINO4FH_TILES:
-                if 'U4FH' not in rt:
-                    rt['U4FH'] = self.alloc((self.lib.ct_conv_wino4f_h2_packed_bytes(st.cin, st.cout),), torch.uint8)
-            elif 'U4F' not in rt:
-                rt['U4F'] = self.alloc((self.lib.ct_conv_wino4f_packed_bytes(st.cin, st.cout),), torch.uint8)
-        elif tile in WINOX_TILES:
-            if not rt.get('winox_ok'):
-                raise _lib.CtdetError('%s: geometry has no Winograd bf16x3 path (cin %% 16)' % st.name)
-            if 'UX' not in rt:
-                rt['UX'] = self.alloc((self.lib.ct_conv_wino_x3_packed_bytes(st.cin, st.cout),), torch.uint8)
-        else:
-            key = 'U' if tile == 2 else 'U4'
-            if key not in rt:
-                sizeof = self.lib.ct_conv_wino_packed_floats if tile == 2 else self.lib.ct_conv_wino4_packed_floats
-                rt[key] = self.alloc((sizeof(st.cin, st.cout),))
         rt['wino'] = tile
         self._pack_wino(st)
 
@@ -572,32 +539,8 @@ class HipBackend:
         n = len(st.parts)
         ptrs = (C.c_void_p * n)(*[p.weight.detach().data_ptr() for p in st.parts])
         couts = (C.c_int * n)(*[p.cout for p in st.parts])
-        if st.rt['wino'] == 4:
-            _lib.check(self.lib.ct_conv_pack_weights_wino4(ptrs, couts, n, st.cin, st.rt['U4'].data_ptr(), self._stream()),
-                       'ct_conv_pack_weights_wino4')
-            return
-        if st.rt['wino'] in WINOX_TILES:
-            _lib.check(self.lib.ct_conv_pack_weights_wino_x3(ptrs, couts, n, st.cin, st.rt['UX'].data_ptr(), self._stream()),
-                       'ct_conv_pack_weights_wino_x3')
-            return
-        if st.rt['wino'] in WINO4H_TILES:
-            _lib.check(self.lib.ct_conv_pack_weights_wino4s_h2(ptrs, couts, n, st.cin, st.rt['U4H'].data_ptr(), self._stream()),
-                       'ct_conv_pack_weights_wino4s_h2')
-            return
-        if st.rt['wino'] in WINO4S_TILES:
-            _lib.check(self.lib.ct_conv_pack_weights_wino4s(ptrs, couts, n, st.cin, st.rt['U4S'].data_ptr(), self._stream()),
-                       'ct_conv_pack_weights_wino4s')
-            return
-        if st.rt['wino'] in WINO4FH_TILES:
-            _lib.check(self.lib.ct_conv_pack_weights_wino4f_h2(ptrs, couts, n, st.cin, st.rt['U4FH'].data_ptr(), self._stream()),
-                       'ct_conv_pack_weights_wino4f_h2')
-            return
-        if st.rt['wino'] in WINO4F_TILES:
-            _lib.check(self.lib.ct_conv_pack_weights_wino4f(ptrs, couts, n, st.cin, st.rt['U4F'].data_ptr(), self._stream()),
-                       'ct_conv_pack_weights_wino4f')
-            return
-        _lib.check(self.lib.ct_conv_pack_weights_wino(ptrs, couts, n, st.cin, st.rt['U'].data_ptr(), self._stream()),
-                   'ct_conv_pack_weights_wino')
+        f = FORMS[st.rt['wino']]
+        _lib.check(f.pack_weights(self.lib, ptrs, couts, n, st.cin, st.rt[f.key].data_ptr(), self._stream()), f.pack)
 
     def pack_conv(self, st, weights=True):
         """(Re)pack weights and fold the epilogue from the CURRENT parameter values.  weights=False: only the epilogue
@@ -669,56 +612,19 @@ class HipBackend:
         _lib.check(self.lib.ct_absmax_f32(base, d.batch, d.cin * hw, d.in_ctot * hw, rt['amax_own'].data_ptr(), self._stream()),
                    'ct_absmax_f32')
 
+    def reads_max(self, st):
+        """Whether the launch of this conv reads maxima of |input| (ct_conv_desc.in_absmax): the f16x2 operand form."""
+        f = FORMS.get(st.rt.get('wino'))
+        return f.h2 if f is not None else st.rt.get('x3') is not None and self.x3_h2(st.rt['x3'])
+
     def run_conv(self, st):
-        tile = st.rt.get('wino')
-        needs_max = tile in WINO4FH_TILES or (not tile and st.rt.get('x3') is not None and self.x3_h2(st.rt['x3']))
+        f = FORMS.get(st.rt.get('wino'))
+        needs_max = (f.h2 and not f.own_max) if f is not None else st.rt.get('x3') is not None and self.x3_h2(st.rt['x3'])
         if needs_max and (not st.rt['desc'].in_absmax or (st.rt.get('amax_own') is not None and not st.rt.get('amax_frozen'))):
             self._own_absmax(st)
-        if tile in WINO4S_TILES:         # F(4x4,3x3): transform / bf16x3 GEMM / transform (csrc/ct_wino4s.hip)
-            lib, U, ws, var = self.lib, st.rt['U4H' if tile in WINO4H_TILES else 'U4S'].data_ptr(), \
-                self.ws_pool[st.rt.get('ws_key', 0)], WINO4S_VARIANT[tile]
-            pool = st.rt.get('pool')
-            if pool is not None:
-                t, poh, pow_, full = pool
-                _lib.check(lib.ct_conv2d_wino4s_pool_fwd(C.byref(st.rt['desc']), U, ws.data_ptr(), ws.numel(), var,
-                                                         t.data_ptr(), t.shape[1], 0, poh, pow_, int(full), self._stream()),
-                           st.name)
-                return
-            _lib.check(lib.ct_conv2d_wino4s_fwd(C.byref(st.rt['desc']), U, ws.data_ptr(), ws.numel(), var, self._stream()),
-                       st.name)
-            return
-        if tile in WINO4F_TILES:         # F(4x4,3x3) fused on the bf16 matrix pipe (csrc/ct_wino4f.hip)
-            lib, U, var = self.lib, st.rt['U4FH' if tile in WINO4FH_TILES else 'U4F'].data_ptr(), WINO4F_VARIANT[tile]
-            pool = st.rt.get('pool')
-            if pool is not None:
-                t, poh, pow_, full = pool
-                _lib.check(lib.ct_conv2d_wino4f_pool_fwd_v(C.byref(st.rt['desc']), U, var, t.data_ptr(), t.shape[1], 0, poh, pow_,
-                                                           int(full), self._stream()), st.name)
-                return
-            _lib.check(lib.ct_conv2d_wino4f_pool_fwd_v(C.byref(st.rt['desc']), U, var, None, 0, 0, 0, 0, 1, self._stream()), st.name)
-            return
-        if tile in WINOX_TILES:          # F(2x2,3x3) on the bf16 matrix pipe (csrc/ct_wino_x3.hip)
-            lib, U, dual = self.lib, st.rt['UX'].data_ptr(), WINOX_VARIANT[tile]
-            pool = st.rt.get('pool')
-            if pool is not None:
-                t, poh, pow_, full = pool
-                _lib.check(lib.ct_conv2d_wino_x3_pool_fwd(C.byref(st.rt['desc']), U, dual, t.data_ptr(), t.shape[1], 0, poh,
-                                                          pow_, int(full), self._stream()), st.name)
-                return
-            _lib.check(lib.ct_conv2d_wino_x3_fwd(C.byref(st.rt['desc']), U, dual, self._stream()), st.name)
-            return
-        if tile:
-            lib = self.lib
-            U = st.rt['U4' if tile == 4 else 'U'].data_ptr()
-            pool = st.rt.get('pool')
-            if pool is not None:        # fused MaxPool2d(2, 2): (pooled buffer, oh, ow, write_full)
-                t, poh, pow_, full = pool
-                fn = lib.ct_conv2d_wino4_pool_fwd if tile == 4 else lib.ct_conv2d_wino_pool_fwd
-                _lib.check(fn(C.byref(st.rt['desc']), U, t.data_ptr(), t.shape[1], 0, poh, pow_, int(full),
-                              self._stream()), st.name)
-                return
-            fn = lib.ct_conv2d_wino4_fwd if tile == 4 else lib.ct_conv2d_wino_fwd
-            _lib.check(fn(C.byref(st.rt['desc']), U, self._stream()), st.name)
+        if f is not None:
+            _lib.check(f.run(self.lib, C.byref(st.rt['desc']), st.rt[f.key].data_ptr(),
+                             self.ws_pool[st.rt.get('ws_key', 0)] if f.split else None, st.rt.get('pool'), self._stream()), st.name)
             return
         x3 = st.rt.get('x3')
         if x3 is not None:               # fp32 convolution on the bf16 matrix pipe (bf16x3 split, csrc/ct_conv_x3.hip)
@@ -785,8 +691,7 @@ class HipBackend:
         launches get longer bursts (>= ~1 ms of device time): three 30 us launches are inside the timer's noise, and a
         flipped choice lands in the committed table.  A kernel on the f16x2 operand form is timed with the maxima of |input| in
         place (taken once here, as its producer would have left them in a network), not with an absmax pass per launch."""
-        tile = st.rt.get('wino')
-        if tile in H2_TILES or (not tile and st.rt.get('x3') is not None and self.x3_h2(st.rt['x3'])):
+        if self.reads_max(st):
             if not st.rt['desc'].in_absmax or st.rt.get('amax_own') is not None:
                 st.rt['amax_frozen'] = False
                 self._own_absmax(st)
@@ -876,7 +781,7 @@ def wino_tiles(backend=None, st=None):
     env = os.environ.get('CTDET_WINO_TILES')
     tiles = tuple(int(t) for t in (env or '2,4,44,46').split(',') if t)
     if env is None and getattr(backend, 'h2', False):
-        tiles = tiles + H2_OF_TILE_VALUES
+        tiles = tiles + tuple(H2_OF_TILE.values())
     allowed = getattr(backend, 'wino_tile_set', None)
     if allowed is not None:             # a runtime's accuracy policy: its set, narrowed by an explicit CTDET_WINO_TILES
         tiles = tuple(t for t in allowed if env is None or t in tiles)
@@ -886,20 +791,9 @@ def wino_tiles(backend=None, st=None):
             f4 = 4                      # the fused bf16x3 kernel needs 16-channel chunks: such layers keep the fp32 fused kernel
         if cap and st is not None and st.cin <= cap and f4 not in tiles and (env is None or str(f4) in env.split(',')):
             tiles = tiles + (f4,)       # short channel sums: F(4x4) costs little accuracy there
-    if st is not None and not st.rt.get('winox_ok'):
-        tiles = tuple(t for t in tiles if t not in WINOX_TILES)
-    if st is not None and not st.rt.get('wino4s_ok'):
-        tiles = tuple(t for t in tiles if t not in WINO4S_TILES)
-    if st is not None and not st.rt.get('wino4f_ok'):
-        tiles = tuple(t for t in tiles if t not in WINO4F_TILES)
-    if st is not None and not st.rt.get('wino_ok'):          # dilated 3x3: only the three-kernel form
-        tiles = tuple(t for t in tiles if t in WINO4S_TILES)
+    if st is not None:                  # each form's geometry (dilated 3x3: only the three-kernel form)
+        tiles = tuple(t for t in tiles if geometry_ok(st.rt, t) and (t not in FORMS or st.rt.get(FORMS[t].ok)))
     return tiles
-
-
-# bf16x3 tile -> the same kernel on the f16x2 operand form (csrc/ct_f16x2.h: two binary16 pieces, three products)
-H2_OF_TILE = {44: 47, 46: 48}
-H2_OF_TILE_VALUES = tuple(H2_OF_TILE.values())
 
 
 H2_MIN_PIXELS = 8 * 300 * 300
@@ -1021,7 +915,7 @@ def apply_tuned(backend, st, batch, wino4=True):
         cfg = tune_table().get(st.tune_key(batch) + '|h2', cfg)
     names = [backend.lib.ct_conv_config_name(i).decode() for i in range(backend.lib.ct_conv_num_configs())]
     codes = {v: k for k, v in WINO_NAME.items()}
-    usable = cfg in codes and (st.rt.get('wino_ok') or (codes[cfg] in WINO4S_TILES and st.rt.get('wino4s_ok'))) and \
+    usable = cfg in codes and geometry_ok(st.rt, codes[cfg]) and \
         os.environ.get('CTDET_WINO', '1') != '0'
     if usable and st.dil > 1:
         # dilated layer on the three-kernel form: where tile 44 is allowed as such; a runtime with an accuracy policy
@@ -1290,13 +1184,11 @@ class Runtime:
             return
         steps = self.plan.steps
 
-        def consumes(st):
-            return st.rt.get('wino') in H2_TILES or (not st.rt.get('wino') and st.rt.get('x3') is not None and be.x3_h2(st.rt['x3']))
-
         def tracks(st):
             if st.kind != 'conv' or st.segs:
                 return False
-            return st.rt.get('wino') in TRACK_TILES if st.rt.get('wino') else True
+            f = FORMS.get(st.rt.get('wino'))
+            return f.tracks if f is not None else True
         root = {}                          # pooled buffer -> the buffer whose maximum bounds it
         for ps in steps:
             if ps.kind == 'pool':
@@ -1322,7 +1214,7 @@ class Runtime:
             slots, fallback = {}, []
             be.slots_used = 0
             for st in self.conv_steps():
-                if not consumes(st):
+                if not be.reads_max(st):
                     continue
                 b = root_of(st.src)
                 ws = writers.get(b, [])
@@ -1332,13 +1224,13 @@ class Runtime:
                         for w in ws:
                             w.rt['desc'].out_absmax = slots[b]
                     st.rt['desc'].in_absmax = slots[b]
-                elif st.rt.get('wino') != 47:
+                elif not getattr(FORMS.get(st.rt.get('wino')), 'own_max', False):
                     fallback.append(st)
             if not fallback:
                 break
             for st in fallback:            # (a layer that leaves the f16x2 form may stop tracking: wire again)
-                if st.rt.get('wino') == 48:
-                    be.enable_wino(st, tile=46)
+                if st.rt.get('wino'):
+                    be.enable_wino(st, tile=FORMS[st.rt['wino']].plain)
                 else:
                     xn = be.x3_names()
                     be.enable_x3(st, xn.index('x3:' + xn[st.rt['x3']][3:]))

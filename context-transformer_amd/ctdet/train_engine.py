@@ -24,8 +24,9 @@ import os
 import torch
 
 from . import _lib, ops
-from .engine import (F4_TILES, H2_TILES, TRACK_TILES, WINO4F_TILES, WINO4S_TILES, ConvPart, ConvStep, HipBackend, Plan, Runtime,
-                     apply_tuned, operand_form_h2, run_on_streams)
+from .engine import (F4_TILES, WINO4F_TILES, WINO4S_TILES, ConvPart, ConvStep, HipBackend, Plan, Runtime, apply_tuned,
+                     operand_form_h2, run_on_streams)
+from .wino_forms import FORMS
 
 
 class _StepState:
@@ -150,13 +151,10 @@ class TrainRuntime:
                         s.dgrad_tile = 4 if w4_ok and (s.fwd.rt.get('wino') in F4_TILES or
                                                        (wino4 and st.segs and st.oh * st.ow >= 361)) else 2
                         # ... and its three-kernel bf16x3 form (tile 44) where the forward launch runs that one
-                        # (CTDET_TRAIN_W4S=0 keeps the fused kernel); V / M workspace shared by all data gradients
+                        # (CTDET_TRAIN_W4S=0 keeps the fused kernel)
                         if s.fwd.rt.get('wino') in WINO4S_TILES and os.environ.get('CTDET_TRAIN_W4S', '1') != '0' and \
                                 self.lib.ct_conv_wino4s_supported(C.byref(w2)):
                             s.dgrad_tile = 47 if self.h2 else 44
-                            size = self.lib.ct_conv_wino4s_h2_packed_bytes if self.h2 else self.lib.ct_conv_wino4s_packed_bytes
-                            s.U_d = al(((size(zc, st.cin) + 3) // 4,))
-                            w4s_ws = max(w4s_ws, self.lib.ct_conv_wino4s_workspace_bytes(C.byref(w2)))
                         elif s.fwd.rt.get('wino') in WINO4F_TILES and os.environ.get('CTDET_TRAIN_W4F', '1') != '0' and \
                                 zc <= (getattr(backend, 'w4f_max_cin', None) or 1 << 30) and \
                                 self.lib.ct_conv_wino4f_supported(C.byref(w2)):
@@ -166,11 +164,6 @@ class TrainRuntime:
                             # (f16x2, tile 48: where dZ comes from ct_bias_act_backward_amax, which leaves the maxima the fused
                             # kernel needs -- the VGG trunk; a BatchNorm layer's dZ has none: bf16x3)
                             s.dgrad_tile = 48 if self.h2 and not s.is_bn and not st.segs else 46
-                            size = self.lib.ct_conv_wino4f_h2_packed_bytes if s.dgrad_tile == 48 else self.lib.ct_conv_wino4f_packed_bytes
-                            s.U_d = al(((size(zc, st.cin) + 3) // 4,))
-                        else:
-                            sizeof = self.lib.ct_conv_wino4_packed_floats if s.dgrad_tile == 4 else self.lib.ct_conv_wino_packed_floats
-                            s.U_d = al((sizeof(zc, st.cin),))
                 # dilated 3x3 layers (pad = dilation) whose forward launch runs the three-kernel form: their data gradient is
                 # the same dilated convolution with channels swapped and taps rotated -> the same kernels (tiles on the
                 # dilation sub-lattices); the dilated output transform has no accumulate, so a source gradient that was already
@@ -185,8 +178,10 @@ class TrainRuntime:
                     if self.lib.ct_conv_wino4s_supported(C.byref(w2)):
                         s.dgrad_wino = w2
                         s.dgrad_tile = 47 if self.h2 else 44
-                        size = self.lib.ct_conv_wino4s_h2_packed_bytes if self.h2 else self.lib.ct_conv_wino4s_packed_bytes
-                        s.U_d = al(((size(zc, st.cin) + 3) // 4,))
+                if s.dgrad_wino is not None:
+                    f = FORMS[s.dgrad_tile]
+                    s.U_d = f.alloc(self.lib, al, zc, st.cin, dgrad=True)
+                    if f.split:                 # V / M workspace shared by all data gradients
                         w4s_ws = max(w4s_ws, self.lib.ct_conv_wino4s_workspace_bytes(C.byref(w2)))
             # direct data gradients on the bf16 matrix pipe (bf16x3, ct_conv2d_x3_fwd transposed): every layer without
             # a Winograd data gradient whose channel counts fit the k-step; CTDET_X3=0 keeps ct_conv2d_fwd
@@ -350,8 +345,8 @@ class TrainRuntime:
         def tracks(st):
             if st.kind != 'conv' or st.segs or self.state[st.name].is_bn:
                 return False
-            w = fwd(st).rt.get('wino')
-            return w in TRACK_TILES if w else True
+            f = FORMS.get(fwd(st).rt.get('wino'))
+            return f.tracks if f is not None else True
         root = {ps.dst: ps.src for ps in steps if ps.kind == 'pool'}
 
         def root_of(b):
@@ -372,7 +367,8 @@ class TrainRuntime:
             slots, fallback = {}, []
             be.slots_used = 0
             for st in convs:
-                if fwd(st).rt.get('wino') not in H2_TILES:
+                f = FORMS.get(fwd(st).rt.get('wino'))
+                if f is None or not f.h2:
                     continue
                 b = root_of(st.src)
                 ws = writers.get(b, [])
@@ -382,16 +378,16 @@ class TrainRuntime:
                         for w in ws:
                             fwd(w).rt['desc'].out_absmax = slots[b]
                     fwd(st).rt['desc'].in_absmax = slots[b]
-                elif fwd(st).rt.get('wino') == 48:
+                elif not f.own_max:
                     fallback.append(st)
             if not fallback:
                 break
             for st in fallback:
-                be.enable_wino(fwd(st), tile=46)
+                be.enable_wino(fwd(st), tile=FORMS[fwd(st).rt['wino']].plain)
         for st in convs:
             s = self.state[st.name]
             s.dz_amax = None
-            if getattr(s, 'dgrad_wino', None) is not None and s.dgrad_tile in H2_TILES and not s.is_bn and not st.segs:
+            if getattr(s, 'dgrad_wino', None) is not None and FORMS[s.dgrad_tile].h2 and not s.is_bn and not st.segs:
                 s.dz_amax = be.new_slot(self.batch)
                 s.dgrad_wino.in_absmax = s.dz_amax
         self.amax_slots = slots
@@ -441,15 +437,12 @@ class TrainRuntime:
         n = len(wts)
         ptrs = (C.c_void_p * n)(*[w for w, _ in wts])
         couts = (C.c_int * n)(*[c for _, c in wts])
-        if s.dgrad_wino is not None and s.dgrad_tile in H2_TILES:
-            if getattr(self, '_recording', False):
+        if s.dgrad_wino is not None:
+            f = FORMS[s.dgrad_tile]
+            if f.h2 and getattr(self, '_recording', False):
                 return                  # takes the layer's maximum first: not recordable, batched by the f16x2 list of _repack_all
-            pack = self.lib.ct_conv_pack_weights_wino4s_h2_dgrad if s.dgrad_tile == 47 else self.lib.ct_conv_pack_weights_wino4f_h2_dgrad
-            _lib.check(pack(ptrs, couts, n, st.cin, s.U_d.data_ptr(), self._s()), st.name + ' pack dgrad (winograd, f16x2)')
-        elif s.dgrad_wino is not None:
-            pack = {4: self.lib.ct_conv_pack_weights_wino4_dgrad, 44: self.lib.ct_conv_pack_weights_wino4s_dgrad,
-                    46: self.lib.ct_conv_pack_weights_wino4f_dgrad}.get(s.dgrad_tile, self.lib.ct_conv_pack_weights_wino_dgrad)
-            _lib.check(pack(ptrs, couts, n, st.cin, s.U_d.data_ptr(), self._s()), st.name + ' pack dgrad (winograd)')
+            _lib.check(f.pack_weights(self.lib, ptrs, couts, n, st.cin, s.U_d.data_ptr(), self._s(), dgrad=True),
+                       st.name + ' pack dgrad (%s)' % f.name)
         elif s.dgrad_x3 is not None:
             if getattr(self, '_recording', False):
                 return                  # not a recordable pack kind: re-issued every step by _repack_all
@@ -474,9 +467,10 @@ class TrainRuntime:
             if st.kind == 'conv':
                 rt = self.state[st.name].fwd.rt
                 x3 = rt.get('x3')
+                f = FORMS.get(rt.get('wino'))
                 ptrs.append((st.name, rt.get('wino') or 0, -1 if x3 is None else x3,
-                             tuple(sorted((k, v.data_ptr()) for k, v in rt.items()
-                                          if k in ('U', 'U4', 'UX', 'U4H', 'U4FH', 'wpk') and v is not None)),
+                             tuple((k, rt[k].data_ptr()) for k in ((f.key,) if f is not None else ()) + ('wpk',)
+                                   if rt.get(k) is not None),
                              tuple(sorted((bk, t.data_ptr()) for bk, t in rt.get('wx3', {}).items()))))
         if self._pack_table is None or ptrs != self._pack_ptrs:
             lib = self.lib
@@ -490,7 +484,8 @@ class TrainRuntime:
                     # bf16x3 forward layers are split by the batched x3 list below (ct_conv_pack_weights_x3 is not
                     # recordable and would launch right here): only their epilogue is folded
                     # (... and the f16x2 Winograd layouts by the batched list further down: they take the layer's maximum first)
-                    self.be.pack_conv(s.fwd, weights=s.fwd.rt.get('x3') is None and s.fwd.rt.get('wino') not in H2_TILES)
+                    f = FORMS.get(s.fwd.rt.get('wino'))
+                    self.be.pack_conv(s.fwd, weights=s.fwd.rt.get('x3') is None and not (f is not None and f.h2))
                     if s.dgrad is not None:
                         self._pack_dgrad(st, s)
             finally:
@@ -553,10 +548,10 @@ class TrainRuntime:
                 if st.kind != 'conv':
                     continue
                 s = self.state[st.name]
-                t = s.fwd.rt.get('wino')
-                if t in H2_TILES:
-                    h2_item(s.fwd.parts, s.fwd.cin, 0, t, s.fwd.rt['U4H' if t == 47 else 'U4FH'])
-                if getattr(s, 'dgrad_wino', None) is not None and s.dgrad_tile in H2_TILES:
+                f = FORMS.get(s.fwd.rt.get('wino'))
+                if f is not None and f.h2:
+                    h2_item(s.fwd.parts, s.fwd.cin, 0, f.code, s.fwd.rt[f.key])
+                if getattr(s, 'dgrad_wino', None) is not None and FORMS[s.dgrad_tile].h2:
                     h2_item(st.parts, st.cin, 1, s.dgrad_tile, s.U_d, s.zero_w)
             table = torch.frombuffer(bytearray(b''.join(items)), dtype=torch.uint8).to(self.be.device) if items else None
             self._h2_list = (table, len(items), ptrs)
@@ -811,25 +806,18 @@ class TrainRuntime:
                     if not self._batched_packs:
                         self._pack_dgrad(st, s)
                     s.dgrad_wino.res = self.grads[st.src].data_ptr() if acc else None
-                    var4s = 3 if s.dgrad_tile == 47 else 1
-                    if s.dgrad_tile in (44, 47) and st.dil > 1 and acc:
+                    f = FORMS[s.dgrad_tile]
+                    d = s.dgrad_wino
+                    if f.split and st.dil > 1 and acc:
                         g = self.grads[st.src]
                         tmp = torch.empty((g.shape[0], st.cin, st.h, st.w), device=g.device)
-                        w3 = _lib.ConvDesc()
-                        C.memmove(C.byref(w3), C.byref(s.dgrad_wino), C.sizeof(w3))
-                        w3.res, w3.out, w3.out_ctot, w3.out_coff = None, tmp.data_ptr(), st.cin, 0
-                        _lib.check(lib.ct_conv2d_wino4s_fwd(C.byref(w3), s.U_d.data_ptr(), self.dgrad_ws4s.data_ptr(),
-                                                            self.dgrad_ws4s.numel(), var4s, self._s()), st.name + ' dgrad (winograd 4s, dilated)')
+                        d = _lib.ConvDesc()
+                        C.memmove(C.byref(d), C.byref(s.dgrad_wino), C.sizeof(d))
+                        d.res, d.out, d.out_ctot, d.out_coff = None, tmp.data_ptr(), st.cin, 0
+                    _lib.check(f.run(lib, C.byref(d), s.U_d.data_ptr(), self.dgrad_ws4s, None, self._s()),
+                               st.name + ' dgrad (%s)' % f.name)
+                    if d is not s.dgrad_wino:
                         g[:, st.src_coff:st.src_coff + st.cin] += tmp
-                    elif s.dgrad_tile in (44, 47):
-                        _lib.check(lib.ct_conv2d_wino4s_fwd(C.byref(s.dgrad_wino), s.U_d.data_ptr(), self.dgrad_ws4s.data_ptr(),
-                                                            self.dgrad_ws4s.numel(), var4s, self._s()), st.name + ' dgrad (winograd 4s)')
-                    elif s.dgrad_tile in (46, 48):
-                        _lib.check(lib.ct_conv2d_wino4f_pool_fwd_v(C.byref(s.dgrad_wino), s.U_d.data_ptr(), 2 if s.dgrad_tile == 48 else 1,
-                                                                   None, 0, 0, 0, 0, 1, self._s()), st.name + ' dgrad (winograd 4f)')
-                    else:
-                        run = lib.ct_conv2d_wino4_fwd if s.dgrad_tile == 4 else lib.ct_conv2d_wino_fwd
-                        _lib.check(run(C.byref(s.dgrad_wino), s.U_d.data_ptr(), self._s()), st.name + ' dgrad (winograd)')
                 else:
                     if not self._batched_packs:
                         self._pack_dgrad(st, s)
