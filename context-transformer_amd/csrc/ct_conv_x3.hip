@@ -406,8 +406,8 @@ __global__ __launch_bounds__(256, 2) void conv_x3_f32(const X3Args a)
         if (live) {
             const int s = P - n * a.OHW;
             // f16x2: the sums carry 2^(eX[image] + eW); undone with an exact power of two in front of the per-channel scale
-            float ymul = 1.f;
-            if constexpr (H2) ymul = __builtin_ldexpf(1.f, -(eW + ctdet::h2::image_exponent(a.in_amax, n, ctdet::h2::kGrowthNone)));
+            ctdet::h2::pow2x2 ymul{1.f, 1.f};
+            if constexpr (H2) ymul = ctdet::h2::unscale_for(eW, ctdet::h2::image_exponent(a.in_amax, n, ctdet::h2::kGrowthNone));
             float* const orow = a.nseg == 0 ? a.out + ((size_t)n * a.out_ctot + a.out_coff) * a.OHW + s : nullptr;
             const float* const rrow = a.res ? a.res + ((size_t)n * a.res_ctot + a.res_coff) * a.OHW + s : nullptr;
 #pragma unroll
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_f32(const X3Args a)
                     const int cl = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;      // cout inside the tile
                     const int co = m0 + cl;
                     if (co >= a.M) continue;
-                    float v = (H2 ? acc[i][j][r] * ymul : acc[i][j][r]) * ev[cl] + ev[BM + cl];
+                    float v = (H2 ? (acc[i][j][r] * ymul.lo) * ymul.hi : acc[i][j][r]) * ev[cl] + ev[BM + cl];
                     if (rrow) v = v * a.res_scale + rv[r];
                     { const float fl = ev[2 * BM + cl]; v = v < fl ? fl : v; }      // NaN propagates (torch.relu / no clamp)
                     if (track) ctdet::h2::track_absmax(amax_run, v);
@@ -472,11 +472,11 @@ __device__ __forceinline__ void x3_splitk_one(const X3Args& a, const int idx, co
         const int co = idx / a.Npix, P = idx - co * a.Npix;
         const int n = P / a.OHW, s = P - n * a.OHW;
         n_out = n;
-        float ymul = 1.f;       // f16x2 launches: the slabs hold sums scaled by 2^(eX[image] + eW)
-        if (a.eW) ymul = __builtin_ldexpf(1.f, -(*a.eW + ctdet::h2::image_exponent(a.in_amax, n, ctdet::h2::kGrowthNone)));
+        ctdet::h2::pow2x2 ymul{1.f, 1.f};       // f16x2 launches: the slabs hold sums scaled by 2^(eX[image] + eW)
+        if (a.eW) ymul = ctdet::h2::unscale_for(*a.eW, ctdet::h2::image_exponent(a.in_amax, n, ctdet::h2::kGrowthNone));
         float sum = a.ws[idx];
         for (int k = 1; k < a.ksplit; ++k) sum += a.ws[(size_t)k * total + idx];
-        float v = (sum * ymul) * a.scale[co] + a.shift[co];
+        float v = ((sum * ymul.lo) * ymul.hi) * a.scale[co] + a.shift[co];
         if (a.res) v = v * a.res_scale + a.res[((size_t)n * a.res_ctot + a.res_coff + co) * a.OHW + s];
         if (a.lo) { const float fl = a.lo[co]; v = v < fl ? fl : v; }      // NaN propagates
         else if (a.relu) v = v < 0.f ? 0.f : v;

@@ -16,7 +16,9 @@
 // ||G||_inf^2 max|g|) -- so nothing overflows whatever the data, and since the matrix pipe honours SUBNORMAL binary16 inputs
 // (probe, question 1) a value 2^-14 below the scaled maximum still has an exact hi piece and an lo piece that is only
 // coarser in absolute terms (quantum 2^-24 of the scaled unit = 2^-39 of the maximum): the GEMM error is unchanged with a
-// scale 1024 x too small (probe, question 4).  The consumer multiplies the fp32 sums by 2^-(eA + eB) -- exact.
+// scale 1024 x too small (probe, question 4).  The consumer multiplies the fp32 sums by 2^-(eA + eB) -- exact, and applied as TWO
+// powers of two (unscale_for): each exponent may be as large as +-126, their sum is no float, and the product of the two halves
+// is exact wherever the result itself is a normal fp32 number.  So the form holds for every normal fp32 maximum of either operand.
 // An Inf anywhere in an image makes its maximum Inf: the exponent is then 0; a NaN or Inf propagates through the pieces (binary16 has
 // both) like through any fp32 kernel, whatever the exponent.
 #pragma once
@@ -42,13 +44,23 @@ __device__ __forceinline__ void split2(float x0, float x1, int& hi, int& lo)
 }
 
 // Exponent e such that |v| 2^e < 2^15 for every |v| <= 2^growth_log2 * max, given the bit pattern of max >= 0
-// (growth_log2 = ceil(log2) of the transform's gain).  0 for an all-zero, NaN or Inf tensor; clamped to +-100.
+// (growth_log2 = ceil(log2) of the transform's gain).  0 for an all-zero, NaN or Inf tensor; clamped to +-126, the exponents for
+// which 2^e is a normal float: the lower end is never reached (e >= 15 - 128 - 6), the upper one only by maxima below 2^-112,
+// whose pieces then stay that much below 2^15 (precision fades only where the maximum itself is subnormal).
 __host__ __device__ __forceinline__ int exponent_for(unsigned max_bits, int growth_log2)
 {
     if (max_bits == 0u || max_bits >= 0x7F800000u) return 0;
     const int ex = (int)(max_bits >> 23) - 127;              // max < 2^(ex + 1)   (a subnormal maximum: ex = -127, clamped below)
     const int e = 15 - (ex + 1 + growth_log2);
-    return e < -100 ? -100 : e > 100 ? 100 : e;
+    return e < -126 ? -126 : e > 126 ? 126 : e;
+}
+// 2^-(eA + eB) as two exact factors of half the exponent each (|eA|, |eB| <= 126: each half within +-126).  (s * lo) * hi: the
+// intermediate's exponent lies between those of s and of the result, so nothing is lost unless the result itself leaves fp32.
+struct pow2x2 { float lo, hi; };
+__device__ __forceinline__ pow2x2 unscale_for(int eA, int eB)
+{
+    const int t = -(eA + eB), t1 = t >> 1;
+    return {__builtin_ldexpf(1.f, t1), __builtin_ldexpf(1.f, t - t1)};
 }
 constexpr int kGrowthBtB = 6;      // ||B^T||_inf^2 = 5.6875^2 = 32.35 < 2^6 (interpolation points 0, +-3/4, +-3/2, inf: ct_wino4_points.h)
 constexpr int kGrowthGG = 1;       // ||G||_inf^2 = 1.2197^2 = 1.4877 < 2^1

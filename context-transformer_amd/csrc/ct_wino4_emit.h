@@ -12,18 +12,19 @@ constexpr int kEmitInvalidOff = 0x7FFFFFF0;
 
 // y = A^T M A of one tile.  *scale + shift, residual, ReLU / per-channel floor (NaN propagates), the four 2x2 pooling
 // windows a 4x4 tile holds, NCHW or head-scatter stores.  Args: any record with the epilogue fields of Wino4Args.
-// ymul: a factor folded into the per-channel scale (the f16x2 kernels' 2^-(eU + eV): exact).  track / amax_run: the thread's
+// ymul, ymul2: two factors applied to the sums in front of the per-channel scale (the f16x2 kernels' 2^-(eU + eV) in two exact
+// halves, h2::unscale_for; 1, 1 elsewhere).  track / amax_run: the thread's
 // running maximum of |v| over everything this call stores (ct_conv_desc.out_absmax; the caller folds it into the slot once, at
 // the end of the kernel) -- a reference and a flag, not a nullable pointer, so that the value stays in a register.
 template <class Args>
 __device__ __forceinline__ void emit_tile4(const Args& a, const __amdgpu_buffer_rsrc_t rout,
                                            const __amdgpu_buffer_rsrc_t rres, const int n, const int ty, const int tx,
-                                           const int co, const float (&y)[4][4], const float ymul, const bool track, float& amax_run)
+                                           const int co, const float (&y)[4][4], const float ymul, const float ymul2, const bool track, float& amax_run)
 {
     const int OH = a.H, OW = a.W;                      // pad 1, stride 1: same spatial size
     const int oy = 4 * ty, ox = 4 * tx;
     const bool c1 = ox + 1 < OW, c2 = ox + 2 < OW, c3 = ox + 3 < OW;
-    float sc = a.scale[co] * ymul, sh = a.shift[co];
+    float sc = a.scale[co] * ymul2, sh = a.shift[co];      // (exact: a power of two of at most half the total exponent)
     float lo = a.lo ? a.lo[co] : (a.relu ? 0.f : -INFINITY);
     // The three per-channel values are needed by every row below, and every row sits behind its own `yy >= OH` test: left
     // alone, the compiler waits for these loads at the first use in EACH row block with s_waitcnt vmcnt(0) -- which from the
@@ -37,7 +38,7 @@ __device__ __forceinline__ void emit_tile4(const Args& a, const __amdgpu_buffer_
         if (yy >= OH) continue;
         float v[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = y[i][j] * sc + sh;
+        for (int j = 0; j < 4; ++j) v[j] = (y[i][j] * ymul) * sc + sh;
         if (a.res) {
             const unsigned ro = (unsigned)(((((size_t)n * a.res_ctot + a.res_coff + co) * OH + yy) * OW + ox) * 4);
 #pragma unroll
@@ -106,7 +107,7 @@ __device__ __forceinline__ void emit_tile4(const Args& a, const __amdgpu_buffer_
                                            const int co, const float (&y)[4][4])
 {
     float unused = 0.f;
-    emit_tile4(a, rout, rres, n, ty, tx, co, y, 1.f, false, unused);
+    emit_tile4(a, rout, rres, n, ty, tx, co, y, 1.f, 1.f, false, unused);
 }
 
 }  // namespace w4

@@ -478,8 +478,8 @@ __global__ __launch_bounds__(512) void wino_f4x4_3x3_x3(const Wino4fArgs a_in)
         const int o_kk = tid >> 5, o_tl = tid & 31;
         const int o_T = tb0 + o_tl;
         const int o_n = o_T / (a.TY * a.TX);
-        float ymul = 1.f;                 // f16x2: 2^-(eU + eV[image of this thread's tile]) into the per-channel scale
-        if constexpr (H2) ymul = __builtin_ldexpf(1.f, -(*e.eU + ctdet::h2::image_exponent(e.in_amax, o_T < a.NT ? o_n : 0, ctdet::h2::kGrowthBtB)));
+        ctdet::h2::pow2x2 ymul{1.f, 1.f};  // f16x2: 2^-(eU + eV[image of this thread's tile]) in front of the per-channel scale
+        if constexpr (H2) ymul = ctdet::h2::unscale_for(*e.eU, ctdet::h2::image_exponent(e.in_amax, o_T < a.NT ? o_n : 0, ctdet::h2::kGrowthBtB));
         const int o_rem = o_T - o_n * (a.TY * a.TX);
         const int o_ty = o_rem / a.TX, o_tx = o_rem - o_ty * a.TX;
 #pragma unroll
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(512) void wino_f4x4_3x3_x3(const Wino4fArgs a_in)
                     float y[4][4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) at4(z[i], y[i]);
-                    ctdet::w4::emit_tile4(ep, rout, rres, n, ty, tx, co, y, ymul, H2 && e.out_amax != nullptr, amax_run);
+                    ctdet::w4::emit_tile4(ep, rout, rres, n, ty, tx, co, y, ymul.lo, ymul.hi, H2 && e.out_amax != nullptr, amax_run);
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -746,7 +746,7 @@ __device__ __forceinline__ void wino4s_out_one(const Wino4sArgs& a, const int T,
 #pragma unroll
         for (int j = 0; j < 6; ++j) m[i][j] = __builtin_nontemporal_load(src + (size_t)(i * 6 + j) * a.m_plane);
     // f16x2: the operands were scaled by 2^eU, 2^eV[image] (exact powers of two); folded into the per-channel scale of the epilogue
-    float ymul = 1.f;
+    ctdet::h2::pow2x2 ymul{1.f, 1.f};      // f16x2: 2^-(eU + eV[image]) as two exact factors (h2::unscale_for)
     // A^T M A in double, rounded once: this kernel waits for HBM, the fp32 chain of ct_wino4.hip rounds ~10 times per output
     double t[6][4];
 #pragma unroll
@@ -774,8 +774,8 @@ __device__ __forceinline__ void wino4s_out_one(const Wino4sArgs& a, const int T,
         const int sy = q % d;
         const int n = q / d;
         img = n;
-        if constexpr (H2) ymul = __builtin_ldexpf(1.f, -(*a.eU + ctdet::h2::image_exponent(a.amax, n, ctdet::h2::kGrowthBtB)));
-        const float sc = a.scale[co] * ymul, sh = a.shift[co];
+        if constexpr (H2) ymul = ctdet::h2::unscale_for(*a.eU, ctdet::h2::image_exponent(a.amax, n, ctdet::h2::kGrowthBtB));
+        const float sc = a.scale[co] * ymul.hi, sh = a.shift[co];
         const float lo = a.lo ? a.lo[co] : (a.relu ? 0.f : -INFINITY);
         float* const plane = a.out + ((size_t)n * a.out_ctot + a.out_coff + co) * a.H * a.W;
 #pragma unroll
@@ -786,7 +786,7 @@ __device__ __forceinline__ void wino4s_out_one(const Wino4sArgs& a, const int T,
             for (int c = 0; c < 4; ++c) {
                 const int xx = sx + d * (4 * tx + c);
                 if (xx >= a.W) continue;
-                float v = y[r][c] * sc + sh;
+                float v = (y[r][c] * ymul.lo) * sc + sh;
                 v = v < lo ? lo : v;
                 plane[(size_t)yy * a.W + xx] = v;
                 if (track) ctdet::h2::track_absmax(amax_run, v);
@@ -796,12 +796,12 @@ __device__ __forceinline__ void wino4s_out_one(const Wino4sArgs& a, const int T,
     }
     const int n = T / (a.TY * a.TX);
     img = n;
-    if constexpr (H2) ymul = __builtin_ldexpf(1.f, -(*a.eU + ctdet::h2::image_exponent(a.amax, n, ctdet::h2::kGrowthBtB)));
+    if constexpr (H2) ymul = ctdet::h2::unscale_for(*a.eU, ctdet::h2::image_exponent(a.amax, n, ctdet::h2::kGrowthBtB));
     const int rem = T - n * (a.TY * a.TX);
     const int ty = rem / a.TX, tx = rem - ty * a.TX;
     const __amdgpu_buffer_rsrc_t rout = make_rsrc(a.out, a.out_bytes);
     const __amdgpu_buffer_rsrc_t rres = make_rsrc(a.res, a.res_bytes);
-    ctdet::w4::emit_tile4(a, rout, rres, n, ty, tx, co, y, ymul, track, amax_run);
+    ctdet::w4::emit_tile4(a, rout, rres, n, ty, tx, co, y, ymul.lo, ymul.hi, track, amax_run);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -696,19 +696,22 @@ class HipBackend:
                 st.rt['amax_frozen'] = False
                 self._own_absmax(st)
                 st.rt['amax_frozen'] = True
-        self.run_conv(st)
-        torch.cuda.synchronize(self.device)
-        best = float('inf')
-        for r in range(rounds + 1):
-            if r == 1 and best < 1.0 / 3:             # the first burst was the estimate: size the others from it
-                iters = min(64, max(iters, int(1.0 / max(best, 1e-3)) + 1))
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                self.run_conv(st)
-            e1.record()
+        try:
+            self.run_conv(st)
             torch.cuda.synchronize(self.device)
-            best = min(best, e0.elapsed_time(e1) / iters)
+            best = float('inf')
+            for r in range(rounds + 1):
+                if r == 1 and best < 1.0 / 3:             # the first burst was the estimate: size the others from it
+                    iters = min(64, max(iters, int(1.0 / max(best, 1e-3)) + 1))
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    self.run_conv(st)
+                e1.record()
+                torch.cuda.synchronize(self.device)
+                best = min(best, e0.elapsed_time(e1) / iters)
+        finally:
+            self._thaw_absmax(st)
         return best
 
     def tune_conv(self, st, iters=3):
@@ -759,6 +762,36 @@ class HipBackend:
                     self.enable_x3(st, best_x3)
         st.rt['tune_ms'] = times
         return best, times
+
+    @staticmethod
+    def _thaw_absmax(st):
+        """Unfreeze the maxima _time_conv took for its bursts: they belong to the data the tuner saw, and run_conv on a standalone
+        backend takes them again, into the same private slot, from whatever the buffers hold then (a Runtime wires its own
+        slots afterwards)."""
+        st.rt.pop('amax_frozen', None)
+
+
+def absmax_source(steps, tracks):
+    """Whose per-image maxima bound a buffer (ct_conv_desc.in_absmax / out_absmax), for the inference and the training wiring:
+    -> f(buffer) = (root buffer, its writers) or (None, []).  A buffer whose ONLY writer is a max-pool step is bounded by the
+    pool's input (pooled values are a subset of it), and so on along the chain; the root's writers must all satisfy
+    tracks(step).  Any other writer of a buffer on the chain -- a second step storing into the pooled buffer, a kernel that
+    does not fold its maxima -- leaves the buffer without a source: its consumer gets no slot."""
+    writers = {}
+    for st in steps:
+        for b in ([sg.dst for sg in st.segs] if st.kind == 'conv' and st.segs else [st.dst]):
+            writers.setdefault(b, []).append(st)
+
+    def source(b):
+        seen = set()
+        while True:
+            ws = writers.get(b, [])
+            if len(ws) == 1 and ws[0].kind == 'pool' and b not in seen:
+                seen.add(b)
+                b = ws[0].src
+                continue
+            return (b, ws) if ws and all(tracks(w) for w in ws) else (None, [])
+    return source
 
 
 def x3_allowed(st):
@@ -1189,22 +1222,7 @@ class Runtime:
                 return False
             f = FORMS.get(st.rt.get('wino'))
             return f.tracks if f is not None else True
-        root = {}                          # pooled buffer -> the buffer whose maximum bounds it
-        for ps in steps:
-            if ps.kind == 'pool':
-                root[ps.dst] = ps.src
-
-        def root_of(b):
-            while b in root:
-                b = root[b]
-            return b
-        writers = {}
-        for st in steps:
-            if st.kind == 'conv':
-                for b in ([sg.dst for sg in st.segs] if st.segs else [st.dst]):
-                    writers.setdefault(b, []).append(st)
-            elif st.kind != 'pool':
-                writers.setdefault(st.dst, []).append(st)
+        source = absmax_source(steps, tracks)
         while True:
             for st in self.conv_steps():
                 st.rt['desc'].in_absmax = None
@@ -1216,9 +1234,8 @@ class Runtime:
             for st in self.conv_steps():
                 if not be.reads_max(st):
                     continue
-                b = root_of(st.src)
-                ws = writers.get(b, [])
-                if ws and all(tracks(w) for w in ws):
+                b, ws = source(st.src)
+                if b is not None:
                     if b not in slots:
                         slots[b] = be.new_slot(self.batch)
                         for w in ws:

@@ -24,7 +24,7 @@ import os
 import torch
 
 from . import _lib, ops
-from .engine import (F4_TILES, WINO4F_TILES, WINO4S_TILES, ConvPart, ConvStep, HipBackend, Plan, Runtime, apply_tuned,
+from .engine import (F4_TILES, WINO4F_TILES, WINO4S_TILES, ConvPart, ConvStep, HipBackend, Plan, Runtime, absmax_source, apply_tuned,
                      operand_form_h2, run_on_streams)
 from .wino_forms import FORMS
 
@@ -347,19 +347,7 @@ class TrainRuntime:
                 return False
             f = FORMS.get(fwd(st).rt.get('wino'))
             return f.tracks if f is not None else True
-        root = {ps.dst: ps.src for ps in steps if ps.kind == 'pool'}
-
-        def root_of(b):
-            while b in root:
-                b = root[b]
-            return b
-        writers = {}
-        for st in steps:
-            if st.kind == 'conv':
-                for b in ([sg.dst for sg in st.segs] if st.segs else [st.dst]):
-                    writers.setdefault(b, []).append(st)
-            elif st.kind != 'pool':
-                writers.setdefault(st.dst, []).append(st)
+        source = absmax_source(steps, tracks)
         while True:
             for st in convs:
                 fwd(st).rt['desc'].in_absmax = None
@@ -370,9 +358,8 @@ class TrainRuntime:
                 f = FORMS.get(fwd(st).rt.get('wino'))
                 if f is None or not f.h2:
                     continue
-                b = root_of(st.src)
-                ws = writers.get(b, [])
-                if ws and all(tracks(w) for w in ws):
+                b, ws = source(st.src)
+                if b is not None:
                     if b not in slots:
                         slots[b] = be.new_slot(self.batch)
                         for w in ws:

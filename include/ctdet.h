@@ -249,7 +249,14 @@ typedef struct ct_conv_desc {
      *   out_absmax  the launch folds max |y| of everything it stores for image n into line n (atomic max): honoured by the shared
      *               epilogue of ct_conv2d_wino4s_fwd (every variant) and of the f16x2 variant of ct_conv2d_wino4f_pool_fwd_v, by
      *               ct_conv2d_x3_fwd and ct_conv2d_fwd (every configuration; split-K launches: in the finishing kernel); ignored
-     *               by the other kernels (the fp32 / bf16x3 fused Winograd kernels, the bf16 path) and by data-gradient launches. */
+     *               by the other kernels (the fp32 / bf16x3 fused Winograd kernels, the bf16 path) and by data-gradient launches.
+     * Range of the f16x2 kernels: any VALID bound in in_absmax (>= the true maximum; results within the library's 1e-4 for bounds
+     * up to 2^10 x the maximum) and any normal fp32 magnitude of activations and weights for which the fp32 / bf16x3 kernels
+     * themselves stay finite: the power-of-two scales follow the maxima over fp32's whole exponent range and are undone as two
+     * exact factors (csrc/ct_f16x2.h, unscale_for), so conv(x 2^a, w 2^b) = conv(x, w) 2^(a + b) bit for bit wherever no value
+     * leaves fp32's normal range (maxima below 2^-112: still within 1e-4, no longer bit-covariant).  What the form does NOT
+     * give: the low bits of ordinary values next to an outlier in the same image -- one value 2^20 x the rest costs the
+     * Winograd forms 5e-4 of the other outputs' range (2^14: 8e-6; the bf16x3 twins: 5e-7; tests/test_gpu_f16x2_range.py). */
     const unsigned* in_absmax;
     unsigned* out_absmax;
 } ct_conv_desc;

@@ -36,8 +36,9 @@ class _Holder:
 
 
 def _run_conv(x, parts, stride, pad, dil, config=0, res=None, res_scale=1.0, cin_off=0, cin=None,
-              out_ctot=None, out_coff=0, ksplit=None, x3=None):
-    """parts: list of (weight, bias|None, bn_tuple|None, relu).  Returns the NCHW output tensor."""
+              out_ctot=None, out_coff=0, ksplit=None, x3=None, in_absmax=None, out_absmax=None):
+    """parts: list of (weight, bias|None, bn_tuple|None, relu).  Returns the NCHW output tensor.
+    in_absmax / out_absmax: caller-owned device int32 tensors of B lines of CT_ABSMAX_LINE_BYTES for ct_conv_desc."""
     be = engine.HipBackend(DEV)
     cps = []
     for (w, b, bn, relu) in parts:
@@ -66,6 +67,10 @@ def _run_conv(x, parts, stride, pad, dil, config=0, res=None, res_scale=1.0, cin
         st.rt['ksws'].fill_(float('nan'))       # the workspace needs no initialisation
     if x3 is not None:                          # bf16x3 tile config (ct_conv2d_x3_fwd)
         be.enable_x3(st, x3)
+    if in_absmax is not None:
+        st.rt['desc'].in_absmax = in_absmax.data_ptr()
+    if out_absmax is not None:
+        st.rt['desc'].out_absmax = out_absmax.data_ptr()
     be.run_conv(st)
     torch.cuda.synchronize()
     return bufs['y'].cpu()
