@@ -40,6 +40,7 @@ SOURCES = {
     'ct_attn_bwd.hip': [],
     'ct_train.hip': [],
     'ct_box.hip': ['-ffp-contract=off'],
+    'ct_loss.hip': ['-ffp-contract=off'],
     'ct_nms.hip': ['-ffp-contract=off'],
     'ct_post.hip': ['-ffp-contract=off'],
     'ct_cpu_nms.cpp': ['-ffp-contract=off'],

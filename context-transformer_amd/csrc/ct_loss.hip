@@ -1,0 +1,432 @@
+// Fused MultiBoxLoss_combined (layers/modules/multibox_loss_combined.py:76-122 of the reference): three launches
+// forward (per-prior terms, per-image hard-negative selection, batch finish) and one backward.  No sort: the mining
+// keys are non-negative floats, so their bit patterns order like unsigned integers and a four-pass radix select over
+// the image's keys (held in LDS) finds the num_neg-th largest.  Every reduction runs in a fixed order -- no float
+// atomics in this file -- so results are bit-identical from run to run and an image's selection does not depend on
+// its batch mates.  Compiled with -ffp-contract=off.
+#include "ct_common.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <mutex>
+
+namespace {
+
+constexpr int ROW_THREADS = 256;        // per-prior kernels: 256 / G rows per workgroup, G lanes share one row of conf
+constexpr int SEL_THREADS = 1024;       // selection: one workgroup per image
+constexpr int SEL_WAVES = SEL_THREADS / 64;
+constexpr int LDS_MAX_KEYS = 36864;     // 144 KiB of keys + the static arrays below stay inside the 160 KiB of a CU
+
+// One "item" of a conf row: a 16-byte load when the row length is a multiple of 4 (rows are then 16-byte aligned),
+// one float otherwise.  Lanes past the end of the row hold -inf, which neither the max nor the exp-sum sees.
+template <bool VEC>
+__device__ inline float4 load_item(const float* row, int i, int items)
+{
+    const float ninf = -INFINITY;
+    if (i >= items) return make_float4(ninf, ninf, ninf, ninf);
+    if (VEC) return reinterpret_cast<const float4*>(row)[i];
+    return make_float4(row[i], ninf, ninf, ninf);
+}
+
+__device__ inline float max4(float4 v) { return fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)); }
+__device__ inline float sumexp4(float4 v, float m)
+{
+    return (expf(v.x - m) + expf(v.y - m)) + (expf(v.z - m) + expf(v.w - m));
+}
+
+// max and sum(exp(x - max)) of one conf row, spread over the G lanes of a group (xor butterflies: every lane ends
+// with the same value, the order of the additions is fixed by G alone).  v0 = the lane's first item, kept by the caller.
+template <int G, bool VEC>
+__device__ inline void row_max_sumexp(const float* row, int sub, int items, float4 v0, float& m, float& s)
+{
+    m = max4(v0);
+    for (int i = sub + G; i < items; i += G) m = fmaxf(m, max4(load_item<VEC>(row, i, items)));
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    s = sumexp4(v0, m);
+    for (int i = sub + G; i < items; i += G) s += sumexp4(load_item<VEC>(row, i, items), m);
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+}
+
+__device__ inline int class_target(float label, int nfg)
+{
+    // labels.long().clamp_min(0); the upper clamp only keeps a malformed label inside the row
+    const long long t = (long long)label;
+    return (int)(t < 0 ? 0 : (t > nfg ? nfg : t));
+}
+
+__device__ inline float smooth_l1(float d)
+{
+    const float a = fabsf(d);
+    return a < 1.f ? 0.5f * d * d : a - 0.5f;
+}
+
+// ---------------------------------------------------------------------------------------------------- per prior
+// ws[row] = (smooth-L1 sum, objectness CE, mining key, class CE).  The class CE is taken on the fused logits
+// z = [o0 + lse(conf), o1 + conf_1 ..]; since logsumexp(z) = lse(conf) + logsumexp(o0, o1), it is
+// CE_obj(0) for target 0 and (lse(conf) - conf_t) + CE_obj(1) for a foreground target.
+template <int G, bool VEC>
+__global__ __launch_bounds__(ROW_THREADS) void loss_prior_kernel(
+    const float4* __restrict__ loc, const float* __restrict__ conf, const float2* __restrict__ obj,
+    const float4* __restrict__ loc_t, const float2* __restrict__ conf_t, const uint8_t* __restrict__ obj_t,
+    long long rows, int nfg, float4* __restrict__ ws)
+{
+    const int sub = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
+    const bool live = row < rows;
+    const long long r = live ? row : rows - 1;          // dead groups recompute the last row and write nothing
+    const float* crow = conf + r * nfg;
+    const int items = VEC ? nfg / 4 : nfg;
+    const float4 v0 = load_item<VEC>(crow, sub, items);
+    float m, s;
+    row_max_sumexp<G, VEC>(crow, sub, items, v0, m, s);
+    if (sub != 0 || !live) return;
+
+    const float4 a = loc[r], b = loc_t[r];
+    const float l1 = (smooth_l1(a.x - b.x) + smooth_l1(a.y - b.y)) + (smooth_l1(a.z - b.z) + smooth_l1(a.w - b.w));
+    const float2 o = obj[r];
+    const float om = fmaxf(o.x, o.y);
+    const float olse = logf(expf(o.x - om) + expf(o.y - om));
+    const float ce0 = olse - (o.x - om), ce1 = olse - (o.y - om);
+    const bool ot = obj_t[r] != 0;
+    const float ce_obj = ot ? ce1 : ce0;
+    const float key = (!ot && ce_obj > 0.f) ? ce_obj : 0.f;            // never -0 or NaN: the select orders bit patterns
+    const int t = class_target(conf_t[r].x, nfg);
+    float ce_cls = ce0;
+    if (t > 0) ce_cls = ((m + logf(s)) - crow[t - 1]) + ce1;
+    ws[r] = make_float4(l1, ce_obj, key, ce_cls);
+}
+
+// ---------------------------------------------------------------------------------------------------- selection
+__device__ inline double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Sum over the workgroup in a fixed order: butterflies inside each wave, then the 16 wave totals in index order.
+__device__ inline double block_sum(double v, double* red /*[SEL_WAVES]*/)
+{
+    v = wave_sum(v);
+    __syncthreads();                                    // red may still be read from the previous call
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int i = 0; i < SEL_WAVES; ++i) t += red[i];
+    return t;
+}
+
+// Count `digit` in hist for the lanes with `valid`.  The top digit of a mining key is nearly the same for every
+// prior, so up to two rounds first peel the leading lane's digit off with one atomic for the whole wave.
+// Integer atomics only: the counts do not depend on their order.
+__device__ inline void hist_add(unsigned* hist, unsigned digit, bool valid)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const unsigned long long act = __ballot(valid);
+        if (act == 0) return;
+        const int leader = __ffsll((long long)act) - 1;
+        const unsigned d0 = __shfl(digit, leader);
+        const unsigned long long same = __ballot(valid && digit == d0);
+        if (lane == leader) atomicAdd(&hist[d0], (unsigned)__popcll(same));
+        if (digit == d0) valid = false;
+    }
+    if (valid) atomicAdd(&hist[digit], 1u);
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(SEL_THREADS) void loss_select_kernel(
+    const float4* __restrict__ ws, const float2* __restrict__ conf_t, int P, int negpos_ratio,
+    float* __restrict__ w_out, long long* __restrict__ num_pos_out, double* __restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned skeys[];    // [P] when LDS
+    __shared__ unsigned hist[256];
+    __shared__ double red[SEL_WAVES];
+    __shared__ int wcnt[2][SEL_WAVES];
+    __shared__ unsigned s_prefix, s_krem, s_eq;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t base = (size_t)blockIdx.x * P;
+    ws += base; conf_t += base; w_out += base;
+    auto key_at = [&](int i) -> unsigned { return LDS ? skeys[i] : __float_as_uint(ws[i].z); };
+
+    // num_pos = long(sum of weight * pos): fp64 in a fixed order, rounded once to fp32, truncated
+    double acc = 0.0;
+    for (int i = tid; i < P; i += SEL_THREADS) {
+        const float2 ct = conf_t[i];
+        if (ct.x > 0.f) acc += (double)ct.y;
+        if (LDS) skeys[i] = __float_as_uint(ws[i].z);
+    }
+    const float possum = (float)block_sum(acc, red);
+    const long long num_pos = (long long)possum;
+    long long kk = (long long)negpos_ratio * num_pos;
+    kk = kk < 0 ? 0 : (kk > P - 1 ? P - 1 : kk);
+    const unsigned k = (unsigned)kk;                    // hard negatives to draw, < P
+
+    // radix select: after the four passes `thr` is the k-th largest key, `krem` of the `eq` priors equal to it are drawn
+    unsigned thr = 0, krem = k, eq = 0;
+    if (k > 0) {
+        unsigned mask = 0;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();                            // also orders the skeys writes above before the first read
+            for (int i0 = 0; i0 < P; i0 += SEL_THREADS) {
+                const int i = i0 + tid;
+                const unsigned key = i < P ? key_at(i) : 0u;
+                hist_add(hist, (key >> shift) & 255u, i < P && (key & mask) == thr);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned rem = krem, d = 255;
+                for (;; --d) {
+                    const unsigned c = hist[d];
+                    if (rem <= c || d == 0) { s_eq = c; break; }
+                    rem -= c;
+                }
+                s_prefix = thr | (d << shift);
+                s_krem = rem;
+            }
+            __syncthreads();
+            thr = s_prefix; krem = s_krem; eq = s_eq;
+            mask |= 255u << shift;
+        }
+    }
+    const bool ranked = k > 0 && krem < eq;             // the cut-off falls inside a tie group: lowest indices first
+
+    double sl = 0.0, sc = 0.0, so = 0.0;
+    unsigned run = 0;                                   // priors equal to thr seen in earlier chunks
+    int buf = 0;
+    for (int i0 = 0; i0 < P; i0 += SEL_THREADS) {
+        const int i = i0 + tid;
+        const bool in = i < P;
+        const unsigned key = in ? key_at(i) : 0u;
+        const bool iseq = in && k > 0 && key == thr;
+        bool neg = in && k > 0 && key > thr;
+        if (!ranked) {
+            neg = neg || iseq;
+        } else {
+            const unsigned long long mm = __ballot(iseq);
+            if (lane == 0) wcnt[buf][wave] = __popcll(mm);
+            __syncthreads();
+            unsigned before = 0, total = 0;
+            for (int v = 0; v < SEL_WAVES; ++v) {
+                const unsigned c = (unsigned)wcnt[buf][v];
+                before += v < wave ? c : 0u;
+                total += c;
+            }
+            const unsigned rank = run + before + (unsigned)__popcll(mm & ((1ull << lane) - 1ull));
+            neg = neg || (iseq && rank < krem);
+            run += total;
+            buf ^= 1;
+        }
+        if (in) {
+            const float2 ct = conf_t[i];
+            const bool pos = ct.x > 0.f;
+            const float w = (pos || neg) ? ct.y : 0.f;
+            w_out[i] = w;
+            if (pos || w != 0.f) {
+                const float4 v = ws[i];
+                if (pos) sl += (double)(v.x * ct.y);
+                if (w != 0.f) { so += (double)(v.y * w); sc += (double)(v.w * w); }
+            }
+        }
+    }
+    sl = block_sum(sl, red);
+    sc = block_sum(sc, red);
+    so = block_sum(so, red);
+    if (tid == 0) {
+        partial[blockIdx.x * 3 + 0] = sl;
+        partial[blockIdx.x * 3 + 1] = sc;
+        partial[blockIdx.x * 3 + 2] = so;
+        num_pos_out[blockIdx.x] = num_pos;
+    }
+}
+
+// sums = (sum loc, sum cls, sum obj) over the images in index order, n = sum of num_pos
+__global__ void loss_finish_kernel(const double* __restrict__ partial, const long long* __restrict__ num_pos, int batch,
+                                   float* __restrict__ sums, long long* __restrict__ n)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double a = 0.0, b = 0.0, c = 0.0;
+    long long t = 0;
+    for (int i = 0; i < batch; ++i) {
+        a += partial[i * 3 + 0]; b += partial[i * 3 + 1]; c += partial[i * 3 + 2];
+        t += num_pos[i];
+    }
+    sums[0] = (float)a; sums[1] = (float)b; sums[2] = (float)c;
+    n[0] = t;
+}
+
+// ---------------------------------------------------------------------------------------------------- backward
+// With p = softmax(fused logits), s = softmax(obj), q = softmax(conf): p_0 = s_0 and p_k = s_1 q_k, so
+//   d cls / d conf_k = [t >= 1] q_k - [t = k],   d cls / d obj = s - onehot(t >= 1),   d obj-loss / d obj = s - onehot(obj_t).
+// A row with w = 0 (then weight * pos = 0 too) is written as zeros without looking at its logits.
+template <int G, bool VEC>
+__global__ __launch_bounds__(ROW_THREADS) void loss_bwd_kernel(
+    const float4* __restrict__ loc, const float* __restrict__ conf, const float2* __restrict__ obj,
+    const float4* __restrict__ loc_t, const float2* __restrict__ conf_t, const uint8_t* __restrict__ obj_t,
+    const float* __restrict__ w, const float* __restrict__ g, long long rows, int nfg,
+    float4* __restrict__ dloc, float* __restrict__ dconf, float2* __restrict__ dobj)
+{
+    const int sub = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
+    if (row >= rows) return;                            // whole groups leave together; shuffles stay inside a group
+    const float wr = w[row];
+    const float2 ct = conf_t[row];
+    const int t = class_target(ct.x, nfg);
+    const float g0 = g[0], g1 = g[1], g2 = g[2];
+    const float* crow = conf + row * nfg;
+    float* drow = dconf + row * nfg;
+    const int items = VEC ? nfg / 4 : nfg;
+
+    if (wr != 0.f && t > 0) {
+        const float4 v0 = load_item<VEC>(crow, sub, items);
+        float m, s;
+        row_max_sumexp<G, VEC>(crow, sub, items, v0, m, s);
+        const float gw = g1 * wr;
+        for (int i = sub; i < items; i += G) {
+            const float4 v = i == sub ? v0 : load_item<VEC>(crow, i, items);
+            const int c0 = VEC ? 4 * i : i;
+            const float dx = gw * (expf(v.x - m) / s - (c0 == t - 1 ? 1.f : 0.f));
+            if (VEC) {
+                const float dy = gw * (expf(v.y - m) / s - (c0 + 1 == t - 1 ? 1.f : 0.f));
+                const float dz = gw * (expf(v.z - m) / s - (c0 + 2 == t - 1 ? 1.f : 0.f));
+                const float dw = gw * (expf(v.w - m) / s - (c0 + 3 == t - 1 ? 1.f : 0.f));
+                reinterpret_cast<float4*>(drow)[i] = make_float4(dx, dy, dz, dw);
+            } else {
+                drow[i] = dx;
+            }
+        }
+    } else {
+        for (int i = sub; i < items; i += G) {
+            if (VEC) reinterpret_cast<float4*>(drow)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            else drow[i] = 0.f;
+        }
+    }
+    if (sub != 0) return;
+
+    float4 dl = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ct.x > 0.f && ct.y != 0.f) {
+        const float4 a = loc[row], b = loc_t[row];
+        const float gl = g0 * ct.y;
+        dl.x = gl * fminf(fmaxf(a.x - b.x, -1.f), 1.f);
+        dl.y = gl * fminf(fmaxf(a.y - b.y, -1.f), 1.f);
+        dl.z = gl * fminf(fmaxf(a.z - b.z, -1.f), 1.f);
+        dl.w = gl * fminf(fmaxf(a.w - b.w, -1.f), 1.f);
+    }
+    dloc[row] = dl;
+
+    float2 dob = make_float2(0.f, 0.f);
+    if (wr != 0.f) {
+        const float2 o = obj[row];
+        const float om = fmaxf(o.x, o.y);
+        const float e0 = expf(o.x - om), e1 = expf(o.y - om);
+        const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
+        const bool ot = obj_t[row] != 0;
+        const float go = g2 * wr, gc = g1 * wr;
+        dob.x = go * (p0 - (ot ? 0.f : 1.f)) + gc * (p0 - (t == 0 ? 1.f : 0.f));
+        dob.y = go * (p1 - (ot ? 1.f : 0.f)) + gc * (p1 - (t == 0 ? 0.f : 1.f));
+    }
+    dobj[row] = dob;
+}
+
+size_t ws_rows_bytes(int batch, int num_priors) { return ctdet::align_up((size_t)batch * num_priors * sizeof(float4), 256); }
+
+// lanes per conf row: the smallest supported group that holds the row in one item per lane (64 = a whole wave, looping)
+int group_for(int items) { return items <= 4 ? 4 : items <= 8 ? 8 : items <= 16 ? 16 : 64; }
+
+}  // namespace
+
+extern "C" size_t ct_multibox_loss_workspace_bytes(int batch, int num_priors, int num_classes)
+{
+    (void)num_classes;
+    if (batch <= 0 || num_priors <= 0) return 0;
+    return ws_rows_bytes(batch, num_priors) + ctdet::align_up((size_t)batch * 3 * sizeof(double), 256);
+}
+
+// launch KERNEL<G, VEC> for the row length nfg; `vec` (16-byte loads allowed), `rows`, `nfg`, `st` come from the caller
+#define CT_LOSS_DISPATCH(KERNEL, ...)                                                                            \
+    do {                                                                                                         \
+        const int G = group_for(vec ? nfg / 4 : nfg);                                                            \
+        const long long nblk = (rows + ROW_THREADS / G - 1) / (ROW_THREADS / G);                                 \
+        CT_REQUIRE(nblk < 0x7FFFFFFFLL, "%s: too many priors", #KERNEL);                                         \
+        const dim3 grid((unsigned)nblk), block(ROW_THREADS);                                                     \
+        if (vec) {                                                                                               \
+            if (G == 4) hipLaunchKernelGGL((KERNEL<4, true>), grid, block, 0, st, __VA_ARGS__);                  \
+            else if (G == 8) hipLaunchKernelGGL((KERNEL<8, true>), grid, block, 0, st, __VA_ARGS__);             \
+            else if (G == 16) hipLaunchKernelGGL((KERNEL<16, true>), grid, block, 0, st, __VA_ARGS__);           \
+            else hipLaunchKernelGGL((KERNEL<64, true>), grid, block, 0, st, __VA_ARGS__);                        \
+        } else {                                                                                                 \
+            if (G == 4) hipLaunchKernelGGL((KERNEL<4, false>), grid, block, 0, st, __VA_ARGS__);                 \
+            else if (G == 8) hipLaunchKernelGGL((KERNEL<8, false>), grid, block, 0, st, __VA_ARGS__);            \
+            else if (G == 16) hipLaunchKernelGGL((KERNEL<16, false>), grid, block, 0, st, __VA_ARGS__);          \
+            else hipLaunchKernelGGL((KERNEL<64, false>), grid, block, 0, st, __VA_ARGS__);                       \
+        }                                                                                                        \
+        CT_LAUNCH_CHECK(#KERNEL);                                                                                \
+    } while (0)
+
+extern "C" int ct_multibox_loss_fwd(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                                    const float* conf_t, const uint8_t* obj_t, int batch, int num_priors,
+                                    int num_classes, int negpos_ratio, float* sums, long long* num_pos, long long* n,
+                                    float* w, void* ws, size_t ws_bytes, ct_stream_t stream)
+{
+    CT_REQUIRE(loc && conf && obj && loc_t && conf_t && obj_t && sums && num_pos && n && w && ws,
+               "ct_multibox_loss_fwd: null pointer");
+    CT_REQUIRE(batch > 0 && num_priors > 0, "ct_multibox_loss_fwd: batch=%d num_priors=%d", batch, num_priors);
+    CT_REQUIRE(num_classes >= 2, "ct_multibox_loss_fwd: num_classes=%d (at least background and one class)", num_classes);
+    CT_REQUIRE(negpos_ratio >= 0, "ct_multibox_loss_fwd: negpos_ratio=%d", negpos_ratio);
+    const size_t need = ct_multibox_loss_workspace_bytes(batch, num_priors, num_classes);
+    if (ws_bytes < need)
+        return ctdet::fail(CT_ERR_WORKSPACE, "ct_multibox_loss_fwd: workspace %zu < %zu", ws_bytes, need);
+    hipStream_t st = ctdet::as_stream(stream);
+    const long long rows = (long long)batch * num_priors;
+    const int nfg = num_classes - 1;
+    float4* rows_ws = (float4*)ws;
+    double* partial = (double*)((char*)ws + ws_rows_bytes(batch, num_priors));
+
+    const bool vec = nfg % 4 == 0 && (reinterpret_cast<uintptr_t>(conf) & 15) == 0;
+    CT_LOSS_DISPATCH(loss_prior_kernel, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                     (const float2*)conf_t, obj_t, rows, nfg, rows_ws);
+
+    if (num_priors <= LDS_MAX_KEYS) {
+        const size_t lds = (size_t)num_priors * sizeof(unsigned);
+        static std::once_flag once;
+        static hipError_t attr = hipSuccess;
+        std::call_once(once, [] {
+            attr = hipFuncSetAttribute((const void*)loss_select_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       LDS_MAX_KEYS * (int)sizeof(unsigned));
+        });
+        CT_HIP(attr);
+        hipLaunchKernelGGL(loss_select_kernel<true>, dim3(batch), dim3(SEL_THREADS), lds, st, (const float4*)rows_ws,
+                           (const float2*)conf_t, num_priors, negpos_ratio, w, num_pos, partial);
+    } else {
+        hipLaunchKernelGGL(loss_select_kernel<false>, dim3(batch), dim3(SEL_THREADS), 0, st, (const float4*)rows_ws,
+                           (const float2*)conf_t, num_priors, negpos_ratio, w, num_pos, partial);
+    }
+    CT_LAUNCH_CHECK("loss_select_kernel");
+    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(64), 0, st, (const double*)partial, (const long long*)num_pos,
+                       batch, sums, n);
+    CT_LAUNCH_CHECK("loss_finish_kernel");
+    return CT_OK;
+}
+
+extern "C" int ct_multibox_loss_bwd(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                                    const float* conf_t, const uint8_t* obj_t, const float* w, const float* g,
+                                    int batch, int num_priors, int num_classes, float* dloc, float* dconf,
+                                    float* dobj, ct_stream_t stream)
+{
+    CT_REQUIRE(loc && conf && obj && loc_t && conf_t && obj_t && w && g && dloc && dconf && dobj,
+               "ct_multibox_loss_bwd: null pointer");
+    CT_REQUIRE(batch > 0 && num_priors > 0, "ct_multibox_loss_bwd: batch=%d num_priors=%d", batch, num_priors);
+    CT_REQUIRE(num_classes >= 2, "ct_multibox_loss_bwd: num_classes=%d (at least background and one class)", num_classes);
+    hipStream_t st = ctdet::as_stream(stream);
+    const long long rows = (long long)batch * num_priors;
+    const int nfg = num_classes - 1;
+    const bool vec = nfg % 4 == 0 && ((reinterpret_cast<uintptr_t>(conf) | reinterpret_cast<uintptr_t>(dconf)) & 15) == 0;
+    CT_LOSS_DISPATCH(loss_bwd_kernel, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                     (const float2*)conf_t, obj_t, w, g, rows, nfg, (float4*)dloc, dconf, (float2*)dobj);
+    return CT_OK;
+}

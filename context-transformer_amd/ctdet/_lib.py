@@ -92,6 +92,9 @@ SIGNATURES = {
     'ct_jaccard': (_I, [_P, _I, _P, _I, _I, _P, _P]),
     'ct_match_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_match_batched': (_I, [_P, _P, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, _P, _Z, _P]),
+    'ct_multibox_loss_workspace_bytes': (_Z, [_I, _I, _I]),
+    'ct_multibox_loss_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    'ct_multibox_loss_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     'ct_postprocess_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_conv_kpad': (_I, [_I, _I, _I]),

@@ -113,6 +113,51 @@ def match_batched(targets, priors, threshold, variances, want_overlap=False):
     return (loc_t, conf_t, obj_t.bool(), overlap) if want_overlap else (loc_t, conf_t, obj_t.bool())
 
 
+# ------------------------------------------------------------------ loss
+def _u8(t, name):
+    """The matcher's ignore mask: uint8 as ct_match_batched writes it, or the bool view match_batched returns."""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    return _dev(t, name, torch.uint8)
+
+
+def multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio):
+    """layers/modules/multibox_loss_combined.py:76-122 fused (ct_multibox_loss_fwd) -> sums [3] = un-normalised
+    (loc, cls, obj) losses, n int64 [1], num_pos int64 [B], w [B,P] = weight * (pos | hard negative)."""
+    _dev(loc, 'loc')
+    dev = loc.device
+    B, P = loc.shape[0], loc.shape[1]
+    for t, name, last in ((loc, 'loc', 4), (conf, 'conf', num_classes - 1), (obj, 'obj', 2), (loc_t, 'loc_t', 4),
+                          (conf_t, 'conf_t', 2)):
+        if tuple(t.shape) != (B, P, last):
+            raise _lib.CtdetError('%s must be [%d,%d,%d], got %s' % (name, B, P, last, tuple(t.shape)))
+    if tuple(obj_t.shape) != (B, P):
+        raise _lib.CtdetError('obj_t must be [%d,%d], got %s' % (B, P, tuple(obj_t.shape)))
+    sums = torch.empty(3, device=dev)
+    n = torch.empty(1, device=dev, dtype=torch.int64)
+    num_pos = torch.empty(B, device=dev, dtype=torch.int64)
+    w = torch.empty(B, P, device=dev)
+    ws_bytes = lib().ct_multibox_loss_workspace_bytes(B, P, int(num_classes))
+    ws = torch.empty(max(ws_bytes, 1), device=dev, dtype=torch.uint8)
+    check(lib().ct_multibox_loss_fwd(_dev(loc, 'loc'), _dev(conf, 'conf'), _dev(obj, 'obj'), _dev(loc_t, 'loc_t'),
+                                     _dev(conf_t, 'conf_t'), _u8(obj_t, 'obj_t'), B, P, int(num_classes),
+                                     int(negpos_ratio), _dev(sums, 'sums'), _dev(num_pos, 'num_pos', torch.int64),
+                                     _dev(n, 'n', torch.int64), _dev(w, 'w'), _dev(ws, 'ws', torch.uint8), ws_bytes,
+                                     _stream()), 'ct_multibox_loss_fwd')
+    return sums, n, num_pos, w
+
+
+def multibox_loss_backward(loc, conf, obj, loc_t, conf_t, obj_t, w, g, num_classes):
+    """Gradients of (g * sums).sum() w.r.t. (loc, conf, obj); g is a DEVICE [3] tensor (ct_multibox_loss_bwd)."""
+    B, P = loc.shape[0], loc.shape[1]
+    dloc, dconf, dobj = torch.empty_like(loc), torch.empty_like(conf), torch.empty_like(obj)
+    check(lib().ct_multibox_loss_bwd(_dev(loc, 'loc'), _dev(conf, 'conf'), _dev(obj, 'obj'), _dev(loc_t, 'loc_t'),
+                                     _dev(conf_t, 'conf_t'), _u8(obj_t, 'obj_t'), _dev(w, 'w'), _dev(g, 'g'),
+                                     B, P, int(num_classes), _dev(dloc, 'dloc'), _dev(dconf, 'dconf'),
+                                     _dev(dobj, 'dobj'), _stream()), 'ct_multibox_loss_bwd')
+    return dloc, dconf, dobj
+
+
 # ------------------------------------------------------------------ NMS
 def nms_sorted_host(dets_sorted, thresh, ge=False, device_id=0, plain_iou=False):
     """The `_nms` contract (utils/nms/nms_kernel.cu:91-144): host numpy [n,dim>=4] sorted by

@@ -2,26 +2,52 @@
 
 Target assignment (jaccard / match / encode for the whole batch) is ONE call into the HIP
 library (`ct_match_batched`) instead of a Python loop over images and ground truths; the loss
-arithmetic itself (smooth-L1, two cross-entropies, 3:1 hard-negative ranking) is expressed on
-the device tensors with autograd so it stays differentiable w.r.t. the predictions.
+arithmetic itself (smooth-L1, two cross-entropies, 3:1 hard-negative ranking) has two forms: torch ops on
+the device tensors with autograd (the default), or -- `fused=True` / CTDET_LOSS_FUSED=1 -- the library's
+ct_multibox_loss_fwd / _bwd (three launches forward, one backward, no sort) behind one autograd Function.
 targets: list of [G,6] tensors = [x1,y1,x2,y2,label,mixup_weight].
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from collections import namedtuple
 
-from ctdet import ops
+from ctdet import _lib, ops
 
 # what match() assigns to every prior: encoded box [B,P,4], (label, mixup weight) [B,P,2], ignore mask [B,P] bool
 MatchedTargets = namedtuple('MatchedTargets', 'loc_t conf_t obj_t')
 
 
+class FusedMultiBoxLoss(torch.autograd.Function):
+    """(loc, conf, obj, matched targets) -> sums [3] = un-normalised (loc, cls, obj) losses, differentiable w.r.t. the
+    three predictions, plus n [1], num_pos [B], w [B,P] (not differentiable).  The incoming [3] gradient goes to the
+    backward kernel as a device pointer, so a normaliser applied outside (`sums / n`) scales it for free."""
+
+    @staticmethod
+    def forward(ctx, loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio):
+        sums, n, num_pos, w = ops.multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio)
+        ctx.save_for_backward(loc, conf, obj, loc_t, conf_t, obj_t, w)
+        ctx.num_classes = num_classes
+        ctx.mark_non_differentiable(n, num_pos, w)
+        return sums, n, num_pos, w
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        loc, conf, obj, loc_t, conf_t, obj_t, w = ctx.saved_tensors
+        dloc, dconf, dobj = ops.multibox_loss_backward(loc, conf, obj, loc_t, conf_t, obj_t, w,
+                                                       g.to(torch.float32).contiguous(), ctx.num_classes)
+        return dloc, dconf, dobj, None, None, None, None, None
+
+
 class MultiBoxLoss_combined(nn.Module):
     def __init__(self, num_classes, overlap_thresh, prior_for_matching, bkg_label, neg_mining, neg_pos,
-                 neg_overlap, encode_target):
+                 neg_overlap, encode_target, fused=None):
         super().__init__()
+        # fused: the HIP loss kernels instead of the torch ops below; None reads CTDET_LOSS_FUSED (default off)
+        self.fused = os.environ.get('CTDET_LOSS_FUSED', '0') == '1' if fused is None else bool(fused)
         self.num_classes = num_classes
         self.threshold = overlap_thresh
         self.background_label = bkg_label
@@ -55,6 +81,8 @@ class MultiBoxLoss_combined(nn.Module):
             loc_t, conf_t, obj_t = targets
         else:
             loc_t, conf_t, obj_t = self.match(priors, targets, dev)
+        if self.fused:
+            return self._forward_fused(loc_data, conf_data, obj_data, loc_t, conf_t, obj_t)
         labels, weights = conf_t[:, :, 0], conf_t[:, :, 1]
         pos = labels > 0
         num_pos = (weights * pos.float()).sum(1, keepdim=True).long()
@@ -97,3 +125,18 @@ class MultiBoxLoss_combined(nn.Module):
             from ctdet.dist import global_normalizer
             n = global_normalizer(n, dev)
         return {'loss_box_reg': loss_l / n, 'loss_cls': loss_c / n, 'loss_obj': loss_obj / n}
+
+    def _forward_fused(self, loc_data, conf_data, obj_data, loc_t, conf_t, obj_t):
+        for t in (loc_data, conf_data, obj_data, loc_t, conf_t, obj_t):
+            if not t.is_cuda:
+                raise _lib.CtdetError('MultiBoxLoss_combined(fused=True) needs tensors on the HIP device (got %s); '
+                                      'there is no CPU form of the fused loss -- use fused=False' % t.device)
+        sums, n, _, _ = FusedMultiBoxLoss.apply(loc_data.contiguous(), conf_data.contiguous(), obj_data.contiguous(),
+                                                loc_t.contiguous(), conf_t.contiguous(), obj_t.contiguous(),
+                                                self.num_classes, int(self.negpos_ratio))
+        n = n[0]
+        if self.sync_normalizer:
+            from ctdet.dist import global_normalizer
+            n = global_normalizer(n, loc_data.device)
+        losses = sums / n                 # the one torch op: autograd hands g / n to the backward kernel
+        return {'loss_box_reg': losses[0], 'loss_cls': losses[1], 'loss_obj': losses[2]}

@@ -159,6 +159,33 @@ int ct_match_batched(const float* truths, const int* gt_off, int batch, int max_
                      float* loc_t, float* conf_t, uint8_t* obj_t, float* overlap,
                      void* workspace, size_t workspace_bytes, ct_stream_t stream);
 
+/* layers/modules/multibox_loss_combined.py:76-122 (`MultiBoxLoss_combined.forward` after the matching): the loss
+ * arithmetic, fused.  Forward = three launches, backward = one; no allocation, no host synchronisation, capturable.
+ *   loc dev [B,P,4], conf dev [B,P,C-1], obj dev [B,P,2]      the network's raw outputs (C = num_classes >= 2)
+ *   loc_t [B,P,4], conf_t [B,P,2] (label, mixup weight), obj_t uint8 [B,P]      as ct_match_batched writes them
+ *   -> sums dev [3] = (sum loc, sum cls, sum obj) UN-normalised (the caller divides by n or by its data-parallel
+ *      normaliser), num_pos dev int64 [B], n dev int64 [1] = sum of num_pos, w dev [B,P] = weight * (pos | neg),
+ *      the per-prior loss weight the backward reads.
+ * num_pos rule (:76-77): long(sum of weight over priors with label > 0); the sum is accumulated in fp64 in a fixed
+ * order, rounded once to fp32 and truncated, so it does not depend on launch geometry.
+ * Hard negatives (:88-96): num_neg = min(negpos_ratio * num_pos, P - 1) priors with the largest objectness loss (0
+ * where obj_t is set).  Tie rule: priors above the num_neg-th largest loss are drawn; priors EQUAL to it are drawn in
+ * ascending prior index until num_neg is reached (what a stable descending sort gives), zero-loss priors included.
+ * Label -1 (ignored box) rows are evaluated against class 0 and carry weight 0; the background logit is
+ * obj0 + logsumexp(conf).  Bit-reproducible from run to run; an image's selection never depends on its batch mates. */
+size_t ct_multibox_loss_workspace_bytes(int batch, int num_priors, int num_classes);
+int ct_multibox_loss_fwd(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                         const float* conf_t, const uint8_t* obj_t, int batch, int num_priors, int num_classes,
+                         int negpos_ratio, float* sums, long long* num_pos, long long* n, float* w,
+                         void* workspace, size_t workspace_bytes, ct_stream_t stream);
+/* Gradients of g[0]*sums[0] + g[1]*sums[1] + g[2]*sums[2] w.r.t. (loc, conf, obj); g dev [3], w from the forward.
+ * Every element of dloc / dconf / dobj is written (no memset needed); a row with w = 0 gets exact zeros whatever
+ * its logits. */
+int ct_multibox_loss_bwd(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                         const float* conf_t, const uint8_t* obj_t, const float* w, const float* g,
+                         int batch, int num_priors, int num_classes, float* dloc, float* dconf, float* dobj,
+                         ct_stream_t stream);
+
 /* ---------------------------------------- batched test.py post-processing ---- */
 
 /* test.py:136-161 for a batch: per (image, class>=1) select score > conf_thresh, order by
