@@ -41,6 +41,7 @@ SOURCES = {
     'ct_train.hip': [],
     'ct_box.hip': ['-ffp-contract=off'],
     'ct_loss.hip': ['-ffp-contract=off'],
+    'ct_optim.hip': ['-ffp-contract=off'],
     'ct_nms.hip': ['-ffp-contract=off'],
     'ct_post.hip': ['-ffp-contract=off'],
     'ct_cpu_nms.cpp': ['-ffp-contract=off'],

@@ -61,6 +61,11 @@ class CtxGrads(C.Structure):
                                           'fc_w', 'fc_b')]
 
 
+class SgdTensor(C.Structure):
+    _fields_ = [('param', C.c_void_p), ('grad', C.c_void_p), ('momentum_buf', C.c_void_p), ('numel', C.c_int64),
+                ('lr', C.c_float), ('weight_decay', C.c_float), ('first_step', C.c_int)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -95,6 +100,8 @@ SIGNATURES = {
     'ct_multibox_loss_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_multibox_loss_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_multibox_loss_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'ct_sgd_tensors_per_launch': (_I, []),
+    'ct_sgd_step': (_I, [C.POINTER(SgdTensor), _I, _F, _F, _I, _F, _P]),
     'ct_postprocess_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_conv_kpad': (_I, [_I, _I, _I]),

@@ -158,6 +158,31 @@ def multibox_loss_backward(loc, conf, obj, loc_t, conf_t, obj_t, w, g, num_class
     return dloc, dconf, dobj
 
 
+# ------------------------------------------------------------------ optimizer
+def sgd_table(items):
+    """ctypes table of ct_sgd_tensor for `items` = [(param, grad, momentum_buf or None, lr, weight_decay, first_step)];
+    every tensor contiguous fp32 on the HIP device (views at any element offset are fine)."""
+    table = (_lib.SgdTensor * max(len(items), 1))()
+    for i, (p, g, buf, lr, wd, first) in enumerate(items):
+        n = p.numel()
+        if g.numel() != n or (buf is not None and buf.numel() != n):
+            raise _lib.CtdetError('sgd_step: tensor %d has %d elements, its grad %d, its momentum buffer %s'
+                                  % (i, n, g.numel(), None if buf is None else buf.numel()))
+        table[i] = _lib.SgdTensor(_dev(p, 'param').value, _dev(g, 'grad').value, _opt(buf, 'momentum_buf').value, n,
+                                  lr, wd, int(bool(first)))
+    return table
+
+
+def sgd_step(items, momentum, dampening, nesterov, grad_scale=1.0):
+    """torch.optim.SGD's update of every tensor of `items` (see sgd_table) in ceil(len / ct_sgd_tensors_per_launch)
+    launches (ct_sgd_step); params and momentum buffers are updated in place, `first_step` makes buf := d."""
+    if not items:
+        return
+    table = sgd_table(items)
+    check(lib().ct_sgd_step(table, len(items), float(momentum), float(dampening), int(bool(nesterov)),
+                            float(grad_scale), _stream()), 'ct_sgd_step')
+
+
 # ------------------------------------------------------------------ NMS
 def nms_sorted_host(dets_sorted, thresh, ge=False, device_id=0, plain_iou=False):
     """The `_nms` contract (utils/nms/nms_kernel.cu:91-144): host numpy [n,dim>=4] sorted by

@@ -186,6 +186,41 @@ int ct_multibox_loss_bwd(const float* loc, const float* conf, const float* obj, 
                          int batch, int num_priors, int num_classes, float* dloc, float* dconf, float* dobj,
                          ct_stream_t stream);
 
+/* train.py `optimizer.step()` over the parameter groups of utils/solver.py:6-33 (torch.optim.SGD, one group per
+ * tensor, maximize=False): weight decay, momentum, dampening, Nesterov and the update fused into one pass over
+ * (param, grad, momentum_buf) for ALL tensors of a call (csrc/ct_optim.hip).  lr and weight_decay are per tensor (the
+ * per-name multipliers of build_optimizer and the per-iteration schedule cost nothing extra); grad_scale multiplies
+ * every gradient first (1 / world size in data-parallel training).
+ * Arithmetic, every operation rounded separately to fp32 (no FMA), (1 - dampening) computed once on the host in fp32:
+ *     g    = grad * grad_scale
+ *     d    = (weight_decay != 0) ? g + weight_decay * p : g
+ *     buf  = first_step ? d : momentum * buf + (1 - dampening) * d        (only when momentum != 0)
+ *     step = (momentum == 0) ? d : (nesterov ? d + momentum * buf : buf)
+ *     p    = p - lr * step
+ * A NumPy float32 restatement of these lines reproduces the result bit for bit.
+ * Transport and launch count: `items_host` is caller memory and is not read after the call returns -- the tensor
+ * table travels in the kernel arguments, ct_sgd_tensors_per_launch() (80) tensors per launch, with no limit on the
+ * chunks (workgroups) of a launch: a call is ceil(tensors with numel > 0 / 80) launches whatever their sizes, and none
+ * when every tensor is empty.  No allocation, no host synchronisation, asynchronous on `stream`.
+ * Pointers need only 4-byte alignment: a tensor whose pointers share their offset within a 16-byte line is moved in
+ * 16-byte accesses with a scalar first / last group, any other tensor one dword per lane; no byte outside
+ * [ptr, ptr + numel) is touched, and stores are plain vector stores.
+ * n == 0 and numel == 0 are no-ops (the pointers of an empty tensor are not looked at).  CT_ERR_INVALID (nothing
+ * launched): n < 0; numel < 0 or > 2^31-1; for a non-empty tensor a NULL param or grad, a NULL momentum_buf with
+ * momentum != 0, or a pointer that is not 4-byte aligned; nesterov with momentum == 0 or dampening != 0 (torch's own
+ * rule). */
+typedef struct ct_sgd_tensor {
+    float* param;          /* dev, updated in place                               */
+    const float* grad;     /* dev, read only, must not alias param / momentum_buf */
+    float* momentum_buf;   /* dev, NULL iff momentum == 0                         */
+    int64_t numel;         /* 0 .. 2^31-1                                         */
+    float lr, weight_decay;
+    int first_step;        /* 1: buf := d (torch's first step), 0: recurrence     */
+} ct_sgd_tensor;
+int ct_sgd_tensors_per_launch(void);
+int ct_sgd_step(const ct_sgd_tensor* items_host, int n, float momentum, float dampening,
+                int nesterov, float grad_scale, ct_stream_t stream);
+
 /* ---------------------------------------- batched test.py post-processing ---- */
 
 /* test.py:136-161 for a batch: per (image, class>=1) select score > conf_thresh, order by

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
-   python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5]"""
+   python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups]
+   --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
+   --per-tensor-groups: the groups of utils/solver.py::build_optimizer (one per tensor) instead of a single group."""
 import argparse, os, sys, time, types
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,6 +12,7 @@ ap.add_argument('--size', type=int, default=300); ap.add_argument('--batch', typ
 ap.add_argument('--classes', type=int, default=20); ap.add_argument('--steps', type=int, default=5)
 ap.add_argument('--sync', type=int, default=0)
 ap.add_argument('--phase', type=int, default=1); ap.add_argument('--setting', default='transfer')
+ap.add_argument('--fused-sgd', action='store_true'); ap.add_argument('--per-tensor-groups', action='store_true')
 a = ap.parse_args()
 from ctdet import synth, dist as cdist
 from models.RFB_Net_vgg import build_net
@@ -25,7 +28,15 @@ priors = PriorBox(getattr(cfgs, 'VOC_%d' % a.size)).forward().cuda()
 nout = a.classes if a.phase == 1 else net.OBJ_Target.weight.shape[0] + (a.classes if a.setting == 'incre' else 0)
 crit = MultiBoxLoss_combined(nout + 1, 0.5, True, 0, True, 3, 0.5, False)
 crit.sync_normalizer = world > 1
-opt = torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4)
+if a.per_tensor_groups:
+    from utils import solver
+    opt = solver.build_optimizer(types.SimpleNamespace(method='ours', phase=a.phase, lr=1e-4, momentum=0.9, weight_decay=5e-4),
+                                 net, fused=a.fused_sgd)
+elif a.fused_sgd:
+    from ctdet.optim import FusedSGD
+    opt = FusedSGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4)
+else:
+    opt = torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4)
 x = synth.images(a.batch, a.size, 'randn', 1234 + rank).cuda()
 tg = [t.cuda() for t in synth.targets(a.batch, nout + 1, 99 + rank)]
 trt = net.train_runtime(a.batch)
@@ -58,5 +69,6 @@ cdist.barrier('cuda')
 dt = cdist.max_over_ranks((time.perf_counter() - t0) / a.steps, 'cuda')
 if rank == 0:
     n = a.steps
-    print('RFBNet-%d phase %d bs=%d x %d GPU(s): %.1f ms/step = %.1f img/s | fwd %.1f  loss %.1f  bwd %.1f ms | loss %.4f'
-          % (a.size, a.phase, a.batch, world, dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
+    print('RFBNet-%d phase %d bs=%d x %d GPU(s)%s: %.1f ms/step = %.1f img/s | fwd %.1f  loss %.1f  bwd %.1f ms | loss %.4f'
+          % (a.size, a.phase, a.batch, world, ' [%s, %d groups]' % (type(opt).__name__, len(opt.param_groups))
+             if a.fused_sgd or a.per_tensor_groups else '', dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
