@@ -39,6 +39,7 @@ SOURCES = {
     'ct_attn.hip': [],
     'ct_attn_bwd.hip': [],
     'ct_train.hip': [],
+    'ct_wgrad_h2.hip': [],
     'ct_box.hip': ['-ffp-contract=off'],
     'ct_loss.hip': ['-ffp-contract=off'],
     'ct_optim.hip': ['-ffp-contract=off'],

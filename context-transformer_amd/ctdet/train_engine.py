@@ -62,6 +62,10 @@ class TrainRuntime:
         wino_ws = 0
         w4s_ws = 0              # bytes: workspace of the three-kernel Winograd data gradients
         wg4s_ws = 0             # bytes: workspace of the three-kernel Winograd weight gradients
+        wgh2_ws = 0             # bytes: workspace of the f16x2 1x1 weight gradients
+        # CTDET_WGRAD_H2=1 (opt-in, resolved once here): the 1x1 layers that otherwise fall through to ct_conv2d_wgrad run
+        # ct_conv2d_wgrad_h2 (the f16x2 GEMM of csrc/ct_wgrad_h2.hip: no atomics, bit-reproducible)
+        self.wgrad_h2 = os.environ.get('CTDET_WGRAD_H2', '0') not in ('', '0')
         # CTDET_TRAIN_WINO4=0 keeps forward and data-gradient convolutions on F(2x2,3x3) where the table says F(4x4,3x3)
         wino4 = os.environ.get('CTDET_TRAIN_WINO4', '1') != '0'
         # The Winograd launches of the step (forward and data gradients) on the f16x2 operand form (csrc/ct_f16x2.h) wherever the
@@ -232,6 +236,13 @@ class TrainRuntime:
                 s.wgrad_wino = True
                 s.wgrad_tile = 44
                 wg4s_ws = max(wg4s_ws, int(self.lib.ct_conv_wgrad_wino4s_workspace_bytes(C.byref(w))))
+            # ... where it wins (profiles/wgrad_h2_probe.txt): stride 1 on maps from 19x19 up.  The stride-2 layers (one gathered
+            # load per pixel: 1024 -> 768 @19x19 86 -> 118 us) and the maps below 19x19 (20-45 us launches, where the two
+            # maxima passes a BatchNorm layer's dZ needs cost 10 us) stay on ct_conv2d_wgrad.
+            s.wgrad_h2 = self.wgrad_h2 and not s.wgrad_wino and st.stride == 1 and st.oh * st.ow >= 361 and \
+                bool(self.lib.ct_conv_wgrad_h2_supported(C.byref(w)))
+            if s.wgrad_h2:      # one workspace (maxima lines + split-k slabs) shared by all layers: stream ordered
+                wgh2_ws = max(wgh2_ws, int(self.lib.ct_conv_wgrad_h2_workspace_bytes(C.byref(w))))
             if s.wgrad_wino:
                 size = self.lib.ct_conv_wgrad_wino4_workspace_bytes if s.wgrad_tile in (4, 44) else \
                     self.lib.ct_conv_wgrad_wino_workspace_bytes
@@ -252,6 +263,8 @@ class TrainRuntime:
         self.wgrad_ws = al((max(wino_ws // 4, 1),))
         self.dgrad_ws4s = torch.empty(max(w4s_ws, 1), device=backend.device, dtype=torch.uint8)
         self.wgrad_ws4s = torch.empty(max(wg4s_ws, 1), device=backend.device, dtype=torch.uint8)
+        if self.wgrad_h2:
+            self.wgrad_wsh2 = torch.empty(max(wgh2_ws, 1), device=backend.device, dtype=torch.uint8)
         if self.prezero:
             bn_floats = sum(t.numel() for s_ in self.state.values() for t in getattr(s_, 'scratch', []))
             self.bn_scratch = al((max(bn_floats, 1),), torch.float64)
@@ -377,6 +390,8 @@ class TrainRuntime:
             if getattr(s, 'dgrad_wino', None) is not None and FORMS[s.dgrad_tile].h2 and not s.is_bn and not st.segs:
                 s.dz_amax = be.new_slot(self.batch)
                 s.dgrad_wino.in_absmax = s.dz_amax
+            elif getattr(s, 'wgrad_h2', False) and not s.is_bn and not st.segs:
+                s.dz_amax = be.new_slot(self.batch)     # ct_bias_act_backward_amax leaves dZ's maxima for ct_conv2d_wgrad_h2
         self.amax_slots = slots
         self._wired_epoch = be.kernel_epoch
 
@@ -779,6 +794,14 @@ class TrainRuntime:
                     _lib.check(fn(C.byref(s.wgrad), s.dz.data_ptr(), ctot, 0, s.dw.data_ptr(),
                                   (s.wgrad_ws if self.prezero else self.wgrad_ws).data_ptr(), self._s()),
                                st.name + ' wgrad (winograd)')
+                elif s.wgrad_h2:
+                    # X's maxima where the forward wired a slot for this layer's input, dZ's where ct_bias_act_backward_amax
+                    # wrote them (a BatchNorm backward does not track: NULL, the entry point takes the maximum itself)
+                    s.wgrad.in_absmax = s.fwd.rt['desc'].in_absmax
+                    _lib.check(lib.ct_conv2d_wgrad_h2(C.byref(s.wgrad), s.dz.data_ptr(), ctot, 0,
+                                                      None if s.is_bn or st.segs else getattr(s, 'dz_amax', None),
+                                                      s.dw.data_ptr(), self.wgrad_wsh2.data_ptr(), self.wgrad_wsh2.numel(),
+                                                      self._s()), st.name + ' wgrad (f16x2)')
                 else:
                     _lib.check(lib.ct_conv2d_wgrad(C.byref(s.wgrad), s.dz.data_ptr(), ctot, 0, s.dw.data_ptr(),
                                                    self._s()), st.name + ' wgrad')

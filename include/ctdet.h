@@ -588,6 +588,21 @@ size_t ct_conv_wgrad_wino4s_workspace_bytes(const ct_conv_desc* d);
 int ct_conv2d_wgrad_wino4s(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
                            void* workspace, size_t workspace_bytes, ct_stream_t stream);
 
+/* The weight gradient of a 1x1 convolution (pad 0, dilation 1, stride 1 or 2) as ONE GEMM on the f16 matrix pipe in the f16x2
+ * operand form (csrc/ct_wgrad_h2.hip, csrc/ct_f16x2.h): dw[cout][cin] = sum over batch and output pixels of dz * X, fp32
+ * accumulation.  Arguments and result as ct_conv2d_wgrad; dw is OVERWRITTEN (no pre-zeroing).  The sum runs over the whole
+ * batch, so each operand is scaled by ONE power of two per launch, from the maximum over the `batch` lines of d->in_absmax
+ * (X) and dz_absmax (dZ); either may be NULL, the entry point then takes that maximum itself (a pass of ct_absmax_f32 into the
+ * workspace, which may hold anything on entry).  A bound above the true maximum is valid.  Deterministic: k is split over
+ * workgroups in a partition that depends on the descriptor alone, every split writes its own slab of the workspace and a
+ * finishing kernel adds them in order -- no atomics, two calls on the same inputs give the same bits.  The workspace holds
+ * ct_conv_wgrad_h2_workspace_bytes(d) bytes (slabs and the two maxima lines); a smaller one is CT_ERR_WORKSPACE.  Other
+ * geometries and buffers above 2 GiB: CT_ERR_UNSUPPORTED (ct_conv_wgrad_h2_supported() = 0; ct_conv2d_wgrad takes those). */
+int ct_conv_wgrad_h2_supported(const ct_conv_desc* d);
+size_t ct_conv_wgrad_h2_workspace_bytes(const ct_conv_desc* d);
+int ct_conv2d_wgrad_h2(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, const unsigned* dz_absmax, float* dw,
+                       void* workspace, size_t workspace_bytes, ct_stream_t stream);
+
 /* nn.BatchNorm2d(eps 1e-5, momentum 0.01) in training mode (models/RFB_Net_vgg.py:13,19), split in
  * three launches around the conv output z (channel slice [z_coff, z_coff+channels) of an NCHW buffer
  * with z_ctot channels; dz uses the same slicing):

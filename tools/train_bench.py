@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
-   python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups]
+   python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
    --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
+   --wgrad-h2: CTDET_WGRAD_H2=1 for this run (the 1x1 weight gradients on ct_conv2d_wgrad_h2);
    --per-tensor-groups: the groups of utils/solver.py::build_optimizer (one per tensor) instead of a single group."""
 import argparse, os, sys, time, types
 import torch
@@ -13,7 +14,10 @@ ap.add_argument('--classes', type=int, default=20); ap.add_argument('--steps', t
 ap.add_argument('--sync', type=int, default=0)
 ap.add_argument('--phase', type=int, default=1); ap.add_argument('--setting', default='transfer')
 ap.add_argument('--fused-sgd', action='store_true'); ap.add_argument('--per-tensor-groups', action='store_true')
+ap.add_argument('--wgrad-h2', action='store_true')
 a = ap.parse_args()
+if a.wgrad_h2:
+    os.environ['CTDET_WGRAD_H2'] = '1'         # read once, when the TrainRuntime is built
 from ctdet import synth, dist as cdist
 from models.RFB_Net_vgg import build_net
 from layers.functions import PriorBox
