@@ -710,7 +710,12 @@ __global__ __launch_bounds__(256) void head_grad_gather_kernel(const HeadGatherA
     }
 }
 
-inline int grid_for(long total) { return (int)std::min<long>((total + 255) / 256, 256 * 16); }
+// The element-wise kernels above walk an `unsigned idx` grid-stride loop.  `idx += gridDim.x * blockDim.x` is 32-bit
+// arithmetic: with a total within one grid stride of 2^32 the last step would wrap idx to a small value and the loop
+// would never end, so their entry points refuse totals above kMaxLoopElems (2^32 minus the largest stride grid_for gives).
+constexpr long kGridMaxBlocks = 256 * 16;
+constexpr long kMaxLoopElems = 0x100000000L - kGridMaxBlocks * 256;
+inline int grid_for(long total) { return (int)std::min<long>((total + 255) / 256, kGridMaxBlocks); }
 
 }  // namespace
 
@@ -862,7 +867,7 @@ extern "C" int ct_bn_train_apply(const float* z, const float* mean, const float*
     a.batch = batch; a.C = channels; a.HW = hw; a.y_ctot = y_ctot; a.y_coff = y_coff;
     a.res_ctot = res_ctot; a.res_coff = res_coff; a.eps = eps; a.rscale = res_scale; a.relu = relu;
     a.z_ctot = z_ctot; a.z_coff = z_coff;
-    CT_REQUIRE((long)batch * channels * hw < 0xFFFFFFFFL, "ct_bn_train_apply: more than 2^32 elements");
+    CT_REQUIRE((long)batch * channels * hw <= kMaxLoopElems, "ct_bn_train_apply: too many elements (2^32 less one grid stride at most)");
     hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for((long)batch * channels * hw)), dim3(256), 0,
                        ctdet::as_stream(stream), a);
     CT_LAUNCH_CHECK("bn_apply_kernel");
@@ -879,6 +884,7 @@ static int bn_backward_impl(int frozen, const float* dy, int dy_ctot, int dy_cof
 {
     CT_REQUIRE(dy && z && mean && var && gamma && dz && dgamma && dbeta, "ct_bn_train_backward: null pointer");
     CT_REQUIRE(!(relu || lo) || y, "ct_bn_train_backward: ReLU mask needs the forward output");
+    CT_REQUIRE((long)batch * channels * hw <= kMaxLoopElems, "ct_bn_train_backward: too many elements (2^32 less one grid stride at most)");
     BnBwdArgs a{};
     a.dy = dy; a.y = y; a.z = z; a.mean = mean; a.var = var; a.gamma = gamma; a.lo = lo;
     a.dz = dz; a.dgamma = dgamma; a.dbeta = dbeta; a.dres = dres;
@@ -967,7 +973,7 @@ extern "C" int ct_maxpool2d_bwd(const float* x, const float* dy, float* dx, long
                                 ct_stream_t stream)
 {
     CT_REQUIRE(x && dy && dx && planes > 0, "ct_maxpool2d_bwd: bad arguments");
-    CT_REQUIRE(planes * h * w < 0xFFFFFFFFL, "ct_maxpool2d_bwd: more than 2^32 elements");
+    CT_REQUIRE(planes <= kMaxLoopElems && planes * h * w <= kMaxLoopElems, "ct_maxpool2d_bwd: too many elements (2^32 less one grid stride at most)");
     if (k == 2 && stride == 2 && pad == 0 && oh <= (h + 1) / 2 && ow <= (w + 1) / 2 && planes <= 0x7FFFFFFFL) {
         hipLaunchKernelGGL(maxpool2x2_bwd_kernel, dim3((unsigned)planes), dim3(256), 0, ctdet::as_stream(stream), x,
                            dy, dx, h, w, oh, ow, accumulate);
@@ -1007,6 +1013,7 @@ extern "C" int ct_head_grad_gather(const ct_out_segment* segs, int nseg, int bat
                                    float* dz, ct_stream_t stream)
 {
     CT_REQUIRE(segs && dz && nseg >= 1 && nseg <= 3, "ct_head_grad_gather: bad arguments");
+    CT_REQUIRE((long)batch * channels * hw <= kMaxLoopElems, "ct_head_grad_gather: too many elements (2^32 less one grid stride at most)");
     HeadGatherArgs a{};
     for (int g = 0; g < nseg; ++g) a.seg[g] = segs[g];
     a.nseg = nseg; a.dz = dz; a.batch = batch; a.C = channels; a.HW = hw;

@@ -611,7 +611,12 @@ int ct_conv2d_wgrad_h2(const ct_conv_desc* d, const float* dz, int dz_ctot, int 
  *   apply    y = act( ((z-mean)/sqrt(var+eps)*gamma + beta) [* res_scale + res] ) into a channel slice
  *   backward dz, dgamma, dbeta (and the residual branch's gradient) from dy */
 /* `scratch` (both BatchNorm entry points): optional device buffer of 2*channels doubles; with it the per-channel
- * reductions are split over several workgroups per channel (f64 atomics), without it one workgroup per channel. */
+ * reductions are split over several workgroups per channel (f64 atomics), without it one workgroup per channel.
+ * A call that splits (batch*hw >= 4096 and channels < 1024) leaves its two per-channel sums in scratch ([0, channels):
+ * sum z resp. dbeta, [channels, 2*channels): sum z*z resp. dgamma, as doubles); it does NOT return scratch to zero, so
+ * under ct_scratch_prezeroed(1) the caller zeroes a scratch buffer again before every call that uses it
+ * (ctdet/train_engine.py: one buffer per layer, one memset of the arena before each pass).  A call that does not
+ * split neither reads nor writes scratch. */
 int ct_bn_train_stats(const float* z, int batch, int ctot, int coff, int channels, int hw,
                       float* mean, float* var, float momentum, float* running_mean, float* running_var,
                       void* scratch, ct_stream_t stream);
