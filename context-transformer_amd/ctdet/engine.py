@@ -1215,6 +1215,10 @@ class Runtime:
         be = self.backend
         if not hasattr(be, 'new_slot'):
             return
+        if hasattr(be, 'wire_absmax'):          # a backend with rules of its own (the bf16 path: ctdet/engine_bf16.py)
+            self.amax_slots = be.wire_absmax(self)
+            self._wired_epoch = be.kernel_epoch
+            return
         steps = self.plan.steps
 
         def tracks(st):
@@ -1357,7 +1361,9 @@ class Runtime:
             w = st.rt.get('wino')
             if w:
                 tiles[int(w)] = tiles.get(int(w), 0) + 1
+        rec = b.policy_extra(self.conv_steps()) if hasattr(b, 'policy_extra') else {}
         return {
+            **rec,
             'operand_form': 'f16x2' if getattr(b, 'h2', False) else 'bf16x3',
             'direct_twins_f16x2': bool(getattr(b, 'h2_direct', False)),
             'ctx_tiles': ctx_policy(self.net),

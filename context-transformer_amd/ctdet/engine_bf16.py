@@ -7,6 +7,14 @@ MFMA lane needs at a filter tap are one 16-byte load and `torch.cat` is still a 
 fp32 channels-last outputs exactly as the fp32 kernels do, and everything after them (softmax, decode, NMS,
 Context-Transformer block) is the unchanged fp32 code.  What models/RFB_Net_vgg.py:219-248 computes, at bf16
 activation precision: select with `net.conv_dtype = 'bf16'` (or CTDET_DTYPE=bf16) before the first forward.
+
+CTDET_BF16_WINO=1 (read once, when the backend is created; default 0 = the direct kernel everywhere, bit for bit as before):
+the 3x3 / stride 1 layers with a plain bf16 output that the measured rule below selects (WINO_MIN_CIN input channels or more, at
+most WINO_MAX_TILES tiles per launch; CTDET_BF16_WINO_MIN_CIN overrides it)
+run `ct_conv2d_bf16_wino_fwd` instead -- Winograd F(4x4,3x3) with single binary16 operands in the transform domain on the f16
+matrix pipe (csrc/ct_wino_bf16.hip), all such layers of a stream sharing one V / M workspace.  The per-image maxima the route
+scales its operands by travel from a Winograd layer to the next one (directly or through a max-pool); any other input is
+measured by the launch itself.
 """
 import ctypes as C
 import os
@@ -14,11 +22,30 @@ import os
 import torch
 
 from . import _lib
-from .engine import HipBackend
+from .engine import HipBackend, absmax_source
+
+# Which supported layers take the Winograd route when CTDET_BF16_WINO=1: the rule measured by tools/bf16_wino_probe.py
+# (profiles/bf16_wino_probe.txt, every 3x3 / stride 1 shape of RFBNet-300 bs 32 and RFBNet-512 bs 16).  The three-kernel form moves
+# 2 + 2 bytes of V and 4 + 4 of M per (tile, point, channel), so its bytes per flop grow as 1 / cin: it beats the direct kernel
+# only at 512 input channels (1.08 - 1.19x at 19 x 19 / 38 x 38 bs 32 and 32 x 32 bs 16: 800 - 3 200 tiles per launch), is 0.96x
+# at 64 x 64 bs 16 (4 096 tiles) and 0.33 - 0.92x on every narrower layer.  CTDET_BF16_WINO_MIN_CIN (the probe, experiments)
+# replaces the channel rule and lifts the tile limit.
+WINO_MIN_CIN = 512
+WINO_MAX_TILES = 3200
 
 
 class HipBackendBF16(HipBackend):
-    tune_conv = None                 # one tile shape: nothing to tune, no Winograd routing
+    tune_conv = None                 # one tile shape: nothing to tune
+
+    def __init__(self, device):
+        super().__init__(device)
+        self._read_switches()
+
+    def _read_switches(self):
+        self.bf16_wino = os.environ.get('CTDET_BF16_WINO', '0') == '1'
+        forced = os.environ.get('CTDET_BF16_WINO_MIN_CIN')
+        self.bf16_wino_min_cin = int(forced) if forced else WINO_MIN_CIN
+        self.bf16_wino_max_tiles = None if forced else WINO_MAX_TILES
 
     def alloc(self, shape, dtype=torch.float32):
         if len(shape) == 4 and dtype == torch.float32:          # (batch, C, H, W) of the plan -> NHWC bf16
@@ -84,13 +111,19 @@ class HipBackendBF16(HipBackend):
             d.ksplit, d.ksplit_ws, d.ksplit_ws_floats = -1, rt['ksws'].data_ptr(), rt['ksws'].numel()
         rt['desc'] = d
         rt['wino_ok'] = False
+        if getattr(self, 'bf16_wino', False):
+            rt['wino_ok'] = bool(lib.ct_conv_bf16_wino_supported(C.byref(d)))
+            tiles = batch * ((st.h + 3) // 4) * ((st.w + 3) // 4)
+            if rt['wino_ok'] and st.cin >= self.bf16_wino_min_cin and \
+                    (self.bf16_wino_max_tiles is None or tiles <= self.bf16_wino_max_tiles):
+                self.enable_wino(st, True)
 
     def pack_conv(self, st):
         rt, lib = st.rt, self.lib
         n = len(st.parts)
         ws = [p.weight.detach() for p in st.parts]
         for wt in ws:
-            if not (wt.is_cuda and wt.is_contiguous() and wt.dtype == torch.float32):
+            if not (wt.device.type == self.device.type and wt.is_contiguous() and wt.dtype == torch.float32):
                 raise _lib.CtdetError('%s: parameters must be contiguous fp32 on the HIP device' % st.name)
         ptrs = (C.c_void_p * n)(*[wt.data_ptr() for wt in ws])
         couts = (C.c_int * n)(*[p.cout for p in st.parts])
@@ -107,14 +140,91 @@ class HipBackendBF16(HipBackend):
             _lib.check(lib.ct_conv_fold_epilogue(*args, p.cout, off, rt['scale'].data_ptr(),
                                                  rt['shift'].data_ptr(), self._stream()), 'ct_conv_fold_epilogue')
             off += p.cout
+        if rt.get('bf16_wino'):
+            _lib.check(lib.ct_conv_pack_weights_bf16_wino(ptrs, couts, n, st.cin, rt['UW16'].data_ptr(), self._stream()),
+                       'ct_conv_pack_weights_bf16_wino')
         rt['versions'] = self.param_versions(st)
 
-    def enable_wino(self, st, on=True):
-        if on:
-            raise _lib.CtdetError('the bf16 path has no Winograd routing')
+    def enable_wino(self, st, on=True, tile=None):
+        """Route this conv through ct_conv2d_bf16_wino_fwd (CTDET_BF16_WINO=1 only) or back to the direct kernel."""
+        rt = st.rt
+        if not getattr(self, 'bf16_wino', False):
+            if on:
+                raise _lib.CtdetError('the bf16 path has no Winograd routing (CTDET_BF16_WINO=1 enables it)')
+            return
+        self.kernel_epoch += 1
+        if not on:
+            rt['bf16_wino'] = False
+            rt.pop('ws4s_bytes', None)
+            return
+        if not rt.get('wino_ok'):
+            raise _lib.CtdetError('%s: geometry has no bf16 Winograd path' % st.name)
+        if 'UW16' not in rt:
+            rt['UW16'] = torch.empty(self.lib.ct_conv_bf16_wino_packed_bytes(st.cin, st.cout), dtype=torch.uint8,
+                                     device=self.device)
+            dw = _lib.ConvDesc.from_buffer_copy(rt['desc'])      # the same launch geometry, the other weight layout
+            dw.wpacked = rt['UW16'].data_ptr()
+            dw.ksplit, dw.ksplit_ws, dw.ksplit_ws_floats = 0, None, 0
+            rt['desc_w'] = dw
+        rt['ws4s_bytes'] = self.lib.ct_conv_bf16_wino_workspace_bytes(C.byref(rt['desc_w']))
+        self.ws_reserve(rt.get('ws_key', 0), rt['ws4s_bytes'])
+        rt['bf16_wino'] = True
+        self.pack_conv(st)
+
+    def ws_rebuild(self, steps):
+        """One V / M workspace per stream of the schedule, sized for the largest Winograd layer on it."""
+        need = {}
+        for st in steps:
+            if st.rt.get('bf16_wino'):
+                k = st.rt.get('ws_key', 0)
+                need[k] = max(need.get(k, 0), st.rt['ws4s_bytes'])
+        for k in list(self.ws_pool):
+            if k not in need or self.ws_pool[k] is None or self.ws_pool[k].numel() != need[k]:
+                self._ws_drop(k)
+        for k, n in need.items():
+            if self.ws_pool.get(k) is None:
+                self.ws_pool[k] = self.alloc((n,), torch.uint8)
+
+    def wire_absmax(self, runtime):
+        """Maxima of |activation| per image (ct_conv_desc.in_absmax / out_absmax) between the Winograd launches: a buffer whose
+        ONLY writers are Winograd launches -- seen directly or through max-pool steps, whose output the input bounds -- gets a
+        slot that its writers fill and its Winograd readers scale by; every other Winograd layer measures its input itself."""
+        steps = runtime.plan.steps
+        convs = runtime.conv_steps()
+        source = absmax_source(steps, lambda w: w.kind == 'conv' and not w.segs and bool(w.rt.get('bf16_wino')))
+        for st in convs:
+            if 'desc_w' in st.rt:
+                st.rt['desc_w'].in_absmax = None
+                st.rt['desc_w'].out_absmax = None
+        slots = {}
+        self.slots_used = 0
+        for st in convs:
+            if not st.rt.get('bf16_wino'):
+                continue
+            b, ws = source(st.src)
+            if b is None:
+                continue
+            if b not in slots:
+                slots[b] = self.new_slot(runtime.batch)
+                for w in ws:
+                    w.rt['desc_w'].out_absmax = slots[b]
+            st.rt['desc_w'].in_absmax = slots[b]
+        return slots
+
+    def policy_extra(self, steps):
+        return {'bf16_wino': {'switch': 'CTDET_BF16_WINO', 'on': bool(getattr(self, 'bf16_wino', False)),
+                              'min_cin': getattr(self, 'bf16_wino_min_cin', None),
+                              'max_tiles': getattr(self, 'bf16_wino_max_tiles', None),
+                              'layers': sum(1 for st in steps if st.rt.get('bf16_wino'))}}
 
     def run_conv(self, st):
-        _lib.check(self.lib.ct_conv2d_bf16_fwd(C.byref(st.rt['desc']), self._stream()), st.name)
+        rt = st.rt
+        if rt.get('bf16_wino'):
+            ws = self.ws_pool[rt.get('ws_key', 0)]
+            _lib.check(self.lib.ct_conv2d_bf16_wino_fwd(C.byref(rt['desc_w']), ws.data_ptr(), ws.numel(), self._stream()),
+                       st.name)
+            return
+        _lib.check(self.lib.ct_conv2d_bf16_fwd(C.byref(rt['desc']), self._stream()), st.name)
 
     def run_pool(self, st, bufs, batch):
         src, dst = bufs[st.src], bufs[st.dst]

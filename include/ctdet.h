@@ -549,6 +549,33 @@ int ct_nhwc_bf16_to_nchw_f32(const void* y, int batch, int channels, int hw, int
 int ct_maxpool2d_nhwc_bf16(const void* x, void* y, int batch, int channels, int h, int w, int oh, int ow, int k,
                            int stride, int pad, ct_stream_t stream);
 
+/* Winograd F(4x4,3x3) for the bf16 channels-last path (csrc/ct_wino_bf16.hip): the wide 3x3 layers of the VGG trunk
+ * (models/RFB_Net_vgg.py:219-227) with 4x fewer multiplications than ct_conv2d_bf16_fwd.  Same storage and descriptor (bf16 NHWC
+ * `in` / `out` with channel slices, fp32 `scale` / `shift`, `relu`); `wpacked` comes from ct_conv_pack_weights_bf16_wino.  The
+ * transform-domain operands are SINGLE binary16 values on v_mfma_f32_32x32x16_f16 (eleven significant bits: bfloat16 there costs
+ * 6-8x the direct kernel's error), V scaled by one power of two per image taken from the maxima lines (ct_conv_desc.in_absmax,
+ * csrc/ct_f16x2.h), U by one per layer taken from max |g| at packing time; the output transform undoes both exactly.  Three
+ * launches: input transform (V = B^T d B as MFMA fragments), 36 GEMMs M = V U with fp32 accumulation, output transform + epilogue
+ * (rounded once to bf16).  V, M and -- when in_absmax is NULL -- the maxima lines live in the caller's workspace
+ * (ct_conv_bf16_wino_workspace_bytes(desc); launches on different streams need different workspaces).
+ *   ct_conv_bf16_wino_supported   pure host: 1 only for 3x3 / stride 1 / pad 1 / dilation 1, cin % 8 == 0, cin >= 16, oh x ow = h x w,
+ *                                 nseg == 0, res == NULL, lo == NULL.
+ *   in_absmax    NULL: the entry point takes the maxima itself (ct_absmax_bf16_nhwc into the workspace); otherwise ANY valid upper
+ *                bound per image (results stay within the mode's error bound for bounds up to 2^10 x the maximum).
+ *   out_absmax   max |y| of what the launch stores for image n (the bf16 values), folded into line n (atomic max).
+ * Any finite bf16 magnitude of the activations works (3e5 and 1e-6 alike); an all-zero image gives act(shift) exactly; an image's
+ * bits never depend on its batch mates.  The forward entry point refuses (message in ct_last_error_string) unsupported
+ * descriptors (CT_ERR_UNSUPPORTED), in / out buffers beyond 32-bit offsets (CT_ERR_UNSUPPORTED), slices that are not multiples of
+ * 8 input channels (CT_ERR_INVALID) and a short workspace (CT_ERR_WORKSPACE). */
+int ct_conv_bf16_wino_supported(const ct_conv_desc* d);
+size_t ct_conv_bf16_wino_packed_bytes(int cin, int cout);
+int ct_conv_pack_weights_bf16_wino(const float* const* w, const int* cout, int nparts, int cin, void* out, ct_stream_t stream);
+size_t ct_conv_bf16_wino_workspace_bytes(const ct_conv_desc* d);
+int ct_conv2d_bf16_wino_fwd(const ct_conv_desc* d, void* workspace, size_t workspace_bytes, ct_stream_t stream);
+/* max |x| per image over the channel slice [coff, coff + c) of an NHWC bf16 map [batch][hw][ctot]: CLEARS the `batch` lines
+ * (CT_ABSMAX_LINE_BYTES each, the bit pattern of the fp32 value of the maximum in the first word) and then fills them. */
+int ct_absmax_bf16_nhwc(const void* x, int batch, int hw, int ctot, int coff, int c, unsigned* lines, ct_stream_t stream);
+
 /* ------------------------------------------------------------ training side ---- */
 /* What `losses.backward()` (train.py:228) makes autograd/cuDNN do for the layers above.  The data
  * gradient of a convolution is ct_conv2d_fwd with desc.transposed = 1. */
