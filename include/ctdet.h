@@ -583,7 +583,9 @@ int ct_absmax_bf16_nhwc(const void* x, int batch, int hw, int ctot, int coff, in
 /* Weight gradient of the convolution described by `d` (forward geometry; d->in = the forward input
  * X, d->wpacked/scale/shift/out unused):  dw[cout][cin][kh][kw] (dense fp32, overwritten) =
  * sum over batch and output pixels of dz[n][co][oh][ow] * X[n][ci][ih][iw];  dz is the channel slice
- * [dz_coff, dz_coff+cout) of an NCHW buffer with dz_ctot channels. */
+ * [dz_coff, dz_coff+cout) of an NCHW buffer with dz_ctot channels.  "Overwritten" holds for whatever dw contains on entry
+ * (NaN included): the pixel splits add into dw after one memset inside the call.  Under ct_scratch_prezeroed(1) that
+ * memset is the caller's, and the call ADDS the gradient to what dw holds. */
 int ct_conv2d_wgrad(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
                     ct_stream_t stream);
 

@@ -70,6 +70,7 @@ def test_wino_wgrad_vs_autograd(g, variant):
     torch.cuda.synchronize()
     e_w, e_d = rel_err(dw.cpu().double(), w.grad), rel_err(dw2.cpu().double(), w.grad)
     assert e_w < tol, (g, e_w, e_d)
+    assert e_d < 1e-5, (g, e_d)             # the direct kernel on the same shape: its own bound (tests/test_gpu_conv_grad.py)
     # a second call reuses the workspace (zeroed inside) and overwrites dw
     _lib.check(getattr(lib, run)(C.byref(d), dzd.data_ptr(), zctot, zcoff, dw2.data_ptr(), ws.data_ptr(),
                                         _s()), 'wgrad wino again')
