@@ -29,6 +29,7 @@
 
 namespace {
 
+using ctdet::f16x8;
 // y = Linear(x) + x (as ctx_project_kernel), written as bf16x3 pieces in MFMA fragment order:
 //   mode 0 (theta -> Q, B operand of S^T = K Q^T): Qx[b][row][piece 3][octet 8][8]      element d at octet d/8, slot d%8
 //   mode 1 (phi -> K, A operand of S^T):           Kx[b][tile][piece][octet 8][key 32][8]
@@ -89,7 +90,6 @@ __global__ __launch_bounds__(256) void ctx_project_x3_kernel(const float* __rest
 constexpr int NPH = 2;
 constexpr int XTH_BYTES = NPH * 8 * KT * 16;       // one 32-row tile as f16x2 fragments: 8 KB
 constexpr int XQH_BYTES = NPH * 8 * 16;            // one row in the register-operand layout: 256 B
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct ProjH2Set {                                 // one projection of a launch (blockIdx.z selects)
     const float* x; const float* W; const float* bias;

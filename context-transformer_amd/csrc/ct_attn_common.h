@@ -1,11 +1,16 @@
 // Shared pieces of the Context-Transformer kernels (forward: ct_attn.hip, backward: ct_attn_bwd.hip).
 #pragma once
 #include "ct_common.h"
+#include "ct_device.h"
 #include <algorithm>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ctdet::bf16x8;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::split3;
+using ctdet::pack_hi;
 constexpr int DP = 64;      // padded feature dim
 constexpr int QW = 32;      // queries per wave
 constexpr int QB = 128;     // queries per workgroup
@@ -14,24 +19,8 @@ constexpr int KT = 32;      // keys per tile
 __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // ---- bf16x3 operand fragments (csrc/ct_conv_x3.hip has the arithmetic) ----
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int XT_BYTES = 3 * 8 * KT * 16;          // one 32-row tile of a [rows][64] operand as bf16x3 fragments: 12 KB
 constexpr int XQ_BYTES = 3 * 8 * 16;               // one row in the register-operand layout: 384 B
-
-// x = hi + mid + lo exactly (three bfloat16 pieces by truncation); returns the fp32 bit patterns whose upper halves
-// are the pieces
-__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l)
-{
-    h = __builtin_bit_cast(unsigned, x) & 0xFFFF0000u;
-    const float r1 = x - __builtin_bit_cast(float, h);
-    m = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-    l = __builtin_bit_cast(unsigned, r1 - __builtin_bit_cast(float, m));
-}
-__device__ __forceinline__ int pack_hi(unsigned e0, unsigned e1)
-{
-    return (int)__builtin_amdgcn_perm(e1, e0, 0x07060302u);
-}
 
 // element (row, feature o) of a [rows_pad][64] operand, split and stored in one of three fragment orders:
 //   mode 0  rows as the register (B) operand of a contraction over features:  [b][row][piece 3][octet 8][8]

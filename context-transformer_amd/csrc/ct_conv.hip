@@ -24,6 +24,7 @@
 // k ordering: k = ci*KH*KW + tap (the natural [cout][cin][kh][kw] order); a k-step covers
 // CPB whole input channels so the row -> (channel, tap) split is a compile-time constant.
 #include "ct_common.h"
+#include "ct_device.h"
 #include "ct_f16x2.h"
 #include <algorithm>
 #include <cmath>
@@ -34,11 +35,12 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::kMaxBufBytes;
+using ctdet::make_rsrc;
 
-constexpr int kInvalidOff = 0x7FFFFFF0;          // >= num_records of every descriptor -> loads 0
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;  // descriptors stay below 2 GiB
 
 struct ConvArgs {
     const float* in;
@@ -64,11 +66,6 @@ struct ConvArgs {
     float* ws;                      // [ksplit][M][Npix] partial sums, reduced in fixed order by conv_splitk_epilogue
     unsigned* out_amax;             // ct_conv_desc.out_absmax (per-image max |y| of what the launch stores), or null
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
 
 template <int KH, int KW, int CPB, int BM, int BN, int WAVES_M, int MINW>
 __global__ __launch_bounds__(256, MINW) void conv_igemm_f32(const ConvArgs a)

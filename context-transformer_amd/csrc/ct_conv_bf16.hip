@@ -22,6 +22,7 @@
 //   MFMAs + fragment reads alone 147 us (59 %); every KB a wave moves costs ~100 issue cycles whichever way it goes
 //   (DMA piece, or buffer_load + ds_write_b128), and a 128 x 128 tile moves 8 KB per wave per 512 MFMA cycles.
 #include "ct_common.h"
+#include "ct_device.h"
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -29,12 +30,13 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kInvalidOff = 0x7FFFFFF0;
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
+using ctdet::bf16x8;
+using ctdet::f32x4;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::kMaxBufBytes;
+using ctdet::make_rsrc;
 constexpr int KSMALL = 8;                      // cin <= 8 (the image): one k-step = 4 taps x 8 channels
 
 struct Bf16Args {
@@ -58,11 +60,6 @@ struct Bf16Args {
     int ksplit, steps_per_split;    // > 1: blockIdx.y owns k-steps [y*sps, (y+1)*sps) and writes raw sums to its slab
     float* ws;                      // [ksplit][Npix][M] fp32, reduced in order by conv_bf16_splitk_epilogue
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
 
 __device__ __forceinline__ unsigned short f2bf(float f)      // round to nearest even (torch's float -> bfloat16)
 {

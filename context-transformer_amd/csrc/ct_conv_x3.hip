@@ -25,6 +25,7 @@
 //   LDS double buffered, one barrier per k-step; the loads of step s+1 are issued before the MFMAs of step s.
 // Small maps use the same deterministic slab split-K as ct_conv2d_fwd (desc->ksplit).
 #include "ct_common.h"
+#include "ct_device.h"
 #include "ct_f16x2.h"
 #include <algorithm>
 #include <cmath>
@@ -36,13 +37,16 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using ctdet::bf16x8;
+using ctdet::f16x8;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::kMaxBufBytes;
+using ctdet::make_rsrc;
+using ctdet::split3;
+using ctdet::pack_hi;
 
-constexpr int kInvalidOff = 0x7FFFFFF0;
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
 
 struct X3Args {
     const float* in;
@@ -73,27 +77,6 @@ struct X3Args {
     const int* eW;
     unsigned* out_amax;             // ct_conv_desc.out_absmax: max |y| of what the launch stores, or null (any form)
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-
-// x = hi + mid + lo exactly (fp32 has 24 significant bits, every piece keeps the next 8 by truncation); returns
-// the three fp32 bit patterns whose upper halves are the bf16 pieces
-__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l)
-{
-    h = __builtin_bit_cast(unsigned, x) & 0xFFFF0000u;
-    const float r1 = x - __builtin_bit_cast(float, h);
-    m = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-    l = __builtin_bit_cast(unsigned, r1 - __builtin_bit_cast(float, m));
-}
-
-// upper halves of (e0, e1) -> one dword [bf16 e0 | bf16 e1 << 16]
-__device__ __forceinline__ int pack_hi(unsigned e0, unsigned e1)
-{
-    return (int)__builtin_amdgcn_perm(e1, e0, 0x07060302u);
-}
 
 // DUAL: the hi.hi products accumulate in one register block, the five small products (2^-8 .. 2^-16 of it) in a second
 //   one, added at the end -- the large accumulator then sees K / 16 roundings instead of 6 K / 16 (measured: 2.5x less

@@ -21,32 +21,29 @@
 // factors and stores: no atomics, dw is overwritten, two calls give the same bits.
 // Buffers above 2 GiB (32-bit buffer offsets) are REFUSED with a message; ct_conv2d_wgrad takes them in batch chunks.
 #include "ct_common.h"
+#include "ct_device.h"
 #include "ct_f16x2.h"
 #include <algorithm>
 
 namespace {
 
+using ctdet::f16x8;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::kMaxBufBytes;
+using ctdet::make_rsrc;
 using ctdet::h2::exponent_for;
 using ctdet::h2::kGrowthNone;
 using ctdet::h2::kLineWords;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(4))) Pix8 { float v[8]; };      // 8 pixels of a plane: two 16-byte loads
-constexpr int kInvalidOff = 0x7FFFFFF0;
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
 constexpr int BT = 128;                     // workgroup tile: BT couts x BT cins
 constexpr int GROUP = 8;                    // pixels per k group (one lane's fragment)
 constexpr int STAGE_GROUPS = 8;             // groups per stage: 64 k = 4 MFMA k steps
 constexpr int FRAG_BYTES = 1024;            // 64 lanes x 8 binary16
 constexpr int LDS_BYTES = 4 * 8 * 2 * FRAG_BYTES;      // [k16 step 4][row block 8][piece 2]
 constexpr size_t kSlabBudget = (size_t)32 << 20;       // the split count keeps the slabs of one launch below this
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
 
 struct WgradH2Args {
     const float* x;

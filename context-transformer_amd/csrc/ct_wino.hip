@@ -21,15 +21,18 @@
 //   each thread applies A^T M A for a (channel, tile) pair and the usual epilogue
 //   (*scale + shift, residual, ReLU / per-channel floor, optional fused 2x2 max-pool, NCHW or head scatter).
 #include "ct_common.h"
+#include "ct_wino_launch.h"
 #include "ct_wino_pack.h"
 #include <algorithm>
 #include <mutex>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kInvalidOff = 0x7FFFFFF0;
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
+using ctdet::f32x4;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::make_rsrc;
 constexpr int CC = 8;                       // channels per chunk
 constexpr int TB = 64;                      // tiles per workgroup
 constexpr int KB = 64;                      // output channels per workgroup
@@ -59,11 +62,6 @@ struct WinoArgs {
     ct_out_segment seg[3];
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-
 __global__ __launch_bounds__(512) void wino_f2x2_3x3_f32(const WinoArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -86,7 +84,6 @@ __global__ __launch_bounds__(512) void wino_f2x2_3x3_f32(const WinoArgs a)
     // One 16-byte buffer load per patch row (4 consecutive pixels from x0 = 2tx-1; dword aligned).  Rows outside
     // the image use the out-of-range offset (-> zeros).  The left padding column (tx == 0, x0 = -1) is handled by
     // loading from x = 0 and shifting the unpack by one; the columns right of the image are masked after the load.
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
     int voffr[4];
     bool lp, m2, m3;
     {
@@ -119,7 +116,6 @@ __global__ __launch_bounds__(512) void wino_f2x2_3x3_f32(const WinoArgs a)
         for (int i = 0; i < 4; ++i) {
             // Reinterpret the WHOLE vector before taking components: on this toolchain
             // bit_cast<float>(int_vector.y) compiles to component 0 for every lane of the vector.
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
             const f32x4 q = __builtin_bit_cast(f32x4, r[i]);
             const float vx = q.x, vy = q.y, vz = q.z, vw = q.w;
             d[i * 4 + 0] = lp ? 0.f : vx;
@@ -171,7 +167,6 @@ __global__ __launch_bounds__(512) void wino_f2x2_3x3_f32(const WinoArgs a)
     // ct_conv_pack_weights_wino in exactly that order: four coalesced 16-byte loads per lane and chunk, no LDS
     // copy, no LDS reads for A.  Per iteration c:   MFMAs of chunk c  |  U(c+1) -> the other register set  |
     // transform patch(c+1) -> V buffer (c+1)&1  |  patch(c+2) -> registers  |  barrier
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const f32x4* Ug = reinterpret_cast<const f32x4*>(a.U + (size_t)kb * a.chunks * CHUNK_FLOATS) + wave * 256 + lane;
     auto load_u = [&](int c, f32x4 (&u)[4]) {
 #pragma unroll
@@ -461,44 +456,11 @@ extern "C" int ct_conv_pack_weights_wino_dgrad(const float* const* w, const int*
     return ctdet::pack_wino_any(w, cout, nparts, cin, 1, 2, upacked, stream, "ct_conv_pack_weights_wino_dgrad");
 }
 
-extern "C" int ct_conv2d_wino_pool_fwd(const ct_conv_desc* d, const float* upacked, float* pool_out, int pool_ctot,
-                                       int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream);
-
-extern "C" int ct_conv2d_wino_fwd(const ct_conv_desc* d, const float* upacked, ct_stream_t stream)
+static int launch_wino(const ct_conv_desc* d, const float* upacked, const ctdet::PoolOut& pool, ct_stream_t stream, const char* who)
 {
-    return ct_conv2d_wino_pool_fwd(d, upacked, nullptr, 0, 0, 0, 0, 1, stream);
-}
-
-extern "C" int ct_conv2d_wino_pool_fwd(const ct_conv_desc* d, const float* upacked, float* pool_out, int pool_ctot,
-                                       int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
-{
-    CT_REQUIRE(d && upacked, "ct_conv2d_wino_fwd: null pointer");
-    CT_REQUIRE(d->in && (d->out || d->nseg > 0) && d->scale && d->shift, "ct_conv2d_wino_fwd: null tensor");
-    if (!wino_ok(d))
-        return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_wino_fwd: needs 3x3 stride 1 dilation 1 pad 1, cin %% 8 == 0 "
-                           "(got %dx%d s%d d%d p%d cin=%d nseg=%d)", d->kh, d->kw, d->stride, d->dil,
-                           d->pad_h, d->cin, d->nseg);
-    CT_REQUIRE(d->batch > 0 && d->cout > 0, "ct_conv2d_wino_fwd: bad shape");
-    CT_REQUIRE(write_full || pool_out, "ct_conv2d_wino_pool_fwd: nothing to write");
-    if (pool_out) {
-        CT_REQUIRE(pool_coff >= 0 && pool_coff + d->cout <= pool_ctot, "ct_conv2d_wino_pool_fwd: pooled output slice");
-        CT_REQUIRE((pool_oh == d->oh / 2 || pool_oh == (d->oh + 1) / 2) && (pool_ow == d->ow / 2 || pool_ow == (d->ow + 1) / 2),
-                   "ct_conv2d_wino_pool_fwd: pooled size %dx%d for a %dx%d map", pool_oh, pool_ow, d->oh, d->ow);
-    }
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "ct_conv2d_wino_fwd: input slice");
-    if (d->nseg == 0)
-        CT_REQUIRE(d->out_coff >= 0 && d->out_coff + d->cout <= d->out_ctot, "ct_conv2d_wino_fwd: output slice");
-    else {
-        CT_REQUIRE(!pool_out && write_full, "ct_conv2d_wino_fwd: pooling with segmented output");
-        for (int g = 0; g < d->nseg; ++g) CT_REQUIRE(d->seg[g].ptr, "ct_conv2d_wino_fwd: null segment");
-    }
-    CT_REQUIRE(!d->res || (d->res_coff >= 0 && d->res_coff + d->cout <= d->res_ctot), "ct_conv2d_wino_fwd: residual slice");
-    const long long img_in_bytes = (long long)d->in_ctot * d->h * d->w * 4;
-    CT_REQUIRE(img_in_bytes < kMaxBufBytes, "ct_conv2d_wino_fwd: one image exceeds 2 GiB");
-    const long long img_out_bytes = d->nseg ? 4 : (long long)d->out_ctot * d->oh * d->ow * 4;
-    const long long img_res_bytes = d->res ? (long long)d->res_ctot * d->oh * d->ow * 4 : 0;
-    CT_REQUIRE(img_out_bytes < kMaxBufBytes && img_res_bytes < kMaxBufBytes, "ct_conv2d_wino_fwd: one image exceeds 2 GiB");
-    const int max_chunk = (int)std::max<long long>(1, kMaxBufBytes / std::max(img_in_bytes, std::max(img_out_bytes, img_res_bytes)));
+    if (int rc = ctdet::wino_check_desc(d, upacked, d && wino_ok(d), who, "3x3 stride 1 dilation 1 pad 1, cin % 8 == 0")) return rc;
+    ctdet::WinoLimits lim;
+    if (int rc = ctdet::wino_check_launch(d, who, pool, &lim)) return rc;
     hipStream_t st = ctdet::as_stream(stream);
     {
         static std::once_flag once;
@@ -509,34 +471,12 @@ extern "C" int ct_conv2d_wino_pool_fwd(const ct_conv_desc* d, const float* upack
         });
         CT_HIP(attr_err);
     }
-    const int OHW = d->oh * d->ow;
-    for (int b0 = 0; b0 < d->batch; b0 += max_chunk) {
-        const int nb = std::min(max_chunk, d->batch - b0);
+    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) {
+        const int nb = std::min(lim.max_chunk, d->batch - b0);
         WinoArgs a{};
-        a.in = d->in + (size_t)b0 * d->in_ctot * d->h * d->w;
-        a.U = upacked;
-        a.scale = d->scale; a.shift = d->shift; a.lo = d->lo;
-        a.res = d->res ? d->res + (size_t)b0 * d->res_ctot * OHW : nullptr;
-        a.out = d->nseg ? nullptr : d->out + (size_t)b0 * d->out_ctot * OHW;
-        a.nseg = d->nseg;
-        for (int g = 0; g < d->nseg; ++g) {
-            a.seg[g] = d->seg[g];
-            a.seg[g].ptr += (size_t)b0 * d->seg[g].img_stride;
-        }
-        a.in_bytes = (unsigned)(img_in_bytes * nb);
-        a.out_bytes = (unsigned)(img_out_bytes * nb);
-        a.res_bytes = (unsigned)(img_res_bytes * nb);
-        a.Cin = d->cin; a.H = d->h; a.W = d->w; a.in_ctot = d->in_ctot; a.in_coff = d->in_coff;
-        a.M = d->cout; a.chunks = d->cin / CC;
-        a.TY = (d->oh + 1) / 2; a.TX = (d->ow + 1) / 2;
-        a.NT = nb * a.TY * a.TX;
+        ctdet::wino_fill(a, d, upacked, lim, pool, b0, nb, 2);
+        a.chunks = d->cin / CC;
         a.tile_blocks = (a.NT + TB - 1) / TB;
-        a.out_ctot = d->out_ctot; a.out_coff = d->out_coff;
-        a.res_ctot = d->res_ctot; a.res_coff = d->res_coff; a.res_scale = d->res_scale;
-        a.relu = d->relu;
-        a.pool_out = pool_out ? pool_out + (size_t)b0 * pool_ctot * pool_oh * pool_ow : nullptr;
-        a.pool_ctot = pool_ctot; a.pool_coff = pool_coff; a.pool_oh = pool_oh; a.pool_ow = pool_ow;
-        a.write_full = write_full;
         a.kblocks = (d->cout + KB - 1) / KB;
         // 8 XCD-local sequences of (tile block group, cout block); sequences past the last tile block exit at once
         const int groups = (a.tile_blocks + 7) / 8;
@@ -544,4 +484,15 @@ extern "C" int ct_conv2d_wino_pool_fwd(const ct_conv_desc* d, const float* upack
         CT_LAUNCH_CHECK("wino_f2x2_3x3_f32");
     }
     return CT_OK;
+}
+
+extern "C" int ct_conv2d_wino_fwd(const ct_conv_desc* d, const float* upacked, ct_stream_t stream)
+{
+    return launch_wino(d, upacked, {nullptr, 0, 0, 0, 0, 1}, stream, "ct_conv2d_wino_fwd");
+}
+
+extern "C" int ct_conv2d_wino_pool_fwd(const ct_conv_desc* d, const float* upacked, float* pool_out, int pool_ctot,
+                                       int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
+{
+    return launch_wino(d, upacked, {pool_out, pool_ctot, pool_coff, pool_oh, pool_ow, write_full}, stream, "ct_conv2d_wino_pool_fwd");
 }

@@ -25,6 +25,7 @@
 //   floor, optional fused 2x2 max-pool -- a 4x4 tile holds four pooling windows --, NCHW or head scatter).
 #include "ct_common.h"
 #include "ct_wino_pack.h"
+#include "ct_wino_launch.h"
 #include "ct_wino4_points.h"
 #include "ct_wino4_emit.h"
 #include <algorithm>
@@ -34,13 +35,13 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ctdet::f32x4;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::make_rsrc;
 typedef float f32x3 __attribute__((ext_vector_type(3)));
 typedef int i32x3 __attribute__((ext_vector_type(3)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-constexpr int kInvalidOff = 0x7FFFFFF0;
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
 constexpr int CC = 8;                       // channels per chunk
 constexpr int TB = 32;                      // tiles per workgroup
 constexpr int KB = 64;                      // output channels per workgroup
@@ -85,11 +86,6 @@ struct Wino4Args {
     int streamk;
     float* sk_ws;
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
 
 using ctdet::w4::bt6;      // x -> B^T x, m -> A^T m for the points 0, +-3/4, +-3/2, inf (ct_wino4_points.h)
 using ctdet::w4::at4;
@@ -499,36 +495,11 @@ extern "C" int ct_conv_pack_weights_wino4_dgrad(const float* const* w, const int
     return ctdet::pack_wino_any(w, cout, nparts, cin, 1, 4, upacked, stream, "ct_conv_pack_weights_wino4_dgrad");
 }
 
-extern "C" int ct_conv2d_wino4_pool_fwd(const ct_conv_desc* d, const float* upacked, float* pool_out, int pool_ctot,
-                                        int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
+static int launch_wino4(const ct_conv_desc* d, const float* upacked, const ctdet::PoolOut& pool, ct_stream_t stream, const char* who)
 {
-    CT_REQUIRE(d && upacked, "ct_conv2d_wino4_fwd: null pointer");
-    CT_REQUIRE(d->in && (d->out || d->nseg > 0) && d->scale && d->shift, "ct_conv2d_wino4_fwd: null tensor");
-    if (!wino4_ok(d))
-        return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_wino4_fwd: needs 3x3 stride 1 dilation 1 pad 1, cin %% 8 == 0 "
-                           "(got %dx%d s%d d%d p%d cin=%d nseg=%d)", d->kh, d->kw, d->stride, d->dil,
-                           d->pad_h, d->cin, d->nseg);
-    CT_REQUIRE(d->batch > 0 && d->cout > 0, "ct_conv2d_wino4_fwd: bad shape");
-    CT_REQUIRE(write_full || pool_out, "ct_conv2d_wino4_pool_fwd: nothing to write");
-    if (pool_out) {
-        CT_REQUIRE(pool_coff >= 0 && pool_coff + d->cout <= pool_ctot, "ct_conv2d_wino4_pool_fwd: pooled output slice");
-        CT_REQUIRE((pool_oh == d->oh / 2 || pool_oh == (d->oh + 1) / 2) && (pool_ow == d->ow / 2 || pool_ow == (d->ow + 1) / 2),
-                   "ct_conv2d_wino4_pool_fwd: pooled size %dx%d for a %dx%d map", pool_oh, pool_ow, d->oh, d->ow);
-    }
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "ct_conv2d_wino4_fwd: input slice");
-    if (d->nseg == 0)
-        CT_REQUIRE(d->out_coff >= 0 && d->out_coff + d->cout <= d->out_ctot, "ct_conv2d_wino4_fwd: output slice");
-    else {
-        CT_REQUIRE(!pool_out && write_full, "ct_conv2d_wino4_fwd: pooling with segmented output");
-        for (int g = 0; g < d->nseg; ++g) CT_REQUIRE(d->seg[g].ptr, "ct_conv2d_wino4_fwd: null segment");
-    }
-    CT_REQUIRE(!d->res || (d->res_coff >= 0 && d->res_coff + d->cout <= d->res_ctot), "ct_conv2d_wino4_fwd: residual slice");
-    const long long img_in_bytes = (long long)d->in_ctot * d->h * d->w * 4;
-    CT_REQUIRE(img_in_bytes < kMaxBufBytes, "ct_conv2d_wino4_fwd: one image exceeds 2 GiB");
-    const long long img_out_bytes = d->nseg ? 4 : (long long)d->out_ctot * d->oh * d->ow * 4;
-    const long long img_res_bytes = d->res ? (long long)d->res_ctot * d->oh * d->ow * 4 : 0;
-    CT_REQUIRE(img_out_bytes < kMaxBufBytes && img_res_bytes < kMaxBufBytes, "ct_conv2d_wino4_fwd: one image exceeds 2 GiB");
-    const int max_chunk = (int)std::max<long long>(1, kMaxBufBytes / std::max(img_in_bytes, std::max(img_out_bytes, img_res_bytes)));
+    if (int rc = ctdet::wino_check_desc(d, upacked, d && wino4_ok(d), who, "3x3 stride 1 dilation 1 pad 1, cin % 8 == 0")) return rc;
+    ctdet::WinoLimits lim;
+    if (int rc = ctdet::wino_check_launch(d, who, pool, &lim)) return rc;
     hipStream_t st = ctdet::as_stream(stream);
     {
         static std::once_flag once;
@@ -540,33 +511,12 @@ extern "C" int ct_conv2d_wino4_pool_fwd(const ct_conv_desc* d, const float* upac
         CT_HIP(attr_err);
     }
     const int OHW = d->oh * d->ow;
-    for (int b0 = 0; b0 < d->batch; b0 += max_chunk) {
-        const int nb = std::min(max_chunk, d->batch - b0);
+    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) {
+        const int nb = std::min(lim.max_chunk, d->batch - b0);
         Wino4Args a{};
-        a.in = d->in + (size_t)b0 * d->in_ctot * d->h * d->w;
-        a.U = upacked;
-        a.scale = d->scale; a.shift = d->shift; a.lo = d->lo;
-        a.res = d->res ? d->res + (size_t)b0 * d->res_ctot * OHW : nullptr;
-        a.out = d->nseg ? nullptr : d->out + (size_t)b0 * d->out_ctot * OHW;
-        a.nseg = d->nseg;
-        for (int g = 0; g < d->nseg; ++g) {
-            a.seg[g] = d->seg[g];
-            a.seg[g].ptr += (size_t)b0 * d->seg[g].img_stride;
-        }
-        a.in_bytes = (unsigned)(img_in_bytes * nb);
-        a.out_bytes = (unsigned)(img_out_bytes * nb);
-        a.res_bytes = (unsigned)(img_res_bytes * nb);
-        a.Cin = d->cin; a.H = d->h; a.W = d->w; a.in_ctot = d->in_ctot; a.in_coff = d->in_coff;
-        a.M = d->cout; a.chunks = d->cin / CC;
-        a.TY = (d->oh + 3) / 4; a.TX = (d->ow + 3) / 4;
-        a.NT = nb * a.TY * a.TX;
+        ctdet::wino_fill(a, d, upacked, lim, pool, b0, nb, 4);
+        a.chunks = d->cin / CC;
         a.tile_blocks = (a.NT + TB - 1) / TB;
-        a.out_ctot = d->out_ctot; a.out_coff = d->out_coff;
-        a.res_ctot = d->res_ctot; a.res_coff = d->res_coff; a.res_scale = d->res_scale;
-        a.relu = d->relu;
-        a.pool_out = pool_out ? pool_out + (size_t)b0 * pool_ctot * pool_oh * pool_ow : nullptr;
-        a.pool_ctot = pool_ctot; a.pool_coff = pool_coff; a.pool_oh = pool_oh; a.pool_ow = pool_ow;
-        a.write_full = write_full;
         a.kblocks = (d->cout + KB - 1) / KB;
         // split over input channels when the (tile block, cout block) grid cannot fill the chip (desc->ksplit: -1 auto,
         // > 1 forced, else off; needs the caller's slab workspace and an unchunked, unpooled launch)
@@ -574,7 +524,7 @@ extern "C" int ct_conv2d_wino4_pool_fwd(const ct_conv_desc* d, const float* upac
         a.chunks_per_slice = a.chunks;
         a.Npix = nb * OHW;
         a.ws = nullptr;
-        if (d->ksplit_ws && nb == d->batch && !pool_out && (d->ksplit == -1 || d->ksplit == -2 || d->ksplit > 1)) {
+        if (d->ksplit_ws && nb == d->batch && !pool.pool_out && (d->ksplit == -1 || d->ksplit == -2 || d->ksplit > 1)) {
             static const int target = getenv("CTDET_W4_SPLIT_TARGET") ? atoi(getenv("CTDET_W4_SPLIT_TARGET")) : 256;
             const int wgs = a.tile_blocks * a.kblocks;
             int want = d->ksplit > 1 ? d->ksplit : target / std::max(wgs, 1);      // auto: at most one workgroup per CU in total
@@ -625,7 +575,13 @@ extern "C" int ct_conv2d_wino4_pool_fwd(const ct_conv_desc* d, const float* upac
     return CT_OK;
 }
 
+extern "C" int ct_conv2d_wino4_pool_fwd(const ct_conv_desc* d, const float* upacked, float* pool_out, int pool_ctot,
+                                        int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
+{
+    return launch_wino4(d, upacked, {pool_out, pool_ctot, pool_coff, pool_oh, pool_ow, write_full}, stream, "ct_conv2d_wino4_pool_fwd");
+}
+
 extern "C" int ct_conv2d_wino4_fwd(const ct_conv_desc* d, const float* upacked, ct_stream_t stream)
 {
-    return ct_conv2d_wino4_pool_fwd(d, upacked, nullptr, 0, 0, 0, 0, 1, stream);
+    return launch_wino4(d, upacked, {nullptr, 0, 0, 0, 0, 1}, stream, "ct_conv2d_wino4_fwd");
 }

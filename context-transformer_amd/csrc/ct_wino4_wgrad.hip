@@ -27,6 +27,7 @@
 // Tile ranges are split over blockIdx.y; partial sums meet in the workspace dU[36][cout][cin] through f32 atomics, and
 // wino4_wgrad_finish applies G^T . G per (k, c) into the dense dw[cout][cin][3][3].
 #include "ct_common.h"
+#include "ct_device.h"
 #include "ct_wino4_points.h"
 #include <algorithm>
 #include <cstdlib>
@@ -34,13 +35,14 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ctdet::f32x4;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::kMaxBufBytes;
+using ctdet::make_rsrc;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
-constexpr int kInvalidOff = 0x7FFFFFF0;
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
 constexpr int TT = 8;                        // tiles per chunk
 constexpr int CB = 32;                       // channels per block side
 constexpr int XS = CB * 8;                   // floats per transform point and operand: [channel 32][parity 2][pair 4]
@@ -55,11 +57,6 @@ struct W4WArgs {
     int Cin, Cout, H, W, x_ctot, x_coff, dz_ctot, dz_coff;
     int TY, TX, NT, chunks, chunks_per_split, cblocks;
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
 
 using ctdet::w4::bt6;      // x -> B^T x, e -> A e, u -> G^T u for the points 0, +-3/4, +-3/2, inf (ct_wino4_points.h)
 using ctdet::w4::a6;

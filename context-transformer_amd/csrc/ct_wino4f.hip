@@ -27,6 +27,7 @@
 // One accumulator per output, piece products smallest first: with cin <= 256 the large sum sees cin / 16 * 6 roundings
 // (the fp32 MFMA: cin), measured in tests/test_gpu_wino.py::test_wino_rounding_error_vs_fp64.
 #include "ct_common.h"
+#include "ct_wino_launch.h"
 #include "ct_wino_pack.h"
 #include "ct_wino4_points.h"
 #include "ct_wino4_emit.h"
@@ -38,13 +39,16 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kInvalidOff = 0x7FFFFFF0;
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
+using ctdet::bf16x8;
+using ctdet::f16x8;
+using ctdet::f32x4;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::kMaxBufBytes;
+using ctdet::make_rsrc;
+using ctdet::split3;
+using ctdet::pack_hi;
 constexpr int CC = ctdet::kWinoX3CC;        // 16 channels per chunk = one MFMA k-group
 constexpr int TB = 32;                      // tiles per workgroup
 constexpr int KB = ctdet::kWinoKB;          // 64 output channels per workgroup
@@ -117,27 +121,8 @@ struct EpiArgs {
     ct_out_segment seg[3];
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-
 using ctdet::w4::bt6;
 using ctdet::w4::at4;
-
-// x = hi + mid + lo exactly (3 x 8 significant bits by truncation); the upper halves of the three words are the pieces
-__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l)
-{
-    h = __builtin_bit_cast(unsigned, x) & 0xFFFF0000u;
-    const float r1 = x - __builtin_bit_cast(float, h);
-    m = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-    l = __builtin_bit_cast(unsigned, r1 - __builtin_bit_cast(float, m));
-}
-
-__device__ __forceinline__ int pack_hi(unsigned e0, unsigned e1)      // [bf16 e0 | bf16 e1 << 16]
-{
-    return (int)__builtin_amdgcn_perm(e1, e0, 0x07060302u);
-}
 
 // Measurement build only (CTDET_EXTRA_FLAGS=-DCTDET_W4F_TRACE, tools/w4f_trace.py): wave 0 of every workgroup stamps the
 // 100 MHz real-time counter (s_memrealtime: the shader clock counters of different XCDs are unrelated) at its phase boundaries into ct_wino4f_trace_buffer()[workgroup][8].
@@ -613,58 +598,18 @@ extern "C" int ct_conv_pack_weights_wino4f_h2_dgrad(const float* const* w, const
     return ctdet::pack_wino_h2(w, cout, nparts, cin, 1, 48, upacked, stream, "ct_conv_pack_weights_wino4f_h2_dgrad");
 }
 
-static int wino4f_launch(const ct_conv_desc* d, const void* upacked, int variant, float* pool_out, int pool_ctot,
-                         int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream);
-
-extern "C" int ct_conv2d_wino4f_pool_fwd(const ct_conv_desc* d, const void* upacked, float* pool_out, int pool_ctot,
-                                         int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
+static int wino4f_launch(const ct_conv_desc* d, const void* upacked, int variant, const ctdet::PoolOut& pool, ct_stream_t stream,
+                         const char* who)
 {
-    return wino4f_launch(d, upacked, 1, pool_out, pool_ctot, pool_coff, pool_oh, pool_ow, write_full, stream);
-}
-
-extern "C" int ct_conv2d_wino4f_pool_fwd_v(const ct_conv_desc* d, const void* upacked, int variant, float* pool_out, int pool_ctot,
-                                           int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
-{
-    return wino4f_launch(d, upacked, variant, pool_out, pool_ctot, pool_coff, pool_oh, pool_ow, write_full, stream);
-}
-
-static int wino4f_launch(const ct_conv_desc* d, const void* upacked, int variant, float* pool_out, int pool_ctot,
-                         int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
-{
-    const char* who = "ct_conv2d_wino4f_fwd";
     CT_REQUIRE(variant == 1 || variant == 2, "%s: variant %d (1 = bf16x3, 2 = f16x2)", who, variant);
     const bool h2 = variant == 2;
     CT_REQUIRE(!h2 || (d && d->in_absmax), "%s: the f16x2 form needs the maximum of |input| (ct_conv_desc.in_absmax: the producer's "
                "out_absmax slot, or ct_absmax_f32)", who);
-    CT_REQUIRE(d && upacked, "%s: null pointer", who);
-    CT_REQUIRE(d->in && (d->out || d->nseg > 0) && d->scale && d->shift, "%s: null tensor", who);
-    if (!wino4f_ok(d))
-        return ctdet::fail(CT_ERR_UNSUPPORTED, "%s: needs 3x3 stride 1 dilation 1 pad 1, cin %% 16 == 0 "
-                           "(got %dx%d s%d d%d p%d cin=%d nseg=%d)", who, d->kh, d->kw, d->stride, d->dil,
-                           d->pad_h, d->cin, d->nseg);
-    CT_REQUIRE(d->batch > 0 && d->cout > 0, "%s: bad shape", who);
-    CT_REQUIRE(write_full || pool_out, "%s: nothing to write", who);
-    if (pool_out) {
-        CT_REQUIRE(pool_coff >= 0 && pool_coff + d->cout <= pool_ctot, "%s: pooled output slice", who);
-        CT_REQUIRE((pool_oh == d->oh / 2 || pool_oh == (d->oh + 1) / 2) && (pool_ow == d->ow / 2 || pool_ow == (d->ow + 1) / 2),
-                   "%s: pooled size %dx%d for a %dx%d map", who, pool_oh, pool_ow, d->oh, d->ow);
-    }
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "%s: input slice", who);
-    if (d->nseg == 0)
-        CT_REQUIRE(d->out_coff >= 0 && d->out_coff + d->cout <= d->out_ctot, "%s: output slice", who);
-    else {
-        CT_REQUIRE(!pool_out && write_full, "%s: pooling with segmented output", who);
-        for (int g = 0; g < d->nseg; ++g) CT_REQUIRE(d->seg[g].ptr, "%s: null segment", who);
-    }
-    CT_REQUIRE(!d->res || (d->res_coff >= 0 && d->res_coff + d->cout <= d->res_ctot), "%s: residual slice", who);
-    const long long img_in_bytes = (long long)d->in_ctot * d->h * d->w * 4;
-    CT_REQUIRE(img_in_bytes < kMaxBufBytes, "%s: one image exceeds 2 GiB", who);
-    const long long img_out_bytes = d->nseg ? 4 : (long long)d->out_ctot * d->oh * d->ow * 4;
-    const long long img_res_bytes = d->res ? (long long)d->res_ctot * d->oh * d->ow * 4 : 0;
-    CT_REQUIRE(img_out_bytes < kMaxBufBytes && img_res_bytes < kMaxBufBytes, "%s: one image exceeds 2 GiB", who);
+    if (int rc = ctdet::wino_check_desc(d, upacked, d && wino4f_ok(d), who, "3x3 stride 1 dilation 1 pad 1, cin % 16 == 0")) return rc;
+    ctdet::WinoLimits lim;
+    if (int rc = ctdet::wino_check_launch(d, who, pool, &lim)) return rc;
     const size_t u_bytes = h2 ? ctdet::wino_h2_trailer_offset(d->cin, d->cout, 48) : ct_conv_wino4f_packed_bytes(d->cin, d->cout);
     CT_REQUIRE(u_bytes < (size_t)kMaxBufBytes, "%s: packed weights exceed 2 GiB", who);
-    const int max_chunk = (int)std::max<long long>(1, kMaxBufBytes / std::max(img_in_bytes, std::max(img_out_bytes, img_res_bytes)));
     hipStream_t st = ctdet::as_stream(stream);
     {
         static std::once_flag once;
@@ -678,35 +623,13 @@ static int wino4f_launch(const ct_conv_desc* d, const void* upacked, int variant
         });
         CT_HIP(attr_err);
     }
-    const int OHW = d->oh * d->ow;
-    for (int b0 = 0; b0 < d->batch; b0 += max_chunk) {
-        const int nb = std::min(max_chunk, d->batch - b0);
+    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) {
+        const int nb = std::min(lim.max_chunk, d->batch - b0);
         Wino4fArgs a{};
-        a.in = d->in + (size_t)b0 * d->in_ctot * d->h * d->w;
-        a.U = static_cast<const unsigned char*>(upacked);
+        ctdet::wino_fill(a, d, upacked, lim, pool, b0, nb, 4);
         a.u_bytes = (unsigned)u_bytes;
-        a.scale = d->scale; a.shift = d->shift; a.lo = d->lo;
-        a.res = d->res ? d->res + (size_t)b0 * d->res_ctot * OHW : nullptr;
-        a.out = d->nseg ? nullptr : d->out + (size_t)b0 * d->out_ctot * OHW;
-        a.nseg = d->nseg;
-        for (int g = 0; g < d->nseg; ++g) {
-            a.seg[g] = d->seg[g];
-            a.seg[g].ptr += (size_t)b0 * d->seg[g].img_stride;
-        }
-        a.in_bytes = (unsigned)(img_in_bytes * nb);
-        a.out_bytes = (unsigned)(img_out_bytes * nb);
-        a.res_bytes = (unsigned)(img_res_bytes * nb);
-        a.Cin = d->cin; a.H = d->h; a.W = d->w; a.in_ctot = d->in_ctot; a.in_coff = d->in_coff;
-        a.M = d->cout; a.chunks = d->cin / CC;
-        a.TY = (d->oh + 3) / 4; a.TX = (d->ow + 3) / 4;
-        a.NT = nb * a.TY * a.TX;
+        a.chunks = d->cin / CC;
         a.tile_blocks = (a.NT + TB - 1) / TB;
-        a.out_ctot = d->out_ctot; a.out_coff = d->out_coff;
-        a.res_ctot = d->res_ctot; a.res_coff = d->res_coff; a.res_scale = d->res_scale;
-        a.relu = d->relu;
-        a.pool_out = pool_out ? pool_out + (size_t)b0 * pool_ctot * pool_oh * pool_ow : nullptr;
-        a.pool_ctot = pool_ctot; a.pool_coff = pool_coff; a.pool_oh = pool_oh; a.pool_ow = pool_ow;
-        a.write_full = write_full;
         a.in_amax = d->in_absmax ? d->in_absmax + (size_t)b0 * ctdet::h2::kLineWords : nullptr;
         a.out_amax = d->out_absmax ? d->out_absmax + (size_t)b0 * ctdet::h2::kLineWords : nullptr;
         a.eU = h2 ? reinterpret_cast<const int*>(static_cast<const unsigned char*>(upacked) + u_bytes) + 1 : nullptr;
@@ -737,7 +660,20 @@ static int wino4f_launch(const ct_conv_desc* d, const void* upacked, int variant
     return CT_OK;
 }
 
+extern "C" int ct_conv2d_wino4f_pool_fwd(const ct_conv_desc* d, const void* upacked, float* pool_out, int pool_ctot,
+                                         int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
+{
+    return wino4f_launch(d, upacked, 1, {pool_out, pool_ctot, pool_coff, pool_oh, pool_ow, write_full}, stream, "ct_conv2d_wino4f_pool_fwd");
+}
+
+extern "C" int ct_conv2d_wino4f_pool_fwd_v(const ct_conv_desc* d, const void* upacked, int variant, float* pool_out, int pool_ctot,
+                                           int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
+{
+    return wino4f_launch(d, upacked, variant, {pool_out, pool_ctot, pool_coff, pool_oh, pool_ow, write_full}, stream,
+                         "ct_conv2d_wino4f_pool_fwd_v");
+}
+
 extern "C" int ct_conv2d_wino4f_fwd(const ct_conv_desc* d, const void* upacked, ct_stream_t stream)
 {
-    return ct_conv2d_wino4f_pool_fwd(d, upacked, nullptr, 0, 0, 0, 0, 1, stream);
+    return wino4f_launch(d, upacked, 1, {nullptr, 0, 0, 0, 0, 1}, stream, "ct_conv2d_wino4f_fwd");
 }

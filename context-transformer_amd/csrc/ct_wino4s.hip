@@ -24,6 +24,7 @@
 // form is for layers with >= 256 channels on maps up to 75 x 75; the fused kernels keep the rest.
 #include "ct_common.h"
 #include <type_traits>
+#include "ct_wino_launch.h"
 #include "ct_wino_pack.h"
 #include "ct_wino4_points.h"
 #include "ct_wino4_emit.h"
@@ -35,14 +36,18 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ctdet::bf16x8;
+using ctdet::f16x8;
+using ctdet::f32x4;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::kMaxBufBytes;
+using ctdet::make_rsrc;
+using ctdet::split3;
+using ctdet::pack_hi;
 typedef float f32x3 __attribute__((ext_vector_type(3)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x3 __attribute__((ext_vector_type(3)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int kInvalidOff = 0x7FFFFFF0;
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
 constexpr int CC = 16;                      // input channels per k-step (one bf16 MFMA k-group)
 constexpr int TB = 32;                      // tiles per transform workgroup = one operand fragment
 constexpr int NXI = 36;                     // transform points
@@ -56,7 +61,6 @@ constexpr int PT_STRIDE = CC * TB;          // wino4s_in: floats per point in LD
 constexpr int IN_LDS_BYTES = NXI * PT_STRIDE * 4;      // 72 KB
 // The f16x2 operand form (variant 3, round 6): two binary16 pieces per value instead of three bfloat16 ones, three piece
 // products instead of six (see the section "f16x2" below)
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int HP = 2;                                  // pieces per value
@@ -111,27 +115,8 @@ struct GemmArgs {
     int rows, cols;              // live rows (couts) / columns (tiles): 32 x 32 accumulator blocks wholly outside issue no MFMAs
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-
 using ctdet::w4::bt6;
 using ctdet::w4::at4;
-
-// x = hi + mid + lo exactly (3 x 8 significant bits by truncation); the upper halves of the three words are the pieces
-__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l)
-{
-    h = __builtin_bit_cast(unsigned, x) & 0xFFFF0000u;
-    const float r1 = x - __builtin_bit_cast(float, h);
-    m = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-    l = __builtin_bit_cast(unsigned, r1 - __builtin_bit_cast(float, m));
-}
-
-__device__ __forceinline__ int pack_hi(unsigned e0, unsigned e1)      // [bf16 e0 | bf16 e1 << 16]
-{
-    return (int)__builtin_amdgcn_perm(e1, e0, 0x07060302u);
-}
 
 // The operand fragments of eight channels of one (point, 32-tile block): bf16x3 = three 16-byte pieces (hi, mid, lo by
 // truncation), f16x2 = two (hi, lo by rounding) of the values scaled by vscale = 2^eV.
@@ -1381,47 +1366,25 @@ extern "C" int ct_conv_pack_weights_wino4s_dgrad(const float* const* w, const in
     return ctdet::pack_wino_any(w, cout, nparts, cin, 1, 44, (float*)upacked, stream, "ct_conv_pack_weights_wino4s_dgrad");
 }
 
-extern "C" int ct_conv2d_wino4s_pool_fwd(const ct_conv_desc* d, const void* upacked, void* workspace,
-                                         size_t workspace_bytes, int variant, float* pool_out, int pool_ctot,
-                                         int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
+static int launch_wino4s(const ct_conv_desc* d, const void* upacked, void* workspace, size_t workspace_bytes, int variant,
+                         const ctdet::PoolOut& pool, ct_stream_t stream, const char* who)
 {
-    CT_REQUIRE(d && upacked && workspace, "ct_conv2d_wino4s_fwd: null pointer");
-    CT_REQUIRE(d->in && (d->out || d->nseg > 0) && d->scale && d->shift, "ct_conv2d_wino4s_fwd: null tensor");
-    if (!wino4s_ok(d))
-        return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_wino4s_fwd: needs 3x3 stride 1 pad = dilation (dilated: plain NCHW output), cin %% 16 == 0 "
-                           "(got %dx%d s%d d%d p%d cin=%d nseg=%d)", d->kh, d->kw, d->stride, d->dil,
-                           d->pad_h, d->cin, d->nseg);
-    CT_REQUIRE(variant == 1 || variant == 3, "ct_conv2d_wino4s_fwd: variant %d (1 = bf16x3, 3 = f16x2; both with two accumulators -- the one-accumulator "
-               "variant 2 of rounds 4-5 was removed)", variant);
+    if (int rc = ctdet::wino_check_desc(d, upacked && workspace, d && wino4s_ok(d), who,
+                                        "3x3 stride 1 pad = dilation (dilated: plain NCHW output), cin % 16 == 0"))
+        return rc;
+    CT_REQUIRE(variant == 1 || variant == 3, "%s: variant %d (1 = bf16x3, 3 = f16x2; both with two accumulators -- the one-accumulator "
+               "variant 2 of rounds 4-5 was removed)", who, variant);
     const bool h2 = variant == 3;
-    CT_REQUIRE(d->batch > 0 && d->cout > 0, "ct_conv2d_wino4s_fwd: bad shape");
-    CT_REQUIRE(write_full || pool_out, "ct_conv2d_wino4s_pool_fwd: nothing to write");
-    CT_REQUIRE(d->dil == 1 || !pool_out, "ct_conv2d_wino4s_pool_fwd: fused pooling on a dilated layer");
-    if (pool_out) {
-        CT_REQUIRE(pool_coff >= 0 && pool_coff + d->cout <= pool_ctot, "ct_conv2d_wino4s_pool_fwd: pooled output slice");
-        CT_REQUIRE((pool_oh == d->oh / 2 || pool_oh == (d->oh + 1) / 2) && (pool_ow == d->ow / 2 || pool_ow == (d->ow + 1) / 2),
-                   "ct_conv2d_wino4s_pool_fwd: pooled size %dx%d for a %dx%d map", pool_oh, pool_ow, d->oh, d->ow);
-    }
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "ct_conv2d_wino4s_fwd: input slice");
-    if (d->nseg == 0)
-        CT_REQUIRE(d->out_coff >= 0 && d->out_coff + d->cout <= d->out_ctot, "ct_conv2d_wino4s_fwd: output slice");
-    else {
-        CT_REQUIRE(!pool_out && write_full, "ct_conv2d_wino4s_fwd: pooling with segmented output");
-        for (int g = 0; g < d->nseg; ++g) CT_REQUIRE(d->seg[g].ptr, "ct_conv2d_wino4s_fwd: null segment");
-    }
-    CT_REQUIRE(!d->res || (d->res_coff >= 0 && d->res_coff + d->cout <= d->res_ctot), "ct_conv2d_wino4s_fwd: residual slice");
-    const long long img_in_bytes = (long long)d->in_ctot * d->h * d->w * 4;
-    CT_REQUIRE(img_in_bytes < kMaxBufBytes, "ct_conv2d_wino4s_fwd: one image exceeds 2 GiB");
-    const long long img_out_bytes = d->nseg ? 4 : (long long)d->out_ctot * d->oh * d->ow * 4;
-    const long long img_res_bytes = d->res ? (long long)d->res_ctot * d->oh * d->ow * 4 : 0;
-    CT_REQUIRE(img_out_bytes < kMaxBufBytes && img_res_bytes < kMaxBufBytes, "ct_conv2d_wino4s_fwd: one image exceeds 2 GiB");
-    const int max_chunk = (int)std::max<long long>(1, kMaxBufBytes / std::max(img_in_bytes, std::max(img_out_bytes, img_res_bytes)));
+    CT_REQUIRE(d->dil == 1 || !pool.pool_out, "%s: fused pooling on a dilated layer", who);
+    ctdet::WinoLimits lim;
+    if (int rc = ctdet::wino_check_launch(d, who, pool, &lim)) return rc;
+    const int max_chunk = lim.max_chunk;
     const size_t hdr_bytes = h2 ? ctdet::align_up((size_t)std::min(d->batch, max_chunk) * LINE_BYTES, 256) : 0;
     {
         const Sizes s = sizes_of(std::min(d->batch, max_chunk), d->oh, d->ow, d->cin, d->cout, d->dil, h2 ? OPBH : OPB);
-        CT_REQUIRE(workspace_bytes >= hdr_bytes + s.v_bytes + s.m_bytes, "ct_conv2d_wino4s_fwd: workspace of %zu bytes, needs %zu "
-                   "(ct_conv_wino4s_workspace_bytes)", workspace_bytes, hdr_bytes + s.v_bytes + s.m_bytes);
-        CT_REQUIRE((size_t)s.chunks * OPB < (size_t)kMaxBufBytes, "ct_conv2d_wino4s_fwd: too many input channels");
+        CT_REQUIRE(workspace_bytes >= hdr_bytes + s.v_bytes + s.m_bytes, "%s: workspace of %zu bytes, needs %zu "
+                   "(ct_conv_wino4s_workspace_bytes)", who, workspace_bytes, hdr_bytes + s.v_bytes + s.m_bytes);
+        CT_REQUIRE((size_t)s.chunks * OPB < (size_t)kMaxBufBytes, "%s: too many input channels", who);
     }
     hipStream_t st = ctdet::as_stream(stream);
     {
@@ -1441,34 +1404,14 @@ extern "C" int ct_conv2d_wino4s_pool_fwd(const ct_conv_desc* d, const void* upac
     }
     // f16x2: k-groups per barrier / ring depth of the GEMM pipeline (measurement switch; default below)
     static const int h2_pipe = [] { const char* e = std::getenv("CTDET_W4H_PIPE"); return e ? std::atoi(e) : 22; }();
-    const int OHW = d->oh * d->ow;
     for (int b0 = 0; b0 < d->batch; b0 += max_chunk) {
         const int nb = std::min(max_chunk, d->batch - b0);
         const Sizes s = sizes_of(nb, d->oh, d->ow, d->cin, d->cout, d->dil, h2 ? OPBH : OPB);
         Wino4sArgs a{};
-        a.in = d->in + (size_t)b0 * d->in_ctot * d->h * d->w;
-        a.U = static_cast<const unsigned short*>(upacked);
-        a.scale = d->scale; a.shift = d->shift; a.lo = d->lo;
-        a.res = d->res ? d->res + (size_t)b0 * d->res_ctot * OHW : nullptr;
-        a.out = d->nseg ? nullptr : d->out + (size_t)b0 * d->out_ctot * OHW;
-        a.nseg = d->nseg;
-        for (int g = 0; g < d->nseg; ++g) {
-            a.seg[g] = d->seg[g];
-            a.seg[g].ptr += (size_t)b0 * d->seg[g].img_stride;
-        }
-        a.in_bytes = (unsigned)(img_in_bytes * nb);
-        a.out_bytes = (unsigned)(img_out_bytes * nb);
-        a.res_bytes = (unsigned)(img_res_bytes * nb);
-        a.Cin = d->cin; a.H = d->h; a.W = d->w; a.in_ctot = d->in_ctot; a.in_coff = d->in_coff;
-        a.M = d->cout; a.chunks = s.chunks; a.kblocks = s.kblocks;
+        ctdet::wino_fill(a, d, upacked, lim, pool, b0, nb, 0);
+        a.chunks = s.chunks; a.kblocks = s.kblocks;
         a.TY = s.TY; a.TX = s.TX; a.NT = s.NT; a.Tpad = s.Tpad;
         a.tblk32 = s.Tpad / TB; a.tblk128 = s.Tpad / BT;
-        a.out_ctot = d->out_ctot; a.out_coff = d->out_coff;
-        a.res_ctot = d->res_ctot; a.res_coff = d->res_coff; a.res_scale = d->res_scale;
-        a.relu = d->relu;
-        a.pool_out = pool_out ? pool_out + (size_t)b0 * pool_ctot * pool_oh * pool_ow : nullptr;
-        a.pool_ctot = pool_ctot; a.pool_coff = pool_coff; a.pool_oh = pool_oh; a.pool_ow = pool_ow;
-        a.write_full = write_full;
         a.dil = d->dil;
         a.V = reinterpret_cast<unsigned short*>(static_cast<unsigned char*>(workspace) + hdr_bytes);
         a.Mw = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + hdr_bytes + s.v_bytes);
@@ -1537,10 +1480,18 @@ extern "C" int ct_conv2d_wino4s_pool_fwd(const ct_conv_desc* d, const void* upac
     return CT_OK;
 }
 
+extern "C" int ct_conv2d_wino4s_pool_fwd(const ct_conv_desc* d, const void* upacked, void* workspace,
+                                         size_t workspace_bytes, int variant, float* pool_out, int pool_ctot,
+                                         int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream)
+{
+    return launch_wino4s(d, upacked, workspace, workspace_bytes, variant, {pool_out, pool_ctot, pool_coff, pool_oh, pool_ow, write_full},
+                         stream, "ct_conv2d_wino4s_pool_fwd");
+}
+
 extern "C" int ct_conv2d_wino4s_fwd(const ct_conv_desc* d, const void* upacked, void* workspace, size_t workspace_bytes,
                                     int variant, ct_stream_t stream)
 {
-    return ct_conv2d_wino4s_pool_fwd(d, upacked, workspace, workspace_bytes, variant, nullptr, 0, 0, 0, 0, 1, stream);
+    return launch_wino4s(d, upacked, workspace, workspace_bytes, variant, {nullptr, 0, 0, 0, 0, 1}, stream, "ct_conv2d_wino4s_fwd");
 }
 
 extern "C" int ct_conv_wgrad_wino4s_supported(const ct_conv_desc* d) { return d && wino4s_wg_ok(d) ? 1 : 0; }

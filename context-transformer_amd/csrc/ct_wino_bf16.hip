@@ -21,22 +21,24 @@
 //            rne to bf16, stored into the channel slice; max |y| of what it stores folded per image into out_absmax.
 // An image's result does not depend on its batch mates: its exponent is its own, and a tile's sums run over k in one order.
 #include "ct_common.h"
+#include "ct_device.h"
 #include "ct_f16x2.h"
 #include "ct_wino4_points.h"
 #include <algorithm>
 
 namespace {
 
+using ctdet::f16x8;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kMaxBufBytes;
 using ctdet::h2::exponent_for;
 using ctdet::h2::kGrowthBtB;
 using ctdet::h2::kGrowthGG;
 using ctdet::h2::kLineWords;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kMaxParts = 6;
@@ -44,7 +46,6 @@ constexpr int FRAG_BYTES = 1024;            // 64 lanes x 8 binary16: one 32 x 1
 constexpr int TRAILER_BYTES = 256;          // word 0: eU, word 1: bit pattern of max |g|
 constexpr int STAGE_KS = 4;                 // k-steps per LDS stage (64 channels)
 constexpr int GEMM_LDS = 2 * 4 * STAGE_KS * FRAG_BYTES;       // [operand][block of 32][k-step]
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
 
 __device__ __forceinline__ float bf16_lo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); }

@@ -33,6 +33,7 @@
 //   pairs and the usual epilogue (scale / shift, residual, floor, fused 2x2 max-pool, NCHW or head scatter).
 #include "ct_common.h"
 #include "ct_wino_pack.h"
+#include "ct_wino_launch.h"
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -40,13 +41,16 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using ctdet::bf16x8;
+using ctdet::f32x4;
+using ctdet::f32x16;
+using ctdet::i32x4;
+using ctdet::kInvalidOff;
+using ctdet::kMaxBufBytes;
+using ctdet::make_rsrc;
+using ctdet::split3;
+using ctdet::pack_hi;
 typedef int i32x2 __attribute__((ext_vector_type(2)));
-constexpr int kInvalidOff = 0x7FFFFFF0;
-constexpr long long kMaxBufBytes = 0x7FFFFF00LL;
 constexpr int CC = ctdet::kWinoX3CC;        // 16 channels per chunk = one MFMA k-group
 constexpr int TB = 32;                      // tiles per workgroup
 constexpr int KB = ctdet::kWinoKB;          // 64 output channels per workgroup
@@ -76,25 +80,6 @@ struct WinoX3Args {
     int nseg;                // > 0: channels-last scatter into the flattened head buffers (ct_out_segment)
     ct_out_segment seg[3];
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-
-// x = hi + mid + lo exactly (3 x 8 significant bits by truncation); the upper halves of the three words are the pieces
-__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l)
-{
-    h = __builtin_bit_cast(unsigned, x) & 0xFFFF0000u;
-    const float r1 = x - __builtin_bit_cast(float, h);
-    m = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-    l = __builtin_bit_cast(unsigned, r1 - __builtin_bit_cast(float, m));
-}
-
-__device__ __forceinline__ int pack_hi(unsigned e0, unsigned e1)      // [bf16 e0 | bf16 e1 << 16]
-{
-    return (int)__builtin_amdgcn_perm(e1, e0, 0x07060302u);
-}
 
 // Epilogue of one (cout, 2x2 output tile): y = the output-transformed sums [row 0: x, x+1 | row 1: x, x+1].
 // scale / shift, residual, floor, the 2x2 pooling window, NCHW or head-scatter stores (the arithmetic of ct_wino.hip).
@@ -441,38 +426,15 @@ extern "C" int ct_conv_pack_weights_wino_x3_dgrad(const float* const* w, const i
 
 // variant 1: two accumulators, eight waves (the only one left: the four-wave / two-workgroups-per-CU form with one accumulator,
 // variant 2 of rounds 4-5, never won a layer in the pipeline and was removed in round 6)
-static int launch_wino_x3(const ct_conv_desc* d, const void* upacked, int dual, float* pool_out, int pool_ctot,
-                          int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream, const char* who)
+static int launch_wino_x3(const ct_conv_desc* d, const void* upacked, int dual, const ctdet::PoolOut& pool, ct_stream_t stream,
+                          const char* who)
 {
-    CT_REQUIRE(d && upacked, "%s: null pointer", who);
-    CT_REQUIRE(d->in && (d->out || d->nseg > 0) && d->scale && d->shift, "%s: null tensor", who);
-    if (!winox3_ok(d))
-        return ctdet::fail(CT_ERR_UNSUPPORTED, "%s: needs 3x3 stride 1 dilation 1 pad 1, cin %% 16 == 0 "
-                           "(got %dx%d s%d d%d p%d cin=%d nseg=%d)", who, d->kh, d->kw, d->stride, d->dil,
-                           d->pad_h, d->cin, d->nseg);
-    CT_REQUIRE(d->batch > 0 && d->cout > 0, "%s: bad shape", who);
-    CT_REQUIRE(write_full || pool_out, "%s: nothing to write", who);
-    if (pool_out) {
-        CT_REQUIRE(pool_coff >= 0 && pool_coff + d->cout <= pool_ctot, "%s: pooled output slice", who);
-        CT_REQUIRE((pool_oh == d->oh / 2 || pool_oh == (d->oh + 1) / 2) && (pool_ow == d->ow / 2 || pool_ow == (d->ow + 1) / 2),
-                   "%s: pooled size %dx%d for a %dx%d map", who, pool_oh, pool_ow, d->oh, d->ow);
-    }
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "%s: input slice", who);
-    if (d->nseg == 0)
-        CT_REQUIRE(d->out_coff >= 0 && d->out_coff + d->cout <= d->out_ctot, "%s: output slice", who);
-    else {
-        CT_REQUIRE(!pool_out && write_full, "%s: pooling with segmented output", who);
-        for (int g = 0; g < d->nseg; ++g) CT_REQUIRE(d->seg[g].ptr, "%s: null segment", who);
-    }
-    CT_REQUIRE(!d->res || (d->res_coff >= 0 && d->res_coff + d->cout <= d->res_ctot), "%s: residual slice", who);
-    const long long img_in_bytes = (long long)d->in_ctot * d->h * d->w * 4;
-    CT_REQUIRE(img_in_bytes < kMaxBufBytes, "%s: one image exceeds 2 GiB", who);
-    const long long img_out_bytes = d->nseg ? 4 : (long long)d->out_ctot * d->oh * d->ow * 4;
-    const long long img_res_bytes = d->res ? (long long)d->res_ctot * d->oh * d->ow * 4 : 0;
-    CT_REQUIRE(img_out_bytes < kMaxBufBytes && img_res_bytes < kMaxBufBytes, "%s: one image exceeds 2 GiB", who);
+    if (dual != 1) return ctdet::fail(CT_ERR_INVALID, "%s: variant %d (only 1 = two accumulators exists)", who, dual);
+    if (int rc = ctdet::wino_check_desc(d, upacked, d && winox3_ok(d), who, "3x3 stride 1 dilation 1 pad 1, cin % 16 == 0")) return rc;
+    ctdet::WinoLimits lim;
+    if (int rc = ctdet::wino_check_launch(d, who, pool, &lim)) return rc;
     const size_t u_bytes = ct_conv_wino_x3_packed_bytes(d->cin, d->cout);
     CT_REQUIRE(u_bytes < (size_t)kMaxBufBytes, "%s: packed weights exceed 2 GiB", who);
-    const int max_chunk = (int)std::max<long long>(1, kMaxBufBytes / std::max(img_in_bytes, std::max(img_out_bytes, img_res_bytes)));
     hipStream_t st = ctdet::as_stream(stream);
     {
         static std::once_flag once;
@@ -485,35 +447,13 @@ static int launch_wino_x3(const ct_conv_desc* d, const void* upacked, int dual, 
         });
         CT_HIP(attr_err);
     }
-    const int OHW = d->oh * d->ow;
-    for (int b0 = 0; b0 < d->batch; b0 += max_chunk) {
-        const int nb = std::min(max_chunk, d->batch - b0);
+    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) {
+        const int nb = std::min(lim.max_chunk, d->batch - b0);
         WinoX3Args a{};
-        a.in = d->in + (size_t)b0 * d->in_ctot * d->h * d->w;
-        a.U = (const unsigned char*)upacked;
+        ctdet::wino_fill(a, d, upacked, lim, pool, b0, nb, 2);
         a.u_bytes = (unsigned)u_bytes;
-        a.scale = d->scale; a.shift = d->shift; a.lo = d->lo;
-        a.res = d->res ? d->res + (size_t)b0 * d->res_ctot * OHW : nullptr;
-        a.out = d->nseg ? nullptr : d->out + (size_t)b0 * d->out_ctot * OHW;
-        a.nseg = d->nseg;
-        for (int g = 0; g < d->nseg; ++g) {
-            a.seg[g] = d->seg[g];
-            a.seg[g].ptr += (size_t)b0 * d->seg[g].img_stride;
-        }
-        a.in_bytes = (unsigned)(img_in_bytes * nb);
-        a.out_bytes = (unsigned)(img_out_bytes * nb);
-        a.res_bytes = (unsigned)(img_res_bytes * nb);
-        a.Cin = d->cin; a.H = d->h; a.W = d->w; a.in_ctot = d->in_ctot; a.in_coff = d->in_coff;
-        a.M = d->cout; a.chunks = d->cin / CC;
-        a.TY = (d->oh + 1) / 2; a.TX = (d->ow + 1) / 2;
-        a.NT = nb * a.TY * a.TX;
+        a.chunks = d->cin / CC;
         a.tile_blocks = (a.NT + TB - 1) / TB;
-        a.out_ctot = d->out_ctot; a.out_coff = d->out_coff;
-        a.res_ctot = d->res_ctot; a.res_coff = d->res_coff; a.res_scale = d->res_scale;
-        a.relu = d->relu;
-        a.pool_out = pool_out ? pool_out + (size_t)b0 * pool_ctot * pool_oh * pool_ow : nullptr;
-        a.pool_ctot = pool_ctot; a.pool_coff = pool_coff; a.pool_oh = pool_oh; a.pool_ow = pool_ow;
-        a.write_full = write_full;
         a.kblocks = (d->cout + KB - 1) / KB;
         // 8 XCD-local sequences of (tile block group, cout block); sequences past the last tile block exit at once
         const int groups = (a.tile_blocks + 7) / 8;
@@ -532,12 +472,11 @@ extern "C" int ct_conv2d_wino_x3_pool_fwd(const ct_conv_desc* d, const void* upa
                                           int pool_ctot, int pool_coff, int pool_oh, int pool_ow, int write_full,
                                           ct_stream_t stream)
 {
-    if (dual != 1) return ctdet::fail(CT_ERR_INVALID, "ct_conv2d_wino_x3_fwd: variant %d (only 1 = two accumulators exists)", dual);
-    return launch_wino_x3(d, upacked, dual, pool_out, pool_ctot, pool_coff, pool_oh, pool_ow, write_full, stream,
-                          "ct_conv2d_wino_x3_fwd");
+    return launch_wino_x3(d, upacked, dual, {pool_out, pool_ctot, pool_coff, pool_oh, pool_ow, write_full}, stream,
+                          "ct_conv2d_wino_x3_pool_fwd");
 }
 
 extern "C" int ct_conv2d_wino_x3_fwd(const ct_conv_desc* d, const void* upacked, int dual, ct_stream_t stream)
 {
-    return ct_conv2d_wino_x3_pool_fwd(d, upacked, dual, nullptr, 0, 0, 0, 0, 1, stream);
+    return launch_wino_x3(d, upacked, dual, {nullptr, 0, 0, 0, 0, 1}, stream, "ct_conv2d_wino_x3_fwd");
 }
