@@ -6,6 +6,7 @@
 
 namespace {
 
+using ctdet::acc_row;
 using ctdet::bf16x8;
 using ctdet::f32x16;
 using ctdet::i32x4;
@@ -15,8 +16,6 @@ constexpr int DP = 64;      // padded feature dim
 constexpr int QW = 32;      // queries per wave
 constexpr int QB = 128;     // queries per workgroup
 constexpr int KT = 32;      // keys per tile
-
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // ---- bf16x3 operand fragments (csrc/ct_conv_x3.hip has the arithmetic) ----
 constexpr int XT_BYTES = 3 * 8 * KT * 16;          // one 32-row tile of a [rows][64] operand as bf16x3 fragments: 12 KB

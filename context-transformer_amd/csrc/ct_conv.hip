@@ -24,14 +24,14 @@
 // k ordering: k = ci*KH*KW + tap (the natural [cout][cin][kh][kw] order); a k-step covers
 // CPB whole input channels so the row -> (channel, tap) split is a compile-time constant.
 #include "ct_common.h"
+#include "ct_conv_emit.h"
+#include "ct_conv_launch.h"
 #include "ct_device.h"
 #include "ct_f16x2.h"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 #include <cstdlib>
-#include <mutex>
-#include <unordered_set>
 
 namespace {
 
@@ -63,7 +63,7 @@ struct ConvArgs {
     int tiles_m, tiles_n;
     int transposed;
     int ksplit, steps_per_split;    // > 1: blockIdx.y owns k-steps [y*sps, (y+1)*sps) and writes its raw sums to ws
-    float* ws;                      // [ksplit][M][Npix] partial sums, reduced in fixed order by conv_splitk_epilogue
+    float* ws;                      // [ksplit][M][Npix] partial sums, reduced in fixed order by conv_splitk_finish
     unsigned* out_amax;             // ct_conv_desc.out_absmax (per-image max |y| of what the launch stores), or null
 };
 
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_f32(const ConvArgs a)
     if (a.ksplit > 1) {
         // split-K (small maps: too few tiles to fill the chip, k loop latency bound): every split stores its raw
         // partial sums in its own slab ws[split][co][pixel] (no atomics: the result does not depend on timing);
-        // conv_splitk_epilogue adds the slabs in order and applies the epilogue
+        // conv_splitk_finish adds the slabs in order and applies the epilogue
         float* const slab = a.ws + (size_t)blockIdx.y * a.M * a.Npix;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -295,17 +295,8 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_f32(const ConvArgs a)
     }
 
     // ---- epilogue ----
-    // per-cout epilogue vectors once per workgroup through LDS (the operand tiles are dead after the last barrier)
-    // instead of a per-lane global gather for every output (round 3, measured on the bf16x3 twin of this kernel:
-    // a third of a workgroup's fixed time)
-    float* const ev = smem;                   // [3][BM]: scale, shift, floor
-    for (int i = tid; i < BM; i += 256) {
-        const int co = m0 + i;
-        const bool in = co < a.M;
-        ev[i] = in ? a.scale[co] : 0.f;
-        ev[BM + i] = in ? a.shift[co] : 0.f;
-        ev[2 * BM + i] = !in ? 0.f : a.lo ? a.lo[co] : (a.relu ? 0.f : -INFINITY);
-    }
+    float* const ev = smem;                   // [3][BM]: scale, shift, floor (the operand tiles are dead after the last barrier)
+    for (int i = tid; i < BM; i += 256) ctdet::stage_epilogue_vector<BM>(ev, a, m0, i);
     __syncthreads();
     const bool track = a.out_amax != nullptr;       // ct_conv_desc.out_absmax: per-image maxima of |v| of what the launch stores
 #pragma unroll
@@ -474,41 +465,6 @@ __global__ __launch_bounds__(256) void conv_valu3x3_f32(const ConvArgs a)
     }
 }
 
-// epilogue of a split-K convolution: sum of the slabs in split order, then the same arithmetic as the fused one
-__global__ __launch_bounds__(256) void conv_splitk_epilogue(const ConvArgs a)
-{
-    const int total = a.M * a.Npix;
-    const bool track = a.out_amax != nullptr;
-    const int rounds = (total + gridDim.x * 256 - 1) / (gridDim.x * 256);       // the same trip count for every lane (flush below)
-    for (int it = 0; it < rounds; ++it) {
-        const int idx = (it * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
-        float amax_run = 0.f;
-        int img = -1;
-        if (idx < total) {
-            const int co = idx / a.Npix, P = idx - co * a.Npix;
-            const int n = P / a.OHW, s = P - n * a.OHW;
-            img = n;
-            float sum = a.ws[idx];
-            for (int k = 1; k < a.ksplit; ++k) sum += a.ws[(size_t)k * total + idx];
-            float v = sum * a.scale[co] + a.shift[co];
-            if (a.res) v = v * a.res_scale + a.res[((size_t)n * a.res_ctot + a.res_coff + co) * a.OHW + s];
-            if (a.lo) { const float fl = a.lo[co]; v = v < fl ? fl : v; }      // NaN propagates
-            else if (a.relu) v = v < 0.f ? 0.f : v;
-            if (track) ctdet::h2::track_absmax(amax_run, v);
-            if (a.nseg == 0) {
-                a.out[((size_t)n * a.out_ctot + a.out_coff + co) * a.OHW + s] = v;
-            } else {
-#pragma unroll
-                for (int g = 0; g < 3; ++g)
-                    if (g < a.nseg && co >= a.seg[g].co_begin && co < a.seg[g].co_end)
-                        a.seg[g].ptr[(size_t)n * a.seg[g].img_stride + a.seg[g].base +
-                                     (size_t)s * a.seg[g].pix_stride + (co - a.seg[g].co_begin)] = v;
-            }
-        }
-        if (track) ctdet::h2::flush_absmax(a.out_amax, img, amax_run);
-    }
-}
-
 // --------------------------------------------------------------------------------------
 struct PackArgs {
     const float* w[6];
@@ -597,17 +553,7 @@ constexpr int cpb_for(int kh, int kw, int bn)
 template <typename K>
 hipError_t launch_one(K kernel, size_t smem, const ConvArgs& a, hipStream_t st)
 {
-    if (smem > 64 * 1024) {              // opt in to > 64 KiB of LDS once per kernel
-        static std::mutex mu;
-        static std::unordered_set<const void*> raised;
-        const void* fn = reinterpret_cast<const void*>(kernel);
-        std::lock_guard<std::mutex> lock(mu);
-        if (!raised.count(fn)) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return e;
-            raised.insert(fn);
-        }
-    }
+    if (hipError_t e = ctdet::raise_lds_limit(reinterpret_cast<const void*>(kernel), smem)) return e;
     hipLaunchKernelGGL(kernel, dim3(a.tiles_m * a.tiles_n, a.ksplit > 1 ? a.ksplit : 1), dim3(256), smem, st, a);
     return hipGetLastError();
 }
@@ -759,38 +705,18 @@ extern "C" int ct_conv2d_fwd(const ct_conv_desc* d, ct_stream_t stream)
     CT_REQUIRE(d->batch > 0 && d->cin > 0 && d->cout > 0 && d->h > 0 && d->w > 0,
                "ct_conv2d_fwd: bad shape");
     CT_REQUIRE(d->stride >= 1 && d->dil >= 1, "ct_conv2d_fwd: stride/dilation");
-    if (!d->transposed) {
-        const int eoh = (d->h + 2 * d->pad_h - d->dil * (d->kh - 1) - 1) / d->stride + 1;
-        const int eow = (d->w + 2 * d->pad_w - d->dil * (d->kw - 1) - 1) / d->stride + 1;
-        CT_REQUIRE(eoh == d->oh && eow == d->ow, "ct_conv2d_fwd: oh/ow %dx%d != expected %dx%d", d->oh,
-                   d->ow, eoh, eow);
-    } else {    // data gradient: (h,w) = spatial size of dY, (oh,ow) = spatial size of dX
-        const int fh = (d->oh + 2 * d->pad_h - d->dil * (d->kh - 1) - 1) / d->stride + 1;
-        const int fw = (d->ow + 2 * d->pad_w - d->dil * (d->kw - 1) - 1) / d->stride + 1;
-        CT_REQUIRE(fh == d->h && fw == d->w, "ct_conv2d_fwd(transposed): dY %dx%d != forward output %dx%d of a %dx%d input",
-                   d->h, d->w, fh, fw, d->oh, d->ow);
-    }
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "ct_conv2d_fwd: input slice");
+    const char* const who = "ct_conv2d_fwd";
+    if (int rc = ctdet::conv_check_sizes(d, who)) return rc;
     CT_REQUIRE(d->m_pad >= d->cout && d->m_pad % 4 == 0, "ct_conv2d_fwd: m_pad");
     const int kpad = ct_conv_kpad(d->cin, d->kh, d->kw);
     if (kpad < 0)
         return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_fwd: %dx%d filters not built", d->kh, d->kw);
     CT_REQUIRE(d->k_pad == kpad, "ct_conv2d_fwd: k_pad=%d, expected %d", d->k_pad, kpad);
-    CT_REQUIRE(d->nseg >= 0 && d->nseg <= 3, "ct_conv2d_fwd: nseg");
-    if (d->nseg == 0) {
-        CT_REQUIRE(d->out && d->out_coff >= 0 && d->out_coff + d->cout <= d->out_ctot,
-                   "ct_conv2d_fwd: output slice");
-        CT_REQUIRE(!d->res || (d->res_coff >= 0 && d->res_coff + d->cout <= d->res_ctot),
-                   "ct_conv2d_fwd: residual slice");
-    } else {
-        CT_REQUIRE(!d->res, "ct_conv2d_fwd: residual with segmented output");
-        for (int g = 0; g < d->nseg; ++g) CT_REQUIRE(d->seg[g].ptr, "ct_conv2d_fwd: null segment");
-    }
+    if (int rc = ctdet::conv_check_outputs(d, who)) return rc;
     CT_REQUIRE((long long)d->k_pad * d->m_pad * 4 < kMaxBufBytes, "ct_conv2d_fwd: weights too large");
-
-    const long long img_in_bytes = (long long)d->in_ctot * d->h * d->w * 4;
-    CT_REQUIRE(img_in_bytes < kMaxBufBytes, "ct_conv2d_fwd: one image exceeds 2 GiB");
-    const int max_chunk = (int)std::max<long long>(1, kMaxBufBytes / img_in_bytes);
+    long long img_in_bytes;
+    int max_chunk;
+    if (int rc = ctdet::conv_check_image(d, who, &img_in_bytes, &max_chunk)) return rc;
 
     const bool valu_ok = d->kh == 3 && d->kw == 3 && d->cin == 3 && !d->transposed && d->nseg == 0 && !d->res &&
                          d->cout % 8 == 0 && d->batch <= max_chunk && (long long)d->batch * d->oh * d->ow < 0x7FFFFFFFLL;
@@ -803,13 +729,9 @@ extern "C" int ct_conv2d_fwd(const ct_conv_desc* d, ct_stream_t stream)
             return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_fwd: config 'valu' is for 3x3 convolutions of 3 input channels "
                                "into a multiple of 8 output channels, NCHW output, no residual");
         ConvArgs a{};
-        a.in = d->in; a.wpk = d->wpacked; a.scale = d->scale; a.shift = d->shift; a.lo = d->lo; a.out = d->out;
-        a.Cin = d->cin; a.H = d->h; a.W = d->w; a.in_ctot = d->in_ctot; a.in_coff = d->in_coff;
-        a.M = d->cout; a.M_pad = d->m_pad;
-        a.stride = d->stride; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.dil = d->dil;
-        a.OW = d->ow; a.OHW = d->oh * d->ow; a.Npix = d->batch * a.OHW;
-        a.out_ctot = d->out_ctot; a.out_coff = d->out_coff; a.relu = d->relu;
-        a.out_amax = d->out_absmax;
+        ctdet::conv_fill(a, d, 0, d->batch, img_in_bytes);      // valu_ok: the whole batch is one chunk
+        a.wpk = d->wpacked;
+        a.M_pad = d->m_pad;
         static const int ppt = getenv("CTDET_VALU_PPT") ? atoi(getenv("CTDET_VALU_PPT")) : 2;
         if (ppt == 1)
             hipLaunchKernelGGL((conv_valu3x3_f32<3, 1>), dim3((a.Npix + 255) / 256), dim3(256), 0, ctdet::as_stream(stream), a);
@@ -824,61 +746,20 @@ extern "C" int ct_conv2d_fwd(const ct_conv_desc* d, ct_stream_t stream)
     for (int b0 = 0; b0 < d->batch; b0 += max_chunk) {
         const int nb = std::min(max_chunk, d->batch - b0);
         ConvArgs a{};
-        a.in = d->in + (size_t)b0 * d->in_ctot * d->h * d->w;
+        ctdet::conv_fill(a, d, b0, nb, img_in_bytes);
+        if (d->transposed) a.out_amax = nullptr;      // a data gradient records no maxima here (ct_conv2d_x3_fwd does)
         a.wpk = d->wpacked;
-        a.scale = d->scale;
-        a.shift = d->shift;
-        a.lo = d->lo;
-        a.OW = d->ow;
-        a.OHW = d->oh * d->ow;
-        a.res = d->res ? d->res + (size_t)b0 * d->res_ctot * a.OHW : nullptr;
-        a.out = d->nseg == 0 ? d->out + (size_t)b0 * d->out_ctot * a.OHW : nullptr;
-        a.in_bytes = (unsigned)(img_in_bytes * nb);
         a.w_bytes = (unsigned)((long long)d->k_pad * d->m_pad * 4);
-        a.Cin = d->cin;
-        a.H = d->h;
-        a.W = d->w;
-        a.in_ctot = d->in_ctot;
-        a.in_coff = d->in_coff;
-        a.M = d->cout;
         a.M_pad = d->m_pad;
         a.nsteps = (d->cin + cpb - 1) / cpb;
-        a.stride = d->stride;
-        a.pad_h = d->pad_h;
-        a.pad_w = d->pad_w;
-        a.dil = d->dil;
-        a.transposed = d->transposed;
-        a.Npix = nb * a.OHW;
-        a.out_ctot = d->out_ctot;
-        a.out_coff = d->out_coff;
-        a.res_ctot = d->res_ctot;
-        a.res_coff = d->res_coff;
-        a.res_scale = d->res_scale;
-        a.relu = d->relu;
-        a.out_amax = (d->out_absmax && !d->transposed) ? d->out_absmax + (size_t)b0 * ctdet::h2::kLineWords : nullptr;
-        a.nseg = d->nseg;
-        for (int g = 0; g < d->nseg; ++g) {
-            a.seg[g] = d->seg[g];
-            a.seg[g].ptr += (size_t)b0 * d->seg[g].img_stride;
-        }
         a.tiles_m = (d->cout + bm - 1) / bm;
         a.tiles_n = (a.Npix + bn - 1) / bn;
-        a.ksplit = 1;
-        a.steps_per_split = a.nsteps;
-        int want = d->ksplit;
-        if (want < 0) {     // auto: aim at ~3 workgroups per CU, at least two k-steps per split
-            static const int target = getenv("CTDET_KSPLIT_TARGET") ? atoi(getenv("CTDET_KSPLIT_TARGET")) : 768;
-            const int tiles = a.tiles_m * a.tiles_n;
-            want = tiles * 2 > target ? 1 : std::min(a.nsteps / 2, target / tiles);
-        }
-        const long long slab = (long long)d->cout * a.Npix;
-        if (d->ksplit_ws && slab > 0) want = (int)std::min<long long>(want, d->ksplit_ws_floats / slab);
-        if (want > 1 && d->ksplit_ws && nb == d->batch && a.nsteps >= 2 && slab < 0x7FFFFFFFLL) {
-            const int ks = std::min(want, a.nsteps);
-            a.steps_per_split = (a.nsteps + ks - 1) / ks;
-            a.ksplit = (a.nsteps + a.steps_per_split - 1) / a.steps_per_split;
-            a.ws = d->ksplit_ws;
-        }
+        static const int target = getenv("CTDET_KSPLIT_TARGET") ? atoi(getenv("CTDET_KSPLIT_TARGET")) : 768;
+        const ctdet::SplitK sk = ctdet::plan_splitk(d->ksplit, a.tiles_m * a.tiles_n, a.nsteps, (long long)d->cout * a.Npix,
+                                                    d->ksplit_ws, d->ksplit_ws_floats, nb == d->batch, target);
+        a.ksplit = sk.ksplit;
+        a.steps_per_split = sk.steps_per_split;
+        if (sk.ksplit > 1) a.ws = d->ksplit_ws;
         hipError_t e;
         hipStream_t st = ctdet::as_stream(stream);
         if (d->kh == 3 && d->kw == 3) e = launch_geo<3, 3>(cfg, a, st);
@@ -891,8 +772,8 @@ extern "C" int ct_conv2d_fwd(const ct_conv_desc* d, ct_stream_t stream)
             return ctdet::fail(CT_ERR_HIP, "conv_igemm_f32 launch failed: %s", hipGetErrorString(e));
         if (a.ksplit > 1) {
             const int total = a.M * a.Npix;
-            hipLaunchKernelGGL(conv_splitk_epilogue, dim3(std::min((total + 255) / 256, 2048)), dim3(256), 0, st, a);
-            CT_LAUNCH_CHECK("conv_splitk_epilogue");
+            hipLaunchKernelGGL(ctdet::conv_splitk_finish<ConvArgs>, dim3(std::min((total + 255) / 256, 2048)), dim3(256), 0, st, a);
+            CT_LAUNCH_CHECK("conv_splitk_finish");
         }
     }
     return CT_OK;

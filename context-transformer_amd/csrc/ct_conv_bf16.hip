@@ -22,11 +22,10 @@
 //   MFMAs + fragment reads alone 147 us (59 %); every KB a wave moves costs ~100 issue cycles whichever way it goes
 //   (DMA piece, or buffer_load + ds_write_b128), and a 128 x 128 tile moves 8 KB per wave per 512 MFMA cycles.
 #include "ct_common.h"
+#include "ct_conv_launch.h"
 #include "ct_device.h"
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
-#include <unordered_set>
 
 namespace {
 
@@ -466,11 +465,7 @@ __global__ __launch_bounds__(256) void conv_bf16_splitk_epilogue(const Bf16Args 
             reinterpret_cast<unsigned short*>(a.out)[(size_t)P * a.out_ctot + a.out_coff + co] = f2bf(v);
         } else {
             const int n = P / a.OHW, s = P - n * a.OHW;
-#pragma unroll
-            for (int g = 0; g < 3; ++g)
-                if (g < a.nseg && co >= a.seg[g].co_begin && co < a.seg[g].co_end)
-                    a.seg[g].ptr[(size_t)n * a.seg[g].img_stride + a.seg[g].base +
-                                 (size_t)s * a.seg[g].pix_stride + (co - a.seg[g].co_begin)] = v;
+            ctdet::scatter_segments(a, n, s, co, v);
         }
     }
 }
@@ -689,40 +684,25 @@ extern "C" int ct_conv2d_bf16_fwd(const ct_conv_desc* d, ct_stream_t stream)
     a.out_ctot = d->out_ctot; a.out_coff = d->out_coff; a.res_ctot = d->res_ctot; a.res_coff = d->res_coff;
     a.res_scale = d->res_scale; a.relu = d->relu; a.nseg = d->nseg;
     for (int g = 0; g < d->nseg; ++g) a.seg[g] = d->seg[g];
-    int tiles_n = 0;
     hipStream_t st = ctdet::as_stream(stream);
+    hipError_t lds_err = hipSuccess;
     auto go = [&](auto kernel, int bm, int bn, int bk, int nt) {
-        tiles_n = (a.Npix + bm - 1) / bm;
+        const int tiles_n = (a.Npix + bm - 1) / bm;
         a.tiles_m = (d->cout + bn - 1) / bn;
         const int taps = d->kh * d->kw;
         const int nsteps = a.cin_pad == KSMALL ? (taps + bk / 8 - 1) / (bk / 8) : taps * (a.cin_pad / bk);
-        a.ksplit = 1;
-        a.steps_per_split = nsteps;
-        int want = d->ksplit;
-        const int tiles = a.tiles_m * tiles_n;
-        if (want < 0) want = tiles * 2 > 768 ? 1 : std::min(nsteps / 2, 768 / tiles);   // ~3 workgroups per CU
-        if (bm == 256) want = 1;
-        const long long slab = (long long)d->cout * a.Npix;
-        if (d->ksplit_ws && slab > 0) want = (int)std::min<long long>(want, d->ksplit_ws_floats / slab);
-        if (want > 1 && d->ksplit_ws && nsteps >= 2 && slab < 0x7FFFFFFFLL) {
-            a.steps_per_split = (nsteps + want - 1) / want;
-            a.ksplit = (nsteps + a.steps_per_split - 1) / a.steps_per_split;
-            a.ws = d->ksplit_ws;
-        }
+        // the 256 x 256 tile is only launched unsplit; the batch is never chunked here
+        const ctdet::SplitK sk = ctdet::plan_splitk(bm == 256 ? 1 : d->ksplit, a.tiles_m * tiles_n, nsteps, (long long)d->cout * a.Npix,
+                                                    d->ksplit_ws, d->ksplit_ws_floats, true, 768);
+        a.ksplit = sk.ksplit;
+        a.steps_per_split = sk.steps_per_split;
+        if (sk.ksplit > 1) a.ws = d->ksplit_ws;
         const bool dma = a.cin_pad != KSMALL;
         const size_t ring = (size_t)(dma && bk == 32 ? 3 : 2) * (bm + bn) * (dma ? bk * 2 : bk * 2 + 16);
         const size_t srow = (size_t)bn * 4 + 16;
         const size_t smem = std::max(ring, (bm * srow <= ring || !(dma && bk == 32) ? bm : 64) * srow);   // operand ring | output staging
-        static std::mutex mu;
-        static std::unordered_set<const void*> raised;
-        if (smem > 64 * 1024) {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!raised.count((const void*)kernel)) {
-                if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-                    return;
-                raised.insert((const void*)kernel);
-            }
-        }
+        lds_err = ctdet::raise_lds_limit((const void*)kernel, smem);
+        if (lds_err != hipSuccess) return;
         hipLaunchKernelGGL(kernel, dim3(a.tiles_m * tiles_n, a.ksplit), dim3(nt), smem, st, a);
     };
     const int tn128 = (a.Npix + 127) / 128;
@@ -749,6 +729,8 @@ extern "C" int ct_conv2d_bf16_fwd(const ct_conv_desc* d, ct_stream_t stream)
         else if (wide_bk == 32) go(conv_bf16_nhwc<128, 128, 32, false, 256>, 128, 128, 32, 256);
         else go(conv_bf16_nhwc<128, 128, 64, false, 256>, 128, 128, 64, 256);
     }
+    if (lds_err != hipSuccess)
+        return ctdet::fail(CT_ERR_HIP, "ct_conv2d_bf16_fwd: raising the LDS limit of conv_bf16_nhwc failed: %s", hipGetErrorString(lds_err));
     CT_LAUNCH_CHECK("conv_bf16_nhwc");
     if (a.ksplit > 1) {
         hipLaunchKernelGGL(conv_bf16_splitk_epilogue, dim3(std::min((a.Npix * a.M + 255) / 256, 2048)), dim3(256), 0, st, a);

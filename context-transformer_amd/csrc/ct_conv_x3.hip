@@ -25,15 +25,15 @@
 //   LDS double buffered, one barrier per k-step; the loads of step s+1 are issued before the MFMAs of step s.
 // Small maps use the same deterministic slab split-K as ct_conv2d_fwd (desc->ksplit).
 #include "ct_common.h"
+#include "ct_conv_emit.h"
+#include "ct_conv_launch.h"
 #include "ct_device.h"
 #include "ct_f16x2.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <type_traits>
-#include <unordered_set>
 
 namespace {
 
@@ -365,17 +365,8 @@ __global__ __launch_bounds__(256, 2) void conv_x3_f32(const X3Args a)
     }
 
     // ---- epilogue (the arithmetic of ct_conv2d_fwd) ----
-    // per-cout epilogue vectors once per workgroup through LDS (the operand tiles are dead after the last barrier): a
-    // per-lane global gather of scale / shift / floor for each of a lane's 64 outputs cost a third of the fixed time
-    // of a workgroup (1x1 16->1024 @19x19 bs 32, one k-step: 39.9 -> 25.8 us)
-    float* const ev = reinterpret_cast<float*>(lds);              // [3][BM]: scale, shift, floor
-    for (int i = tid; i < BM; i += 256) {
-        const int co = m0 + i;
-        const bool in = co < a.M;
-        ev[i] = in ? a.scale[co] : 0.f;
-        ev[BM + i] = in ? a.shift[co] : 0.f;
-        ev[2 * BM + i] = !in ? 0.f : a.lo ? a.lo[co] : (a.relu ? 0.f : -INFINITY);
-    }
+    float* const ev = reinterpret_cast<float*>(lds);              // [3][BM]: scale, shift, floor (the operand tiles are dead)
+    for (int i = tid; i < BM; i += 256) ctdet::stage_epilogue_vector<BM>(ev, a, m0, i);
     __syncthreads();
     const bool track = a.out_amax != nullptr;
     int eW = 0;
@@ -429,50 +420,6 @@ __global__ __launch_bounds__(256, 2) void conv_x3_f32(const X3Args a)
         }
         // ct_conv_desc.out_absmax: every lane arrives here; one atomic per image present in the wave
         if (track) ctdet::h2::flush_absmax(a.out_amax, n, amax_run);
-    }
-}
-
-__device__ __forceinline__ void x3_splitk_one(const X3Args& a, int idx, int total, bool track, float& amax_run, int& n_out);
-
-// sum of the split-K slabs in split order, then the fused epilogue (f16x2 launches: the slabs hold the scaled sums)
-__global__ __launch_bounds__(256) void conv_x3_splitk_epilogue(const X3Args a)
-{
-    const int total = a.M * a.Npix;
-    const bool track = a.out_amax != nullptr;
-    const int rounds = (total + gridDim.x * 256 - 1) / (gridDim.x * 256);       // the same trip count for every lane (flush below)
-    for (int it = 0; it < rounds; ++it) {
-        const int idx = (it * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
-        float amax_run = 0.f;
-        int n = -1;
-        if (idx < total) x3_splitk_one(a, idx, total, track, amax_run, n);
-        if (track) ctdet::h2::flush_absmax(a.out_amax, n, amax_run);
-    }
-}
-
-__device__ __forceinline__ void x3_splitk_one(const X3Args& a, const int idx, const int total, const bool track, float& amax_run, int& n_out)
-{
-    {
-        const int co = idx / a.Npix, P = idx - co * a.Npix;
-        const int n = P / a.OHW, s = P - n * a.OHW;
-        n_out = n;
-        ctdet::h2::pow2x2 ymul{1.f, 1.f};       // f16x2 launches: the slabs hold sums scaled by 2^(eX[image] + eW)
-        if (a.eW) ymul = ctdet::h2::unscale_for(*a.eW, ctdet::h2::image_exponent(a.in_amax, n, ctdet::h2::kGrowthNone));
-        float sum = a.ws[idx];
-        for (int k = 1; k < a.ksplit; ++k) sum += a.ws[(size_t)k * total + idx];
-        float v = ((sum * ymul.lo) * ymul.hi) * a.scale[co] + a.shift[co];
-        if (a.res) v = v * a.res_scale + a.res[((size_t)n * a.res_ctot + a.res_coff + co) * a.OHW + s];
-        if (a.lo) { const float fl = a.lo[co]; v = v < fl ? fl : v; }      // NaN propagates
-        else if (a.relu) v = v < 0.f ? 0.f : v;
-        if (track) ctdet::h2::track_absmax(amax_run, v);
-        if (a.nseg == 0) {
-            a.out[((size_t)n * a.out_ctot + a.out_coff + co) * a.OHW + s] = v;
-        } else {
-#pragma unroll
-            for (int g = 0; g < 3; ++g)
-                if (g < a.nseg && co >= a.seg[g].co_begin && co < a.seg[g].co_end)
-                    a.seg[g].ptr[(size_t)n * a.seg[g].img_stride + a.seg[g].base +
-                                 (size_t)s * a.seg[g].pix_stride + (co - a.seg[g].co_begin)] = v;
-        }
     }
 }
 
@@ -594,17 +541,7 @@ constexpr int kNumX3 = sizeof(kX3) / sizeof(kX3[0]);
 template <typename K>
 hipError_t launch_x3(K kernel, size_t smem, const X3Args& a, hipStream_t st)
 {
-    if (smem > 64 * 1024) {
-        static std::mutex mu;
-        static std::unordered_set<const void*> raised;
-        const void* fn = reinterpret_cast<const void*>(kernel);
-        std::lock_guard<std::mutex> lock(mu);
-        if (!raised.count(fn)) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return e;
-            raised.insert(fn);
-        }
-    }
+    if (hipError_t e = ctdet::raise_lds_limit(reinterpret_cast<const void*>(kernel), smem)) return e;
     hipLaunchKernelGGL(kernel, dim3(a.tiles_m * a.tiles_n, a.ksplit > 1 ? a.ksplit : 1), dim3(256), smem, st, a);
     return hipGetLastError();
 }
@@ -765,27 +702,11 @@ extern "C" int ct_conv2d_x3_fwd(const ct_conv_desc* d, const void* wx3, int conf
     CT_REQUIRE(config >= 0 && config < kNumX3, "ct_conv2d_x3_fwd: config %d (0..%d)", config, kNumX3 - 1);
     CT_REQUIRE(d->batch > 0 && d->cin > 0 && d->cout > 0 && d->h > 0 && d->w > 0, "ct_conv2d_x3_fwd: bad shape");
     CT_REQUIRE(d->kh >= 1 && d->kw >= 1 && d->stride >= 1 && d->dil >= 1, "ct_conv2d_x3_fwd: filter geometry");
-    if (!d->transposed) {
-        const int eoh = (d->h + 2 * d->pad_h - d->dil * (d->kh - 1) - 1) / d->stride + 1;
-        const int eow = (d->w + 2 * d->pad_w - d->dil * (d->kw - 1) - 1) / d->stride + 1;
-        CT_REQUIRE(eoh == d->oh && eow == d->ow, "ct_conv2d_x3_fwd: oh/ow %dx%d != expected %dx%d", d->oh, d->ow, eoh, eow);
-    } else {    // data gradient: (h,w) = spatial size of dY, (oh,ow) = spatial size of dX (ct_conv2d_fwd's contract)
-        if (d->stride > 2)
-            return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_x3_fwd(transposed): stride %d (1 or 2)", d->stride);
-        const int fh = (d->oh + 2 * d->pad_h - d->dil * (d->kh - 1) - 1) / d->stride + 1;
-        const int fw = (d->ow + 2 * d->pad_w - d->dil * (d->kw - 1) - 1) / d->stride + 1;
-        CT_REQUIRE(fh == d->h && fw == d->w, "ct_conv2d_x3_fwd(transposed): dY %dx%d != forward output %dx%d of a %dx%d input",
-                   d->h, d->w, fh, fw, d->oh, d->ow);
-    }
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "ct_conv2d_x3_fwd: input slice");
-    CT_REQUIRE(d->nseg >= 0 && d->nseg <= 3, "ct_conv2d_x3_fwd: nseg");
-    if (d->nseg == 0) {
-        CT_REQUIRE(d->out && d->out_coff >= 0 && d->out_coff + d->cout <= d->out_ctot, "ct_conv2d_x3_fwd: output slice");
-        CT_REQUIRE(!d->res || (d->res_coff >= 0 && d->res_coff + d->cout <= d->res_ctot), "ct_conv2d_x3_fwd: residual slice");
-    } else {
-        CT_REQUIRE(!d->res, "ct_conv2d_x3_fwd: residual with segmented output");
-        for (int g = 0; g < d->nseg; ++g) CT_REQUIRE(d->seg[g].ptr, "ct_conv2d_x3_fwd: null segment");
-    }
+    if (d->transposed && d->stride > 2)
+        return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_x3_fwd(transposed): stride %d (1 or 2)", d->stride);
+    const char* const who = "ct_conv2d_x3_fwd";
+    if (int rc = ctdet::conv_check_sizes(d, who)) return rc;
+    if (int rc = ctdet::conv_check_outputs(d, who)) return rc;
     const int bm = kX3[config].bm, bn = kX3[config].bn, bk = kX3[config].bk;
     const bool h2 = kX3[config].h2 != 0;
     CT_REQUIRE(!h2 || d->in_absmax, "ct_conv2d_x3_fwd: the f16x2 configurations need the maximum of |input| (ct_conv_desc.in_absmax: "
@@ -798,79 +719,37 @@ extern "C" int ct_conv2d_x3_fwd(const ct_conv_desc* d, const void* wx3, int conf
     const size_t wbytes = h2 ? ct_conv_x3h_packed_bytes(d->cin, d->cout, d->kh, d->kw, bk) - kX3hTrailerBytes
                              : ct_conv_x3_packed_bytes(d->cin, d->cout, d->kh, d->kw, bk);
     CT_REQUIRE((long long)wbytes < kMaxBufBytes, "ct_conv2d_x3_fwd: weights too large");
-    const long long img_in_bytes = (long long)d->in_ctot * d->h * d->w * 4;
-    CT_REQUIRE(img_in_bytes < kMaxBufBytes, "ct_conv2d_x3_fwd: one image exceeds 2 GiB");
-    const int max_chunk = (int)std::max<long long>(1, kMaxBufBytes / img_in_bytes);
+    long long img_in_bytes;
+    int max_chunk;
+    if (int rc = ctdet::conv_check_image(d, who, &img_in_bytes, &max_chunk)) return rc;
     hipStream_t st = ctdet::as_stream(stream);
 
     for (int b0 = 0; b0 < d->batch; b0 += max_chunk) {
         const int nb = std::min(max_chunk, d->batch - b0);
         X3Args a{};
-        a.in = d->in + (size_t)b0 * d->in_ctot * d->h * d->w;
+        ctdet::conv_fill(a, d, b0, nb, img_in_bytes);
         a.wx3 = static_cast<const unsigned char*>(wx3);
-        a.scale = d->scale;
-        a.shift = d->shift;
-        a.lo = d->lo;
-        a.OW = d->ow;
-        a.OHW = d->oh * d->ow;
-        a.res = d->res ? d->res + (size_t)b0 * d->res_ctot * a.OHW : nullptr;
-        a.out = d->nseg == 0 ? d->out + (size_t)b0 * d->out_ctot * a.OHW : nullptr;
-        a.in_bytes = (unsigned)(img_in_bytes * nb);
         a.w_bytes = (unsigned)wbytes;
-        a.Cin = d->cin;
-        a.H = d->h;
-        a.W = d->w;
-        a.in_ctot = d->in_ctot;
-        a.in_coff = d->in_coff;
-        a.M = d->cout;
         a.M_pad = m_pad;
         a.cgroups = (d->cin + bk - 1) / bk;
         a.KH = d->kh;
         a.KW = d->kw;
         a.nsteps = a.cgroups * d->kh * d->kw;
-        a.stride = d->stride;
-        a.pad_h = d->pad_h;
-        a.pad_w = d->pad_w;
-        a.dil = d->dil;
-        a.Npix = nb * a.OHW;
-        a.out_ctot = d->out_ctot;
-        a.out_coff = d->out_coff;
-        a.res_ctot = d->res_ctot;
-        a.res_coff = d->res_coff;
-        a.res_scale = d->res_scale;
-        a.relu = d->relu;
-        a.transposed = d->transposed;
         a.in_amax = d->in_absmax ? d->in_absmax + (size_t)b0 * ctdet::h2::kLineWords : nullptr;
         a.eW = h2 ? reinterpret_cast<const int*>(static_cast<const unsigned char*>(wx3) + wbytes) + 1 : nullptr;
-        a.out_amax = d->out_absmax ? d->out_absmax + (size_t)b0 * ctdet::h2::kLineWords : nullptr;
-        a.nseg = d->nseg;
-        for (int g = 0; g < d->nseg; ++g) {
-            a.seg[g] = d->seg[g];
-            a.seg[g].ptr += (size_t)b0 * d->seg[g].img_stride;
-        }
         a.tiles_m = (d->cout + bm - 1) / bm;
         a.tiles_n = (a.Npix + bn - 1) / bn;
-        a.ksplit = 1;
-        a.steps_per_split = a.nsteps;
-        int want = d->ksplit;
-        if (want < 0) {     // auto: ~3 workgroups per CU, at least two k-steps per split
-            const int tiles = a.tiles_m * a.tiles_n;
-            want = tiles * 2 > 768 ? 1 : std::min(a.nsteps / 2, 768 / tiles);
-        }
-        const long long slab = (long long)d->cout * a.Npix;
-        if (d->ksplit_ws && slab > 0) want = (int)std::min<long long>(want, d->ksplit_ws_floats / slab);
-        if (want > 1 && d->ksplit_ws && nb == d->batch && a.nsteps >= 2 && slab < 0x7FFFFFFFLL) {
-            const int ks = std::min(want, a.nsteps);
-            a.steps_per_split = (a.nsteps + ks - 1) / ks;
-            a.ksplit = (a.nsteps + a.steps_per_split - 1) / a.steps_per_split;
-            a.ws = d->ksplit_ws;
-        }
+        const ctdet::SplitK sk = ctdet::plan_splitk(d->ksplit, a.tiles_m * a.tiles_n, a.nsteps, (long long)d->cout * a.Npix,
+                                                    d->ksplit_ws, d->ksplit_ws_floats, nb == d->batch, 768);
+        a.ksplit = sk.ksplit;
+        a.steps_per_split = sk.steps_per_split;
+        if (sk.ksplit > 1) a.ws = d->ksplit_ws;
         hipError_t e = launch_cfg(config, a, st);
         if (e != hipSuccess) return ctdet::fail(CT_ERR_HIP, "conv_x3_f32 launch failed: %s", hipGetErrorString(e));
         if (a.ksplit > 1) {
             const int total = a.M * a.Npix;
-            hipLaunchKernelGGL(conv_x3_splitk_epilogue, dim3(std::min((total + 255) / 256, 2048)), dim3(256), 0, st, a);
-            CT_LAUNCH_CHECK("conv_x3_splitk_epilogue");
+            hipLaunchKernelGGL(ctdet::conv_splitk_finish<X3Args>, dim3(std::min((total + 255) / 256, 2048)), dim3(256), 0, st, a);
+            CT_LAUNCH_CHECK("conv_splitk_finish");
         }
     }
     return CT_OK;

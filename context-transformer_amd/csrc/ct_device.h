@@ -1,5 +1,5 @@
-// Device-side helpers every kernel file shares, defined once: the buffer descriptor, the vector types, and the split that
-// defines the bf16x3 operand form.  A translation unit pulls in what it uses with using-declarations.
+// Device-side helpers every kernel file shares, defined once: the buffer descriptor, the vector types, the split that
+// defines the bf16x3 operand form, the accumulator row of the 32x32 MFMA and the multibox head scatter.  A translation unit pulls in what it uses with using-declarations.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +32,21 @@ __device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsign
 __device__ __forceinline__ int pack_hi(unsigned e0, unsigned e1)      // [bf16 e0 | bf16 e1 << 16]
 {
     return (int)__builtin_amdgcn_perm(e1, e0, 0x07060302u);
+}
+
+// row of a 32x32 MFMA accumulator block that register r (0..15) of a lane in half hsel (lane >> 5) holds; the column is lane & 31
+__device__ __forceinline__ constexpr int acc_row(int r, int hsel) { return (r & 3) + 8 * (r >> 2) + 4 * hsel; }
+
+// One value of output channel co at pixel s of image n into the flattened multibox head buffers (ct_out_segment: channels-last
+// per segment).  Args is any kernel-argument record with nseg and seg[3].
+template <typename Args>
+__device__ __forceinline__ void scatter_segments(const Args& a, int n, int s, int co, float v)
+{
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+        if (g < a.nseg && co >= a.seg[g].co_begin && co < a.seg[g].co_end)
+            a.seg[g].ptr[(size_t)n * a.seg[g].img_stride + a.seg[g].base +
+                         (size_t)s * a.seg[g].pix_stride + (co - a.seg[g].co_begin)] = v;
 }
 
 }  // namespace ctdet

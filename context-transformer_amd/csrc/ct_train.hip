@@ -3,11 +3,10 @@
 // backward, bias+ReLU backward, max-pool backward and the head-gradient gather.  The data gradient
 // of a convolution is the `transposed` mode of ct_conv2d_fwd (ct_conv.hip).
 #include "ct_common.h"
+#include "ct_conv_launch.h"
 #include "ct_device.h"
 #include "ct_f16x2.h"
 #include <algorithm>
-#include <mutex>
-#include <unordered_set>
 
 namespace {
 
@@ -230,7 +229,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(const WgradArgs a)
         for (int i = 0; i < TB; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * hsel;
+                const int m = m0 + wm0 + 32 * i + ctdet::acc_row(r, hsel);
                 if (m < a.Cout) unsafeAtomicAdd(a.dw + (size_t)m * a.Ncols + col, acc[i][j][r] + acc2[i][j][r]);
             }
     }
@@ -792,15 +791,7 @@ static int wgrad_impl(const ct_conv_desc* d, const float* dz, int dz_ctot, int d
     const size_t smem = (pipelined ? 4 : 2) * 64 * (size_t)(bt + 1) * 4;
     hipError_t le = hipSuccess;
     auto go = [&](auto kernel) {
-        if (smem > 64 * 1024) {
-            static std::mutex mu;
-            static std::unordered_set<const void*> done;
-            std::lock_guard<std::mutex> lk(mu);
-            if (!done.count((const void*)kernel)) {
-                le = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-                done.insert((const void*)kernel);
-            }
-        }
+        le = ctdet::raise_lds_limit((const void*)kernel, smem);
         if (le == hipSuccess) hipLaunchKernelGGL(kernel, grid, block, smem, st, a);
     };
 #define CT_WGRAD_GO(KH, KW)                                                    \

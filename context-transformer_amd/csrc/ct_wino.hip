@@ -292,7 +292,7 @@ __global__ __launch_bounds__(512) void wino_f2x2_3x3_f32(const WinoArgs a)
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int k = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int k = i * 32 + ctdet::acc_row(r, h);
                     lds[(2 * wave + x) * MXI + k * MS + l31] = tbk == 0 ? acc[x][i][0][r] : acc[x][i][1][r];
                 }
         __syncthreads();

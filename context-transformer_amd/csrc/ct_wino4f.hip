@@ -473,11 +473,11 @@ __global__ __launch_bounds__(512) void wino_f4x4_3x3_x3(const Wino4fArgs a_in)
             for (int p = 0; p < 4; ++p)
 #pragma unroll
                 for (int r = 0; r < 8; ++r)
-                    lds[(xi0 + p) * (16 * 32) + ((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + l31] = acc[2 * p + (q >> 1)][8 * (q & 1) + r];
+                    lds[(xi0 + p) * (16 * 32) + ctdet::acc_row(r, h) * 32 + l31] = acc[2 * p + (q >> 1)][8 * (q & 1) + r];
             if ((wave & 1) == (q >> 1)) {
 #pragma unroll
                 for (int r = 0; r < 8; ++r)
-                    lds[xi_half * (16 * 32) + ((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + l31] = acc[8][8 * (q & 1) + r];
+                    lds[xi_half * (16 * 32) + ctdet::acc_row(r, h) * 32 + l31] = acc[8][8 * (q & 1) + r];
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();

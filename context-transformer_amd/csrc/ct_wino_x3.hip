@@ -365,7 +365,7 @@ __global__ __launch_bounds__(512) void wino_f2x2_3x3_x3(const WinoX3Args a)
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int k = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int k = i * 32 + ctdet::acc_row(r, h);
                 lds[(2 * wave + x) * MXI + k * MS + l31] = acc[x][i][r];
             }
     __syncthreads();

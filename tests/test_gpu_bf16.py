@@ -24,8 +24,10 @@ def _close(got, want):
 
 
 def _conv_bf16(x, parts, stride, pad, dil, relu, res=None, res_scale=1.0, out_ctot=None, out_coff=0, cin_off=0, cin=None,
-               ksplit=0):
-    """x [B,ctot,H,W] fp32, parts = [w [Cout_i,Cin,k,k]]; -> [B, sum Cout, OH, OW] fp32 of the bf16 result."""
+               ksplit=0, segs=None):
+    """x [B,ctot,H,W] fp32, parts = [w [Cout_i,Cin,k,k]]; -> [B, sum Cout, OH, OW] fp32 of the bf16 result.
+    segs = [(co_begin, co_end, base, size)]: the multibox head form (fp32, channels-last per segment, rows of `size` floats per
+    image, NaN-filled) -> the list of [B, size] buffers instead, and the reference before any rounding to bf16."""
     lib = _lib.lib()
     B, ctot, H, W = x.shape
     cin = cin if cin is not None else ctot - cin_off
@@ -53,6 +55,11 @@ def _conv_bf16(x, parts, stride, pad, dil, relu, res=None, res_scale=1.0, out_ct
     d.wpacked, d.scale, d.shift = wp.data_ptr(), scale.data_ptr(), shift.data_ptr()
     d.cout, d.kh, d.kw, d.stride, d.pad_h, d.pad_w, d.dil, d.oh, d.ow = cout, kh, kw, stride, pad, pad, dil, OH, OW
     d.out, d.out_ctot, d.out_coff, d.relu = yb.data_ptr(), octot, out_coff, int(relu)
+    flats = [torch.full((B, size), float('nan'), device=DEV) for (_c0, _c1, _base, size) in segs or []]
+    for g_, (c0, c1, base, size) in enumerate(segs or []):
+        d.out, d.nseg = None, len(segs)
+        sg = d.seg[g_]
+        sg.ptr, sg.co_begin, sg.co_end, sg.pix_stride, sg.img_stride, sg.base = flats[g_].data_ptr(), c0, c1, c1 - c0, size, base
     rb = None
     if res is not None:
         rd = res.to(DEV).contiguous()
@@ -72,6 +79,8 @@ def _conv_bf16(x, parts, stride, pad, dil, relu, res=None, res_scale=1.0, out_ct
         want = want * res_scale + res.bfloat16().float()
     if relu:
         want = F.relu(want)
+    if segs:
+        return [f.cpu() for f in flats], want, yb
     return y.cpu(), want.bfloat16().float(), yb
 
 
@@ -145,6 +154,32 @@ def test_conv_bf16_split_k():
         assert _close(got, want), ks
         again, _, _ = _conv_bf16(x, [w], 1, 1, 1, True, res=res, res_scale=0.7, ksplit=ks)
         assert torch.equal(got, again), 'split-K must be run-to-run deterministic'
+
+
+def test_conv_bf16_split_k_into_head_segments():
+    """nseg > 0 through conv_bf16_splitk_epilogue: batch 2, 64 channels, 5x5 map, 3x3 pad 1, segments of 24 + 12 + 6 = 42 output
+    channels (a ragged last 32-channel block, segment boundaries inside and across the blocks), ksplit 3 against the unsplit launch
+    and the torch reference; outside the segments nothing is written, and a second run is bit-equal."""
+    g = torch.Generator().manual_seed(42)
+    B, H, W, couts = 2, 5, 5, (24, 12, 6)
+    x = torch.randn(B, 64, H, W, generator=g)
+    parts = [torch.randn(c, 64, 3, 3, generator=g) * 0.06 for c in couts]
+    segs, c0 = [], 0
+    for c in couts:
+        segs.append((c0, c0 + c, 7 * c, 7 * c + H * W * c + 5 * c))
+        c0 += c
+    unsplit, want, _ = _conv_bf16(x, parts, 1, 1, 1, False, segs=segs)
+    split, _, _ = _conv_bf16(x, parts, 1, 1, 1, False, segs=segs, ksplit=3)
+    again, _, _ = _conv_bf16(x, parts, 1, 1, 1, False, segs=segs, ksplit=3)
+    assert (want < 0).any()
+    for g_, (c0, c1, base, size) in enumerate(segs):
+        cnt = H * W * (c1 - c0)
+        ref = want[:, c0:c1].permute(0, 2, 3, 1).reshape(B, -1)
+        for tag, flat in (('unsplit', unsplit[g_]), ('ksplit3', split[g_])):
+            assert torch.isnan(flat[:, :base]).all() and torch.isnan(flat[:, base + cnt:]).all(), (tag, g_)
+            assert _close(flat[:, base:base + cnt], ref), (tag, g_, (flat[:, base:base + cnt] - ref).abs().max())
+        assert _close(split[g_][:, base:base + cnt], unsplit[g_][:, base:base + cnt]), g_
+        assert torch.equal(split[g_].view(torch.int32), again[g_].view(torch.int32)), 'split-K must be run-to-run deterministic'
 
 
 def test_maxpool_nhwc_bf16():

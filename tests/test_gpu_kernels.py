@@ -208,6 +208,39 @@ def test_conv_split_k():
     assert torch.isnan(got[:, :5]).all() and torch.isnan(got[:, 69:]).all()
 
 
+def check_split_k_head_segments(**kernel):
+    """Split-K into the flattened head buffers (nseg > 0), through the finishing kernel's scatter: batch 2, 64 channels, 5x5 map,
+    3x3 pad 1, three segments of 24 + 12 + 6 = 42 output channels -- a ragged last 32-row block with segment boundaries inside
+    and across the blocks -- at ksplit 3 against the unsplit launch and the fp64 torch reference; what lies outside the segments
+    stays as it was (NaN) and a second run is bit-equal.  kernel: config= / x3= of test_gpu_absmax._launch."""
+    from test_gpu_absmax import _launch, _ref           # (that module imports this one)
+    g = torch.Generator().manual_seed(42)
+    B, Cin, H, W, couts = 2, 64, 5, 5, (24, 12, 6)
+    x = torch.randn(B, Cin, H, W, generator=g)
+    parts = [(torch.randn(c, Cin, 3, 3, generator=g) * 0.06, torch.rand(c, generator=g) - 0.5, None, False) for c in couts]
+    segs, c0 = [], 0
+    for name, c in zip(('loc', 'conf', 'obj'), couts):
+        segs.append((name, c0, c0 + c, 7 * c, 7 * c + H * W * c + 5 * c))       # channels [c0, c0 + c) at base 7 c of a longer row
+        c0 += c
+    want = _ref(x, parts, 1, 1, 1)
+    unsplit = _launch(x, parts, 1, 1, 1, segs=segs, ksplit=0, track=False, **kernel)['flat']
+    split = _launch(x, parts, 1, 1, 1, segs=segs, ksplit=3, track=False, **kernel)['flat']
+    again = _launch(x, parts, 1, 1, 1, segs=segs, ksplit=3, track=False, **kernel)['flat']
+    for (n, c0, c1, base, size) in segs:
+        cnt = H * W * (c1 - c0)
+        ref = want[:, c0:c1].permute(0, 2, 3, 1).reshape(B, -1)
+        for tag, flat in (('unsplit', unsplit[n]), ('ksplit3', split[n])):
+            assert flat.shape == (B, size)
+            assert torch.isnan(flat[:, :base]).all() and torch.isnan(flat[:, base + cnt:]).all(), (kernel, tag, n)
+            assert rel_err(flat[:, base:base + cnt], ref) < TOL, (kernel, tag, n)
+        assert rel_err(split[n][:, base:base + cnt], unsplit[n][:, base:base + cnt]) < TOL, (kernel, n)
+        assert torch.equal(split[n].view(torch.int32), again[n].view(torch.int32)), (kernel, n, 'split-K must be run-to-run deterministic')
+
+
+def test_conv_split_k_into_head_segments():
+    check_split_k_head_segments(config=0)
+
+
 def test_maxpool_variants():
     g = torch.Generator().manual_seed(3)
     # (19, 19) / (32, 32) / odd shapes with k 3, stride 1, pad 1: the plane kernel of pool5 (one plane, odd plane counts,

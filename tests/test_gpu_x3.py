@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 from conftest import rel_err
 from ctdet import _lib
-from test_gpu_kernels import CONV_CASES, TOL, _bn, _ref_conv, _run_conv
+from test_gpu_kernels import CONV_CASES, TOL, _bn, _ref_conv, _run_conv, check_split_k_head_segments
 
 pytestmark = pytest.mark.gpu
 
@@ -76,6 +76,32 @@ def test_x3_split_k_deterministic():
             assert rel_err(got, want) < TOL, (ks, cfg)
             again = _run_conv(x, [(w, None, bn, True)], 1, 1, 1, res=res, res_scale=0.7, ksplit=ks, x3=cfg)
             assert torch.equal(got, again)
+
+
+@pytest.mark.parametrize('cfg', [0, 2, 6, 8], ids=['x3k16', 'x3k32', 'h2k16', 'h2k32'])
+def test_x3_split_k_into_head_segments(cfg):
+    """bf16x3 and f16x2, k-steps of 16 and 32 channels (the f16x2 slabs hold scaled sums: the finishing kernel unscales)."""
+    lib = _lib.lib()
+    assert lib.ct_conv_x3_config_bk(cfg) == (16 if cfg in (0, 6) else 32) and lib.ct_conv_x3_config_h2(cfg) == int(cfg >= 6)
+    check_split_k_head_segments(x3=cfg)
+
+
+def test_x3_split_k_with_a_per_channel_floor():
+    """Mixed ReLU / non-ReLU parts (ct_conv_desc.lo is non-null: a floor per output channel) through the finishing kernel, into a
+    channel slice of a wider buffer: the second half of test_gpu_kernels.test_conv_split_k on this kernel."""
+    g = torch.Generator().manual_seed(21)
+    x2 = torch.randn(3, 512, 10, 10, generator=g)
+    w1 = torch.randn(40, 512, 1, 1, generator=g) * 0.05
+    w2 = torch.randn(24, 512, 1, 1, generator=g) * 0.05
+    parts = [(w1, None, _bn(40, g), True), (w2, None, _bn(24, g), False)]
+    want = _ref_conv(x2, parts, 2, 0, 1)
+    assert (want[:, 40:] < 0).any()                     # the non-ReLU part keeps negative values
+    for cfg in (1, 3, 7, 9):                            # k-steps of 16 and 32 channels, bf16x3 and f16x2
+        got = _run_conv(x2, parts, 2, 0, 1, out_ctot=80, out_coff=5, ksplit=4, x3=cfg)
+        assert rel_err(got[:, 5:69], want) < TOL, cfg
+        assert torch.isnan(got[:, :5]).all() and torch.isnan(got[:, 69:]).all(), cfg
+        again = _run_conv(x2, parts, 2, 0, 1, out_ctot=80, out_coff=5, ksplit=4, x3=cfg)
+        assert torch.equal(got[:, 5:69], again[:, 5:69]), cfg
 
 
 GATE_CASES = [  # the non-Winograd layers of RFBNet-300 with the longest reductions: B, Cin, H, W, Cout, k, pad, dil
