@@ -8,6 +8,7 @@
 // exactly as the uint8 image cv2 returns.
 #include "ct_common.h"
 #include <algorithm>
+#include <cstdlib>
 
 namespace {
 
@@ -98,7 +99,7 @@ struct AugPlan {            // one image; mirrors the python struct in ctdet/ops
     int H, W;
     int crop_l, crop_t, crop_w, crop_h;
     int exp_w, exp_h, exp_left, exp_top;      // canvas size (= crop size when not expanded) and placement
-    int mirror, interp;                       // interp: 0 linear, 1 nearest, 2 area
+    int mirror, interp;                       // interp: 0 linear, 1 nearest, 2 area; 3 bicubic, 4 Lanczos4 (taps entry only)
     int flags, hue_delta;                     // flags: 1 brightness, 2 contrast, 4 hue, 8 saturation
     float beta, alpha, sat_alpha;
     float fill[3];
@@ -151,32 +152,35 @@ __device__ inline void distort_px(int& b, int& g, int& r, const AugPlan& p)
     r = min(max(__float2int_rn(R), 0), 255);
 }
 
-// pixel (x, y) of the image that enters the resize: mirror -> canvas -> crop -> source (+ distortion)
-__device__ inline void final_px(const unsigned char* __restrict__ img, const AugPlan& p, int x, int y, float (&o)[3])
+// pixel (x, y) of the image that enters the resize: mirror -> canvas -> crop -> source (+ distortion), 8 bit
+__device__ inline void final_px_u8(const unsigned char* __restrict__ img, const AugPlan& p, int x, int y, int (&o)[3])
 {
     if (p.mirror) x = p.exp_w - 1 - x;
     const int cx = x - p.exp_left, cy = y - p.exp_top;
     if ((unsigned)cx >= (unsigned)p.crop_w || (unsigned)cy >= (unsigned)p.crop_h) {
-        o[0] = (float)(int)p.fill[0]; o[1] = (float)(int)p.fill[1]; o[2] = (float)(int)p.fill[2];   // means cast to uint8
+        o[0] = (int)p.fill[0]; o[1] = (int)p.fill[1]; o[2] = (int)p.fill[2];   // means cast to uint8
         return;
     }
     const unsigned char* s = img + ((long)(p.crop_t + cy) * p.W + (p.crop_l + cx)) * 3;
     int b = s[0], g = s[1], r = s[2];
     if (p.flags) distort_px(b, g, r, p);
-    o[0] = (float)b; o[1] = (float)g; o[2] = (float)r;
+    o[0] = b; o[1] = g; o[2] = r;
 }
 
-__global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __restrict__ src, const AugPlan* __restrict__ plans,
-                                                      float* __restrict__ out, int S, float m0, float m1, float m2)
+__device__ inline void final_px(const unsigned char* __restrict__ img, const AugPlan& p, int x, int y, float (&o)[3])
 {
-    const int n = blockIdx.y;
-    const AugPlan p = plans[n];
-    const unsigned char* img = src + p.src_off;
-    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= S * S) return;
-    const int dy = pix / S, dx = pix - dy * S;
+    int v[3];
+    final_px_u8(img, p, x, y, v);
+    o[0] = (float)v[0]; o[1] = (float)v[1]; o[2] = (float)v[2];
+}
+
+// output pixel (dx, dy) of the float filters (interp 0 linear, 1 nearest, 2 area; anything else runs as linear), before
+// rounding.  The one definition both augmentation kernels call.
+__device__ inline void float_filter_px(const unsigned char* __restrict__ img, const AugPlan& p, int S, int dx, int dy,
+                                       float (&acc)[3])
+{
     const float sx = (float)p.exp_w / S, sy = (float)p.exp_h / S;
-    float acc[3] = {0.f, 0.f, 0.f};
+    acc[0] = acc[1] = acc[2] = 0.f;
     if (p.interp == 1) {                        // INTER_NEAREST: floor(d * scale)
         final_px(img, p, min((int)floorf(dx * sx), p.exp_w - 1), min((int)floorf(dy * sy), p.exp_h - 1), acc);
     } else if (p.interp == 2 && (sx > 1.f || sy > 1.f)) {      // INTER_AREA when shrinking: fractional box average
@@ -208,11 +212,144 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
         for (int c = 0; c < 3; ++c)
             acc[c] = (1.f - fy) * ((1.f - fx) * v00[c] + fx * v01[c]) + fy * ((1.f - fx) * v10[c] + fx * v11[c]);
     }
+}
+
+// cv2.resize returns uint8: round to nearest, then float32 minus mean
+__device__ inline void store_float_px(const float (&acc)[3], float* __restrict__ o, int S, float m0, float m1, float m2)
+{
     const float mean[3] = {m0, m1, m2};
-    float* o = out + (long)n * 3 * S * S + pix;
 #pragma unroll
-    for (int c = 0; c < 3; ++c)       // cv2.resize returns uint8: round to nearest, then float32 minus mean
+    for (int c = 0; c < 3; ++c)
         o[(long)c * S * S] = fminf(fmaxf(rintf(acc[c]), 0.f), 255.f) - mean[c];
+}
+
+__global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __restrict__ src, const AugPlan* __restrict__ plans,
+                                                      float* __restrict__ out, int S, float m0, float m1, float m2)
+{
+    const int n = blockIdx.y;
+    const AugPlan p = plans[n];
+    const unsigned char* img = src + p.src_off;
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= S * S) return;
+    const int dy = pix / S, dx = pix - dy * S;
+    float acc[3];
+    float_filter_px(img, p, S, dx, dy, acc);
+    store_float_px(acc, out + (long)n * 3 * S * S + pix, S, m0, m1, m2);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The two higher-order filters (interp 3 bicubic, 4 Lanczos4): OpenCV's 8-bit separable fixed-point resize.  The
+// taps (`first` index and 11-bit coefficients per output coordinate) are HOST decisions like the rest of the plan
+// (ctdet/ops.py resize_taps: the Lanczos4 coefficients need a double sin/cos, which a device evaluates differently
+// in the last bit); the device does integer work only, so its pixels are bit-reproducible:
+//   h[r][d] = sum_j cx[d][j] * P(clamp(first_x[d] + j), r),   v = sum_j cy[d][j] * h[clamp(first_y[d] + j)][.],
+//   pixel = clamp((v + 2^21) >> 22, 0, 255).
+// The kernel clamps every index it forms from a table to the canvas, so no table content can make it read outside
+// the image.  Sums wrap modulo 2^32 (unsigned accumulation): defined for every table, meaningful for those whose
+// rows keep |v| inside int32 (include/ctdet.h).
+constexpr int TAP_TW = 32, TAP_TH = 8;          // output tile of one workgroup (256 threads, one pixel each)
+constexpr int TAP_LDS_WORDS = 9728;             // 38 KiB: packed source window + horizontal pass; 4 workgroups per CU
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+__device__ __forceinline__ float tap_result(unsigned v, float mean)
+{
+    return (float)clampi((int)(v + (1u << 21)) >> 22, 0, 255) - mean;
+}
+
+// One workgroup = one 32x8 output tile of one image, so every branch on the plan or on the tile's window is
+// block-uniform.  interp 0..2 (and unknown values): float_filter_px, the code of augment_kernel.  interp 3 / 4:
+//   tiled form   the tile's source window goes through final_px_u8 (crop, canvas, mirror, distortion) ONCE per source
+//                pixel into LDS as packed BGR, then a horizontal pass into an int32 LDS image, then the vertical pass;
+//   gather form  a thread evaluates final_px_u8 k x k times for its own pixel -- any canvas size; taken when the
+//                window does not fit TAP_LDS_WORDS, when the canvas fill is no 8-bit value, or when tiled == 0.
+// Both forms add the same integers modulo 2^32, so they agree bit for bit.
+__global__ __launch_bounds__(256) void augment_taps_kernel(const unsigned char* __restrict__ src, const AugPlan* __restrict__ plans,
+                                                           const ct_resize_tap* __restrict__ taps, float* __restrict__ out,
+                                                           int S, int tiles_x, int tiled, float m0, float m1, float m2)
+{
+    __shared__ ct_resize_tap tap_x[TAP_TW], tap_y[TAP_TH];
+    __shared__ unsigned lds[TAP_LDS_WORDS];
+    const int n = blockIdx.y, tid = threadIdx.x;
+    const AugPlan p = plans[n];
+    const unsigned char* img = src + p.src_off;
+    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const int lx = tid % TAP_TW, ly = tid / TAP_TW;
+    const int dx = tile_x * TAP_TW + lx, dy = tile_y * TAP_TH + ly;
+    const bool live = dx < S && dy < S;
+    float* o = out + (long)n * 3 * S * S + (long)dy * S + dx;
+    if (p.interp != 3 && p.interp != 4) {
+        if (!live) return;
+        float acc[3];
+        float_filter_px(img, p, S, dx, dy, acc);
+        store_float_px(acc, o, S, m0, m1, m2);
+        return;
+    }
+    const int k = p.interp == 3 ? 4 : 8;
+    const int nx = p.exp_w, ny = p.exp_h;
+    // the tile's tap records; coordinates past the image edge reuse the last one (computed, never stored)
+    const ct_resize_tap* tab = taps + (long)n * 2 * S;
+    if (tid < TAP_TW) tap_x[tid] = tab[min(tile_x * TAP_TW + tid, S - 1)];
+    else if (tid < TAP_TW + TAP_TH) tap_y[tid - TAP_TW] = tab[S + min(tile_y * TAP_TH + (tid - TAP_TW), S - 1)];
+    __syncthreads();
+    // source window of the tile: min / max over the clamped indices the passes below will form (no order assumed)
+    int x0 = nx - 1, x1 = 0, y0 = ny - 1, y1 = 0;
+    for (int i = 0; i < TAP_TW; ++i) {
+        x0 = min(x0, clampi(tap_x[i].first, 0, nx - 1));
+        x1 = max(x1, clampi(tap_x[i].first + k - 1, 0, nx - 1));
+    }
+    for (int i = 0; i < TAP_TH; ++i) {
+        y0 = min(y0, clampi(tap_y[i].first, 0, ny - 1));
+        y1 = max(y1, clampi(tap_y[i].first + k - 1, 0, ny - 1));
+    }
+    const long ww = (long)x1 - x0 + 1, wh = (long)y1 - y0 + 1;
+    const bool fill_u8 = (unsigned)(int)p.fill[0] < 256u && (unsigned)(int)p.fill[1] < 256u && (unsigned)(int)p.fill[2] < 256u;
+    unsigned v[3] = {0u, 0u, 0u};
+    if (tiled && fill_u8 && ww > 0 && wh > 0 && ww * wh + 3 * wh * TAP_TW <= TAP_LDS_WORDS) {
+        const int w = (int)ww, h = (int)wh;
+        unsigned* hbuf = lds + w * h;                         // [3][h][TAP_TW]
+        for (int i = tid; i < w * h; i += 256) {
+            const int y = i / w, x = i - y * w;
+            int c[3];
+            final_px_u8(img, p, x0 + x, y0 + y, c);
+            lds[i] = (unsigned)c[0] | (unsigned)c[1] << 8 | (unsigned)c[2] << 16;
+        }
+        __syncthreads();
+        for (int i = tid; i < h * TAP_TW; i += 256) {         // horizontal pass: row r of the window, output column d
+            const int r = i / TAP_TW, d = i - r * TAP_TW;
+            unsigned a[3] = {0u, 0u, 0u};
+            for (int j = 0; j < k; ++j) {
+                const unsigned px = lds[r * w + clampi(tap_x[d].first + j, 0, nx - 1) - x0];
+                const unsigned cf = (unsigned)(int)tap_x[d].c[j];
+                a[0] += cf * (px & 255u); a[1] += cf * (px >> 8 & 255u); a[2] += cf * (px >> 16);
+            }
+            hbuf[i] = a[0]; hbuf[h * TAP_TW + i] = a[1]; hbuf[2 * h * TAP_TW + i] = a[2];
+        }
+        __syncthreads();
+        for (int j = 0; j < k; ++j) {                         // vertical pass
+            const int r = clampi(tap_y[ly].first + j, 0, ny - 1) - y0;
+            const unsigned cf = (unsigned)(int)tap_y[ly].c[j];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] += cf * hbuf[(c * h + r) * TAP_TW + lx];
+        }
+    } else {
+        for (int jy = 0; jy < k; ++jy) {
+            const int y = clampi(tap_y[ly].first + jy, 0, ny - 1);
+            unsigned a[3] = {0u, 0u, 0u};
+            for (int jx = 0; jx < k; ++jx) {
+                int c[3];
+                final_px_u8(img, p, clampi(tap_x[lx].first + jx, 0, nx - 1), y, c);
+                const unsigned cf = (unsigned)(int)tap_x[lx].c[jx];
+                a[0] += cf * (unsigned)c[0]; a[1] += cf * (unsigned)c[1]; a[2] += cf * (unsigned)c[2];
+            }
+            const unsigned cf = (unsigned)(int)tap_y[ly].c[jy];
+            v[0] += cf * a[0]; v[1] += cf * a[1]; v[2] += cf * a[2];
+        }
+    }
+    if (!live) return;
+    o[0] = tap_result(v[0], m0);
+    o[(long)S * S] = tap_result(v[1], m1);
+    o[2L * S * S] = tap_result(v[2], m2);
 }
 
 __global__ __launch_bounds__(256) void mixup_blend_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -238,6 +375,23 @@ extern "C" int ct_preproc_augment(const unsigned char* src, const void* plans, i
     hipLaunchKernelGGL(augment_kernel, grid, dim3(256), 0, ctdet::as_stream(stream), src, (const AugPlan*)plans, out, size,
                        means3[0], means3[1], means3[2]);
     CT_LAUNCH_CHECK("augment_kernel");
+    return CT_OK;
+}
+
+extern "C" int ct_preproc_augment_taps(const unsigned char* src, const void* plans, const ct_resize_tap* taps, int batch,
+                                       int size, const float* means3, float* out, ct_stream_t stream)
+{
+    CT_REQUIRE(src && plans && taps && out && means3, "ct_preproc_augment_taps: null pointer");
+    CT_REQUIRE(batch > 0 && batch <= 65535 && size > 0 && size <= 4096, "ct_preproc_augment_taps: batch=%d size=%d", batch, size);
+    static_assert(sizeof(ct_resize_tap) == 20, "ct_resize_tap layout is mirrored in ctdet/_lib.py");
+    static const int tiled = [] {                   // CTDET_AUG_TILED=0: gather form everywhere (read once)
+        const char* e = getenv("CTDET_AUG_TILED");
+        return !(e && e[0] == '0' && e[1] == 0);
+    }();
+    const int tiles_x = (size + TAP_TW - 1) / TAP_TW, tiles_y = (size + TAP_TH - 1) / TAP_TH;
+    hipLaunchKernelGGL(augment_taps_kernel, dim3(tiles_x * tiles_y, batch), dim3(256), 0, ctdet::as_stream(stream), src,
+                       (const AugPlan*)plans, taps, out, size, tiles_x, tiled, means3[0], means3[1], means3[2]);
+    CT_LAUNCH_CHECK("augment_taps_kernel");
     return CT_OK;
 }
 

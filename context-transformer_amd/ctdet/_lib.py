@@ -66,6 +66,11 @@ class SgdTensor(C.Structure):
                 ('lr', C.c_float), ('weight_decay', C.c_float), ('first_step', C.c_int)]
 
 
+class ResizeTap(C.Structure):
+    """ct_resize_tap: first source index (unclamped) and the 11-bit coefficients of one output coordinate."""
+    _fields_ = [('first', C.c_int), ('c', C.c_short * 8)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -209,6 +214,7 @@ SIGNATURES = {
     'ct_maxpool2d_fwd': (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
     'ct_preproc_resize': (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     'ct_preproc_augment': (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    'ct_preproc_augment_taps': (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     'ct_mixup_blend': (_I, [_P, _P, _P, _I, _L, _P, _P]),
     'ct_ctx_pool_fwd': (_I, [_P, _LL, _P, _LL, _I, _I, _I, _I, _I, _P]),
     'ct_ctx_attention_workspace_bytes': (_Z, [_I, _I, _I, _I]),

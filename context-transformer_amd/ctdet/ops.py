@@ -5,6 +5,7 @@ hand-written HIP kernels through ctypes and raises if the tensors are not on a H
 there is deliberately NO CPU / PyTorch fallback for these ops.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -318,6 +319,72 @@ class Preprocessor:
         return out
 
 
+# ------------------------------------------------------------------ resize taps (host decisions of the augmentation)
+RESIZE_TAPS = {'cubic': 4, 'lanczos4': 8}           # kind -> taps per axis; AugPlan.interp 3 and 4
+INTERP_KIND = {3: 'cubic', 4: 'lanczos4'}
+TAP_DTYPE = np.dtype([('first', '<i4'), ('c', '<i2', (8,))])        # ct_resize_tap
+assert TAP_DTYPE.itemsize == C.sizeof(_lib.ResizeTap) == 20
+
+
+def resize_coeffs(x, kind):
+    """float32 fractions [S] -> int16 [S, k]: OpenCV's bicubic (A = -0.75) / Lanczos4 weights in float32, as 11-bit
+    fixed point (round half to even, saturated).  The Lanczos4 kernel is OpenCV's sin/cos form, trigonometry in
+    double; that double sin/cos is why this is host work (include/ctdet.h)."""
+    f32 = np.float32
+    x = np.asarray(x, dtype=f32)
+    if kind == 'cubic':
+        A, xp, xm = f32(-0.75), x + f32(1), f32(1) - x
+        c0 = ((A * xp - f32(5) * A) * xp + f32(8) * A) * xp - f32(4) * A
+        c1 = ((A + f32(2)) * x - (A + f32(3))) * x * x + f32(1)
+        c2 = ((A + f32(2)) * xm - (A + f32(3))) * xm * xm + f32(1)
+        w = np.stack([c0, c1, c2, f32(1) - c0 - c1 - c2], 1)
+    elif kind == 'lanczos4':
+        s = 0.70710678118654752440084436210485
+        cs = np.array([[1, 0], [-s, -s], [0, 1], [s, -s], [-1, 0], [s, s], [0, -1], [-s, s]])
+        y0 = -(x.astype(np.float64) + 3.0) * np.pi * 0.25
+        s0, c0 = np.sin(y0), np.cos(y0)
+        t = (x + f32(3))[:, None] - np.arange(8, dtype=f32)[None, :]           # float32, like OpenCV's `x+3-i`
+        y = -t.astype(np.float64) * np.pi * 0.25
+        near = np.abs(t) < f32(1e-6)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            w = ((cs[None, :, 0] * s0[:, None] + cs[None, :, 1] * c0[:, None]) / (y * y)).astype(f32)
+        w[near] = f32(1e30)
+        total = np.zeros(len(x), dtype=f32)
+        for i in range(8):                          # float32 sum in tap order
+            total = total + w[:, i]
+        w = w * (f32(1) / total)[:, None]
+    else:
+        raise ValueError('resize_coeffs: kind %r (known: %s)' % (kind, sorted(RESIZE_TAPS)))
+    assert w.dtype == f32
+    return np.clip(np.rint(w * f32(2048)), -32768, 32767).astype(np.int16)
+
+
+@functools.lru_cache(maxsize=4096)
+def resize_taps(n_src, S, kind):
+    """Taps of one axis of cv2.resize's 8-bit bicubic / Lanczos4 path, n_src source pixels -> S output pixels:
+    (first int32 [S] = floor(f), ic int16 [S, k]); tap j of output d reads source index
+    clamp(first[d] - (k/2 - 1) + j, 0, n_src - 1).  No edge reset of the fraction, unlike the linear filter.
+    Cached per (n_src, S, kind); the arrays are read-only."""
+    if kind not in RESIZE_TAPS:
+        raise ValueError('resize_taps: kind %r (known: %s)' % (kind, sorted(RESIZE_TAPS)))
+    scale = 1.0 / (S / float(n_src))
+    f = ((np.arange(S) + 0.5) * scale - 0.5).astype(np.float32)
+    fl = np.floor(f)
+    first, ic = fl.astype(np.int32), resize_coeffs(f - fl, kind)
+    first.setflags(write=False)
+    ic.setflags(write=False)
+    return first, ic
+
+
+def tap_records(n_src, S, kind):
+    """The S ct_resize_tap records of one axis: `first` unclamped at the first tap (the kernel clamps)."""
+    first, ic = resize_taps(int(n_src), int(S), kind)
+    rec = np.zeros(S, dtype=TAP_DTYPE)
+    rec['first'] = first - (RESIZE_TAPS[kind] // 2 - 1)
+    rec['c'][:, :ic.shape[1]] = ic
+    return rec
+
+
 class AugPlan(C.Structure):
     """One image's augmentation decisions (csrc/ct_preproc.hip AugPlan, 96 bytes)."""
     _fields_ = [('src_off', C.c_longlong), ('H', C.c_int), ('W', C.c_int),
@@ -333,7 +400,8 @@ assert C.sizeof(AugPlan) == 96
 
 class Augmenter:
     """Batched training-time augmentation (data/data_augment.py:164-221) on the device: the host hands over the
-    uint8 images and one AugPlan per image (the random decisions); ONE launch writes float32 [B,3,S,S]."""
+    uint8 images and one AugPlan per image (the random decisions); ONE launch writes float32 [B,3,S,S].  A batch
+    with a bicubic or Lanczos4 image (interp 3 / 4) also carries their taps and goes to ct_preproc_augment_taps."""
 
     def __init__(self, size, means, device, max_batch=32, max_pixels=512 * 512):
         self.size, self.device, self.max_batch = size, torch.device(device), max_batch
@@ -344,6 +412,7 @@ class Augmenter:
         self.dev = torch.empty(self.cap, dtype=torch.uint8, device=self.device)
         self.plan_h = torch.empty(max_batch * 96, dtype=torch.uint8).pin_memory()
         self.plan_d = torch.empty(max_batch * 96, dtype=torch.uint8, device=self.device)
+        self.tap_h = self.tap_d = None      # ct_resize_tap staging, allocated by the first batch that needs it
         self.copied = None
 
     def __call__(self, images, plans, out=None):
@@ -382,9 +451,28 @@ class Augmenter:
         self.copied.record()
         if out is None:
             out = torch.empty(n, 3, self.size, self.size, device=self.device, dtype=torch.float32)
-        check(lib().ct_preproc_augment(_dev(self.dev, 'src', torch.uint8), _dev(self.plan_d, 'plans', torch.uint8), n,
-                                       self.size, C.cast(self.means, C.c_void_p), _dev(out, 'out'), _stream()),
-              'ct_preproc_augment')
+        if not any(p['interp'] in INTERP_KIND for p in plans):
+            check(lib().ct_preproc_augment(_dev(self.dev, 'src', torch.uint8), _dev(self.plan_d, 'plans', torch.uint8), n,
+                                           self.size, C.cast(self.means, C.c_void_p), _dev(out, 'out'), _stream()),
+                  'ct_preproc_augment')
+            return out
+        # bicubic / Lanczos4 images: their taps are host decisions too (resize_taps), uploaded like the plans
+        S = self.size
+        if self.tap_h is None:
+            self.tap_h = torch.zeros(self.max_batch * 2 * S * 20, dtype=torch.uint8).pin_memory()
+            self.tap_d = torch.zeros(self.max_batch * 2 * S * 20, dtype=torch.uint8, device=self.device)
+        recs_t = np.zeros((n, 2, S), dtype=TAP_DTYPE)               # images with interp 0..2 ignore theirs
+        for i, p in enumerate(plans):
+            kind = INTERP_KIND.get(p['interp'])
+            if kind:
+                recs_t[i, 0], recs_t[i, 1] = tap_records(p['exp'][0], S, kind), tap_records(p['exp'][1], S, kind)
+        nb = n * 2 * S * 20
+        self.tap_h[:nb] = torch.from_numpy(recs_t.reshape(-1).view(np.uint8))
+        self.tap_d[:nb].copy_(self.tap_h[:nb], non_blocking=True)
+        self.copied.record()
+        check(lib().ct_preproc_augment_taps(_dev(self.dev, 'src', torch.uint8), _dev(self.plan_d, 'plans', torch.uint8),
+                                            _dev(self.tap_d, 'taps', torch.uint8), n, S, C.cast(self.means, C.c_void_p),
+                                            _dev(out, 'out'), _stream()), 'ct_preproc_augment_taps')
         return out
 
 

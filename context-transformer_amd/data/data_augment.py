@@ -8,10 +8,12 @@ distortion -> expand -> mirror -> resize -> minus means, returning (CHW tensor, 
 MI355X way: the random DECISIONS are the reference's scalar host logic -- drawn here with the same `random` calls in
 the same order, so a seeded run makes the same choices -- and produce a 96-byte plan per image; the PIXELS of a whole
 batch are then produced by one gather kernel (`ct_preproc_augment`) that never materialises the cropped / distorted /
-expanded intermediates.  `preproc.batch(images, targets)` is the batched entry that keeps 8 GPUs fed;
-`mixup_targets` / `mixup_images` are the mixup of data/voc0712.py:240-275.
+expanded intermediates.  `filters='cv2'` (or CTDET_AUG_FILTERS=cv2) adds the bicubic and Lanczos4 resize filters the
+reference also draws (`ct_preproc_augment_taps`); the default maps those two draws onto linear.
+`preproc.batch(images, targets)` is the batched entry that keeps 8 GPUs fed; `mixup_targets` / `mixup_images` are the mixup of data/voc0712.py:240-275.
 """
 import math
+import os
 import random
 
 import numpy as np
@@ -21,9 +23,11 @@ from ctdet import ops
 from utils.box_utils import matrix_iou
 
 CROP_MODES = (None, (0.1, None), (0.3, None), (0.5, None), (0.7, None), (0.9, None), (None, None))
-# preproc_for_test draws one of cv2's [LINEAR, CUBIC, AREA, NEAREST, LANCZOS4]; the device kernel has
-# linear (0), nearest (1) and area (2) -- the two higher-order filters run as linear (augmentation noise either way)
+# preproc_for_test draws one of cv2's [LINEAR, CUBIC, AREA, NEAREST, LANCZOS4].  The device has all five: linear (0),
+# nearest (1), area (2), bicubic (3) and Lanczos4 (4).  'fast', the default, runs the two higher-order draws as linear
+# (one float gather launch, no tap tables); 'cv2' gives each draw the filter the reference uses.
 INTERP_OF_DRAW = (0, 0, 2, 1, 0)
+INTERP_FILTERS = {'fast': INTERP_OF_DRAW, 'cv2': (0, 3, 2, 1, 4)}
 
 
 class BaseTransform(object):
@@ -56,7 +60,14 @@ def _plan(h, w):
 
 
 class preproc(object):
-    def __init__(self, resize, rgb_means, p, device='cuda', max_batch=32, rng=None):
+    def __init__(self, resize, rgb_means, p, device='cuda', max_batch=32, rng=None, filters=None):
+        """filters: 'fast' or 'cv2' (INTERP_FILTERS); None reads CTDET_AUG_FILTERS, default 'fast'.  Either way the
+        random draws are the same in number and order."""
+        if filters is None:
+            filters = os.environ.get('CTDET_AUG_FILTERS', 'fast')
+        if filters not in INTERP_FILTERS:
+            raise ValueError('preproc: filters=%r (known: %s)' % (filters, ', '.join(sorted(INTERP_FILTERS))))
+        self.filters, self.interp_of_draw = filters, INTERP_FILTERS[filters]
         self.means, self.resize, self.p = rgb_means, resize, p
         self.device, self.max_batch = torch.device(device), max_batch
         self.rng = rng or random          # the reference uses the module-level generator
@@ -148,7 +159,7 @@ class preproc(object):
             plan['mirror'] = 1
             boxes = boxes.copy()
             boxes[:, 0::2] = width - boxes[:, 2::-2]
-        plan['interp'] = INTERP_OF_DRAW[rng.randrange(5)]            # preproc_for_test (:158-161)
+        plan['interp'] = self.interp_of_draw[rng.randrange(5)]            # preproc_for_test (:158-161)
         boxes = boxes.copy()
         boxes[:, 0::2] /= width
         boxes[:, 1::2] /= height
@@ -156,7 +167,7 @@ class preproc(object):
         bt, lt = boxes[keep], labels[keep].copy()
         if len(bt) == 0 or (cls is not None and (lt != (cls + 1)).all()):
             plan = _plan(height_o, width_o)              # the original image, resized (:205-212)
-            plan['interp'] = INTERP_OF_DRAW[rng.randrange(5)]
+            plan['interp'] = self.interp_of_draw[rng.randrange(5)]
             return plan, targets_o
         return plan, np.hstack((bt, np.expand_dims(lt, 1)))
 

@@ -709,6 +709,33 @@ int ct_preproc_resize(const unsigned char* src, const long long* offsets, const 
  * not in this image): tolerance-based parity. */
 int ct_preproc_augment(const unsigned char* src, const void* plans, int batch, int size, const float* means3,
                        float* out, ct_stream_t stream);
+
+/* One output coordinate of a separable fixed-point resize filter: source index of its first tap and the 11-bit
+ * coefficients (2048 = 1.0) of taps first, first + 1, ...  The 4-tap filter uses c[0..3], the rest 0. */
+typedef struct { int first; short c[8]; } ct_resize_tap;   /* 20 bytes */
+
+/* ct_preproc_augment plus the two filters cv2.resize draws besides linear / nearest / area: plan.interp 3 =
+ * bicubic (4 taps), 4 = Lanczos4 (8 taps), as OpenCV's 8-bit path computes them -- two separable passes in int32:
+ *   h[r][d] = sum_j cx[d][j] * P(ix[d][j], r),   v = sum_j cy[d][j] * h[iy[d][j]][.],
+ *   pixel = clamp((v + 2^21) >> 22, 0, 255), then minus mean, CHW,
+ * P being the image that enters the resize (crop, distortion, canvas, mirror: the plan, unchanged layout).
+ * `taps` = device array of batch * 2 * size records, image n's at taps + n*2*size: `size` records for x, then
+ * `size` for y.  They are host decisions like the plan (ctdet/ops.py resize_taps: the Lanczos4 coefficients need a
+ * double sin / cos that host and device round differently); the device does integer work only, so its pixels are
+ * bit-reproducible.
+ * SAFETY RULE: `first` is stored unclamped (floor(f) - (k/2 - 1)); the KERNEL clamps first + j to [0, n-1] of the
+ * canvas before every read, so no table content can make it read outside the image -- this entry cannot inspect
+ * device tables, the clamp is what makes foreign tables memory-safe.
+ * Results are defined only for tables whose rows keep |v| inside int32; those of the two filters do (positive taps
+ * of a row sum to <= 2780, |v| <= 255 * 2780^2 < 2^31).  Foreign tables are memory-safe but otherwise unspecified.
+ * Images with interp 0..2 ignore their tables and come out bit-identical to ct_preproc_augment on the same plans
+ * (one device function serves both kernels); ct_preproc_augment itself keeps treating unknown interp values as
+ * linear.  Two forms of the same integer sums, chosen per workgroup: the source window of a 32x8 output tile
+ * staged once in LDS when it fits, a per-pixel gather otherwise; CTDET_AUG_TILED=0 (read once per process) forces
+ * the gather form everywhere.  They agree bit for bit. */
+int ct_preproc_augment_taps(const unsigned char* src, const void* plans, const ct_resize_tap* taps, int batch,
+                            int size, const float* means3, float* out, ct_stream_t stream);
+
 /* mixup of two image batches, data/voc0712.py:262: out = img1 * lambd[n] + img2 * (1 - lambd[n]). */
 int ct_mixup_blend(const float* img1, const float* img2, const float* lambd, int batch, long per_image,
                    float* out, ct_stream_t stream);
