@@ -77,6 +77,7 @@ _F = C.c_float
 _Z = C.c_size_t
 _L = C.c_long
 _LL = C.c_longlong
+_D = C.c_double
 
 # name -> (restype, argtypes); every symbol include/ctdet.h declares
 SIGNATURES = {
@@ -109,6 +110,8 @@ SIGNATURES = {
     'ct_sgd_step': (_I, [C.POINTER(SgdTensor), _I, _F, _F, _I, _F, _P]),
     'ct_postprocess_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    'ct_voc_match': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _D, _P, _P, _I, _P, _P]),
+    'ct_voc_pr': (_I, [_P, _P, _LL, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     'ct_conv_kpad': (_I, [_I, _I, _I]),
     'ct_conv_mpad': (_I, [_I]),
     'ct_conv_num_configs': (_I, []),

@@ -14,15 +14,21 @@ from .pipeline import DetectionPipeline
 
 
 def detect_dataset(net, priors, dataset, transform, num_fg, batch=32, max_per_image=200, thresh=0.01,
-                   force_cpu_rule=False, progress=None):
-    """-> all_boxes[cls][img] (cls 0 = background, empty lists as in test.py:107-108)."""
+                   force_cpu_rule=False, progress=None, evaluator=None, keep_boxes=True):
+    """-> all_boxes[cls][img] (cls 0 = background, empty lists as in test.py:107-108).
+
+    evaluator: an evaluate.DeviceVOCEvaluator over this data set (image i of the data set = its image_ids[i]); every
+    batch's device output is handed to evaluator.add, the padding images of the ragged last batch as -1.
+    keep_boxes=False: no host copy of the detections at all -- no per-batch synchronisation -- and None is returned;
+    the post-processing's overflow flag is collected on the device and looked at once, after the last batch."""
     n = len(dataset)
-    all_boxes = [[[] for _ in range(n)] for _ in range(num_fg + 1)]
+    all_boxes = [[[] for _ in range(n)] for _ in range(num_fg + 1)] if keep_boxes else None
     if n == 0:
         return all_boxes
     pipe = DetectionPipeline(net, priors, batch, num_fg, conf_thresh=thresh, max_per_image=max_per_image,
                              force_cpu_rule=force_cpu_rule)
     dev = pipe.device
+    overflowed = None if keep_boxes else torch.zeros_like(pipe.post.overflow)
     x = torch.zeros(batch, 3, net.size, net.size, device=dev)
     for start in range(0, n, batch):
         m = min(batch, n - start)
@@ -37,22 +43,42 @@ def detect_dataset(net, priors, dataset, transform, num_fg, batch=32, max_per_im
                 x[k].copy_(transform(img), non_blocking=True)
         if m < batch:
             x[m:].zero_()
-        pipe.run(x, image_wh=wh)
-        per_image = pipe.results()
-        for k in range(m):
-            for j in range(1, num_fg + 1):
-                all_boxes[j][start + k] = per_image[k][j]
+        out_dets, out_count = pipe.run(x, image_wh=wh)
+        if evaluator is not None:
+            evaluator.add(out_dets, out_count, [start + k if k < m else -1 for k in range(batch)])
+        if keep_boxes:
+            per_image = pipe.results()
+            for k in range(m):
+                for j in range(1, num_fg + 1):
+                    all_boxes[j][start + k] = per_image[k][j]
+        else:
+            overflowed |= pipe.post.overflow
         if progress is not None:
             progress(start + m, n)
+    if overflowed is not None and int(overflowed.item()):
+        raise evaluate.CtdetError('postprocess output capacity %d exceeded; raise out_cap' % pipe.post.cap)
     return all_boxes
 
 
 def do_test(net, priors, dataset, transform, num_fg, save_folder, batch=32, max_per_image=200, thresh=0.01,
-            force_cpu_rule=False, retest=False):
-    """test.py:96-175: detect, write `detections.pkl`, hand over to the dataset's evaluator."""
+            force_cpu_rule=False, retest=False, evaluator=None, keep_boxes=True):
+    """test.py:96-175: detect, write `detections.pkl`, hand over to the dataset's evaluator.
+
+    With `evaluator` (evaluate.DeviceVOCEvaluator) the second result is its (aps, mean) instead of the data set's own
+    evaluation; keep_boxes=False then also skips the host copies and `detections.pkl`, and the first result is None."""
     import pickle
+    if retest and (evaluator is not None or not keep_boxes):
+        raise ValueError('retest reads detections.pkl: it has nothing to feed a device evaluator and needs the boxes')
+    if evaluator is None and not keep_boxes:
+        raise ValueError('keep_boxes=False needs an evaluator: nothing would be left of the detections')
     os.makedirs(save_folder, exist_ok=True)
     det_file = os.path.join(save_folder, 'detections.pkl')
+    if evaluator is not None:
+        all_boxes = detect_dataset(net, priors, dataset, transform, num_fg, batch, max_per_image, thresh,
+                                   force_cpu_rule, evaluator=evaluator, keep_boxes=keep_boxes)
+        if keep_boxes:
+            evaluate.save_detections(all_boxes, det_file)
+        return all_boxes, evaluator.finish()
     if retest:
         with open(det_file, 'rb') as f:
             all_boxes = pickle.load(f)

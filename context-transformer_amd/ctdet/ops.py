@@ -270,6 +270,31 @@ class PostProcessor:
         return res
 
 
+# ------------------------------------------------------------------ VOC evaluation
+def voc_match(out_dets, out_count, image_index, ev, cap):
+    """ct_voc_match of one pipeline batch into the buffers of `ev` (evaluate.DeviceVOCEvaluator): the packed ground
+    truth gt_boxes / gt_label / gt_difficult / gt_off, the records keys / flags and the status words."""
+    check(lib().ct_voc_match(_dev(out_dets, 'out_dets'), _dev(out_count, 'out_count', torch.int32), out_dets.shape[0],
+                             ev.T, int(cap), _dev(image_index, 'image_index', torch.int32), ev.N,
+                             _dev(ev.gt_boxes, 'gt_boxes'), _dev(ev.gt_label, 'gt_label', torch.int32),
+                             _dev(ev.gt_difficult, 'gt_difficult', torch.uint8), _dev(ev.gt_off, 'gt_off', torch.int32),
+                             ev.G, ev.max_gt, float(ev.ovthresh), _dev(ev.keys, 'keys', torch.int64),
+                             _dev(ev.flags, 'flags', torch.uint8), ev.per_image_cap,
+                             _dev(ev.status, 'status', torch.int32), _stream()), 'ct_voc_match')
+
+
+def voc_pr(ev, order, cls_off, thresholds=None):
+    """ct_voc_pr over the records of `ev` in the order of the key sort: fills ev.rec / ev.prec (sorted positions) and
+    ev.ap.  thresholds: host float64 array for the VOC07 rule (np.arange(0., 1.1, 0.1)), None for the area metric."""
+    thr = np.ascontiguousarray(thresholds if thresholds is not None else [], dtype=np.float64)
+    ev.pr_status.zero_()
+    check(lib().ct_voc_pr(_dev(ev.flags, 'flags', torch.uint8), _dev(order, 'order', torch.int64), ev.flags.numel(),
+                          _dev(cls_off, 'cls_off', torch.int64), _dev(ev.num_pos, 'num_pos', torch.int32), ev.T,
+                          thr.ctypes.data_as(C.c_void_p), len(thr), _dev(ev.rec, 'rec', torch.float64),
+                          _dev(ev.prec, 'prec', torch.float64), _dev(ev.ap, 'ap', torch.float64),
+                          _dev(ev.pr_status, 'pr_status', torch.int32), _stream()), 'ct_voc_pr')
+
+
 # ------------------------------------------------------------------ input transform
 class Preprocessor:
     """Batched BaseTransform (data/data_augment.py:224-266) on the device: uint8 HxWx3 images of

@@ -240,6 +240,70 @@ int ct_postprocess_batched(const float* boxes, const float* scores, int batch, i
                            int* out_index, int* overflow,
                            void* workspace, size_t workspace_bytes, ct_stream_t stream);
 
+/* ------------------------------------------------- PASCAL VOC evaluation ---- */
+
+/* data/voc0712.py:339-426 (`_do_python_eval`) + data/voc_eval.py:134-203 (`voc_eval`) on the device, fed from the
+ * buffers the post-processing leaves: the match rule per pipeline batch (ct_voc_match), then -- after the caller has
+ * sorted the 64-bit keys -- the precision / recall curve and the AP per class (ct_voc_pr).  Host twin:
+ * ctdet/evaluate.py voc_eval_lines with stable=True; the two agree bit for bit in rec, prec and the 11-point AP.
+ *
+ * ct_voc_match: one launch per batch, no allocation, no host synchronisation, plain vector stores.
+ *   out_dets dev [B,T,cap,5], out_count dev [B,T]     as the post-processing writes them (each segment in descending
+ *                                                     score order); counts are clamped to 0 .. cap
+ *   image_index dev [B]                               data set index of each image; < 0 = padding image, ignored
+ *   gt_boxes dev [G,4] fp32 (VOC pixel coordinates: integers, exact), gt_label dev int [G] in 1 .. T,
+ *   gt_difficult dev uint8 [G], gt_off dev int [num_images+1] indexed by data set index; an image's boxes of one class
+ *   keep the order of the annotation (the first maximal IoU wins, as np.argmax).  max_gt_per_image = the largest
+ *   gt_off[i+1] - gt_off[i], computed by the caller: above CT_VOC_MAX_GT_PER_IMAGE the call is CT_ERR_INVALID.
+ * Every kept row is first rounded the way the results files round it (data/voc0712.py:360-376):
+ *   coordinate c -> rint((double)(c + 1.0f) * 10) / 10.0   == float('{:.1f}'.format(c + 1)), the + 1 in fp32 like numpy
+ *   score s      -> n = rint((double)s * 1000)             == the integer '{:.3f}'.format(s) prints, half-even
+ * then matched within its (image, class) segment in evaluation order -- n descending, then row ascending: the stored
+ * order of a descending segment -- (voc_eval.py:160-190): IoU in double with the + 1 pixel
+ * convention and the host's operation order, best = first maximum; IoU > ovthresh: a difficult box makes the row
+ * neither, a free box a true positive (the box is taken), a taken box a false positive; anything else, no ground truth
+ * of the class included, is a false positive.
+ * Records: row number e of the image in (class, row) order goes to slot image_index * per_image_cap + e of
+ *   rec_key dev int64 [num_images * per_image_cap]:  class-1 << 53 | (2^20-1 - n) << 33 | image_index << 12 | row
+ *   rec_flag dev uint8 [num_images * per_image_cap]: CT_VOC_TP / CT_VOC_FP / CT_VOC_NEITHER
+ * so that ascending keys = (class ascending, n descending, image ascending, row ascending) = the order a stable
+ * argsort(-score) of the results lines gives.  Keys are unique; the caller fills unused slots with
+ * CT_VOC_KEY_UNUSED, which sorts last.  Hence num_fg <= 1023, cap <= 4096, num_images <= 2^21.
+ * status dev int [2], zeroed by the caller once: status[0] collects CT_VOC_OVERFLOW (an image has more rows than
+ * per_image_cap: none of its rows is written), CT_VOC_BAD_INDEX (image_index >= num_images, or a gt_off entry outside
+ * 0 .. num_gt, descending, or more than CT_VOC_MAX_GT_PER_IMAGE apart: the image is skipped) and CT_VOC_BAD_SCORE (a
+ * score whose n is outside 0 .. 2^20-1 or NaN: clamped); status[1] = the largest row count of an image seen so far, the
+ * per_image_cap to ask for.  Feeding one image twice is not detected: the later records replace the earlier ones. */
+#define CT_VOC_MAX_GT_PER_IMAGE 1024
+#define CT_VOC_MAX_THRESHOLDS 16
+#define CT_VOC_KEY_UNUSED INT64_MAX
+enum { CT_VOC_NEITHER = 0, CT_VOC_TP = 1, CT_VOC_FP = 2 };
+enum { CT_VOC_OVERFLOW = 1, CT_VOC_BAD_INDEX = 2, CT_VOC_BAD_SCORE = 4 };
+int ct_voc_match(const float* out_dets, const int* out_count, int batch, int num_fg, int cap,
+                 const int* image_index, int num_images, const float* gt_boxes, const int* gt_label,
+                 const uint8_t* gt_difficult, const int* gt_off, int num_gt, int max_gt_per_image,
+                 double ovthresh, long long* rec_key, uint8_t* rec_flag, int per_image_cap, int* status,
+                 ct_stream_t stream);
+/* data/voc_eval.py:192-201 + voc_ap (:33-66): one workgroup per class c = 0 .. num_fg-1 over the rows
+ * cls_off[c] .. cls_off[c+1]-1 of the sorted order.
+ *   rec_flag dev uint8 [num_records]; order dev int64 [num_records] = the permutation of the key sort (row i of the
+ *   sorted order has flag rec_flag[order[i]]), or NULL when rec_flag is already in sorted order
+ *   cls_off dev int64 [num_fg+1] (the first sorted position of each class's keys; ascending, within 0 .. num_records)
+ *   num_pos dev int [num_fg]: the class's non-difficult ground-truth boxes
+ * tp / fp are scanned as integers; rec = tp / num_pos and prec = tp / max(tp + fp, DBL_EPSILON) in double go to
+ * rec_out / prec_out (dev double [num_records], sorted positions; either may be NULL).  ap_out dev double [num_fg]:
+ *   num_thresholds > 0: the VOC07 rule over thresholds_host (host double [num_thresholds], np.arange(0., 1.1, 0.1) for
+ *     the reference's 11 points; copied into the launch): p = max prec over rec >= t, else 0; ap = ap + p / num_thresholds
+ *     in threshold order -- equal to the host's value;
+ *   num_thresholds == 0: the area under the monotone precision envelope; its terms equal the host's, the order of the
+ *     sum differs from np.sum's pairwise order (at most (number of recall steps) * 2^-52 apart).
+ * A class without rows gives 0.0; num_pos == 0 with rows gives 0.0 (11-point) / NaN (area), as on the host.
+ * status dev int [1]: collects CT_VOC_BAD_INDEX for a cls_off or order entry out of range (never dereferenced). */
+int ct_voc_pr(const uint8_t* rec_flag, const long long* order, long long num_records,
+              const long long* cls_off, const int* num_pos, int num_fg, const double* thresholds_host,
+              int num_thresholds, double* rec_out, double* prec_out, double* ap_out, int* status,
+              ct_stream_t stream);
+
 /* ------------------------------------------------------------ convolution ---- */
 
 /* One fused convolution of the RFBNet-VGG stack.  Replaces the ATen sequence
