@@ -33,6 +33,7 @@
 #include "ct_wino4_emit.h"
 #include "ct_f16x2.h"
 #include <algorithm>
+#include <atomic>
 #include <cstddef>
 #include <cstdlib>
 #include <mutex>
@@ -98,6 +99,7 @@ struct Wino4fArgs {
     const unsigned* in_amax;
     const int* eU;
     unsigned* out_amax;      // any form: ct_conv_desc.out_absmax, max |y| of what the launch stores, or null
+    unsigned pool_bytes;     // bytes of the pooled output this launch may touch (the LEAN epilogue stores it through a descriptor)
 };
 
 // The epilogue's view of the arguments (ct_wino4_emit.h is a template over any record with these members).  The persistent
@@ -141,7 +143,9 @@ __device__ unsigned long long* g_w4f_trace = nullptr;
 // PLAIN: no residual, no per-channel floor, no head scatter (a.res == a.lo == nullptr, a.nseg == 0): what the narrow trunk layers
 // this kernel exists for use (bias + ReLU, optionally the fused 2x2 max-pool) -- the epilogue then needs a third of the scalar
 // registers and none of those branches.
-template <bool SEG, bool PLAIN, bool H2>
+// LEAN (PLAIN only): the output passes work out a tile's geometry once per item and run ct_wino4_emit.h's straight-line
+// emit_tile4_plain per quarter instead of emit_tile4 (same bits; CTDET_W4F_LEAN_EPI=0 launches the LEAN = false twin).
+template <bool SEG, bool PLAIN, bool H2, bool LEAN = false>
 __global__ __launch_bounds__(512) void wino_f4x4_3x3_x3(const Wino4fArgs a_in)
 {
     const Wino4fArgs& a = a_in;
@@ -467,6 +471,22 @@ __global__ __launch_bounds__(512) void wino_f4x4_3x3_x3(const Wino4fArgs a_in)
         if constexpr (H2) ymul = ctdet::h2::unscale_for(*e.eU, ctdet::h2::image_exponent(e.in_amax, o_T < a.NT ? o_n : 0, ctdet::h2::kGrowthBtB));
         const int o_rem = o_T - o_n * (a.TY * a.TX);
         const int o_ty = o_rem / a.TX, o_tx = o_rem - o_ty * a.TX;
+        static_assert(!LEAN || PLAIN, "the lean epilogue is the PLAIN one");
+        // LEAN: the tile's rows, columns, offsets and pooling windows for channel kb KB + o_kk, once; a quarter adds 16 q planes
+        const __amdgpu_buffer_rsrc_t rpool = make_rsrc(e.pool_out, LEAN && e.pool_out ? e.pool_bytes : 0u);
+        ctdet::w4::Tile4Plan plan;
+        float sc4[4] = {0.f, 0.f, 0.f, 0.f}, sh4[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (LEAN) {
+            ctdet::w4::plan_tile4(ep, o_T < a.NT, o_n, o_ty, o_tx, kb * KB + o_kk, plan);
+            // the four quarters' scale and shift leave here, in front of every store of the item (a channel past the last reads 0
+            // through the descriptor and is not used)
+            const __amdgpu_buffer_rsrc_t rsc = make_rsrc(e.scale, (unsigned)a.M * 4u), rsh = make_rsrc(e.shift, (unsigned)a.M * 4u);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                sc4[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsc, (kb * KB + o_kk + 16 * q) * 4, 0, 0));
+                sh4[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsh, (kb * KB + o_kk + 16 * q) * 4, 0, 0));
+            }
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
@@ -512,7 +532,10 @@ __global__ __launch_bounds__(512) void wino_f4x4_3x3_x3(const Wino4fArgs a_in)
                     float y[4][4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) at4(z[i], y[i]);
-                    ctdet::w4::emit_tile4(ep, rout, rres, n, ty, tx, co, y, ymul.lo, ymul.hi, H2 && e.out_amax != nullptr, amax_run);
+                    if constexpr (LEAN)
+                        ctdet::w4::emit_tile4_plain(ep, plan, rout, rpool, sc4[q], sh4[q], 16 * q, y, ymul.lo, ymul.hi, H2 && e.out_amax != nullptr, amax_run);
+                    else
+                        ctdet::w4::emit_tile4(ep, rout, rres, n, ty, tx, co, y, ymul.lo, ymul.hi, H2 && e.out_amax != nullptr, amax_run);
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -598,6 +621,27 @@ extern "C" int ct_conv_pack_weights_wino4f_h2_dgrad(const float* const* w, const
     return ctdet::pack_wino_h2(w, cout, nparts, cin, 1, 48, upacked, stream, "ct_conv_pack_weights_wino4f_h2_dgrad");
 }
 
+// Which epilogue the PLAIN launches run: the lean one, or emit_tile4's per-row one (the A/B switch).  CTDET_W4F_LEAN_EPI=0 selects the
+// latter; the variable is read ONCE, at the first launch that asks.  ct_wino4f_set_lean_epilogue overrides it inside a process (the
+// bit-identity tests run both twins): 1 / 0 = lean / per-row, negative = back to what the environment says.  A captured graph keeps
+// the kernel it was captured with.
+static std::atomic<int> g_lean_epilogue{-1};          // -1: not resolved yet
+static bool lean_epilogue_on()
+{
+    int v = g_lean_epilogue.load(std::memory_order_relaxed);
+    if (v < 0) {
+        static const int from_env = [] { const char* e = std::getenv("CTDET_W4F_LEAN_EPI"); return e && e[0] == '0' ? 0 : 1; }();
+        v = from_env;
+    }
+    return v != 0;
+}
+
+extern "C" int ct_wino4f_set_lean_epilogue(int on)
+{
+    g_lean_epilogue.store(on < 0 ? -1 : (on != 0 ? 1 : 0), std::memory_order_relaxed);
+    return CT_OK;
+}
+
 static int wino4f_launch(const ct_conv_desc* d, const void* upacked, int variant, const ctdet::PoolOut& pool, ct_stream_t stream,
                          const char* who)
 {
@@ -617,12 +661,14 @@ static int wino4f_launch(const ct_conv_desc* d, const void* upacked, int variant
         std::call_once(once, [] {
             const void* fs[] = {(const void*)wino_f4x4_3x3_x3<false, false, false>, (const void*)wino_f4x4_3x3_x3<false, true, false>,
                                 (const void*)wino_f4x4_3x3_x3<true, false, false>, (const void*)wino_f4x4_3x3_x3<false, false, true>,
-                                (const void*)wino_f4x4_3x3_x3<false, true, true>, (const void*)wino_f4x4_3x3_x3<true, false, true>};
+                                (const void*)wino_f4x4_3x3_x3<false, true, true>, (const void*)wino_f4x4_3x3_x3<true, false, true>,
+                                (const void*)wino_f4x4_3x3_x3<false, true, false, true>, (const void*)wino_f4x4_3x3_x3<false, true, true, true>};
             for (const void* f : fs)
                 if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, W4F_LDS_BYTES);
         });
         CT_HIP(attr_err);
     }
+    const bool lean_on = lean_epilogue_on();
     for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) {
         const int nb = std::min(lim.max_chunk, d->batch - b0);
         Wino4fArgs a{};
@@ -634,6 +680,10 @@ static int wino4f_launch(const ct_conv_desc* d, const void* upacked, int variant
         a.out_amax = d->out_absmax ? d->out_absmax + (size_t)b0 * ctdet::h2::kLineWords : nullptr;
         a.eU = h2 ? reinterpret_cast<const int*>(static_cast<const unsigned char*>(upacked) + u_bytes) + 1 : nullptr;
         a.kblocks = (d->cout + KB - 1) / KB;
+        // the lean epilogue addresses the pooled output with 32-bit offsets through a descriptor: it has to stay below 2 GiB too
+        const long long pool_bytes = a.pool_out ? (long long)nb * pool.pool_ctot * pool.pool_oh * pool.pool_ow * 4 : 0;
+        const bool lean = lean_on && pool_bytes < kMaxBufBytes;
+        a.pool_bytes = lean ? (unsigned)pool_bytes : 0u;
         // 8 XCD-local sequences of (tile block group, cout block); sequences past the last tile block exit at once
         const int groups = (a.tile_blocks + 7) / 8;
         const int items = 8 * groups * a.kblocks;
@@ -648,10 +698,12 @@ static int wino4f_launch(const ct_conv_desc* d, const void* upacked, int variant
         const dim3 grid(std::min(items, cus));
         if (h2) {
             if (a.nseg > 0) hipLaunchKernelGGL((wino_f4x4_3x3_x3<true, false, true>), grid, dim3(512), W4F_LDS_BYTES, st, a);
+            else if (!a.res && !a.lo && lean) hipLaunchKernelGGL((wino_f4x4_3x3_x3<false, true, true, true>), grid, dim3(512), W4F_LDS_BYTES, st, a);
             else if (!a.res && !a.lo) hipLaunchKernelGGL((wino_f4x4_3x3_x3<false, true, true>), grid, dim3(512), W4F_LDS_BYTES, st, a);
             else hipLaunchKernelGGL((wino_f4x4_3x3_x3<false, false, true>), grid, dim3(512), W4F_LDS_BYTES, st, a);
         } else {
             if (a.nseg > 0) hipLaunchKernelGGL((wino_f4x4_3x3_x3<true, false, false>), grid, dim3(512), W4F_LDS_BYTES, st, a);
+            else if (!a.res && !a.lo && lean) hipLaunchKernelGGL((wino_f4x4_3x3_x3<false, true, false, true>), grid, dim3(512), W4F_LDS_BYTES, st, a);
             else if (!a.res && !a.lo) hipLaunchKernelGGL((wino_f4x4_3x3_x3<false, true, false>), grid, dim3(512), W4F_LDS_BYTES, st, a);
             else hipLaunchKernelGGL((wino_f4x4_3x3_x3<false, false, false>), grid, dim3(512), W4F_LDS_BYTES, st, a);
         }

@@ -192,6 +192,7 @@ SIGNATURES = {
     'ct_conv_pack_weights_wino4f_h2_dgrad': (_I, [_P, _P, _I, _I, _P, _P]),
     'ct_conv2d_wino4f_pool_fwd_v': (_I, [C.POINTER(ConvDesc), _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     'ct_conv2d_wino4f_fwd': (_I, [C.POINTER(ConvDesc), _P, _P]),
+    'ct_wino4f_set_lean_epilogue': (_I, [_I]),
     'ct_conv2d_wino4f_pool_fwd': (_I, [C.POINTER(ConvDesc), _P, _P, _I, _I, _I, _I, _I, _P]),
     'ct_conv_wino4_supported': (_I, [C.POINTER(ConvDesc)]),
     'ct_conv_wino4_packed_floats': (_Z, [_I, _I]),

@@ -550,6 +550,11 @@ int ct_conv_pack_weights_wino4f_h2_dgrad(const float* const* w, const int* cout,
                                          ct_stream_t stream);
 int ct_conv2d_wino4f_pool_fwd_v(const ct_conv_desc* desc, const void* upacked, int variant, float* pool_out, int pool_ctot,
                                 int pool_coff, int pool_oh, int pool_ow, int write_full, ct_stream_t stream);
+/* The launches without residual, per-channel floor and head scatter run an epilogue that works out a tile's geometry once per work
+ * item; CTDET_W4F_LEAN_EPI=0 (read once per process) keeps the per-row epilogue of the other launches instead -- same bits, for the
+ * A/B.  This call overrides the variable inside a process: on = 1 / 0, negative = back to the environment's choice.  Not
+ * synchronised with launches in flight on other threads beyond the flag itself. */
+int ct_wino4f_set_lean_epilogue(int on);
 
 /* ---- "bf16x3": the fp32 convolution of ct_conv2d_fwd on the bf16 matrix pipe (csrc/ct_conv_x3.hip) ----
  * Same layers (models/RFB_Net_vgg.py:7-22 BasicConv, the plain Conv2d layers, the multibox heads :238-248), the same
