@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
+#include <mutex>
+#include <unordered_set>
 #include "ctdet.h"
 
 namespace ctdet {
@@ -63,6 +65,20 @@ int launch_pack_direct_batched(const void* items_dev, int n, hipStream_t st);
 int launch_pack_wino_batched(const void* items_dev, int n, hipStream_t st);
 size_t pack_direct_item_bytes();
 size_t pack_wino_item_bytes();
+
+// Kernels that ask for more than 64 KiB of dynamic LDS must opt in: one hipFuncSetAttribute per kernel and process.  A failed
+// attempt is returned and not remembered: the next launch of that kernel tries again.
+inline hipError_t raise_lds_limit(const void* fn, size_t bytes)
+{
+    if (bytes <= 64 * 1024) return hipSuccess;
+    static std::mutex mu;
+    static std::unordered_set<const void*> raised;
+    std::lock_guard<std::mutex> lock(mu);
+    if (raised.count(fn)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) raised.insert(fn);
+    return e;
+}
 
 template <typename T>
 __host__ __device__ inline T ceil_div(T a, T b) { return (a + b - 1) / b; }

@@ -1,7 +1,5 @@
 // Host-side launch code the direct convolution launchers share, written once (the style of ct_wino_launch.h: `who` first in
 // every message, nothing here allocates):
-//   raise_lds_limit    the opt-in to more than 64 KiB of LDS, once per kernel (ct_conv2d_fwd, ct_conv2d_x3_fwd,
-//                      ct_conv2d_bf16_fwd, ct_conv2d_wgrad);
 //   conv_check_*       the descriptor checks ct_conv2d_fwd and ct_conv2d_x3_fwd have in common.  Three functions, not one:
 //                      each launcher has checks of its own between them (packed-weight sizes, the f16x2 requirements, ...),
 //                      and callers see the order in which a descriptor is judged;
@@ -13,24 +11,8 @@
 #include "ct_device.h"
 #include "ct_f16x2.h"
 #include <algorithm>
-#include <mutex>
-#include <unordered_set>
 
 namespace ctdet {
-
-// Kernels that ask for more than 64 KiB of dynamic LDS must opt in: one hipFuncSetAttribute per kernel and process.  A failed
-// attempt is returned and not remembered: the next launch of that kernel tries again.
-inline hipError_t raise_lds_limit(const void* fn, size_t bytes)
-{
-    if (bytes <= 64 * 1024) return hipSuccess;
-    static std::mutex mu;
-    static std::unordered_set<const void*> raised;
-    std::lock_guard<std::mutex> lock(mu);
-    if (raised.count(fn)) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) raised.insert(fn);
-    return e;
-}
 
 // forward: (oh, ow) is the output size of an (h, w) input.  transposed (data gradient): (h, w) = spatial size of dY, (oh, ow) =
 // spatial size of dX, the forward convolution's input.  Then the input channel slice.

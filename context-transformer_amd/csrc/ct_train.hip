@@ -3,9 +3,9 @@
 // backward, bias+ReLU backward, max-pool backward and the head-gradient gather.  The data gradient
 // of a convolution is the `transposed` mode of ct_conv2d_fwd (ct_conv.hip).
 #include "ct_common.h"
-#include "ct_conv_launch.h"
 #include "ct_device.h"
 #include "ct_f16x2.h"
+#include "ct_wgrad_launch.h"
 #include <algorithm>
 
 namespace {
@@ -715,49 +715,17 @@ inline int grid_for(long total) { return (int)std::min<long>((total + 255) / 256
 
 }  // namespace
 
-static int wgrad_impl(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, bool zero,
-                      ct_stream_t stream);
-
-extern "C" int ct_conv2d_wgrad(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff,
-                               float* dw, ct_stream_t stream)
+// the images [b0, b0 + nb) of the batch; the first chunk zeroes dw
+static int wgrad_chunk(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, const ctdet::WgradLimits& lim,
+                       int b0, int nb, ct_stream_t stream)
 {
-    CT_REQUIRE(d && d->in && dz && dw, "ct_conv2d_wgrad: null pointer");
-    CT_REQUIRE(d->batch > 0 && d->cin > 0 && d->cout > 0, "ct_conv2d_wgrad: bad shape");
-    // buffers above 2 GiB (32-bit buffer offsets): batch chunks accumulate into the same dw
-    const long long img_x = (long long)d->in_ctot * d->h * d->w * 4, img_z = (long long)dz_ctot * d->oh * d->ow * 4;
-    CT_REQUIRE(img_x < kMaxBufBytes && img_z < kMaxBufBytes, "ct_conv2d_wgrad: one image exceeds 2 GiB");
-    const int max_chunk = (int)std::max<long long>(1, (kMaxBufBytes - 1) / std::max(img_x, img_z));
-    if (d->batch <= max_chunk) return wgrad_impl(d, dz, dz_ctot, dz_coff, dw, true, stream);
-    for (int b0 = 0; b0 < d->batch; b0 += max_chunk) {
-        ct_conv_desc sub = *d;
-        sub.batch = std::min(max_chunk, d->batch - b0);
-        sub.in = d->in + (size_t)b0 * (img_x / 4);
-        const int rc = wgrad_impl(&sub, dz + (size_t)b0 * (img_z / 4), dz_ctot, dz_coff, dw, b0 == 0, stream);
-        if (rc != CT_OK) return rc;
-    }
-    return CT_OK;
-}
-
-static int wgrad_impl(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, bool zero,
-                      ct_stream_t stream)
-{
-    CT_REQUIRE(d && d->in && dz && dw, "ct_conv2d_wgrad: null pointer");
-    CT_REQUIRE(d->batch > 0 && d->cin > 0 && d->cout > 0, "ct_conv2d_wgrad: bad shape");
-    CT_REQUIRE(dz_coff >= 0 && dz_coff + d->cout <= dz_ctot, "ct_conv2d_wgrad: dZ slice");
-    const int eoh = (d->h + 2 * d->pad_h - d->dil * (d->kh - 1) - 1) / d->stride + 1;
-    const int eow = (d->w + 2 * d->pad_w - d->dil * (d->kw - 1) - 1) / d->stride + 1;
-    CT_REQUIRE(eoh == d->oh && eow == d->ow, "ct_conv2d_wgrad: oh/ow mismatch");
-    const long long x_bytes = (long long)d->batch * d->in_ctot * d->h * d->w * 4;
-    const long long z_bytes = (long long)d->batch * dz_ctot * d->oh * d->ow * 4;
-    CT_REQUIRE(x_bytes < kMaxBufBytes && z_bytes < kMaxBufBytes,
-               "ct_conv2d_wgrad: buffers above 2 GiB are not supported yet (split the batch)");
     WgradArgs a{};
-    a.x = d->in; a.dz = dz; a.dw = dw;
-    a.x_bytes = (unsigned)x_bytes; a.dz_bytes = (unsigned)z_bytes;
-    a.Cin = d->cin; a.H = d->h; a.W = d->w; a.x_ctot = d->in_ctot; a.x_coff = d->in_coff;
-    a.Cout = d->cout; a.OW = d->ow; a.OHW = d->oh * d->ow; a.dz_ctot = dz_ctot; a.dz_coff = dz_coff;
+    ctdet::wgrad_fill(a, d, dz, dz_ctot, dz_coff, lim, b0, nb);
+    a.dw = dw;
+    a.H = d->h; a.W = d->w;
+    a.OW = d->ow; a.OHW = d->oh * d->ow;
     a.stride = d->stride; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.dil = d->dil;
-    a.Npix = d->batch * a.OHW;
+    a.Npix = nb * a.OHW;
     a.Ncols = d->cin * d->kh * d->kw;
     // the 128x128 variant (TB = 2) measured slower on the RFBNet shapes (fewer pixel splits in flight, the
     // 64 gathers per thread arrive in one burst); kept for experiments behind CTDET_WGRAD_TB=2
@@ -780,10 +748,11 @@ static int wgrad_impl(const ct_conv_desc* d, const float* dz, int dz_ctot, int d
         if (eff > best + 1e-9) { best = eff; splits = sp; }
         if (eff >= 0.92) break;
     }
-    a.pix_per_split = ((a.Npix + splits - 1) / splits + 63) / 64 * 64;
-    splits = (a.Npix + a.pix_per_split - 1) / a.pix_per_split;
+    const ctdet::Split sp = ctdet::even_split((a.Npix + 63) / 64, splits);       // in blocks of 64 pixels
+    a.pix_per_split = sp.per_split * 64;
+    splits = sp.splits;
     hipStream_t st = ctdet::as_stream(stream);
-    if (zero && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dw, 0, (size_t)d->cout * a.Ncols * 4, st));
+    if (b0 == 0 && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dw, 0, (size_t)d->cout * a.Ncols * 4, st));
     const bool tapmajor = d->cin % bt == 0 && !(getenv("CTDET_WGRAD_GENERIC"));
     const bool tapmajor_for_smem = tapmajor;
     const dim3 grid(tiles, splits), block(256);
@@ -810,6 +779,23 @@ static int wgrad_impl(const ct_conv_desc* d, const float* dz, int dz_ctot, int d
 #undef CT_WGRAD_GO
     CT_HIP(le);
     CT_LAUNCH_CHECK("conv_wgrad_f32");
+    return CT_OK;
+}
+
+extern "C" int ct_conv2d_wgrad(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff,
+                               float* dw, ct_stream_t stream)
+{
+    const char* who = "ct_conv2d_wgrad";
+    if (int rc = ctdet::wgrad_check_pointers(d, dz, dw, ctdet::no_workspace(), who)) return rc;
+    if (int rc = ctdet::wgrad_check_slices(d, dz_ctot, dz_coff, who)) return rc;
+    const int eoh = (d->h + 2 * d->pad_h - d->dil * (d->kh - 1) - 1) / d->stride + 1;
+    const int eow = (d->w + 2 * d->pad_w - d->dil * (d->kw - 1) - 1) / d->stride + 1;
+    CT_REQUIRE(eoh == d->oh && eow == d->ow, "%s: oh/ow mismatch", who);
+    // buffers above 2 GiB (32-bit buffer offsets): batch chunks accumulate into the same dw
+    ctdet::WgradLimits lim;
+    if (int rc = ctdet::wgrad_limits(d, dz_ctot, who, &lim, kMaxBufBytes - 1)) return rc;
+    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk)
+        if (int rc = wgrad_chunk(d, dz, dz_ctot, dz_coff, dw, lim, b0, std::min(lim.max_chunk, d->batch - b0), stream)) return rc;
     return CT_OK;
 }
 

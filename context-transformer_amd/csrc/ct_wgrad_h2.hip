@@ -23,7 +23,7 @@
 #include "ct_common.h"
 #include "ct_device.h"
 #include "ct_f16x2.h"
-#include <algorithm>
+#include "ct_wgrad_launch.h"
 
 namespace {
 
@@ -263,8 +263,9 @@ Layout layout_of(const ct_conv_desc* d)
     long want = std::max<long>(1, (512 + tiles - 1) / tiles);
     want = std::min<long>(want, std::max(1, l.stages / 2));
     want = std::min<long>(want, std::max<size_t>(1, kSlabBudget / l.dw_bytes));
-    l.stages_per_split = (int)((l.stages + want - 1) / want);
-    l.splits = (l.stages + l.stages_per_split - 1) / l.stages_per_split;
+    const ctdet::Split sp = ctdet::even_split(l.stages, (int)want);
+    l.stages_per_split = sp.per_split;
+    l.splits = sp.splits;
     return l;
 }
 
@@ -294,25 +295,20 @@ extern "C" int ct_conv2d_wgrad_h2(const ct_conv_desc* d, const float* dz, int dz
                                   const unsigned* dz_absmax, float* dw, void* workspace, size_t workspace_bytes,
                                   ct_stream_t stream)
 {
-    CT_REQUIRE(d, "ct_conv2d_wgrad_h2: d is null");
-    CT_REQUIRE(d->in, "ct_conv2d_wgrad_h2: d->in is null");
-    CT_REQUIRE(dz, "ct_conv2d_wgrad_h2: dz is null");
-    CT_REQUIRE(dw, "ct_conv2d_wgrad_h2: dw is null");
-    CT_REQUIRE(workspace, "ct_conv2d_wgrad_h2: workspace is null");
-    CT_REQUIRE(d->batch > 0 && d->cin > 0 && d->cout > 0 && d->h > 0 && d->w > 0, "ct_conv2d_wgrad_h2: bad shape in d");
+    const char* who = "ct_conv2d_wgrad_h2";
+    if (int rc = ctdet::wgrad_check_pointers(d, dz, dw, workspace, who)) return rc;
+    CT_REQUIRE(d->batch > 0 && d->cin > 0 && d->cout > 0 && d->h > 0 && d->w > 0, "%s: bad shape in d", who);
     if (!(d->kh == 1 && d->kw == 1 && d->pad_h == 0 && d->pad_w == 0 && d->dil == 1 && (d->stride == 1 || d->stride == 2)))
-        return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_wgrad_h2: geometry of d: needs a 1x1 filter, pad 0, dilation 1, "
-                           "stride 1 or 2 (got %dx%d pad %d,%d dilation %d stride %d)", d->kh, d->kw, d->pad_h, d->pad_w,
-                           d->dil, d->stride);
+        return ctdet::fail(CT_ERR_UNSUPPORTED, "%s: geometry of d: needs a 1x1 filter, pad 0, dilation 1, stride 1 or 2 (got %dx%d "
+                           "pad %d,%d dilation %d stride %d)", who, d->kh, d->kw, d->pad_h, d->pad_w, d->dil, d->stride);
     CT_REQUIRE(d->oh == (d->h - 1) / d->stride + 1 && d->ow == (d->w - 1) / d->stride + 1,
-               "ct_conv2d_wgrad_h2: oh/ow mismatch in d (%dx%d for a %dx%d input, stride %d)", d->oh, d->ow, d->h, d->w, d->stride);
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "ct_conv2d_wgrad_h2: input slice in_coff/in_ctot of d");
-    CT_REQUIRE(dz_coff >= 0 && dz_coff + d->cout <= dz_ctot, "ct_conv2d_wgrad_h2: dz slice dz_coff/dz_ctot");
-    const long long x_bytes = (long long)d->batch * d->in_ctot * d->h * d->w * 4;
-    const long long z_bytes = (long long)d->batch * dz_ctot * d->oh * d->ow * 4;
-    if (x_bytes >= kMaxBufBytes || z_bytes >= kMaxBufBytes)
-        return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_wgrad_h2: buffers of d->in / dz above 2 GiB are not built "
-                           "(ct_conv2d_wgrad takes them in batch chunks)");
+               "%s: oh/ow mismatch in d (%dx%d for a %dx%d input, stride %d)", who, d->oh, d->ow, d->h, d->w, d->stride);
+    if (int rc = ctdet::wgrad_check_slices(d, dz_ctot, dz_coff, who)) return rc;
+    // one launch covers the batch; an oversized one is a missing kernel here, not a bad argument
+    const ctdet::WgradLimits lim = ctdet::wgrad_sizes(d, dz_ctot);
+    if (lim.x_bytes >= kMaxBufBytes || lim.z_bytes >= kMaxBufBytes)
+        return ctdet::fail(CT_ERR_UNSUPPORTED, "%s: buffers of d->in / dz above 2 GiB are not built (ct_conv2d_wgrad takes them in "
+                           "batch chunks)", who);
     const Layout l = layout_of(d);
     const size_t need = 2 * l.lines_bytes + slab_bytes(l);
     if (workspace_bytes < need)
@@ -342,12 +338,12 @@ extern "C" int ct_conv2d_wgrad_h2(const ct_conv_desc* d, const float* dz, int dz
         }
     }
     WgradH2Args a{};
-    a.x = d->in; a.dz = dz; a.slabs = reinterpret_cast<float*>(ws + 2 * l.lines_bytes);
+    ctdet::wgrad_fill(a, d, dz, dz_ctot, dz_coff, lim, 0, d->batch);
+    a.slabs = reinterpret_cast<float*>(ws + 2 * l.lines_bytes);
     a.x_lines = x_lines; a.z_lines = z_lines;
-    a.x_bytes = (unsigned)x_bytes; a.dz_bytes = (unsigned)z_bytes;
-    a.batch = d->batch; a.Cin = d->cin; a.Cout = d->cout;
-    a.HW = HW; a.W = d->w; a.x_ctot = d->in_ctot; a.x_coff = d->in_coff;
-    a.OHW = OHW; a.OW = d->ow; a.dz_ctot = dz_ctot; a.dz_coff = dz_coff;
+    a.batch = d->batch;
+    a.HW = HW; a.W = d->w;
+    a.OHW = OHW; a.OW = d->ow;
     a.stride = d->stride;
     a.G = l.G; a.groups = l.groups;
     a.tiles_m = l.tiles_m; a.stages_per_split = l.stages_per_split;

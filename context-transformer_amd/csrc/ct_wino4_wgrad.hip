@@ -25,13 +25,12 @@
 //   four that only run MFMAs, four that only load and transform, double-buffered LDS, one barrier per chunk) was 45 %
 //   SLOWER (1109 us): the transform waves run at half speed beside an MFMA wave on their SIMD.
 // Tile ranges are split over blockIdx.y; partial sums meet in the workspace dU[36][cout][cin] through f32 atomics, and
-// wino4_wgrad_finish applies G^T . G per (k, c) into the dense dw[cout][cin][3][3].
+// wino4_wgrad_finish applies G^T . G per (k, c) into the dense dw[cout][cin][3][3].  The launcher is the one of ct_wgrad_launch.h
+// (launch_wgrad_wino), shared with ct_wino_wgrad.hip.
 #include "ct_common.h"
 #include "ct_device.h"
 #include "ct_wino4_points.h"
-#include <algorithm>
-#include <cstdlib>
-#include <mutex>
+#include "ct_wgrad_launch.h"
 
 namespace {
 
@@ -39,7 +38,6 @@ using ctdet::f32x4;
 using ctdet::f32x16;
 using ctdet::i32x4;
 using ctdet::kInvalidOff;
-using ctdet::kMaxBufBytes;
 using ctdet::make_rsrc;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
@@ -265,16 +263,13 @@ __global__ __launch_bounds__(256) void wino4_wgrad_finish(const float* __restric
     }
 }
 
-bool w4w_ok(const ct_conv_desc* d)
-{
-    return d->kh == 3 && d->kw == 3 && d->stride == 1 && d->dil == 1 && d->pad_h == 1 && d->pad_w == 1 &&
-           d->oh == d->h && d->ow == d->w && !d->transposed && d->cin >= 1 && d->cout >= 1 &&
-           (long long)d->in_ctot * d->h * d->w * 4 < kMaxBufBytes;
-}
+// two workgroups per CU, one round
+const ctdet::WinoWgradForm kForm = {"ct_conv2d_wgrad_wino4", "wino4_wgrad_f32", "wino4_wgrad_finish", 4, 36, CB, 256, W4W_LDS_BYTES, 512,
+                                    "CTDET_W4W_WGS"};
 
 }  // namespace
 
-extern "C" int ct_conv_wgrad_wino4_supported(const ct_conv_desc* d) { return d && w4w_ok(d) ? 1 : 0; }
+extern "C" int ct_conv_wgrad_wino4_supported(const ct_conv_desc* d) { return d && ctdet::wgrad_wino_ok(d) ? 1 : 0; }
 
 extern "C" size_t ct_conv_wgrad_wino4_workspace_bytes(const ct_conv_desc* d)
 {
@@ -284,55 +279,5 @@ extern "C" size_t ct_conv_wgrad_wino4_workspace_bytes(const ct_conv_desc* d)
 extern "C" int ct_conv2d_wgrad_wino4(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
                                      void* workspace, ct_stream_t stream)
 {
-    CT_REQUIRE(d && dz && dw && workspace && d->in, "ct_conv2d_wgrad_wino4: null pointer");
-    if (!w4w_ok(d))
-        return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_wgrad_wino4: needs 3x3 stride 1 dilation 1 pad 1 "
-                           "(got %dx%d s%d d%d p%d)", d->kh, d->kw, d->stride, d->dil, d->pad_h);
-    CT_REQUIRE(d->batch > 0, "ct_conv2d_wgrad_wino4: bad shape");
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "ct_conv2d_wgrad_wino4: input slice");
-    CT_REQUIRE(dz_coff >= 0 && dz_coff + d->cout <= dz_ctot, "ct_conv2d_wgrad_wino4: dz slice");
-    const long long img_x = (long long)d->in_ctot * d->h * d->w * 4, img_z = (long long)dz_ctot * d->h * d->w * 4;
-    CT_REQUIRE(img_z < kMaxBufBytes, "ct_conv2d_wgrad_wino4: one image exceeds 2 GiB");
-    const int max_chunk = (int)std::max<long long>(1, kMaxBufBytes / std::max(img_x, img_z));
-    hipStream_t st = ctdet::as_stream(stream);
-    {
-        static std::once_flag once;
-        static hipError_t attr_err = hipSuccess;
-        std::call_once(once, [] {
-            attr_err = hipFuncSetAttribute((const void*)wino4_wgrad_f32, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           W4W_LDS_BYTES);
-        });
-        CT_HIP(attr_err);
-    }
-    float* dU = static_cast<float*>(workspace);
-    const int KC = d->cout * d->cin;
-    if (!ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dU, 0, (size_t)36 * KC * 4, st));
-    const int kblocks = (d->cout + CB - 1) / CB, cblocks = (d->cin + CB - 1) / CB;
-    for (int b0 = 0; b0 < d->batch; b0 += max_chunk) {
-        const int nb = std::min(max_chunk, d->batch - b0);
-        W4WArgs a{};
-        a.x = d->in + (size_t)b0 * d->in_ctot * d->h * d->w;
-        a.dz = dz + (size_t)b0 * dz_ctot * d->h * d->w;
-        a.dU = dU;
-        a.x_bytes = (unsigned)(img_x * nb);
-        a.dz_bytes = (unsigned)(img_z * nb);
-        a.Cin = d->cin; a.Cout = d->cout; a.H = d->h; a.W = d->w;
-        a.x_ctot = d->in_ctot; a.x_coff = d->in_coff; a.dz_ctot = dz_ctot; a.dz_coff = dz_coff;
-        a.TY = (d->h + 3) / 4; a.TX = (d->w + 3) / 4;
-        a.NT = nb * a.TY * a.TX;
-        a.chunks = (a.NT + TT - 1) / TT;
-        a.cblocks = cblocks;
-        const int blocks = kblocks * cblocks;
-        // two workgroups per CU, one round
-        static const int wgs = getenv("CTDET_W4W_WGS") ? atoi(getenv("CTDET_W4W_WGS")) : 512;
-        int splits = std::max(1, std::min(a.chunks, wgs / blocks));
-        splits = std::min(splits, 65535);
-        a.chunks_per_split = (a.chunks + splits - 1) / splits;
-        splits = (a.chunks + a.chunks_per_split - 1) / a.chunks_per_split;
-        hipLaunchKernelGGL(wino4_wgrad_f32, dim3(blocks, splits), dim3(256), W4W_LDS_BYTES, st, a);
-        CT_LAUNCH_CHECK("wino4_wgrad_f32");
-    }
-    hipLaunchKernelGGL(wino4_wgrad_finish, dim3((KC + 255) / 256), dim3(256), 0, st, dU, dw, KC);
-    CT_LAUNCH_CHECK("wino4_wgrad_finish");
-    return CT_OK;
+    return ctdet::launch_wgrad_wino(kForm, wino4_wgrad_f32, wino4_wgrad_finish, d, dz, dz_ctot, dz_coff, dw, workspace, stream);
 }

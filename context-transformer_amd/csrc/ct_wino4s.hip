@@ -25,6 +25,7 @@
 #include "ct_common.h"
 #include <type_traits>
 #include "ct_wino_launch.h"
+#include "ct_wgrad_launch.h"
 #include "ct_wino_pack.h"
 #include "ct_wino4_points.h"
 #include "ct_wino4_emit.h"
@@ -1175,9 +1176,9 @@ WgSizes wg_sizes_of(int batch, int oh, int ow, int cin, int cout, int dil)
     s.cb = (cin + BT - 1) / BT;
     // k splits: about three rounds of two workgroups per CU, at least 8 k-steps each
     const int wgs = NXI * s.rb * s.cb;
-    s.splits = std::max(1, std::min((1536 + wgs - 1) / wgs, s.kchunks / 8));
-    s.cps = (s.kchunks + s.splits - 1) / s.splits;
-    s.splits = (s.kchunks + s.cps - 1) / s.cps;
+    const ctdet::Split sp = ctdet::even_split(s.kchunks, std::max(1, std::min((1536 + wgs - 1) / wgs, s.kchunks / 8)));
+    s.splits = sp.splits;
+    s.cps = sp.per_split;
     s.e_plane = (size_t)s.rb * s.kchunks * OPB;
     s.v_plane = (size_t)s.cb * s.kchunks * OPB;
     s.m_plane = (size_t)s.rb * BM * s.cb * BT;
@@ -1506,33 +1507,24 @@ extern "C" size_t ct_conv_wgrad_wino4s_workspace_bytes(const ct_conv_desc* d)
 extern "C" int ct_conv2d_wgrad_wino4s(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
                                       void* workspace, size_t workspace_bytes, ct_stream_t stream)
 {
-    CT_REQUIRE(d && dz && dw && workspace && d->in, "ct_conv2d_wgrad_wino4s: null pointer");
+    const char* who = "ct_conv2d_wgrad_wino4s";
+    if (int rc = ctdet::wgrad_check_pointers(d, dz, dw, workspace, who)) return rc;
     if (!wino4s_wg_ok(d))
-        return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_wgrad_wino4s: needs 3x3 stride 1 pad = dilation, cin %% 16 == 0 "
-                           "(got %dx%d s%d d%d p%d cin=%d)", d->kh, d->kw, d->stride, d->dil, d->pad_h, d->cin);
-    CT_REQUIRE(d->batch > 0, "ct_conv2d_wgrad_wino4s: bad shape");
-    CT_REQUIRE(dz_coff >= 0 && dz_coff + d->cout <= dz_ctot, "ct_conv2d_wgrad_wino4s: dz slice");
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "ct_conv2d_wgrad_wino4s: input slice");
-    const long long x_bytes = (long long)d->batch * d->in_ctot * d->h * d->w * 4;
-    const long long z_bytes = (long long)d->batch * dz_ctot * d->oh * d->ow * 4;
-    CT_REQUIRE(x_bytes < kMaxBufBytes && z_bytes < kMaxBufBytes, "ct_conv2d_wgrad_wino4s: a tensor exceeds 2 GiB (use ct_conv2d_wgrad_wino4)");
+        return ctdet::fail(CT_ERR_UNSUPPORTED, "%s: needs 3x3 stride 1 pad = dilation, cin %% 16 == 0 (got %dx%d s%d d%d p%d cin=%d)",
+                           who, d->kh, d->kw, d->stride, d->dil, d->pad_h, d->cin);
+    if (int rc = ctdet::wgrad_check_slices(d, dz_ctot, dz_coff, who)) return rc;
+    ctdet::WgradLimits lim;
+    if (int rc = ctdet::wgrad_limits(d, dz_ctot, who, &lim)) return rc;
+    const long long x_bytes = lim.x_bytes, z_bytes = lim.z_bytes;       // one launch covers the batch (no chunking)
+    CT_REQUIRE(x_bytes < kMaxBufBytes && z_bytes < kMaxBufBytes, "%s: a tensor exceeds 2 GiB (use ct_conv2d_wgrad_wino4)", who);
     const WgSizes s = wg_sizes_of(d->batch, d->oh, d->ow, d->cin, d->cout, d->dil);
-    CT_REQUIRE(workspace_bytes >= s.e_bytes + s.v_bytes + s.m_bytes, "ct_conv2d_wgrad_wino4s: workspace of %zu bytes, needs %zu",
-               workspace_bytes, s.e_bytes + s.v_bytes + s.m_bytes);
-    CT_REQUIRE((size_t)s.kchunks * OPB < (size_t)kMaxBufBytes, "ct_conv2d_wgrad_wino4s: too many tiles for one launch");
+    CT_REQUIRE(workspace_bytes >= s.e_bytes + s.v_bytes + s.m_bytes, "%s: workspace of %zu bytes, needs %zu", who, workspace_bytes,
+               s.e_bytes + s.v_bytes + s.m_bytes);
+    CT_REQUIRE((size_t)s.kchunks * OPB < (size_t)kMaxBufBytes, "%s: too many tiles for one launch", who);
     hipStream_t st = ctdet::as_stream(stream);
-    {
-        static std::once_flag once;
-        static hipError_t attr_err = hipSuccess;
-        std::call_once(once, [] {
-            attr_err = hipFuncSetAttribute((const void*)wino4s_tk<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TK_LDS_BYTES);
-            if (attr_err == hipSuccess)
-                attr_err = hipFuncSetAttribute((const void*)wino4s_tk<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TK_LDS_BYTES);
-            if (attr_err == hipSuccess)
-                attr_err = hipFuncSetAttribute((const void*)wino4s_gemm<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-        });
-        CT_HIP(attr_err);
-    }
+    for (const void* fn : {(const void*)wino4s_tk<true>, (const void*)wino4s_tk<false>})
+        CT_HIP(ctdet::raise_lds_limit(fn, TK_LDS_BYTES));
+    CT_HIP(ctdet::raise_lds_limit((const void*)wino4s_gemm<true>, GEMM_LDS_BYTES));
     unsigned char* E = static_cast<unsigned char*>(workspace);
     unsigned char* V = E + s.e_bytes;
     float* M = reinterpret_cast<float*>(V + s.v_bytes);

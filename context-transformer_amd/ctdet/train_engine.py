@@ -26,6 +26,7 @@ import torch
 from . import _lib, ops
 from .engine import (F4_TILES, WINO4F_TILES, WINO4S_TILES, ConvPart, ConvStep, HipBackend, Plan, Runtime, absmax_source, apply_tuned,
                      operand_form_h2, run_on_streams)
+from . import wgrad_routes
 from .wino_forms import FORMS
 
 
@@ -59,13 +60,9 @@ class TrainRuntime:
                 self.ctx_params.update(fc_w=net.fc_base.weight, fc_b=net.fc_base.bias)
             for prm in self.ctx_params.values():
                 self._reg(prm)
-        wino_ws = 0
         w4s_ws = 0              # bytes: workspace of the three-kernel Winograd data gradients
-        wg4s_ws = 0             # bytes: workspace of the three-kernel Winograd weight gradients
-        wgh2_ws = 0             # bytes: workspace of the f16x2 1x1 weight gradients
-        # CTDET_WGRAD_H2=1 (opt-in, resolved once here): the 1x1 layers that otherwise fall through to ct_conv2d_wgrad run
-        # ct_conv2d_wgrad_h2 (the f16x2 GEMM of csrc/ct_wgrad_h2.hip: no atomics, bit-reproducible)
-        self.wgrad_h2 = os.environ.get('CTDET_WGRAD_H2', '0') not in ('', '0')
+        wgrad_ws = {}           # bytes: the shared weight-gradient workspaces, by the runtime attribute that holds them
+        self.wgrad_h2 = wgrad_routes.h2_enabled(os.environ)         # opt-in, resolved once here
         # CTDET_TRAIN_WINO4=0 keeps forward and data-gradient convolutions on F(2x2,3x3) where the table says F(4x4,3x3)
         wino4 = os.environ.get('CTDET_TRAIN_WINO4', '1') != '0'
         # The Winograd launches of the step (forward and data gradients) on the f16x2 operand form (csrc/ct_f16x2.h) wherever the
@@ -207,47 +204,11 @@ class TrainRuntime:
             w.kh, w.kw, w.stride, w.pad_h, w.pad_w, w.dil = st.kh, st.kw, st.stride, st.ph, st.pw, st.dil
             w.oh, w.ow = st.oh, st.ow
             s.wgrad = w
-            # 3x3 / stride 1 / pad 1: Winograd F(3x3, 2x2) weight gradient; one workspace shared by all layers
-            # (stream ordered).  Maps below 10x10 stay on the direct kernel (tile padding costs more than the
-            # transform saves there); CTDET_WGRAD_WINO=0 keeps the direct kernel everywhere.
-            s.wgrad_wino = bool(int(os.environ.get('CTDET_WGRAD_WINO', '1'))) and st.oh * st.ow >= 100 and \
-                bool(self.lib.ct_conv_wgrad_wino_supported(C.byref(w)))
-            # F(3x3, 4x4) from 19x19 maps up (15-20 % faster than F(3x3, 2x2) there, tools/wgrad_probe.py; slower on
-            # 10x10); CTDET_WGRAD_WINO4=0 keeps F(3x3, 2x2)
-            s.wgrad_tile = 4 if s.wgrad_wino and st.oh * st.ow >= 361 and \
-                os.environ.get('CTDET_WGRAD_WINO4', '1') != '0' else 2
-            # the three-kernel bf16x3 form (ct_conv2d_wgrad_wino4s) for the wide layers: from CTDET_WGRAD_W4S_MIN_CIN input
-            # channels up (default 256; 0 = never) where cin x cout >= 2^17 -- conv4_x, conv5_x, the 19x19 RFB layers
-            # (profiles/r04_wgrad_probe.txt: 512 -> 512 @38x38 778 -> 503 us, 512 -> 512 @19x19 253 -> 184, 256 -> 512 @38x38
-            # 437 -> 366; the multibox heads (cout 126..156: 238 -> 353) and 256 -> 256 @75x75 (750 -> 804) stay fused).  Its
-            # workspace (E, V, dU slabs) is shared: weight gradients run in stream order.
-            w4s_min = int(os.environ.get('CTDET_WGRAD_W4S_MIN_CIN', '256') or 0)
-            # dilated 3x3 layers (conv6: 512 -> 1024, dilation 6) have no fused Winograd weight gradient; the three-kernel form
-            # takes them with the tiles on the dilation sub-lattices, under the same size rule
-            dilated = (st.kh, st.kw, st.stride) == (3, 3, 1) and st.dil > 1 and st.ph == st.pw == st.dil and \
-                os.environ.get('CTDET_TRAIN_W4S_DIL', '1') != '0'
-            # dilated layers: the alternative is the direct fp32 kernel, so the rule is looser -- conv6 and the 256-channel RFB
-            # branches (same-box A/B of the step: 2^17 / 2^16 / 2^14 with 128 channels: 38.2-40.1 / 37.7-38.2 / 38.4-38.5 ms)
-            dil_prod = int(os.environ.get('CTDET_WGRAD_W4S_DIL_PROD', str(1 << 16)))
-            dil_cin = int(os.environ.get('CTDET_WGRAD_W4S_DIL_CIN', '256'))
-            if ((s.wgrad_wino and s.wgrad_tile == 4 and st.cin >= w4s_min and st.cin * ctot >= (1 << 17)) or
-                    (dilated and st.cin >= dil_cin and st.cin * ctot >= dil_prod)) and w4s_min and \
-                    self.lib.ct_conv_wgrad_wino4s_supported(C.byref(w)):
-                s.wgrad_wino = True
-                s.wgrad_tile = 44
-                wg4s_ws = max(wg4s_ws, int(self.lib.ct_conv_wgrad_wino4s_workspace_bytes(C.byref(w))))
-            # ... where it wins (profiles/wgrad_h2_probe.txt): stride 1 on maps from 19x19 up.  The stride-2 layers (one gathered
-            # load per pixel: 1024 -> 768 @19x19 86 -> 118 us) and the maps below 19x19 (20-45 us launches, where the two
-            # maxima passes a BatchNorm layer's dZ needs cost 10 us) stay on ct_conv2d_wgrad.
-            s.wgrad_h2 = self.wgrad_h2 and not s.wgrad_wino and st.stride == 1 and st.oh * st.ow >= 361 and \
-                bool(self.lib.ct_conv_wgrad_h2_supported(C.byref(w)))
-            if s.wgrad_h2:      # one workspace (maxima lines + split-k slabs) shared by all layers: stream ordered
-                wgh2_ws = max(wgh2_ws, int(self.lib.ct_conv_wgrad_h2_workspace_bytes(C.byref(w))))
-            if s.wgrad_wino:
-                size = self.lib.ct_conv_wgrad_wino4_workspace_bytes if s.wgrad_tile in (4, 44) else \
-                    self.lib.ct_conv_wgrad_wino_workspace_bytes
-                s.wgrad_ws_bytes = int(size(C.byref(w))) if s.wgrad_tile != 44 else 64
-                wino_ws = max(wino_ws, s.wgrad_ws_bytes)
+            # its entry point (ctdet/wgrad_routes.py) and what that asks of the route's workspace: one per route, shared by all
+            # layers (weight gradients run in stream order)
+            s.wgrad_route = wgrad_routes.choose(self.lib, st, w, ctot, os.environ)
+            s.wgrad_ws_bytes = s.wgrad_route.workspace_bytes(self.lib, w)
+            wgrad_ws[s.wgrad_route.ws] = max(wgrad_ws.get(s.wgrad_route.ws, 0), s.wgrad_ws_bytes)
             for p in st.parts:
                 self._reg(p.weight)
                 if p.bn is not None:
@@ -260,11 +221,11 @@ class TrainRuntime:
         # shared one) and -- through the gradient arena below -- the bias / split weight gradients.  CTDET_PREZERO=0 keeps
         # the per-launch memsets.
         self.prezero = os.environ.get('CTDET_PREZERO', '1') != '0'
-        self.wgrad_ws = al((max(wino_ws // 4, 1),))
+        self.wgrad_ws = al((max(wgrad_ws.get('wgrad_ws', 0) // 4, 1),))
         self.dgrad_ws4s = torch.empty(max(w4s_ws, 1), device=backend.device, dtype=torch.uint8)
-        self.wgrad_ws4s = torch.empty(max(wg4s_ws, 1), device=backend.device, dtype=torch.uint8)
+        self.wgrad_ws4s = torch.empty(max(wgrad_ws.get('wgrad_ws4s', 0), 1), device=backend.device, dtype=torch.uint8)
         if self.wgrad_h2:
-            self.wgrad_wsh2 = torch.empty(max(wgh2_ws, 1), device=backend.device, dtype=torch.uint8)
+            self.wgrad_wsh2 = torch.empty(max(wgrad_ws.get('wgrad_wsh2', 0), 1), device=backend.device, dtype=torch.uint8)
         if self.prezero:
             bn_floats = sum(t.numel() for s_ in self.state.values() for t in getattr(s_, 'scratch', []))
             self.bn_scratch = al((max(bn_floats, 1),), torch.float64)
@@ -273,7 +234,7 @@ class TrainRuntime:
                 for i, t in enumerate(getattr(s_, 'scratch', [])):
                     s_.scratch[i] = self.bn_scratch[o:o + t.numel()]
                     o += t.numel()
-            sizes = [(s_, s_.wgrad_ws_bytes // 4) for s_ in self.state.values() if s_.wgrad_wino]
+            sizes = [(s_, s_.wgrad_ws_bytes // 4) for s_ in self.state.values() if s_.wgrad_route.zeroed]
             self.wgrad_ws_all = al((max(sum((n + 63) // 64 * 64 for _, n in sizes), 1),))
             o = 0
             for s_, n in sizes:
@@ -390,7 +351,7 @@ class TrainRuntime:
             if getattr(s, 'dgrad_wino', None) is not None and FORMS[s.dgrad_tile].h2 and not s.is_bn and not st.segs:
                 s.dz_amax = be.new_slot(self.batch)
                 s.dgrad_wino.in_absmax = s.dz_amax
-            elif getattr(s, 'wgrad_h2', False) and not s.is_bn and not st.segs:
+            elif s.wgrad_route.dz_amax and not s.is_bn and not st.segs:
                 s.dz_amax = be.new_slot(self.batch)     # ct_bias_act_backward_amax leaves dZ's maxima for ct_conv2d_wgrad_h2
         self.amax_slots = slots
         self._wired_epoch = be.kernel_epoch
@@ -785,26 +746,14 @@ class TrainRuntime:
                 s.ev_dz.record(main)
                 side.wait_event(s.ev_dz)
             with torch.cuda.stream(side if side is not None else main):
-                if s.wgrad_wino and s.wgrad_tile == 44:
-                    _lib.check(lib.ct_conv2d_wgrad_wino4s(C.byref(s.wgrad), s.dz.data_ptr(), ctot, 0, s.dw.data_ptr(),
-                                                          self.wgrad_ws4s.data_ptr(), self.wgrad_ws4s.numel(), self._s()),
-                               st.name + ' wgrad (winograd 4s)')
-                elif s.wgrad_wino:
-                    fn = lib.ct_conv2d_wgrad_wino4 if s.wgrad_tile == 4 else lib.ct_conv2d_wgrad_wino
-                    _lib.check(fn(C.byref(s.wgrad), s.dz.data_ptr(), ctot, 0, s.dw.data_ptr(),
-                                  (s.wgrad_ws if self.prezero else self.wgrad_ws).data_ptr(), self._s()),
-                               st.name + ' wgrad (winograd)')
-                elif s.wgrad_h2:
+                r = s.wgrad_route
+                ws = None if r.ws is None else s.wgrad_ws if r.zeroed and self.prezero else getattr(self, r.ws)
+                if r.dz_amax:
                     # X's maxima where the forward wired a slot for this layer's input, dZ's where ct_bias_act_backward_amax
                     # wrote them (a BatchNorm backward does not track: NULL, the entry point takes the maximum itself)
                     s.wgrad.in_absmax = s.fwd.rt['desc'].in_absmax
-                    _lib.check(lib.ct_conv2d_wgrad_h2(C.byref(s.wgrad), s.dz.data_ptr(), ctot, 0,
-                                                      None if s.is_bn or st.segs else getattr(s, 'dz_amax', None),
-                                                      s.dw.data_ptr(), self.wgrad_wsh2.data_ptr(), self.wgrad_wsh2.numel(),
-                                                      self._s()), st.name + ' wgrad (f16x2)')
-                else:
-                    _lib.check(lib.ct_conv2d_wgrad(C.byref(s.wgrad), s.dz.data_ptr(), ctot, 0, s.dw.data_ptr(),
-                                                   self._s()), st.name + ' wgrad')
+                _lib.check(r.run(lib, s.wgrad, s.dz, ctot, s.dw, ws, None if s.is_bn or st.segs else getattr(s, 'dz_amax', None),
+                                 self._s()), st.name + r.label)
             off = 0
             for p in st.parts:
                 put(p.weight, s.dw[off:off + p.cout])

@@ -654,7 +654,10 @@ int ct_absmax_bf16_nhwc(const void* x, int batch, int hw, int ctot, int coff, in
  * sum over batch and output pixels of dz[n][co][oh][ow] * X[n][ci][ih][iw];  dz is the channel slice
  * [dz_coff, dz_coff+cout) of an NCHW buffer with dz_ctot channels.  "Overwritten" holds for whatever dw contains on entry
  * (NaN included): the pixel splits add into dw after one memset inside the call.  Under ct_scratch_prezeroed(1) that
- * memset is the caller's, and the call ADDS the gradient to what dw holds. */
+ * memset is the caller's, and the call ADDS the gradient to what dw holds.  The five weight-gradient entry points share their
+ * argument checks: a null pointer (named in the message), a non-positive batch / cin / cout, an input slice outside d->in_ctot
+ * (in_coff < 0 or in_coff + cin > in_ctot; this entry point did not check it before) or a dz slice outside dz_ctot is
+ * CT_ERR_INVALID. */
 int ct_conv2d_wgrad(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
                     ct_stream_t stream);
 

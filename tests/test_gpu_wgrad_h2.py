@@ -230,7 +230,7 @@ def test_step_gradients_match_fp64_autograd_with_the_switch(monkeypatch):
     out, R = step()
     trt = net.train_runtime(B)
     assert trt.wgrad_h2
-    moved = [n for n, s_ in trt.state.items() if s_.wgrad_h2]
+    moved = [n for n, s_ in trt.state.items() if s_.wgrad_route.name == 'h2']
     assert len(moved) >= 5, moved           # stride 1 from 19x19 up (the selection rule of train_engine.py)
     steps = {st.name: st for st in trt.plan.steps if st.kind == 'conv'}
     assert all((steps[n].kh, steps[n].kw) == (1, 1) for n in moved)

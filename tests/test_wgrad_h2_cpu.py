@@ -263,7 +263,7 @@ def test_switch_on_moves_exactly_the_selected_1x1_layers(monkeypatch):
     lib = _lib.lib()
     need = max(lib.ct_conv_wgrad_h2_workspace_bytes(C.byref(rt.state[n].wgrad)) for n in ('P1', 'P2', 'P3'))
     assert rt.wgrad_wsh2.numel() == need
-    assert {n for n, s in rt.state.items() if s.wgrad_h2} == {'P1', 'P2', 'P3'}
+    assert {n for n, s in rt.state.items() if s.wgrad_route.name == 'h2'} == {'P1', 'P2', 'P3'}
     calls_on, calls_off = _wgrad_calls(on), _wgrad_calls(off)
     assert len(calls_on) == len(calls_off) == 7
     assert all(lib.ct_conv_wgrad_h2_supported(C.byref(rt.state[n].wgrad)) == 1 for n in ('P1', 'P2', 'P3', 'S', 'T'))

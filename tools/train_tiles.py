@@ -10,4 +10,4 @@ for st in trt.plan.steps:
     if st.kind=='conv':
         s = trt.state[st.name]
         if s.fwd.rt.get('wino') or getattr(s,'dgrad_tile',None):
-            print(st.name, st.cin, st.cout, st.h, 'fwd', s.fwd.rt.get('wino'), 'dgrad', getattr(s,'dgrad_tile',None) if s.dgrad is not None and s.dgrad_wino is not None else None, 'wgrad', s.wgrad_tile if s.wgrad_wino else None)
+            print(st.name, st.cin, st.cout, st.h, 'fwd', s.fwd.rt.get('wino'), 'dgrad', getattr(s,'dgrad_tile',None) if s.dgrad is not None and s.dgrad_wino is not None else None, 'wgrad', s.wgrad_route.name)
