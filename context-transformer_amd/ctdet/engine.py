@@ -21,6 +21,7 @@ launch descriptors (tests/emu_backend.py) and check the wiring without a GPU; th
 ships exactly one backend, the HIP one, and `RFBNet.forward` refuses non-HIP devices.
 """
 import ctypes as C
+import dataclasses
 import json
 import math
 import os
@@ -29,7 +30,9 @@ from typing import List, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, conv_policy
+from .conv_policy import (CTX_DIL_W4S_DEFAULT, CTX_F4_MAX_CIN_DEFAULT, CTX_F4_TILE_DEFAULT, CTX_TILES_DEFAULT,  # noqa: F401
+                          CTX_W4S_MIN_CIN_DEFAULT, F4_TILES, H2_MIN_PIXELS, H2_OF_TILE, WINO4F_TILES, WINO4S_TILES, WINO_NAME)
 from .wino_forms import FORMS, geometry_ok
 
 # CTDET_TUNE_TABLE: another table file (A/B measurements of a re-tuned table against the committed one)
@@ -348,17 +351,35 @@ class Plan:
 # ConvStep.rt['config'] values selecting a Winograd kernel, and the st.rt['wino'] codes they select (wino_forms.FORMS)
 WINO, WINO4, WINOX, WINO4S, WINO4F, WINO4H, WINO4FH = (FORMS[c].config for c in (2, 4, 23, 44, 46, 47, 48))
 WINO_TILE = {f.config: c for c, f in FORMS.items()}
-WINO_NAME = {c: f.name for c, f in FORMS.items()}
-WINO4S_TILES = tuple(c for c, f in FORMS.items() if f.split)
-WINO4F_TILES = tuple(c for c, f in FORMS.items() if f.ok == 'wino4f_ok')
 H2_TILES = tuple(c for c, f in FORMS.items() if f.h2)
-F4_TILES = tuple(c for c, f in FORMS.items() if f.f4)
-# bf16x3 tile -> the same kernel on the f16x2 operand form (csrc/ct_f16x2.h: two binary16 pieces, three products)
-H2_OF_TILE = {f.plain: c for c, f in FORMS.items() if f.h2}
 
 
 class HipBackend:
     """Executes plan steps through libctdet (the only backend the product ships)."""
+    # The kernel policy (ctdet/conv_policy.py).  A Runtime / TrainRuntime assigns the one it resolved for its network and batch
+    # before it prepares the first layer; a backend no runtime has bound (kernel tests, tools/) resolves the default from the
+    # environment at each use.
+    _policy = None
+    _kernels = None
+
+    @property
+    def policy(self):
+        return self._policy if self._policy is not None else conv_policy.resolve(None, None, os.environ)
+
+    @policy.setter
+    def policy(self, p):
+        self._policy = p
+
+    h2 = property(lambda self: self.policy.h2)
+    h2_direct = property(lambda self: self.policy.h2_direct)
+    wino_tile_set = property(lambda self: self.policy.tile_set)
+
+    @property
+    def kernels(self):
+        """The library's kernel lists (conv_policy.Kernels), asked once."""
+        if self._kernels is None:
+            self._kernels = conv_policy.Kernels.of(self.lib)
+        return self._kernels
 
     def __init__(self, device):
         self.device = torch.device(device)
@@ -733,7 +754,8 @@ class HipBackend:
         st.rt['desc'].config = best + 1
         st.rt['config'] = best + 1
         best_x3 = None
-        if x3_allowed(st):
+        policy = self.policy
+        if conv_policy.x3_allowed(policy, st):
             for cfg in range(self.lib.ct_conv_x3_num_configs()):
                 if st.cin % self.x3_bk(cfg) or not self.x3_names()[cfg].endswith('d') or self.x3_h2(cfg):   # (the table holds the bf16x3 names)
                     times.append(float('inf'))      # k-step does not divide cin / single accumulator (accuracy gate)
@@ -744,7 +766,7 @@ class HipBackend:
                 if t < best_t:
                     best_x3, best_t = cfg, t
             self.enable_x3(st, best_x3)
-        if (st.rt.get('wino_ok') or st.rt.get('wino4s_ok')) and os.environ.get('CTDET_WINO', '1') != '0':
+        if (st.rt.get('wino_ok') or st.rt.get('wino4s_ok')) and policy.wino:
             best_tile = 0
             for tile in wino_tiles(self, st):
                 self.enable_wino(st, tile=tile)
@@ -794,227 +816,64 @@ def absmax_source(steps, tracks):
     return source
 
 
+# ---- the kernel policy as seen from here: thin views of ctdet/conv_policy.py on the process environment
+def _env_policy(net=None, batch=None):
+    return conv_policy.resolve(net, batch, os.environ)
+
+
 def x3_allowed(st):
-    """bf16x3 (ct_conv2d_x3_fwd) is a candidate for every forward conv except the 3-channel image layer (K = 27:
-    nothing to gain); CTDET_X3=0 keeps the fp32 MFMA kernel everywhere."""
-    return os.environ.get('CTDET_X3', '1') != '0' and st.cin >= 16 and st.cin % 16 == 0
+    return conv_policy.x3_allowed(_env_policy(), st)
 
 
 def wino_tiles(backend=None, st=None):
-    """Winograd variants the tuner / the table may use (st.rt['wino'] codes).  Default '2,4,44,46': the two fp32-MFMA kernels,
-    the three-kernel F(4x4,3x3) / bf16x3 form with two accumulators (csrc/ct_wino4s.hip) and the fused F(4x4,3x3) / bf16x3
-    kernel for the narrow layers on big maps (csrc/ct_wino4f.hip).  The fused F(2x2) bf16x3
-    form (23) is faster than the fused fp32 kernels per layer ALONE (512 -> 512 @38x38: 742 -> 630 us) but not in the
-    two-stream pipeline (same-box A/B of two tables: 3 360-3 371 vs 3 228-3 398 images/s) and slower
-    than tile 44 wherever that applies, so the committed table does not hold it; CTDET_WINO_TILES=2,4,23,44 lets the tuner
-    time it.  A runtime with an accuracy policy
-    (ctx_tile_set: networks with the Context-Transformer block) uses ITS set instead (narrowed by an explicit
-    CTDET_WINO_TILES), plus F(4x4) / fp32 on layers with at most wino4_max_cin input channels (and tile 44 from
-    ctx_w4s_min_cin input channels up, see apply_tuned)."""
-    env = os.environ.get('CTDET_WINO_TILES')
-    tiles = tuple(int(t) for t in (env or '2,4,44,46').split(',') if t)
-    if env is None and getattr(backend, 'h2', False):
-        tiles = tiles + tuple(H2_OF_TILE.values())
-    allowed = getattr(backend, 'wino_tile_set', None)
-    if allowed is not None:             # a runtime's accuracy policy: its set, narrowed by an explicit CTDET_WINO_TILES
-        tiles = tuple(t for t in allowed if env is None or t in tiles)
-        cap = getattr(backend, 'wino4_max_cin', None)
-        f4 = ctx_f4_tile()
-        if cap and st is not None and st.cin <= cap and f4 in WINO4F_TILES and not st.rt.get('wino4f_ok'):
-            f4 = 4                      # the fused bf16x3 kernel needs 16-channel chunks: such layers keep the fp32 fused kernel
-        if cap and st is not None and st.cin <= cap and f4 not in tiles and (env is None or str(f4) in env.split(',')):
-            tiles = tiles + (f4,)       # short channel sums: F(4x4) costs little accuracy there
-    if st is not None:                  # each form's geometry (dilated 3x3: only the three-kernel form)
-        tiles = tuple(t for t in tiles if geometry_ok(st.rt, t) and (t not in FORMS or st.rt.get(FORMS[t].ok)))
-    return tiles
-
-
-H2_MIN_PIXELS = 8 * 300 * 300
+    """Winograd variants the tuner / the table may use under the backend's policy (conv_policy.wino_tiles), on step st if given."""
+    return conv_policy.wino_tiles(backend.policy if backend is not None else _env_policy(),
+                                  conv_policy.Layer(cin=st.cin, geo=st.rt) if st is not None else None)
 
 
 def operand_form_h2(net, batch=None):
-    """(winograd, direct): whether an inference runtime runs its bf16x3 Winograd table entries on the f16x2 operand form, and
-    whether it may use the f16x2 twins of the direct kernel's tiles (csrc/ct_f16x2.h: two binary16 pieces, three products; same
-    error against fp64 per layer, tests/test_gpu_wino.py::test_wino_rounding_error_vs_fp64, half the matrix instructions).
-    CTDET_H2: '1' (default) = from batch x size^2 >= 8 x 300^2 up, '2' = always, '0' = never.  Why a threshold: an f16x2 launch
-    waits for its input's maxima when it starts and folds its own in when it ends -- a few us per launch that the launch-bound
-    small batches do not get back (same-box, images/s bf16x3 -> f16x2: RFBNet-300 bs 4 2 065 -> 1 830, bs 8 2 850 -> 2 990,
-    bs 16 3 450 -> 3 945, bs 32 4 005 -> 4 655; RFBNet-512 bs 4 1 120 -> 1 126, bs 8 1 340 -> 1 438, bs 32 1 608 -> 1 805;
-    profiles/r06_ab_batches.txt).  Networks with the Context-Transformer block (ctx_policy): under the shipped policy 'h2' the
-    Winograd forms at EVERY batch size and never the direct twins -- the combination the parity sweeps were made on; under a
-    tile-set policy neither."""
-    mode = os.environ.get('CTDET_H2', '1')
-    pol = ctx_policy(net)
-    if mode == '0' or (pol is not None and pol not in ('h2', 'any')):
-        return False, False
-    if pol == 'h2':
-        return True, False
-    size = int(getattr(net, 'size', 300) or 300)
-    on = mode == '2' or batch is None or batch * size * size >= H2_MIN_PIXELS
-    return on, on and os.environ.get('CTDET_H2_X3', '1') != '0'
-
-
-CTX_TILES_DEFAULT = 'h2'
-SIDE_AFTER_DEFAULT = ''
+    """(winograd, direct) of an inference runtime: ConvPolicy.h2 / h2_direct."""
+    p = _env_policy(net, batch)
+    return p.h2, p.h2_direct
 
 
 def ctx_policy(net):
-    """CTDET_CTX_TILES for a network with the Context-Transformer block (models/RFB_Net_vgg.py:253-271), None for any other:
-    'h2' (default, round 6), 'any', or a comma list of Winograd tile codes (the round-2 .. 5 tile-set policies; '2,23' was
-    round 5's)."""
-    if not (getattr(net, 'method', None) == 'ours' and getattr(net, 'phase', 1) == 2):
-        return None
-    return os.environ.get('CTDET_CTX_TILES', CTX_TILES_DEFAULT)
+    return _env_policy(net).ctx_tiles
 
 
 def ctx_tile_set(net):
-    """Winograd tile SET of networks with the Context-Transformer block; None = no restriction (every other network, and the
-    policies 'h2' / 'any').
-
-    The block's un-scaled theta.phi^T softmax is near-arg-max and amplifies a perturbation of its INPUT (the conf-head
-    output) ~1000x (tools/ctx_parity.py --budget: 970x), so the reference's own fp32 CPU path sits 5..7e-5 from an fp64
-    evaluation, two correct fp32 evaluations differ by up to ~1e-4, and which side of north_star's flat 1e-4 the worst of 7e5
-    elements lands on is decided by single layers' summation orders: every policy is a MEASURED choice over the nine sweep cases
-    (bs {2, 8, 32} x seeds {1234, 7, 99}) x the reference at 8 and 128 threads, not a guarantee for other seeds.
-
-    Round 6, shipped: 'h2' -- the unconstrained table with its F(4x4,3x3) entries on the f16x2 operand form (three-kernel form with
-    two accumulators, fused kernel) and the direct layers on bf16x3 with two accumulators (operand_form_h2).  All 18 pairs inside
-    1e-4 (worst 9.76e-5), RFBNet-300 + Context-Transformer bs 32 at 3 640 images/s against 2 560 for round 5's policy; on ten
-    further cases (seeds 1..5, bs 8 / 32) 2 of 20 pairs above 1e-4 against 5 of 20 for round 5's policy
-    (profiles/r06_ctx_policy.txt, r06_ctx_policy_seeds.txt).  With the direct layers on f16x2 too: 3 750 images/s, one pair at
-    1.01e-4.  Round 5, still available as CTDET_CTX_TILES=2,23: F(2x2,3x3) on bf16x3 with two accumulators (tile 23: per-layer
-    error vs fp64 4e-7 against 2e-6 for F(4x4,3x3)) except a fused fp32 F(4x4) on the short channel sums (ctx_f4_max_cin): 18 / 18
-    inside 1e-4 too (worst 9.2e-5), at 2 560 images/s.  Layers without 16-channel chunks keep F(2x2,3x3) on the fp32 MFMA."""
-    v = ctx_policy(net)
-    if v is None or v in ('any', 'h2'):
-        return None
-    return tuple(int(t) for t in v.split(',') if t)
-
-
-CTX_F4_MAX_CIN_DEFAULT = '128'
+    return _env_policy(net).tile_set
 
 
 def ctx_f4_max_cin(net):
-    """Layers of a Context-Transformer network with at most this many input channels keep a fused F(4x4,3x3) kernel where the
-    table picks one (ctx_f4_tile): its rounding error grows with the length of the channel sum, and on conv1_2 .. conv3_1
-    (64 / 128 input channels at 300 x 300 .. 75 x 75) F(2x2,3x3) costs the most time.  Chosen by the round-5 sweeps
-    (profiles/r05_ctx_policy.txt: RFBNet-300 + Context-Transformer bs 32, 9 randn cases, every case judged against the fp32 CPU
-    path at 8 AND at 128 reference threads; three-kernel form off; (ctx_f4_tile, this cap) on the committed table):
-      (4, 128)   2 570 images/s   worst GPU-CPU32 9.0e-5 at 8 threads, 9.2e-5 at 128   all 18 inside 1e-4   <- default
-      (4, 256)   2 619            1.02e-4 / 1.07e-4    3 of 18 above 1e-4 (conv3_2 / conv3_3: 256-channel sums on the fp32 MFMA)
-      (46, 128)  2 670            1.01e-4 / 9.5e-5     1 of 18 above
-      (46, 256)  2 769            1.01e-4 / 9.7e-5     1 of 18 above
-      cap 0 (every Winograd layer on F(2x2,3x3) / bf16x3): 2 353, 9.7e-5 / 1.02e-4, 1 of 18 above
-      round 4's policy (three-kernel F(4x4) from 128 channels up): 2 898, 1.03e-4 / 1.05e-4, 3 of 18 above
-    All of them are within 7.7e-5 of the fp64 evaluation; which side of 1e-4 the worst of 7e5 elements lands on against a
-    reference that is itself 4.8..7.2e-5 from fp64 is decided by single layers' summation orders.  CTDET_CTX_F4_MAX_CIN; 0 = none."""
-    return int(os.environ.get('CTDET_CTX_F4_MAX_CIN', CTX_F4_MAX_CIN_DEFAULT)) if ctx_tile_set(net) is not None else 0
-
-
-CTX_F4_TILE_DEFAULT = '4'
+    return _env_policy(net).f4_max_cin
 
 
 def ctx_f4_tile():
-    """Which F(4x4,3x3) kernel the layers below ctx_f4_max_cin run: 4 = fused on the fp32 MFMA (csrc/ct_wino4.hip), 46 = fused on
-    bf16x3 (csrc/ct_wino4f.hip; layers without 16-channel chunks keep 4).  CTDET_CTX_F4_TILE."""
-    return int(os.environ.get('CTDET_CTX_F4_TILE', CTX_F4_TILE_DEFAULT))
-
-
-CTX_W4S_MIN_CIN_DEFAULT = '0'
-# Context-Transformer networks with ctx_w4s_min_cin > 0: their dilated layers (conv6, the RFB branches) on the three-kernel form
-# too, from that many input channels up (CTDET_CTX_DIL_W4S=0: never)
-CTX_DIL_W4S_DEFAULT = '1'
+    return _env_policy().f4_tile
 
 
 def ctx_w4s_min_cin(net):
-    """Layers of a Context-Transformer network with at least this many input channels that the table runs on F(4x4,3x3)
-    (fused or three-kernel) use the three-kernel bf16x3 form with two accumulators (tile 44: error vs fp64 2e-6 per layer
-    against 3-4e-7 for F(2x2,3x3) / bf16x3 with two accumulators, at 1.7x the speed on the wide layers).  Default 0 = never:
-    with tile 44 on the 512-channel layers one to three of the 18 (case, reference thread count) pairs of the sweep land at
-    1.03-1.05e-4 from the fp32 CPU path (ctx_f4_max_cin has the table), and north_star's contract is a flat 1e-4.
-    CTDET_CTX_W4S_MIN_CIN=128 CTDET_CTX_F4_MAX_CIN=128 is the round-4 policy: +17 % images/s for callers who accept that."""
-    return int(os.environ.get('CTDET_CTX_W4S_MIN_CIN', CTX_W4S_MIN_CIN_DEFAULT)) if ctx_tile_set(net) is not None else 0
+    return _env_policy(net).w4s_min_cin
 
 
 def apply_tuned(backend, st, batch, wino4=True):
-    """Give a prepared conv step the committed tile choice for its shape; False if the table has none.
-    wino4=False maps a 'wino4' entry to 'wino'.  A Winograd entry the runtime's policy excludes (ctx_tile_set) becomes the
-    most accurate allowed variant: F(2x2) on bf16x3 with two accumulators where the layer has 16-channel chunks, else
-    F(2x2) on the fp32 MFMA."""
-    cfg = tune_table().get(st.tune_key(batch))
-    if getattr(backend, 'h2', False):
-        # a runtime on the f16x2 operand forms: where the forms' different speed-ups change which KERNEL FAMILY wins a shape
-        # (tools/tune_convs.py --h2), the table holds that choice under '<key>|h2' (same names: mapped to the f16x2 twins below)
-        cfg = tune_table().get(st.tune_key(batch) + '|h2', cfg)
-    names = [backend.lib.ct_conv_config_name(i).decode() for i in range(backend.lib.ct_conv_num_configs())]
-    codes = {v: k for k, v in WINO_NAME.items()}
-    usable = cfg in codes and geometry_ok(st.rt, codes[cfg]) and \
-        os.environ.get('CTDET_WINO', '1') != '0'
-    if usable and st.dil > 1:
-        # dilated layer on the three-kernel form: where tile 44 is allowed as such; a runtime with an accuracy policy
-        # (Context-Transformer networks) takes it from ctx_w4s_min_cin input channels up (CTDET_CTX_DIL_W4S=0: never --
-        # the layer then runs the table's previous choice, '|alt').  Only tile 44 (and its f16x2 twin 47) exists for these layers: a caller
-        # that rules out F(4x4) (wino4=False) gets the '|alt' entry as well.
-        policy = getattr(backend, 'wino_tile_set', None) is not None
-        if policy:
-            usable = os.environ.get('CTDET_CTX_DIL_W4S', CTX_DIL_W4S_DEFAULT) != '0' and st.cin >= getattr(backend, 'ctx_w4s_min_cin', 0) > 0
-        else:
-            usable = codes[cfg] in wino_tiles(backend, st)
-        usable = usable and wino4
-    if cfg in codes and not usable:
-        cfg = tune_table().get(st.tune_key(batch) + '|alt')       # what the layer ran on before the three-kernel form took it
-    if usable:
-        allowed = wino_tiles(backend, st)
-        want = codes[cfg]
-        if want in F4_TILES and not wino4:
-            want = 2
-        if getattr(backend, 'wino_tile_set', None) is not None:
-            # accuracy policy of this runtime: F(4x4) / fp32 survives only where the policy allows it (short channel sums),
-            # everything else runs the most accurate allowed variant
-            w4s_min = getattr(backend, 'ctx_w4s_min_cin', 0)
-            f4 = ctx_f4_tile()
-            f4 = f4 if f4 in allowed else 4     # tile 46 needs 16-channel chunks
-            if want in F4_TILES and w4s_min and st.cin >= w4s_min and st.rt.get('wino4s_ok'):
-                want = 44                   # three-kernel F(4x4) with two accumulators: 0.4x the rounding of the fused fp32 form
-            elif want in (4,) + WINO4F_TILES and f4 in allowed:
-                want = f4                   # a fused F(4x4) entry below ctx_f4_max_cin input channels (wino_tiles put f4 into the set)
-            else:
-                want = 23 if 23 in allowed else 2 if 2 in allowed or not allowed else allowed[0]
-        elif want in WINO4F_TILES and st.cin > (getattr(backend, 'w4f_max_cin', None) or 1 << 30):
-            # the training runtime of a Context-Transformer network (TrainRuntime sets w4f_max_cin = 128): the fused bf16x3
-            # kernel has ONE accumulator, 3.4e-6 of the output range at 256 input channels and 4.6e-6 at 512 against 1.3-2.0e-6
-            # for the three-kernel form, and the block's backward amplifies that (conf.3's gradient 2.5e-4 from fp64 instead of
-            # <= 1.4e-4 at RFBNet-512 bs 8) -- its wide layers stay on the three-kernel form
-            want = 44 if st.rt.get('wino4s_ok') and 44 in allowed else 4 if 4 in allowed else 2
-        elif want not in allowed:
-            # a three-kernel / fused-bf16x3 F(4x4) entry without its tile in the set (CTDET_WINO_TILES=2,4) is the fused fp32 F(4x4) kernel's layer
-            want = 4 if want in WINO4S_TILES + WINO4F_TILES and 4 in allowed else 2 if 2 in allowed or not allowed else allowed[0]
-        if getattr(backend, 'h2', False) and H2_OF_TILE.get(want) in allowed:
-            want = H2_OF_TILE[want]         # the same kernel on the f16x2 operand form (operand_form_h2)
-        backend.enable_wino(st, tile=want)
-        return True
-    if isinstance(cfg, str) and cfg.startswith('h2:'):
-        # the f16x2 twin of a direct-kernel tile: only from a '<key>|h2' entry (tools/tune_convs.py --h2 times it against the
-        # bf16x3 tile per shape: it wins from batch 8-16 up, not on the launch-bound small batches)
-        xn = backend.x3_names()
-        if getattr(backend, 'h2_direct', False) and cfg in xn and x3_allowed(st) and st.cin % backend.x3_bk(xn.index(cfg)) == 0:
-            backend.enable_x3(st, xn.index(cfg))
-            return True
-        cfg = 'x3:' + cfg[3:]
-    if isinstance(cfg, str) and cfg.startswith('x3:'):
-        xn = backend.x3_names()
-        if cfg in xn and x3_allowed(st) and st.cin % backend.x3_bk(xn.index(cfg)) == 0:     # the k-step must divide cin
-            use = cfg
-            backend.enable_x3(st, xn.index(use))
-            return True
-        cfg = tune_table().get(st.tune_key(batch) + '|f32')       # the best fp32-MFMA tile, recorded next to it
-    if cfg == 'valu' and not (st.cin == 3 and (st.kh, st.kw, st.stride, st.dil) == (3, 3, 1, 1) and st.res is None):
-        cfg = None                      # the vector-ALU kernel exists for the 3-channel image layer only
-    if cfg in names:
-        st.rt['config'] = names.index(cfg) + 1
-        st.rt['desc'].config = st.rt['config']
-        return True
-    return False
+    """Give a prepared conv step the committed tile choice for its shape under the backend's policy (conv_policy.choose_forward);
+    False if the table has none.  wino4=False maps a 'wino4' entry to 'wino'."""
+    policy = backend.policy if wino4 else dataclasses.replace(backend.policy, wino4=False)
+    c = conv_policy.choose_forward(policy, tune_table(), backend.kernels, conv_policy.Layer.of(st, batch))
+    if c is None:
+        return False
+    if c.kind == 'wino':
+        backend.enable_wino(st, tile=c.value)
+    elif c.kind == 'x3':
+        backend.enable_x3(st, c.value)
+    else:
+        st.rt['config'] = st.rt['desc'].config = c.value
+    return True
+
+
+SIDE_AFTER_DEFAULT = ''
 
 
 def run_on_streams(rt, run_step):
@@ -1059,18 +918,13 @@ class Runtime:
         for name, shp in self.plan.buf_shapes.items():
             bufs[name] = backend.alloc((batch,) + tuple(shp))
         self.bufs = bufs
+        self.policy = backend.policy = conv_policy.resolve(net, batch, os.environ)
         for st in self.plan.steps:
             if st.kind == 'conv':
                 backend.prepare_conv(st, bufs, batch)
         # tile config per conv: committed table first (names, so it survives config reordering),
         # live autotune only for shapes the table does not know (CTDET_TUNE=0 disables, =2 forces)
         mode = os.environ.get('CTDET_TUNE', '1') if tune is None else ('1' if tune else '0')
-        backend.wino_tile_set = ctx_tile_set(net)
-        backend.h2, backend.h2_direct = operand_form_h2(net, batch)
-        if os.environ.get('CTDET_CTX_W4F_MAX_CIN') and getattr(net, 'method', None) == 'ours' and getattr(net, 'phase', 1) == 2:
-            backend.w4f_max_cin = int(os.environ['CTDET_CTX_W4F_MAX_CIN'])      # experiments: fused one-accumulator kernel only up to here
-        backend.wino4_max_cin = ctx_f4_max_cin(net)
-        backend.ctx_w4s_min_cin = ctx_w4s_min_cin(net)
         self.tuned = False
         self.live_tuned = []
         self.event_log = None        # set to a list to collect (step, start_event, end_event) per conv
@@ -1082,9 +936,8 @@ class Runtime:
             # shapes the committed table does not serve: timed live (mode 1 / 2) or left to the library's heuristic (mode 0) --
             # either way a tile choice no parity test pinned at that shape (bench.py refuses a headline with any)
             self.live_tuned = [st.tune_key(batch) for st in missing]
-            # CTDET_WINO_FORCE = tile code (experiments, tools/ctx_parity.py): every layer that runs on a Winograd kernel
-            # and has the geometry for it is moved to that variant
-            force = int(os.environ.get('CTDET_WINO_FORCE', '0') or 0)
+            # ConvPolicy.force_tile: every layer that runs on a Winograd kernel and has the geometry for it is moved to that variant
+            force = self.policy.force_tile
             for st in (self.conv_steps() if force else ()):
                 # dilated layers only exist on the three-kernel form: they keep it unless that is what is being forced
                 geo = st.rt.get('wino4s_ok') if force in WINO4S_TILES else st.rt.get('wino4f_ok') if force in WINO4F_TILES else \
@@ -1355,7 +1208,7 @@ class Runtime:
         """Every switch that shaped this runtime's kernel choice, resolved to what is in force (bench.py prints it as
         `config.policy`; a line measured under a non-default switch says so).  `env` lists the CTDET_* variables that are set --
         the library reads a few of its own (launch geometry experiments), so they are named even where Python ignores them."""
-        b = self.backend
+        b, p = self.backend, self.policy
         tiles = {}
         for st in self.conv_steps():
             w = st.rt.get('wino')
@@ -1364,10 +1217,10 @@ class Runtime:
         rec = b.policy_extra(self.conv_steps()) if hasattr(b, 'policy_extra') else {}
         return {
             **rec,
-            'operand_form': 'f16x2' if getattr(b, 'h2', False) else 'bf16x3',
-            'direct_twins_f16x2': bool(getattr(b, 'h2_direct', False)),
-            'ctx_tiles': ctx_policy(self.net),
-            'wino_tile_set': sorted(b.wino_tile_set) if getattr(b, 'wino_tile_set', None) is not None else None,
+            'operand_form': 'f16x2' if p.h2 else 'bf16x3',
+            'direct_twins_f16x2': p.h2_direct,
+            'ctx_tiles': p.ctx_tiles,
+            'wino_tile_set': sorted(p.tile_set) if p.tile_set is not None else None,
             'winograd_layers_by_tile': {str(k): v for k, v in sorted(tiles.items())},
             'tune_table': os.path.basename(TUNE_TABLE),
             'live_tuned_layers': len(self.live_tuned),

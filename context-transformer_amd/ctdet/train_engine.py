@@ -23,9 +23,8 @@ import os
 
 import torch
 
-from . import _lib, ops
-from .engine import (F4_TILES, WINO4F_TILES, WINO4S_TILES, ConvPart, ConvStep, HipBackend, Plan, Runtime, absmax_source, apply_tuned,
-                     operand_form_h2, run_on_streams)
+from . import _lib, conv_policy, ops
+from .engine import ConvPart, ConvStep, HipBackend, Plan, Runtime, absmax_source, apply_tuned, run_on_streams
 from . import wgrad_routes
 from .wino_forms import FORMS
 
@@ -63,15 +62,10 @@ class TrainRuntime:
         w4s_ws = 0              # bytes: workspace of the three-kernel Winograd data gradients
         wgrad_ws = {}           # bytes: the shared weight-gradient workspaces, by the runtime attribute that holds them
         self.wgrad_h2 = wgrad_routes.h2_enabled(os.environ)         # opt-in, resolved once here
-        # CTDET_TRAIN_WINO4=0 keeps forward and data-gradient convolutions on F(2x2,3x3) where the table says F(4x4,3x3)
-        wino4 = os.environ.get('CTDET_TRAIN_WINO4', '1') != '0'
-        # The Winograd launches of the step (forward and data gradients) on the f16x2 operand form (csrc/ct_f16x2.h) wherever the
-        # table's bf16x3 tile has that twin, under the inference runtime's batch rule (engine.operand_form_h2); CTDET_TRAIN_H2=0
-        # keeps bf16x3.  Direct layers stay on bf16x3: their inputs come from the BatchNorm kernels, which do not track maxima.
-        self.h2 = os.environ.get('CTDET_TRAIN_H2', '1') != '0' and operand_form_h2(net, batch)[0]
-        backend.h2, backend.h2_direct = self.h2, False
-        if self.plan.ctx:
-            backend.w4f_max_cin = int(os.environ.get('CTDET_TRAIN_CTX_W4F_MAX_CIN', '128'))      # engine.apply_tuned
+        # the kernel policy of the step (ctdet/conv_policy.py): forward and data-gradient launches; h2 = its Winograd launches run
+        # on the f16x2 operand form (csrc/ct_f16x2.h)
+        policy = self.policy = backend.policy = conv_policy.resolve(net, batch, os.environ, training=True)
+        wino4, self.h2 = policy.wino4, policy.h2
         for st in self.plan.steps:
             if st.kind != 'conv':
                 continue
@@ -110,7 +104,7 @@ class TrainRuntime:
                 s.fwd = st
                 s.dbias = [al((p.cout,)) for p in st.parts]
             # data-gradient launch (not needed for the image itself)
-            s.dgrad = None
+            s.dgrad, s.dgrad_x3 = None, None
             if st.src != 'x':
                 zc = s.zc
                 kpad = self.lib.ct_conv_kpad(zc, st.kh, st.kw)
@@ -134,67 +128,27 @@ class TrainRuntime:
                     d.ksplit, d.ksplit_ws, d.ksplit_ws_floats = -1, s.ksws_d.data_ptr(), s.ksws_d.numel()
                 s.dgrad = d
                 s.kpad_d, s.mpad_d = kpad, mpad
-                # 3x3 / stride 1 / pad 1 layers: the data gradient is itself such a convolution (channels
-                # swapped, taps rotated) -> Winograd kernel on dY with ct_conv_pack_weights_wino_dgrad
-                s.dgrad_wino = None
-                if (st.kh, st.kw, st.stride, st.dil, st.ph, st.pw) == (3, 3, 1, 1, 1, 1) and zc % 8 == 0 \
-                        and st.oh * st.ow >= 19 * 19:
-                    w2 = _lib.ConvDesc()
-                    C.memmove(C.byref(w2), C.byref(d), C.sizeof(d))
-                    w2.transposed = 0
-                    w2.kh = w2.kw = 3
-                    if self.lib.ct_conv_wino_supported(C.byref(w2)):
-                        s.dgrad_wino = w2
-                        # F(4x4,3x3) where the forward launch of this layer uses it (same map, channels swapped) and on
-                        # the multibox heads from 19x19 maps up (their forward launch is a bf16x3 / F(2x2) one chosen for
-                        # cout = 156; the data gradient has cout = the source's channel count)
-                        w4_ok = bool(self.lib.ct_conv_wino4_supported(C.byref(w2)))
-                        s.dgrad_tile = 4 if w4_ok and (s.fwd.rt.get('wino') in F4_TILES or
-                                                       (wino4 and st.segs and st.oh * st.ow >= 361)) else 2
-                        # ... and its three-kernel bf16x3 form (tile 44) where the forward launch runs that one
-                        # (CTDET_TRAIN_W4S=0 keeps the fused kernel)
-                        if s.fwd.rt.get('wino') in WINO4S_TILES and os.environ.get('CTDET_TRAIN_W4S', '1') != '0' and \
-                                self.lib.ct_conv_wino4s_supported(C.byref(w2)):
-                            s.dgrad_tile = 47 if self.h2 else 44
-                        elif s.fwd.rt.get('wino') in WINO4F_TILES and os.environ.get('CTDET_TRAIN_W4F', '1') != '0' and \
-                                zc <= (getattr(backend, 'w4f_max_cin', None) or 1 << 30) and \
-                                self.lib.ct_conv_wino4f_supported(C.byref(w2)):
-                            # ... and the fused bf16x3 F(4x4,3x3) kernel (tile 46) where the forward launch runs it: the narrow
-                            # layers on the big maps, whose data gradients were 7 launches x 1.13 ms of the 37.8 ms step on the
-                            # fp32 kernel (profiles/r05_train_kernel_stats.md)
-                            # (f16x2, tile 48: where dZ comes from ct_bias_act_backward_amax, which leaves the maxima the fused
-                            # kernel needs -- the VGG trunk; a BatchNorm layer's dZ has none: bf16x3)
-                            s.dgrad_tile = 48 if self.h2 and not s.is_bn and not st.segs else 46
-                # dilated 3x3 layers (pad = dilation) whose forward launch runs the three-kernel form: their data gradient is
-                # the same dilated convolution with channels swapped and taps rotated -> the same kernels (tiles on the
-                # dilation sub-lattices); the dilated output transform has no accumulate, so a source gradient that was already
-                # written goes through a scratch tensor (does not happen in these networks)
-                elif (st.kh, st.kw, st.stride) == (3, 3, 1) and st.dil > 1 and st.ph == st.pw == st.dil and zc % 16 == 0 and \
-                        s.fwd.rt.get('wino') in WINO4S_TILES and os.environ.get('CTDET_TRAIN_W4S', '1') != '0' and \
-                        os.environ.get('CTDET_TRAIN_W4S_DIL', '1') != '0':
-                    w2 = _lib.ConvDesc()
-                    C.memmove(C.byref(w2), C.byref(d), C.sizeof(d))
-                    w2.transposed = 0
+                # the data gradient written as a forward convolution on dZ (channels swapped, taps rotated: the packed weights):
+                # what the Winograd kernels launch on, and what their geometry checks are asked about.  The dilated output
+                # transform has no accumulate, so a source gradient that was already written goes through a scratch tensor
+                # (does not happen in these networks)
+                w2 = _lib.ConvDesc()
+                C.memmove(C.byref(w2), C.byref(d), C.sizeof(d))
+                w2.transposed = 0
+                if st.dil > 1:
                     w2.ksplit, w2.ksplit_ws, w2.ksplit_ws_floats = 0, None, 0
-                    if self.lib.ct_conv_wino4s_supported(C.byref(w2)):
-                        s.dgrad_wino = w2
-                        s.dgrad_tile = 47 if self.h2 else 44
+                s.dgrad_tile, s.dgrad_x3 = conv_policy.choose_dgrad(
+                    policy, conv_policy.Layer.of(st, batch, zc, s.is_bn), s.fwd.rt.get('wino'),
+                    lambda form: bool(getattr(self.lib, 'ct_conv_%s_supported' % form)(C.byref(w2))))
+                s.dgrad_wino = w2 if s.dgrad_tile is not None else None
                 if s.dgrad_wino is not None:
                     f = FORMS[s.dgrad_tile]
                     s.U_d = f.alloc(self.lib, al, zc, st.cin, dgrad=True)
                     if f.split:                 # V / M workspace shared by all data gradients
                         w4s_ws = max(w4s_ws, self.lib.ct_conv_wino4s_workspace_bytes(C.byref(w2)))
-            # direct data gradients on the bf16 matrix pipe (bf16x3, ct_conv2d_x3_fwd transposed): every layer without
-            # a Winograd data gradient whose channel counts fit the k-step; CTDET_X3=0 keeps ct_conv2d_fwd
-            s.dgrad_x3 = None
-            if s.dgrad is not None and getattr(s, 'dgrad_wino', None) is None and st.stride <= 2 and \
-                    os.environ.get('CTDET_X3', '1') != '0' and s.zc % 16 == 0 and s.zc >= 32:
-                npix = batch * st.h * st.w
-                tiles128 = -(-st.cin // 128) * -(-npix // 128)
-                cfg = 0 if tiles128 >= 512 else (3 if s.zc % 32 == 0 and -(-st.cin // 64) * -(-npix // 128) < 384 else 1)
-                bk = self.lib.ct_conv_x3_config_bk(cfg)
-                s.dgrad_x3 = cfg
-                s.wx3_d = al((self.lib.ct_conv_x3_packed_bytes(s.zc, st.cin, st.kh, st.kw, bk),), torch.uint8)
+                if s.dgrad_x3 is not None:
+                    s.wx3_d = al((self.lib.ct_conv_x3_packed_bytes(zc, st.cin, st.kh, st.kw, self.lib.ct_conv_x3_config_bk(s.dgrad_x3)),),
+                                 torch.uint8)
             # weight-gradient descriptor = forward geometry on the forward input
             w = _lib.ConvDesc()
             src = self.bufs[st.src]
