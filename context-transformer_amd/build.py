@@ -47,6 +47,7 @@ SOURCES = {
     'ct_nms.hip': ['-ffp-contract=off'],
     'ct_post.hip': ['-ffp-contract=off'],
     'ct_eval.hip': ['-ffp-contract=off'],
+    'ct_coco_eval.hip': ['-ffp-contract=off'],
     'ct_cpu_nms.cpp': ['-ffp-contract=off'],
 }
 COMMON = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-I' + os.path.join(REPO, 'include'),

@@ -112,6 +112,9 @@ SIGNATURES = {
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_voc_match': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _D, _P, _P, _I, _P, _P]),
     'ct_voc_pr': (_I, [_P, _P, _LL, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    'ct_coco_match': (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P,
+                           _P]),
+    'ct_coco_accumulate': (_I, [_P, _P, _P, _P, _LL, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     'ct_conv_kpad': (_I, [_I, _I, _I]),
     'ct_conv_mpad': (_I, [_I]),
     'ct_conv_num_configs': (_I, []),

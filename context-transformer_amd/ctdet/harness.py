@@ -17,8 +17,8 @@ def detect_dataset(net, priors, dataset, transform, num_fg, batch=32, max_per_im
                    force_cpu_rule=False, progress=None, evaluator=None, keep_boxes=True):
     """-> all_boxes[cls][img] (cls 0 = background, empty lists as in test.py:107-108).
 
-    evaluator: an evaluate.DeviceVOCEvaluator over this data set (image i of the data set = its image_ids[i]); every
-    batch's device output is handed to evaluator.add, the padding images of the ragged last batch as -1.
+    evaluator: an evaluate.DeviceVOCEvaluator or evaluate.DeviceCOCOEvaluator over this data set (image i of the data
+    set = its image_ids[i]) -- anything with add(out_dets, out_count, image_index) and finish(); every batch's device output is handed to evaluator.add, the padding images of the ragged last batch as -1.
     keep_boxes=False: no host copy of the detections at all -- no per-batch synchronisation -- and None is returned;
     the post-processing's overflow flag is collected on the device and looked at once, after the last batch."""
     n = len(dataset)
@@ -64,8 +64,8 @@ def do_test(net, priors, dataset, transform, num_fg, save_folder, batch=32, max_
             force_cpu_rule=False, retest=False, evaluator=None, keep_boxes=True):
     """test.py:96-175: detect, write `detections.pkl`, hand over to the dataset's evaluator.
 
-    With `evaluator` (evaluate.DeviceVOCEvaluator) the second result is its (aps, mean) instead of the data set's own
-    evaluation; keep_boxes=False then also skips the host copies and `detections.pkl`, and the first result is None."""
+    With `evaluator` the second result is its finish() -- (aps, mean) of evaluate.DeviceVOCEvaluator, (results, stats)
+    of evaluate.DeviceCOCOEvaluator -- instead of the data set's own evaluation; keep_boxes=False then also skips the host copies and `detections.pkl`, and the first result is None."""
     import pickle
     if retest and (evaluator is not None or not keep_boxes):
         raise ValueError('retest reads detections.pkl: it has nothing to feed a device evaluator and needs the boxes')

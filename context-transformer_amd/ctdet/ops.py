@@ -295,6 +295,38 @@ def voc_pr(ev, order, cls_off, thresholds=None):
                           _dev(ev.pr_status, 'pr_status', torch.int32), _stream()), 'ct_voc_pr')
 
 
+# ------------------------------------------------------------------ COCO evaluation
+def coco_match(out_dets, out_count, image_index, ev, cap):
+    """ct_coco_match of one pipeline batch into the buffers of `ev` (evaluate.DeviceCOCOEvaluator): the packed ground
+    truth, the thresholds, the records keys / matched / ignored and the status words."""
+    i32, f64 = torch.int32, torch.float64
+    check(lib().ct_coco_match(_dev(out_dets, 'out_dets'), _dev(out_count, 'out_count', i32), out_dets.shape[0], ev.T,
+                              int(cap), _dev(image_index, 'image_index', i32), _dev(ev.image_rank, 'image_rank', i32),
+                              ev.N, _dev(ev.gt_boxes, 'gt_boxes', f64), _dev(ev.gt_area, 'gt_area', f64),
+                              _dev(ev.gt_iscrowd, 'gt_iscrowd', torch.uint8), _dev(ev.gt_label, 'gt_label', i32),
+                              _dev(ev.gt_off, 'gt_off', i32), ev.G, _dev(ev.cat_rank, 'cat_rank', i32),
+                              _dev(ev.iou_thrs_dev, 'iou_thrs', f64), ev.n_iou, _dev(ev.area_rng_dev, 'area_rng', f64),
+                              ev.A, _dev(ev.keys, 'keys', torch.int64), _dev(ev.matched, 'matched', torch.int64),
+                              _dev(ev.ignored, 'ignored', torch.int64), ev.per_image_cap,
+                              _dev(ev.status, 'status', i32), _stream()), 'ct_coco_match')
+
+
+def coco_accumulate(keys, matched, ignored, order, cat_off, npig, max_dets, n_iou, rec_thrs, precision, recall, scores,
+                    status):
+    """ct_coco_accumulate over records in the order of the key sort (order None: the records are already sorted) into
+    precision / scores [T,R,K,A,M] and recall [T,K,A,M] (device float64).  matched / ignored hold the 64 mask bits in
+    int64 tensors (torch has no uint64 arithmetic); npig is [K,A] int32, max_dets int32, rec_thrs float64, ascending."""
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
+    K, A = npig.shape
+    check(lib().ct_coco_accumulate(_dev(keys, 'keys', i64), _dev(matched, 'matched', i64),
+                                   _dev(ignored, 'ignored', i64), _opt(order, 'order', i64), keys.numel(),
+                                   _dev(cat_off, 'cat_off', i64), _dev(npig, 'npig', i32), K, A,
+                                   _dev(max_dets, 'max_dets', i32), max_dets.numel(), int(n_iou),
+                                   _dev(rec_thrs, 'rec_thrs', f64), rec_thrs.numel(), _dev(precision, 'precision', f64),
+                                   _dev(recall, 'recall', f64), _dev(scores, 'scores', f64),
+                                   _dev(status, 'acc_status', i32), _stream()), 'ct_coco_accumulate')
+
+
 # ------------------------------------------------------------------ input transform
 class Preprocessor:
     """Batched BaseTransform (data/data_augment.py:224-266) on the device: uint8 HxWx3 images of

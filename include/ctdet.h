@@ -304,6 +304,84 @@ int ct_voc_pr(const uint8_t* rec_flag, const long long* order, long long num_rec
               int num_thresholds, double* rec_out, double* prec_out, double* ap_out, int* status,
               ct_stream_t stream);
 
+/* ------------------------------------------------------- COCO bbox evaluation ---- */
+
+/* utils/pycocotools/cocoeval.py COCOeval(..., 'bbox') evaluate() + accumulate() (useCats = 1) and maskApi.c bbIou on the
+ * device, fed from the buffers the post-processing leaves: the match rule per pipeline batch (ct_coco_match), then --
+ * after the caller has sorted the 64-bit keys -- precision / recall / scores in the reference's layout
+ * (ct_coco_accumulate).  Host twin: ctdet/evaluate.py coco_eval_arrays; the two agree bit for bit.
+ *
+ * ct_coco_match: one launch per batch, no allocation, no host synchronisation, plain vector stores.
+ *   out_dets dev [B,T,cap,5], out_count dev [B,T]   as the post-processing writes them; counts are clamped to 0 .. cap.
+ *                                                   A segment need not be sorted: the stable descending-score rank of
+ *                                                   a row is found by counting (greater score, or equal score and a
+ *                                                   smaller row number); ranks >= CT_COCO_MAX_DETS are dropped
+ *   image_index dev [B]                             data set position of each image; < 0 = padding image, whose rows
+ *                                                   are never read
+ *   image_rank dev int [num_images] or NULL         data set position -> rank of the image by ascending image id
+ *                                                   (the order COCOeval accumulates in); NULL = the identity
+ *   gt_boxes dev double [G,4] as [x, y, w, h], gt_area dev double [G] (the annotation's own area), gt_iscrowd dev
+ *   uint8 [G], gt_label dev int [G] in 1 .. T, gt_off dev int [num_images+1] indexed by image RANK; the boxes of one
+ *   category in one image keep annotation order and are at most CT_COCO_MAX_GT_PER_SEGMENT
+ *   cat_rank dev int [T]                            class c (0-based) -> position of its category on the K axis
+ *   iou_thrs dev double [num_iou_thrs <= 16]        already clamped by the host: min(t, 1 - 1e-10)
+ *   area_rng dev double [num_area_rng <= 4, 2]      inclusive [lo, hi]; num_iou_thrs * num_area_rng <= 64
+ * A kept row [x1,y1,x2,y2,s] becomes [x1, y1, x2-x1+1, y2-y1+1] in double (data/coco.py:242-258), its area w*h.  IoU as
+ * bbIou: w = min(D2+D0, G2+G0) - max(D0, G0), w <= 0 -> 0, h likewise, i = w*h, u = da for a crowd box, else
+ * (da+ga)-i.  Per (threshold, area range) pair the walk of evaluateImg (cocoeval.py:256-299) in rank order: boxes
+ * stably reordered with ignored ones (crowd, or annotation area outside the range) last; a matched non-crowd box is
+ * skipped; the walk breaks on an ignored box once it holds a regular match; IoU < running threshold continues (an
+ * equal IoU matches); the last best box wins.  An unmatched row whose area is outside the range is ignored.
+ * Records: kept row of rank d in class c of the image goes to slot image_rank * per_image_cap + e, e = (kept rows of
+ * the image's classes before c) + d:
+ *   rec_key dev int64:  cat_rank << 56 | ~(order-preserving 32-bit image of the float32 score) << 24 | image_rank << 7 | d
+ *   rec_matched / rec_ignored dev uint64: bit (t * num_area_rng + a) = the row is matched / ignored for that pair
+ * Ascending keys = (category, score descending, image rank, rank in segment) = the stable argsort(-score) of
+ * accumulate() over the images in ascending id.  Keys are unique and 63 bits wide; the caller fills unused slots with
+ * CT_COCO_KEY_UNUSED, which sorts last.  Hence T and K <= 127, num_images <= 131072, cap <= 4096.
+ * status dev int [2], zeroed by the caller once: status[0] collects CT_COCO_OVERFLOW (an image keeps more rows than
+ * per_image_cap: none of them is written), CT_COCO_BAD_INDEX (image_index >= num_images, an image_rank, gt_off or
+ * cat_rank entry out of range, or more than CT_COCO_MAX_GT_PER_SEGMENT boxes in a segment: skipped) and
+ * CT_COCO_BAD_SCORE (a NaN score); status[1] = the largest number of kept rows of an image so far, the per_image_cap to
+ * ask for.  Feeding one image twice is not detected: the later records replace the earlier ones. */
+#define CT_COCO_MAX_GT_PER_SEGMENT 256
+#define CT_COCO_MAX_DETS 100
+#define CT_COCO_MAX_IOU_THRS 16
+#define CT_COCO_MAX_AREA_RNG 4
+#define CT_COCO_MAX_REC_THRS 128
+#define CT_COCO_MAX_CATEGORIES 127
+#define CT_COCO_MAX_IMAGES 131072
+#define CT_COCO_ACC_CHUNK 512
+#define CT_COCO_KEY_UNUSED INT64_MAX
+enum { CT_COCO_OVERFLOW = 1, CT_COCO_BAD_INDEX = 2, CT_COCO_BAD_SCORE = 4 };
+int ct_coco_match(const float* out_dets, const int* out_count, int batch, int num_fg, int cap,
+                  const int* image_index, const int* image_rank, int num_images, const double* gt_boxes,
+                  const double* gt_area, const uint8_t* gt_iscrowd, const int* gt_label, const int* gt_off,
+                  int num_gt, const int* cat_rank, const double* iou_thrs, int num_iou_thrs,
+                  const double* area_rng, int num_area_rng, long long* rec_key,
+                  unsigned long long* rec_matched, unsigned long long* rec_ignored, int per_image_cap,
+                  int* status, ct_stream_t stream);
+/* cocoeval.py:315-418 (accumulate): one workgroup per (category k, area range a, limit m), one wave per IoU threshold,
+ * over the rows cat_off[k] .. cat_off[k+1]-1 of the sorted order whose rank in their segment is < max_dets[m] (one
+ * sort serves every limit: a subsequence of a sorted list is sorted).
+ *   rec_key / rec_matched / rec_ignored dev [num_records]; order dev int64 [num_records] = the permutation of the key
+ *   sort, or NULL when the records are already in sorted order
+ *   cat_off dev int64 [K+1] (first sorted position of each category's keys; ascending, within 0 .. num_records)
+ *   npig dev int [K, num_area_rng]: the category's non-crowd boxes with lo <= area <= hi
+ *   max_dets dev int [num_max_dets <= 4]; rec_thrs dev double [num_rec_thrs <= 128], ascending
+ * tp / fp are scanned as integers in chunks of CT_COCO_ACC_CHUNK rows with a carry; rc = tp / npig and
+ * pr = tp / ((fp + tp) + DBL_EPSILON) in double, the maximum of pr from the right, then for every recall threshold the
+ * envelope and the score at the first row with rc >= threshold, 0 where there is none.  Written in the reference's
+ * layout: precision, scores dev double [T,R,K,A,M], recall dev double [T,K,A,M] (the last rc, 0 without rows); -1
+ * everywhere for a (k, a) with npig == 0.
+ * status dev int [1]: collects CT_COCO_BAD_INDEX for a cat_off or order entry out of range (never dereferenced). */
+int ct_coco_accumulate(const long long* rec_key, const unsigned long long* rec_matched,
+                       const unsigned long long* rec_ignored, const long long* order, long long num_records,
+                       const long long* cat_off, const int* npig, int num_categories, int num_area_rng,
+                       const int* max_dets, int num_max_dets, int num_iou_thrs, const double* rec_thrs,
+                       int num_rec_thrs, double* precision, double* recall, double* scores, int* status,
+                       ct_stream_t stream);
+
 /* ------------------------------------------------------------ convolution ---- */
 
 /* One fused convolution of the RFBNet-VGG stack.  Replaces the ATen sequence
