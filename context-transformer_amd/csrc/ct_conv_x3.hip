@@ -30,6 +30,7 @@
 #include "ct_device.h"
 #include "ct_f16x2.h"
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -77,6 +78,71 @@ struct X3Args {
     const int* eW;
     unsigned* out_amax;             // ct_conv_desc.out_absmax: max |y| of what the launch stores, or null (any form)
 };
+
+// ---- epilogue (the arithmetic of ct_conv2d_fwd), shared by conv_x3_f32 and its pointwise form conv_x3_f32_pw: the wave's
+// (BM/2) x (BN/2) block of sums `acc` (DUAL already folded in) -> scale / shift, residual, floor, maxima, stores.  `lds`: the
+// workgroup's operand tiles, dead after the last barrier of the k-loop.
+template <int BM, int BN, bool H2, int TM, int TN>
+__device__ __forceinline__ void x3_epilogue(const X3Args& a, const f32x16 (&acc)[TM][TN], unsigned char* lds, int m0, int n0,
+                                            int wm0, int wn0, int tid, int l31, int hsel)
+{
+    float* const ev = reinterpret_cast<float*>(lds);              // [3][BM]: scale, shift, floor (the operand tiles are dead)
+    for (int i = tid; i < BM; i += 256) ctdet::stage_epilogue_vector<BM>(ev, a, m0, i);
+    __syncthreads();
+    const bool track = a.out_amax != nullptr;
+    int eW = 0;
+    if constexpr (H2) eW = *a.eW;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int P = n0 + wn0 + j * 32 + l31;
+        const bool live = P < a.Npix;
+        const int n = live ? P / a.OHW : -1;
+        float amax_run = 0.f;                       // a.out_amax: the thread's maximum of |v| over what it stores for pixel P's image
+        if (live) {
+            const int s = P - n * a.OHW;
+            // f16x2: the sums carry 2^(eX[image] + eW); undone with an exact power of two in front of the per-channel scale
+            ctdet::h2::pow2x2 ymul{1.f, 1.f};
+            if constexpr (H2) ymul = ctdet::h2::unscale_for(eW, ctdet::h2::image_exponent(a.in_amax, n, ctdet::h2::kGrowthNone));
+            float* const orow = a.nseg == 0 ? a.out + ((size_t)n * a.out_ctot + a.out_coff) * a.OHW + s : nullptr;
+            const float* const rrow = a.res ? a.res + ((size_t)n * a.res_ctot + a.res_coff) * a.OHW + s : nullptr;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                // the residual values of the whole 32 x 32 block first, sixteen loads in flight: taken one by one between the
+                // stores (which they may alias, so the compiler keeps the order) every load waited a full round trip behind the
+                // previous store -- the RFB blocks' ConvLinear layers ran at 0.6 of the rate of the same GEMM without a shortcut
+                float rv[16];
+                if (rrow) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int co = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
+                        rv[r] = co < a.M ? rrow[(size_t)co * a.OHW] : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int cl = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;      // cout inside the tile
+                    const int co = m0 + cl;
+                    if (co >= a.M) continue;
+                    float v = (H2 ? (acc[i][j][r] * ymul.lo) * ymul.hi : acc[i][j][r]) * ev[cl] + ev[BM + cl];
+                    if (rrow) v = v * a.res_scale + rv[r];
+                    { const float fl = ev[2 * BM + cl]; v = v < fl ? fl : v; }      // NaN propagates (torch.relu / no clamp)
+                    if (track) ctdet::h2::track_absmax(amax_run, v);
+                    if (a.nseg == 0) {
+                        orow[(size_t)co * a.OHW] = v;
+                    } else {
+#pragma unroll
+                        for (int g = 0; g < 3; ++g)
+                            if (g < a.nseg && co >= a.seg[g].co_begin && co < a.seg[g].co_end)
+                                a.seg[g].ptr[(size_t)n * a.seg[g].img_stride + a.seg[g].base +
+                                             (size_t)s * a.seg[g].pix_stride + (co - a.seg[g].co_begin)] = v;
+                    }
+                }
+            }
+        }
+        // ct_conv_desc.out_absmax: every lane arrives here; one atomic per image present in the wave
+        if (track) ctdet::h2::flush_absmax(a.out_amax, n, amax_run);
+    }
+}
 
 // DUAL: the hi.hi products accumulate in one register block, the five small products (2^-8 .. 2^-16 of it) in a second
 //   one, added at the end -- the large accumulator then sees K / 16 roundings instead of 6 K / 16 (measured: 2.5x less
@@ -364,63 +430,223 @@ __global__ __launch_bounds__(256, 2) void conv_x3_f32(const X3Args a)
         return;
     }
 
-    // ---- epilogue (the arithmetic of ct_conv2d_fwd) ----
-    float* const ev = reinterpret_cast<float*>(lds);              // [3][BM]: scale, shift, floor (the operand tiles are dead)
-    for (int i = tid; i < BM; i += 256) ctdet::stage_epilogue_vector<BM>(ev, a, m0, i);
-    __syncthreads();
-    const bool track = a.out_amax != nullptr;
-    int eW = 0;
-    if constexpr (H2) eW = *a.eW;
+    x3_epilogue<BM, BN, H2>(a, acc, lds, m0, n0, wm0, wn0, tid, l31, hsel);
+}
+
+// The pointwise form of the f16x2 twins: 1x1 / stride 1 / pad 0 forward layers, a plain GEMM C[cout][pixel] = W[cout][cin] X[cin][pixel]
+// with X contiguous along the pixels.  Same tiles, wave layout, operand pieces, MFMA order per accumulator and epilogue as
+// conv_x3_f32<BM, BN, BK, true, true> -- every accumulator receives the same MFMA results in the same order, so the results are
+// bit-identical -- without what the generic gather pays per 16 channels:
+//   * ONE barrier per 32 input channels (two MFMA k-groups) for every tile; a k16 configuration consumes two packed steps;
+//   * the weights go HBM -> LDS by LDS-DMA (buffer_load ... lds, 16 bytes per lane): for a fixed (step, piece, octet) the BM rows
+//     of a tile are one contiguous run of the packed buffer and that run IS the LDS image -- 32 channels are eight runs, and
+//     eight runs of M_pad rows are 128 M_pad bytes in the packed buffer whatever the packing k-step; only the ORDER of the eight
+//     runs differs: k16 [k-group][piece][octet 2], k32 [piece][octet 4] (run_of below).  No staging registers, no ds_write_b128;
+//     rows at or beyond M_pad carry the out-of-range offset, for which the DMA writes zeros;
+//   * the activations: a thread's pixel offset is computed once, the channel advances by a wave-uniform scalar add; no tap
+//     counters, no bounds selects (pvalid only, for the last pixel tile).
+// Pipeline of iteration `it` (tile `it` in LDS buffer it & 1): DMA of the weights of tile it + 1 into the other buffer (free since
+// the barrier that ended iteration it - 1), then per k-group the fragment reads and the 3 TM TN MFMAs, and behind the MFMAs the
+// split and LDS write of the activations of tile it + 1 (staging registers) with the re-issue of the same registers' loads for
+// tile it + 2.  The barrier at the end waits for the LDS counter and for the DMA alone: the gathers issued after the DMA (their
+// count is static) stay in flight across it (vmcnt counts loads in issue order).
+template <int BM, int BN, int BK, bool DUAL, bool H2>
+__global__ __launch_bounds__(256, 2) void conv_x3_f32_pw(const X3Args a)
+{
+    static_assert(DUAL && H2 && (BK == 16 || BK == 32), "the pointwise form exists for the dual-accumulator f16x2 twins");
+    constexpr int WM = BM / 2, WN = BN / 2;     // wave tile (2 x 2 waves)
+    constexpr int TM = WM / 32, TN = WN / 32;
+    constexpr int RUN_A = BM * 16, RUN_B = BN * 16;          // bytes of one (k-group, piece, octet) run of a tile
+    constexpr int A_BYTES = 8 * RUN_A, B_BYTES = 8 * RUN_B;  // 32 channels: 2 pieces x 4 octets
+    constexpr int NAD = BM / 32;                             // DMA instructions (64 rows of 16 bytes) per wave and iteration
+    constexpr int OSTR = 256 / BN;                           // octet stride between a thread's gathers
+    constexpr int GPT = 4 / OSTR;                            // k-octets gathered per thread and iteration
+    static_assert(BM % 64 == 0 && 256 % BN == 0 && 4 % OSTR == 0 && GPT >= 1, "staging");
+    // run of (k-group h, piece p, octet o of the group) among the eight runs of an iteration, in the packed buffer's order
+    auto run_of = [](int h, int p, int o) { return BK == 16 ? h * 4 + p * 2 + o : p * 4 + 2 * h + o; };
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];    // 2 x A_BYTES, then 2 x B_BYTES
+    constexpr int B_BASE = 2 * A_BYTES;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, l31 = lane & 31, hsel = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm0 = (wave & 1) * WM, wn0 = (wave >> 1) * WN;
+
+    int wg;
+    {   // XCD-aware tile order (cout-tile fastest), as conv_x3_f32
+        const int nwg = a.tiles_m * a.tiles_n;
+        const int bid = blockIdx.x;
+        const int xcd = bid & 7, local = bid >> 3;
+        const int q = nwg >> 3, r = nwg & 7;
+        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+    }
+    const int m0 = (wg % a.tiles_m) * BM;
+    const int n0 = (wg / a.tiles_m) * BN;
+
+    const __amdgpu_buffer_rsrc_t rin = make_rsrc(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wx3, a.w_bytes);
+
+    // ---- this thread's pixel (B gather): input pixel = output pixel ----
+    const int bp = tid % BN;
+    const int oct0 = __builtin_amdgcn_readfirstlane(tid / BN);       // first k-octet of this thread; next: + OSTR
+    const int HW = a.H * a.W;
+    const int chan_bytes = HW * 4;
+    int b_voff;
+    float vscale;
+    {
+        const int P = n0 + bp;
+        const bool pvalid = P < a.Npix;
+        const int Pc = pvalid ? P : 0;
+        const int n = Pc / a.OHW;
+        const int s = Pc - n * a.OHW;
+        b_voff = pvalid ? ((n * a.in_ctot + a.in_coff) * HW + s) * 4 : kInvalidOff;
+        // split as x 2^eX with eX from the maximum of |input| of THIS pixel's image: a pixel tile may straddle images
+        vscale = __builtin_ldexpf(1.f, ctdet::h2::image_exponent(a.in_amax, n, ctdet::h2::kGrowthNone));
+    }
+
+    // ---- A: this wave's DMA instructions of an iteration: item = wave * NAD + j -> (run, 64-row half of the run) ----
+    int a_voff[NAD], a_dst[NAD];
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int P = n0 + wn0 + j * 32 + l31;
-        const bool live = P < a.Npix;
-        const int n = live ? P / a.OHW : -1;
-        float amax_run = 0.f;                       // a.out_amax: the thread's maximum of |v| over what it stores for pixel P's image
-        if (live) {
-            const int s = P - n * a.OHW;
-            // f16x2: the sums carry 2^(eX[image] + eW); undone with an exact power of two in front of the per-channel scale
-            ctdet::h2::pow2x2 ymul{1.f, 1.f};
-            if constexpr (H2) ymul = ctdet::h2::unscale_for(eW, ctdet::h2::image_exponent(a.in_amax, n, ctdet::h2::kGrowthNone));
-            float* const orow = a.nseg == 0 ? a.out + ((size_t)n * a.out_ctot + a.out_coff) * a.OHW + s : nullptr;
-            const float* const rrow = a.res ? a.res + ((size_t)n * a.res_ctot + a.res_coff) * a.OHW + s : nullptr;
+    for (int j = 0; j < NAD; ++j) {
+        const int item = wave * NAD + j;
+        const int run = item / (BM / 64), half = item % (BM / 64);
+        const int col = m0 + half * 64 + lane;
+        a_voff[j] = col < a.M_pad ? (run * a.M_pad + col) * 16 : kInvalidOff;
+        a_dst[j] = run * RUN_A + half * 1024;          // wave-uniform; the lane's 16 bytes land at + lane * 16
+    }
+    const int a_iter_bytes = 128 * a.M_pad;            // 32 channels x 2 pieces x M_pad rows x 2 bytes
+    const int niter = a.Cin / 32;                      // the launcher's rule: Cin % 32 == 0
+    int a_soff = 0;                                    // next tile of the weights (bytes, wave-uniform)
+    int b_tile_soff = oct0 * 8 * chan_bytes;           // next tile of the activations: its first channel of this thread
+
+    auto dma_a = [&](int buf) {
+        unsigned char* const dst = lds + buf * A_BYTES;
+        (void)dst; (void)rw; (void)a_voff; (void)a_dst; (void)a_soff;         // the host pass does not see the builtin
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef __attribute__((address_space(3))) void* lds_ptr;
 #pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                // the residual values of the whole 32 x 32 block first, sixteen loads in flight: taken one by one between the
-                // stores (which they may alias, so the compiler keeps the order) every load waited a full round trip behind the
-                // previous store -- the RFB blocks' ConvLinear layers ran at 0.6 of the rate of the same GEMM without a shortcut
-                float rv[16];
-                if (rrow) {
+        for (int j = 0; j < NAD; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(dst + a_dst[j]), 16, a_voff[j], a_soff, 0, 0);
+#endif
+        a_soff += a_iter_bytes;
+    };
+
+    float breg[GPT][8];
+    int ph[GPT][4], pl[GPT][4];                       // packed pairs of hi / lo pieces of the tile being stored
+    int ld_soff = 0;
+    auto load_b = [&](int g, int e) {
+        if (e == 0) ld_soff = b_tile_soff + g * (OSTR * 8) * chan_bytes;
+        breg[g][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rin, b_voff, ld_soff, 0));
+        ld_soff += chan_bytes;
+    };
+    auto end_load_b = [&]() { b_tile_soff += 32 * chan_bytes; };
+    auto store_b = [&](int g, int piece, int buf) {
+        const int o4 = oct0 + g * OSTR;                // octet of the iteration: k-group o4 >> 1, octet o4 & 1 of the group
+        i32x4 pk;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int co = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
-                        rv[r] = co < a.M ? rrow[(size_t)co * a.OHW] : 0.f;
-                    }
-                }
+        for (int q = 0; q < 4; ++q) pk[q] = piece == 0 ? ph[g][q] : pl[g][q];
+        *reinterpret_cast<i32x4*>(lds + B_BASE + buf * B_BYTES + run_of(o4 >> 1, piece, o4 & 1) * RUN_B + bp * 16) = pk;
+    };
+    // side work of an iteration as a list of items: per gathered octet 4 x (split of a pair + reload of both) and 2 x (write)
+    constexpr int IPG = 4 + 2;
+    constexpr int NW = GPT * IPG;
+    auto side_item = [&](int w, int buf, auto store_c, auto load_c) {
+        constexpr bool STORE = decltype(store_c)::value, LOAD = decltype(load_c)::value;
+        const int g = w / IPG, r = w % IPG;
+        if (r < 4) {
+            if (STORE) ctdet::h2::split2(breg[g][2 * r] * vscale, breg[g][2 * r + 1] * vscale, ph[g][r], pl[g][r]);
+            if (LOAD) { load_b(g, 2 * r); load_b(g, 2 * r + 1); }
+        } else if (STORE) {
+            store_b(g, r - 4, buf);
+        }
+    };
+
+    f32x16 acc[TM][TN], acs[TM][TN];              // (hi, hi) products; sum of the two small products
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int cl = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;      // cout inside the tile
-                    const int co = m0 + cl;
-                    if (co >= a.M) continue;
-                    float v = (H2 ? (acc[i][j][r] * ymul.lo) * ymul.hi : acc[i][j][r]) * ev[cl] + ev[BM + cl];
-                    if (rrow) v = v * a.res_scale + rv[r];
-                    { const float fl = ev[2 * BM + cl]; v = v < fl ? fl : v; }      // NaN propagates (torch.relu / no clamp)
-                    if (track) ctdet::h2::track_absmax(amax_run, v);
-                    if (a.nseg == 0) {
-                        orow[(size_t)co * a.OHW] = v;
-                    } else {
+    for (int i = 0; i < TM; ++i)
 #pragma unroll
-                        for (int g = 0; g < 3; ++g)
-                            if (g < a.nseg && co >= a.seg[g].co_begin && co < a.seg[g].co_end)
-                                a.seg[g].ptr[(size_t)n * a.seg[g].img_stride + a.seg[g].base +
-                                             (size_t)s * a.seg[g].pix_stride + (co - a.seg[g].co_begin)] = v;
-                    }
-                }
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; acs[i][j][r] = 0.f; }
+
+    constexpr int NMF = 2 * 3 * TM * TN;          // MFMAs per iteration and wave
+    using T_ = std::true_type;
+    using F_ = std::false_type;
+
+    // STORE: tile it + 1 exists (its activations sit in the staging registers, its weights are fetched here); LOAD: tile it + 2 exists
+    auto iteration = [&](int buf, auto store_c, auto load_c) {
+        constexpr bool STORE = decltype(store_c)::value, LOAD = decltype(load_c)::value;
+        if (STORE) dma_a(buf ^ 1);
+        asm volatile("" ::: "memory");            // the DMA stays ahead of this iteration's gathers (the counted wait below)
+        const unsigned char* A = lds + buf * A_BYTES + (wm0 + l31) * 16;
+        const unsigned char* B = lds + B_BASE + buf * B_BYTES + (wn0 + l31) * 16;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            // fragments per k-group, just ahead of their MFMAs (hoisted for the whole iteration they would cost 32 more registers)
+            i32x4 fa[2][TM], fb[2][TN];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i) fa[p][i] = *reinterpret_cast<const i32x4*>(A + run_of(h, p, hsel) * RUN_A + i * 512);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) fb[p][j] = *reinterpret_cast<const i32x4*>(B + run_of(h, p, hsel) * RUN_B + j * 512);
+            }
+            // (lo, hi), (hi, lo) into the small-products accumulator, then (hi, hi) into the large one: conv_x3_f32's order
+            constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
+#pragma unroll
+            for (int u = 0; u < NMF / 2; ++u) {
+                const int t = u / (TM * TN), i = (u / TN) % TM, j = u % TN;
+                f32x16& dst = t < 2 ? acs[i][j] : acc[i][j];
+                dst = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[PA[t]][i]),
+                                                             __builtin_bit_cast(f16x8, fb[PB[t]][j]), dst, 0, 0, 0);
+                const int s = h * (NMF / 2) + u;  // side items spread evenly behind the MFMAs of the iteration
+#pragma unroll
+                for (int w = 0; w < NW; ++w)
+                    if (w * NMF / NW == s) side_item(w, buf ^ 1, store_c, load_c);
             }
         }
-        // ct_conv_desc.out_absmax: every lane arrives here; one atomic per image present in the wave
-        if (track) ctdet::h2::flush_absmax(a.out_amax, n, amax_run);
+        if (LOAD) end_load_b();
+        // bare barrier (conv_x3_f32 says why) behind the LDS counter and the DMA: the GPT * 8 gathers issued after it stay in flight
+        if (STORE) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LOAD ? GPT * 8 : 0) : "memory");
+        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+
+    // prologue: tile 0 -> LDS buffer 0, the activations of tile 1 -> staging registers
+    dma_a(0);
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int w = 0; w < NW; ++w) side_item(w, 0, F_{}, T_{});
+    end_load_b();
+#pragma unroll
+    for (int w = 0; w < NW; ++w) side_item(w, 0, T_{}, F_{});
+    // the DMA of tile 0 was issued ahead of the gathers of tile 0, which the splits above have waited for (loads return in issue
+    // order); the counted wait says so again and leaves the gathers of tile 1 in flight across the barrier, which
+    // __syncthreads() would drain: one exposed memory round trip per workgroup, 5-10 % of a 16-iteration workgroup (Cin = 512)
+    if (niter > 1) {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) side_item(w, 0, F_{}, T_{});
+        end_load_b();
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(GPT * 8) : "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     }
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    int it = 0;
+    for (; it + 2 < niter; ++it) iteration(it & 1, T_{}, T_{});
+    if (it + 1 < niter) { iteration(it & 1, T_{}, F_{}); ++it; }
+    iteration(it & 1, F_{}, F_{});
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] += acs[i][j][r];
+
+    x3_epilogue<BM, BN, H2>(a, acc, lds, m0, n0, wm0, wn0, tid, l31, hsel);
 }
 
 // ---- weight split: [cout][cin][kh][kw] fp32 -> [step = (cgroup, tap)][piece][octet][m_pad][8 bf16] ----
@@ -566,7 +792,43 @@ hipError_t launch_cfg(int cfg, const X3Args& a, hipStream_t st)
     }
 }
 
+// the pointwise form of the four f16x2 twins (configurations 6 .. 9): 32 channels per LDS buffer whatever the packing k-step
+hipError_t launch_cfg_pw(int cfg, const X3Args& a, hipStream_t st)
+{
+    switch (cfg) {
+#define X3_PW_CASE(idx, BM, BN, BK) \
+    case idx: return launch_x3(conv_x3_f32_pw<BM, BN, BK, true, true>, (size_t)2 * 8 * (BM + BN) * 16, a, st);
+        X3_PW_CASE(6, 128, 128, 16)
+        X3_PW_CASE(7, 64, 128, 16)
+        X3_PW_CASE(8, 128, 64, 32)
+        X3_PW_CASE(9, 64, 64, 32)
+#undef X3_PW_CASE
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ct_conv_x3_pointwise_enable: process-wide, initialised ONCE from CTDET_X3_POINTWISE (default on) -- a captured graph must not
+// disagree with what the environment says later
+std::atomic<int>& pointwise_flag()
+{
+    static std::atomic<int> flag{[] {
+        const char* e = getenv("CTDET_X3_POINTWISE");
+        return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : 1;
+    }()};
+    return flag;
+}
+
+// The pure rule of the pointwise form: an f16x2 twin, a forward 1x1 / stride 1 / dilation 1 / pad 0 layer into an NCHW slice (no
+// head scatter), no split-K, whole 32-channel iterations.  Everything else keeps conv_x3_f32.
+bool pointwise_rule(const ct_conv_desc* d, bool h2, int ksplit)
+{
+    return h2 && !d->transposed && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->dil == 1 && d->pad_h == 0 && d->pad_w == 0 &&
+           ksplit <= 1 && d->nseg == 0 && d->cin % 32 == 0;
+}
+
 }  // namespace
+
+extern "C" int ct_conv_x3_pointwise_enable(int on) { return pointwise_flag().exchange(on != 0 ? 1 : 0); }
 
 extern "C" int ct_conv_x3_num_configs(void) { return kNumX3; }
 
@@ -744,7 +1006,8 @@ extern "C" int ct_conv2d_x3_fwd(const ct_conv_desc* d, const void* wx3, int conf
         a.ksplit = sk.ksplit;
         a.steps_per_split = sk.steps_per_split;
         if (sk.ksplit > 1) a.ws = d->ksplit_ws;
-        hipError_t e = launch_cfg(config, a, st);
+        const bool pw = pointwise_flag().load(std::memory_order_relaxed) != 0 && pointwise_rule(d, h2, a.ksplit);
+        hipError_t e = pw ? launch_cfg_pw(config, a, st) : launch_cfg(config, a, st);
         if (e != hipSuccess) return ctdet::fail(CT_ERR_HIP, "conv_x3_f32 launch failed: %s", hipGetErrorString(e));
         if (a.ksplit > 1) {
             const int total = a.M * a.Npix;

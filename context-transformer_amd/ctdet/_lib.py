@@ -209,6 +209,7 @@ SIGNATURES = {
     'ct_conv_x3_config_name': (C.c_char_p, [_I]),
     'ct_conv_x3_config_bk': (_I, [_I]),
     'ct_conv_x3_config_h2': (_I, [_I]),
+    'ct_conv_x3_pointwise_enable': (_I, [_I]),
     'ct_conv_x3_packed_bytes': (_Z, [_I, _I, _I, _I, _I]),
     'ct_conv_x3h_packed_bytes': (_Z, [_I, _I, _I, _I, _I]),
     'ct_conv_pack_weights_x3h': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),

@@ -660,6 +660,12 @@ int ct_conv2d_x3_fwd(const ct_conv_desc* desc, const void* wx3, int config, ct_s
  * binary16 pieces of w 2^eW and a trailer with eW) and need desc->in_absmax; forward only.  Every configuration honours
  * desc->out_absmax (split-K launches: in their finishing kernel). */
 int ct_conv_x3_config_h2(int i);
+/* The pointwise form of the "h2:" configurations: forward 1x1 / stride 1 / dilation 1 / pad 0 launches with cin % 32 == 0, no
+ * split-K and no head scatter (nseg == 0) run conv_x3_f32_pw -- one barrier per 32 input channels, weights by LDS-DMA, no filter
+ * geometry -- whose results are bit-identical to the generic kernel's; everything else keeps the generic kernel.  Process-wide
+ * switch, initial value from CTDET_X3_POINTWISE (read once; default 1).  Returns the previous value.  Set it before a graph is
+ * captured, not between capture and replay. */
+int ct_conv_x3_pointwise_enable(int on);
 size_t ct_conv_x3h_packed_bytes(int cin, int cout, int kh, int kw, int bk);
 int ct_conv_pack_weights_x3h(const float* const* w, const int* cout, int nparts, int cin, int kh, int kw, int bk, void* wx3,
                              ct_stream_t stream);

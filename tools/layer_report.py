@@ -36,16 +36,28 @@ net.device = 'cuda'
 rt = net.runtime(a.batch)
 x = synth.images(a.batch, a.size, 'randn', 1234).cuda()
 lib = _lib.lib()
-with torch.no_grad():
-    for _ in range(3):
-        rt.run_backbone(x)
-    rt.event_log = []
-    for _ in range(a.iters):
-        rt.run_backbone(x)
-    torch.cuda.synchronize()
-agg = {}
-for st, e0, e1 in rt.event_log:
-    agg.setdefault(st.name, [st, 0.0])[1] += e0.elapsed_time(e1) / a.iters
+
+
+def measure():
+    with torch.no_grad():
+        for _ in range(3):
+            rt.run_backbone(x)
+        rt.event_log = []
+        for _ in range(a.iters):
+            rt.run_backbone(x)
+        torch.cuda.synchronize()
+    agg = {}
+    for st, e0, e1 in rt.event_log:
+        agg.setdefault(st.name, [st, 0.0])[1] += e0.elapsed_time(e1) / a.iters
+    return agg
+
+
+# the 1x1 stride-1 layers on an f16x2 tile run the pointwise kernel (conv_x3_f32_pw): their rows also show the generic kernel's time
+prev = lib.ct_conv_x3_pointwise_enable(0)
+generic = measure()
+lib.ct_conv_x3_pointwise_enable(1)
+agg = measure()
+lib.ct_conv_x3_pointwise_enable(prev)
 tot_t = tot_f = 0.0
 print('%-22s %-26s %-9s %9s %8s %6s  %s' % ('step', 'geometry', 'cfg', 'us', 'TFLOP/s', 'frac', 'tune(ms per cfg)'))
 for name, (st, ms) in agg.items():
@@ -57,6 +69,9 @@ for name, (st, ms) in agg.items():
     tune = ' '.join('%.3f' % t for t in st.rt.get('tune_ms', []))
     from ctdet import engine as _e
     kname = _e.WINO_NAME.get(st.rt.get('wino')) or (rt.backend.x3_names()[st.rt['x3']] if st.rt.get('x3') is not None else None)
+    pw = (kname or '').startswith('h2:') and st.kh == 1 and st.kw == 1 and st.stride == 1 and st.cin % 32 == 0 and not getattr(st, 'segs', None)
+    if pw:
+        tune = ('pointwise; generic kernel %.1f us  ' % (generic[name][1] * 1e3)) + tune
     print('%-22s %-26s %-9s %9.1f %8.2f %6.3f  %s' % (name, geo, kname or (lib.ct_conv_config_name(cfg - 1).decode() if cfg else 'auto'),
                                                     ms * 1e3, f / ms / 1e9, f / ms / 1e9 / 157.3, tune))
 print('TOTAL conv %.3f ms/step, %.2f TFLOP/s (%.1f%% of 157.3)' % (tot_t, tot_f / tot_t / 1e9, tot_f / tot_t / 1e9 / 1.573))
