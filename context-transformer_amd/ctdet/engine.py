@@ -354,6 +354,15 @@ WINO_TILE = {f.config: c for c, f in FORMS.items()}
 H2_TILES = tuple(c for c, f in FORMS.items() if f.h2)
 
 
+def weight_parts(parts, zero_w=None):
+    """The weights of a fused conv as the pack entry points take them: (pointer array, cout array, n) over its parts, plus the rows
+    of zero_w where a data gradient pads dZ's channels with zeros."""
+    wts = [(p.weight.detach().data_ptr(), p.cout) for p in parts]
+    if zero_w is not None:
+        wts.append((zero_w.data_ptr(), zero_w.shape[0]))
+    return (C.c_void_p * len(wts))(*[w for w, _ in wts]), (C.c_int * len(wts))(*[c for _, c in wts]), len(wts)
+
+
 class HipBackend:
     """Executes plan steps through libctdet (the only backend the product ships)."""
     # The kernel policy (ctdet/conv_policy.py).  A Runtime / TrainRuntime assigns the one it resolved for its network and batch
@@ -433,8 +442,7 @@ class HipBackend:
         """(Re)size the pool to what the given conv steps need, per key; called once the schedule is known."""
         need = {}
         for st in steps:
-            f = FORMS.get(st.rt.get('wino'))
-            if f is not None and f.split:
+            if self.uses_ws(st):
                 k = st.rt.get('ws_key', 0)
                 need[k] = max(need.get(k, 0), st.rt.get('ws4s_bytes', 0))
         for k in list(self.ws_pool):
@@ -443,6 +451,12 @@ class HipBackend:
         for k, n in need.items():
             if self.ws_pool.get(k) is None:
                 self.ws_pool[k] = self.alloc((n,), torch.uint8)
+
+    @staticmethod
+    def uses_ws(st):
+        """Whether the step's launch takes the shared V / M workspace of its stream."""
+        f = FORMS.get(st.rt.get('wino'))
+        return f is not None and f.split
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -462,15 +476,7 @@ class HipBackend:
         rt['scale'] = torch.ones(mpad, device=self.device)       # entries past cout stay (1, 0)
         rt['shift'] = torch.zeros(mpad, device=self.device)
         relus = [p.relu for p in st.parts]
-        rt['lo'] = None
-        if any(relus) and not all(relus):
-            lo = torch.empty(mpad, device=self.device)
-            off = 0
-            for p in st.parts:
-                lo[off:off + p.cout] = 0.0 if p.relu else -float('inf')
-                off += p.cout
-            lo[off:] = 0.0
-            rt['lo'] = lo
+        rt['lo'] = self._relu_floor(st, mpad)
         rt['kpad'], rt['mpad'] = kpad, mpad
         self.pack_conv(st)
         d = _lib.ConvDesc()
@@ -523,6 +529,18 @@ class HipBackend:
         if rt.get('config', 0) in WINO_TILE:
             self.enable_wino(st, tile=WINO_TILE[rt['config']])
 
+    def _relu_floor(self, st, mpad):
+        """Per-channel lower clamp of a fused conv whose parts do not agree on ReLU (0 / -inf; None where they do)."""
+        relus = [p.relu for p in st.parts]
+        if all(relus) or not any(relus):
+            return None
+        lo = torch.zeros(mpad, device=self.device)
+        off = 0
+        for p in st.parts:
+            lo[off:off + p.cout] = 0.0 if p.relu else -float('inf')
+            off += p.cout
+        return lo
+
     def enable_wino(self, st, on=True, tile=None):
         """Route this conv through a Winograd kernel (3x3 s1 d1 p1 layers only): tile 2 = F(2x2,3x3),
         tile 4 = F(4x4,3x3), 23 = F(2x2,3x3) on the bf16 matrix pipe (cin % 16 == 0), 44 / 46 / 47 / 48 = the F(4x4,3x3) forms on the
@@ -557,23 +575,16 @@ class HipBackend:
         self._pack_wino(st)
 
     def _pack_wino(self, st):
-        n = len(st.parts)
-        ptrs = (C.c_void_p * n)(*[p.weight.detach().data_ptr() for p in st.parts])
-        couts = (C.c_int * n)(*[p.cout for p in st.parts])
         f = FORMS[st.rt['wino']]
-        _lib.check(f.pack_weights(self.lib, ptrs, couts, n, st.cin, st.rt[f.key].data_ptr(), self._stream()), f.pack)
+        _lib.check(f.pack_weights(self.lib, *weight_parts(st.parts), st.cin, st.rt[f.key].data_ptr(), self._stream()), f.pack)
 
     def pack_conv(self, st, weights=True):
         """(Re)pack weights and fold the epilogue from the CURRENT parameter values.  weights=False: only the epilogue
         (the training engine re-packs all weights of a step in one batched launch, ct_pack_run)."""
         rt, lib = st.rt, self.lib
-        n = len(st.parts)
-        ws = [p.weight.detach() for p in st.parts]
-        for wt in ws:
+        for wt in [p.weight.detach() for p in st.parts]:
             if not (wt.is_cuda and wt.is_contiguous() and wt.dtype == torch.float32):
                 raise _lib.CtdetError('%s: parameters must be contiguous fp32 on the HIP device' % st.name)
-        ptrs = (C.c_void_p * n)(*[wt.data_ptr() for wt in ws])
-        couts = (C.c_int * n)(*[p.cout for p in st.parts])
         if not weights:
             pass
         elif rt.get('wino'):                    # only the layout the launch reads; the other one is packed on demand
@@ -583,11 +594,16 @@ class HipBackend:
             self._pack_x3(st)
             rt['wpk_stale'] = True
         else:
-            _lib.check(lib.ct_conv_pack_weights(ptrs, couts, n, st.cin, st.kh, st.kw, rt['wpk'].data_ptr(),
+            _lib.check(lib.ct_conv_pack_weights(*weight_parts(st.parts), st.cin, st.kh, st.kw, rt['wpk'].data_ptr(),
                                                 rt['mpad'], rt['kpad'], self._stream()), 'ct_conv_pack_weights')
             rt['wpk_stale'] = False
-        first = not rt.get('folded')
+        self._fold_epilogue(st, first=not rt.get('folded'))
         rt['folded'] = True
+        rt['versions'] = self.param_versions(st)
+
+    def _fold_epilogue(self, st, first=True):
+        """Fold bias / BatchNorm of every part into the scale / shift vectors (first=False: skip the constant ones)."""
+        rt, lib = st.rt, self.lib
         off = 0
         for p in st.parts:
             if not first and p.bn is None and p.bias is None:
@@ -602,7 +618,6 @@ class HipBackend:
             _lib.check(lib.ct_conv_fold_epilogue(*args, p.cout, off, rt['scale'].data_ptr(),
                                                  rt['shift'].data_ptr(), self._stream()), 'ct_conv_fold_epilogue')
             off += p.cout
-        rt['versions'] = self.param_versions(st)
 
     @staticmethod
     def param_versions(st):
@@ -687,12 +702,9 @@ class HipBackend:
         self._pack_x3(st)
 
     def _pack_x3(self, st):
-        n = len(st.parts)
-        ptrs = (C.c_void_p * n)(*[p.weight.detach().data_ptr() for p in st.parts])
-        couts = (C.c_int * n)(*[p.cout for p in st.parts])
         bk, h2 = self.x3_bk(st.rt['x3']), self.x3_h2(st.rt['x3'])
         pack = self.lib.ct_conv_pack_weights_x3h if h2 else self.lib.ct_conv_pack_weights_x3
-        _lib.check(pack(ptrs, couts, n, st.cin, st.kh, st.kw, bk, st.rt['wx3'][(bk, h2)].data_ptr(), self._stream()),
+        _lib.check(pack(*weight_parts(st.parts), st.cin, st.kh, st.kw, bk, st.rt['wx3'][(bk, h2)].data_ptr(), self._stream()),
                    'ct_conv_pack_weights_x3h' if h2 else 'ct_conv_pack_weights_x3')
 
     def run_pool(self, st, bufs, batch):
@@ -816,13 +828,39 @@ def absmax_source(steps, tracks):
     return source
 
 
+def wire_absmax(be, batch, steps, consumers, desc, reads, tracks, fallback=None):
+    """Hand out the maxima slots of a plan (the ONE wiring loop of Runtime, TrainRuntime and the bf16 backend) -> {buffer: slot}.
+    consumers: the conv steps in launch order; desc(st): the descriptor its launch reads (None: it has none); reads(st): whether
+    that launch reads maxima of its input; tracks(st): whether a writer folds the maxima of what it stores (absmax_source).  A
+    reader whose buffer has a source shares the buffer's slot: handed out at the first reader, out_absmax of the buffer's writers.
+    Readers left without one go to fallback(st), which moves the layer to a kernel that needs none and says so -- then everything
+    is wired again (the moved layer may have stopped tracking); fallback=None leaves them to measure their own input."""
+    source = absmax_source(steps, tracks)
+    while True:
+        for st in consumers:
+            if desc(st) is not None:
+                desc(st).in_absmax = desc(st).out_absmax = None
+        slots, left = {}, []
+        be.slots_used = 0
+        for st in consumers:
+            if not reads(st):
+                continue
+            b, ws = source(st.src)
+            if b is None:
+                left.append(st)
+                continue
+            if b not in slots:
+                slots[b] = be.new_slot(batch)
+                for w in ws:
+                    desc(w).out_absmax = slots[b]
+            desc(st).in_absmax = slots[b]
+        if fallback is None or not [st for st in left if fallback(st)]:
+            return slots
+
+
 # ---- the kernel policy as seen from here: thin views of ctdet/conv_policy.py on the process environment
 def _env_policy(net=None, batch=None):
     return conv_policy.resolve(net, batch, os.environ)
-
-
-def x3_allowed(st):
-    return conv_policy.x3_allowed(_env_policy(), st)
 
 
 def wino_tiles(backend=None, st=None):
@@ -1072,44 +1110,27 @@ class Runtime:
             self.amax_slots = be.wire_absmax(self)
             self._wired_epoch = be.kernel_epoch
             return
-        steps = self.plan.steps
-
         def tracks(st):
             if st.kind != 'conv' or st.segs:
                 return False
             f = FORMS.get(st.rt.get('wino'))
             return f.tracks if f is not None else True
-        source = absmax_source(steps, tracks)
-        while True:
-            for st in self.conv_steps():
-                st.rt['desc'].in_absmax = None
-                st.rt['desc'].out_absmax = None
-                st.rt.pop('amax_own', None)
-                st.rt.pop('amax_frozen', None)
-            slots, fallback = {}, []
-            be.slots_used = 0
-            for st in self.conv_steps():
-                if not be.reads_max(st):
-                    continue
-                b, ws = source(st.src)
-                if b is not None:
-                    if b not in slots:
-                        slots[b] = be.new_slot(self.batch)
-                        for w in ws:
-                            w.rt['desc'].out_absmax = slots[b]
-                    st.rt['desc'].in_absmax = slots[b]
-                elif not getattr(FORMS.get(st.rt.get('wino')), 'own_max', False):
-                    fallback.append(st)
-            if not fallback:
-                break
-            for st in fallback:            # (a layer that leaves the f16x2 form may stop tracking: wire again)
-                if st.rt.get('wino'):
-                    be.enable_wino(st, tile=FORMS[st.rt['wino']].plain)
-                else:
-                    xn = be.x3_names()
-                    be.enable_x3(st, xn.index('x3:' + xn[st.rt['x3']][3:]))
+
+        def to_plain(st):                   # the bf16x3 twin; tile 47 takes the maxima itself, inside its launch
+            if getattr(FORMS.get(st.rt.get('wino')), 'own_max', False):
+                return False
+            if st.rt.get('wino'):
+                be.enable_wino(st, tile=FORMS[st.rt['wino']].plain)
+            else:
+                xn = be.x3_names()
+                be.enable_x3(st, xn.index('x3:' + xn[st.rt['x3']][3:]))
+            return True
+        for st in self.conv_steps():
+            st.rt.pop('amax_own', None)
+            st.rt.pop('amax_frozen', None)
+        self.amax_slots = wire_absmax(be, self.batch, self.plan.steps, self.conv_steps(), lambda st: st.rt['desc'], be.reads_max,
+                                      tracks, to_plain)
         self._wired_epoch = be.kernel_epoch
-        self.amax_slots = slots
 
     def _share_workspaces(self):
         """One three-kernel-Winograd workspace per stream of the schedule (HipBackend.ws_pool) instead of one per layer."""

@@ -22,7 +22,7 @@ import os
 import torch
 
 from . import _lib
-from .engine import HipBackend, absmax_source
+from .engine import HipBackend, weight_parts, wire_absmax
 
 # Which supported layers take the Winograd route when CTDET_BF16_WINO=1: the rule measured by tools/bf16_wino_probe.py
 # (profiles/bf16_wino_probe.txt, every 3x3 / stride 1 shape of RFBNet-300 bs 32 and RFBNet-512 bs 16).  The three-kernel form moves
@@ -71,14 +71,7 @@ class HipBackendBF16(HipBackend):
         rt['scale'] = torch.ones(mpad, device=self.device)
         rt['shift'] = torch.zeros(mpad, device=self.device)
         relus = [p.relu for p in st.parts]
-        rt['lo'] = None
-        if any(relus) and not all(relus):
-            lo = torch.zeros(mpad, device=self.device)
-            off = 0
-            for p in st.parts:
-                lo[off:off + p.cout] = 0.0 if p.relu else -float('inf')
-                off += p.cout
-            rt['lo'] = lo
+        rt['lo'] = self._relu_floor(st, mpad)
         rt['mpad'] = mpad
         self.pack_conv(st)
         d = _lib.ConvDesc()
@@ -120,26 +113,13 @@ class HipBackendBF16(HipBackend):
 
     def pack_conv(self, st):
         rt, lib = st.rt, self.lib
-        n = len(st.parts)
-        ws = [p.weight.detach() for p in st.parts]
-        for wt in ws:
+        for wt in [p.weight.detach() for p in st.parts]:
             if not (wt.device.type == self.device.type and wt.is_contiguous() and wt.dtype == torch.float32):
                 raise _lib.CtdetError('%s: parameters must be contiguous fp32 on the HIP device' % st.name)
-        ptrs = (C.c_void_p * n)(*[wt.data_ptr() for wt in ws])
-        couts = (C.c_int * n)(*[p.cout for p in st.parts])
+        ptrs, couts, n = weight_parts(st.parts)
         _lib.check(lib.ct_conv_pack_weights_bf16(ptrs, couts, n, st.cin, st.kh, st.kw, rt['wpk16'].data_ptr(),
                                                  self._stream()), 'ct_conv_pack_weights_bf16')
-        off = 0
-        for p in st.parts:
-            if p.bn is not None:
-                bn = p.bn
-                args = (bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                        bn.running_var.data_ptr(), float(bn.eps), None)
-            else:
-                args = (None, None, None, None, 0.0, p.bias.data_ptr() if p.bias is not None else None)
-            _lib.check(lib.ct_conv_fold_epilogue(*args, p.cout, off, rt['scale'].data_ptr(),
-                                                 rt['shift'].data_ptr(), self._stream()), 'ct_conv_fold_epilogue')
-            off += p.cout
+        self._fold_epilogue(st)
         if rt.get('bf16_wino'):
             _lib.check(lib.ct_conv_pack_weights_bf16_wino(ptrs, couts, n, st.cin, rt['UW16'].data_ptr(), self._stream()),
                        'ct_conv_pack_weights_bf16_wino')
@@ -171,45 +151,17 @@ class HipBackendBF16(HipBackend):
         rt['bf16_wino'] = True
         self.pack_conv(st)
 
-    def ws_rebuild(self, steps):
-        """One V / M workspace per stream of the schedule, sized for the largest Winograd layer on it."""
-        need = {}
-        for st in steps:
-            if st.rt.get('bf16_wino'):
-                k = st.rt.get('ws_key', 0)
-                need[k] = max(need.get(k, 0), st.rt['ws4s_bytes'])
-        for k in list(self.ws_pool):
-            if k not in need or self.ws_pool[k] is None or self.ws_pool[k].numel() != need[k]:
-                self._ws_drop(k)
-        for k, n in need.items():
-            if self.ws_pool.get(k) is None:
-                self.ws_pool[k] = self.alloc((n,), torch.uint8)
+    @staticmethod
+    def uses_ws(st):
+        return bool(st.rt.get('bf16_wino'))
 
     def wire_absmax(self, runtime):
         """Maxima of |activation| per image (ct_conv_desc.in_absmax / out_absmax) between the Winograd launches: a buffer whose
         ONLY writers are Winograd launches -- seen directly or through max-pool steps, whose output the input bounds -- gets a
         slot that its writers fill and its Winograd readers scale by; every other Winograd layer measures its input itself."""
-        steps = runtime.plan.steps
-        convs = runtime.conv_steps()
-        source = absmax_source(steps, lambda w: w.kind == 'conv' and not w.segs and bool(w.rt.get('bf16_wino')))
-        for st in convs:
-            if 'desc_w' in st.rt:
-                st.rt['desc_w'].in_absmax = None
-                st.rt['desc_w'].out_absmax = None
-        slots = {}
-        self.slots_used = 0
-        for st in convs:
-            if not st.rt.get('bf16_wino'):
-                continue
-            b, ws = source(st.src)
-            if b is None:
-                continue
-            if b not in slots:
-                slots[b] = self.new_slot(runtime.batch)
-                for w in ws:
-                    w.rt['desc_w'].out_absmax = slots[b]
-            st.rt['desc_w'].in_absmax = slots[b]
-        return slots
+        return wire_absmax(self, runtime.batch, runtime.plan.steps, runtime.conv_steps(), lambda st: st.rt.get('desc_w'),
+                           lambda st: bool(st.rt.get('bf16_wino')),
+                           lambda w: w.kind == 'conv' and not w.segs and bool(w.rt.get('bf16_wino')))
 
     def policy_extra(self, steps):
         return {'bf16_wino': {'switch': 'CTDET_BF16_WINO', 'on': bool(getattr(self, 'bf16_wino', False)),

@@ -14,7 +14,7 @@ import torch
 from ctdet import engine, train_engine
 from ctdet.engine import ConvPart, ConvStep, PoolStep
 from ctdet.wino_forms import FORMS
-from test_wino_dispatch_cpu import _Backend
+from test_wino_dispatch_cpu import _Backend, _Train
 
 
 class _Host(_Backend):
@@ -151,11 +151,6 @@ def test_second_writer_on_the_pool_chain_leaves_the_consumer_without_a_slot(extr
         assert c.rt['wino'] == 46 and not c.rt['desc'].in_absmax            # the bf16x3 twin, no maxima
         assert not rt.amax_slots
     _check_wiring(plan.steps, be)
-
-
-class _Train(train_engine.TrainRuntime):
-    def _s(self):
-        return None
 
 
 @pytest.mark.parametrize('extra,wired', [(None, True), ('pooled', False), ('pooled_fused', False), ('source', False)])

@@ -19,7 +19,7 @@ if __name__ == '__main__':
     import conftest  # noqa: F401
 
 from ctdet import engine, train_engine
-from test_absmax_wiring_cpu import _Host
+from test_absmax_wiring_cpu import _Host, _Train
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'conv_policy.json')
 # every switch that takes part in the choice (and the few that shape the descriptors it is made on): cleared before each case
@@ -68,11 +68,6 @@ def _net(name):
         size, phase = NETS[name]
         _nets[name] = build_net(types.SimpleNamespace(method='ours', phase=phase, setting='transfer'), size, 20).eval()
     return _nets[name]
-
-
-class _Train(train_engine.TrainRuntime):
-    def _s(self):
-        return None
 
 
 def _choice(be, rt):

@@ -13,6 +13,7 @@ import torch
 
 from ctdet import _lib, engine, train_engine
 from ctdet.engine import ConvPart, ConvStep, HipBackend
+from test_wino_dispatch_cpu import _Train
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ('ct_conv_wgrad_h2_supported', 'ct_conv_wgrad_h2_workspace_bytes', 'ct_conv2d_wgrad_h2')
@@ -178,11 +179,6 @@ class _Backend(HipBackend):
         st.rt.update(wino_ok=plain, winox_ok=plain, wino4s_ok=True, wino4f_ok=plain)
 
 
-class _Train(train_engine.TrainRuntime):
-    def _s(self):
-        return None
-
-
 def _conv(name, src, dst, hw, cin, cout, k=1, stride=1, bn=False):
     w = torch.nn.Parameter(torch.zeros(cout, cin, k, k))
     bnm = torch.nn.BatchNorm2d(cout) if bn else None
@@ -247,7 +243,7 @@ def test_switch_off_launches_what_the_parent_launched(monkeypatch):
     logs = {}
     for value in (None, '0', ''):
         rt, built, log = _backward_log(monkeypatch, value)
-        assert not rt.wgrad_h2 and not hasattr(rt, 'wgrad_wsh2')
+        assert not rt.wgrad_h2 and rt.wgrad_wsh2 is None
         assert not [e for e in built + log if 'wgrad_h2' in ''.join(map(str, e[:2]))], value       # not even a host query
         logs[value] = log
     assert logs['0'] == logs[None] and logs[''] == logs[None]
