@@ -45,9 +45,10 @@ def _slot(B, seed=0.0):
 
 
 def _launch(x, parts, stride, pad, dil, *, config=0, x3=None, ksplit=None, seed=0.0, res=None, res_scale=1.0, cin_off=0, cin=None,
-            out_ctot=None, out_coff=0, pool=None, segs=None, transposed=False, track=True):
+            out_ctot=None, out_coff=0, pool=None, segs=None, transposed=False, track=True, in_absmax=None):
     """One conv step through engine.HipBackend with a caller-owned slot in desc.out_absmax.  parts: (weight, bias, bn, relu).
-    pool = (ceil, write_full); segs = [(name, co_begin, co_end, base)] + flat sizes -> the three head buffers.
+    pool = (ceil, write_full); segs = [(name, co_begin, co_end, base)] + flat sizes -> the three head buffers; in_absmax: caller-owned
+    device lines for desc.in_absmax (else the engine's own: HipBackend.run_conv).
     -> dict(y, slot, seeded, pooled, flat)"""
     be = engine.HipBackend(DEV)
     cps = []
@@ -90,6 +91,8 @@ def _launch(x, parts, stride, pad, dil, *, config=0, x3=None, ksplit=None, seed=
         st.rt['pool'] = (pooled, poh, pow_, bool(full))
     if transposed:
         d.transposed = 1
+    if in_absmax is not None:
+        d.in_absmax = in_absmax.data_ptr()
     seeded = _slot(B, seed)
     slot = seeded.to(DEV)
     if track:

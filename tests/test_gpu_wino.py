@@ -2,14 +2,17 @@
 bf16 matrix pipe: ct_conv2d_wino_x3_fwd, eight-wave / two accumulators and four-wave / one accumulator, and F(4x4,3x3) as
 transform / bf16x3 GEMM / transform kernels: ct_conv2d_wino4s_fwd, two / one accumulator) against torch-CPU conv2d
 and against the direct implicit-GEMM kernel: same descriptor, same fused epilogues, 1e-4 relative (north_star's fp32
-bar; F(4x4,3x3)'s own rounding is about 2e-5 of the output range at 512 input channels, checked below against fp64)."""
+bar; F(4x4,3x3)'s own rounding is about 2e-6 of the output range at 512 input channels, checked below against fp64).
+The small and ragged shapes are held to float64, per image and per form, in tests/test_gpu_conv_fwd.py."""
 import zlib
 
 import pytest
 import torch
 
 from conftest import rel_err
+from conv_fwd_cases import WINO_BOUND          # per form code: 3e-6, 5e-5, 1e-6, 6e-6, 1.2e-5, 6e-6, 1.2e-5
 from ctdet import _lib, engine
+from ctdet.wino_forms import FORMS
 from test_gpu_kernels import _bn, _ref_conv, _run_conv
 
 pytestmark = pytest.mark.gpu
@@ -202,16 +205,17 @@ def test_conv_input_above_2gib_is_chunked(use_wino):
         assert rel_err(got[n:n + 1], want) < TOL, n
 
 
-@pytest.mark.parametrize('W,bound', [(engine.WINO, 3e-6), (engine.WINO4, 5e-5), (engine.WINOX, 1e-6),
-                                     (engine.WINO4S, 6e-6), (engine.WINO4F, 1.2e-5), (engine.WINO4H, 6e-6),
-                                     (engine.WINO4FH, 1.2e-5)],
-                         ids=VIDS)
+@pytest.mark.parametrize('W,bound', [(FORMS[c].config, WINO_BOUND[c]) for c in (2, 4, 23, 44, 46, 47, 48)], ids=VIDS)
 def test_wino_rounding_error_vs_fp64(W, bound):
     """The transform-domain rounding of each variant on the deepest VGG shape (512 input channels, post-ReLU input):
-    max error over the output range against an fp64 convolution.  Measured 1e-6 for F(2x2,3x3) and 2e-5 for
-    F(4x4,3x3) (interpolation points 0, +-1, +-2, inf; transform entries up to 8).  The bf16x3 forms sum 16 channels
-    inside an MFMA before one rounding; with two accumulators the large sum sees cin / 16 roundings.  The three-kernel
-    F(4x4,3x3) form (bf16x3 GEMMs, output transform in double): measured 2.0e-6 (two accumulators)."""
+    max error over the output range against an fp64 convolution.  Every F(4x4,3x3) kernel takes its transforms from
+    csrc/ct_wino4_points.h: interpolation points 0, +-3/4, +-3/2, inf (tests/test_winograd_algebra_cpu.py pins the matrices).
+    The bound of the fp32 F(4x4,3x3) kernel, 5e-5, dates from the textbook points 0, +-1, +-2, inf (transform entries up to 8,
+    measured 2e-5 then), which no kernel uses any more.  Measured on an MI355X with the present points: F(2x2,3x3) 8.1e-7,
+    F(4x4,3x3) 1.7e-6, F(2x2,3x3) bf16x3 3.0e-7, three-kernel 1.5e-6 (bf16x3) / 1.6e-6 (f16x2), fused 2.9e-6 / 2.3e-6; the
+    direct fp32 kernel 6.0e-7, torch-CPU fp32 2.7e-7.  The bf16x3 forms sum 16 channels inside an MFMA before one rounding;
+    with two accumulators the large sum sees cin / 16 roundings.  The bounds live in tests/conv_fwd_cases.py (WINO_BOUND),
+    which scales them to the small rows of tests/test_gpu_conv_fwd.py."""
     import torch.nn.functional as F
     g = torch.Generator().manual_seed(5)
     x = torch.randn(2, 512, 38, 38, generator=g).relu()

@@ -38,9 +38,11 @@ def _patches(x, m):
     return xp.unfold(2, m + 2, m).unfold(3, m + 2, m)
 
 
-def _wino_forward(x, w, m):
+def _wino_forward(x, w, m, dtype=torch.float64):
+    """dtype: the precision the matrices are cast to (x and w must have it): float32 restates the kernels' arithmetic
+    (tests/conv_fwd_cases.py, wino32)."""
     M = MATS[m]
-    BT, G, AT = (torch.tensor(M[k]) for k in ('BT', 'G', 'AT'))
+    BT, G, AT = (torch.tensor(M[k], dtype=dtype) for k in ('BT', 'G', 'AT'))
     V = torch.einsum('ij,nctxjk,lk->nctxil', BT, _patches(x, m), BT)
     U = torch.einsum('ij,kcjl,ml->kcim', G, w, G)
     Mm = torch.einsum('kcim,nctxim->nktxim', U, V)
