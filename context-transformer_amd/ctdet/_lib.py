@@ -66,6 +66,15 @@ class SgdTensor(C.Structure):
                 ('lr', C.c_float), ('weight_decay', C.c_float), ('first_step', C.c_int)]
 
 
+class GradTensor(C.Structure):
+    _fields_ = [('grad', C.c_void_p), ('numel', C.c_int64)]
+
+
+class ClipState(C.Structure):
+    """ct_clip_state: what ct_grad_norm_clip leaves on the device for ct_sgd_step_clipped."""
+    _fields_ = [('norm', C.c_float), ('coef', C.c_float), ('finite', C.c_int), ('nonfinite', C.c_int)]
+
+
 class ResizeTap(C.Structure):
     """ct_resize_tap: first source index (unclamped) and the 11-bit coefficients of one output coordinate."""
     _fields_ = [('first', C.c_int), ('c', C.c_short * 8)]
@@ -108,6 +117,10 @@ SIGNATURES = {
     'ct_multibox_loss_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     'ct_sgd_tensors_per_launch': (_I, []),
     'ct_sgd_step': (_I, [C.POINTER(SgdTensor), _I, _F, _F, _I, _F, _P]),
+    'ct_grad_norm_tensors_per_launch': (_I, []),
+    'ct_grad_norm_workspace_bytes': (_Z, [C.POINTER(GradTensor), _I]),
+    'ct_grad_norm_clip': (_I, [C.POINTER(GradTensor), _I, _F, _F, _P, _Z, _P, _P]),
+    'ct_sgd_step_clipped': (_I, [C.POINTER(SgdTensor), _I, _F, _F, _I, _F, _P, _P]),
     'ct_postprocess_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_voc_match': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _D, _P, _P, _I, _P, _P]),

@@ -174,14 +174,68 @@ def sgd_table(items):
     return table
 
 
-def sgd_step(items, momentum, dampening, nesterov, grad_scale=1.0):
+def sgd_step(items, momentum, dampening, nesterov, grad_scale=1.0, clip_state=None):
     """torch.optim.SGD's update of every tensor of `items` (see sgd_table) in ceil(len / ct_sgd_tensors_per_launch)
-    launches (ct_sgd_step); params and momentum buffers are updated in place, `first_step` makes buf := d."""
+    launches (ct_sgd_step); params and momentum buffers are updated in place, `first_step` makes buf := d.
+    With `clip_state` (what grad_norm_clip returned) the call is ct_sgd_step_clipped: the state's coef is multiplied
+    into grad_scale on the device, and a non-finite norm skips the update."""
     if not items:
         return
     table = sgd_table(items)
-    check(lib().ct_sgd_step(table, len(items), float(momentum), float(dampening), int(bool(nesterov)),
-                            float(grad_scale), _stream()), 'ct_sgd_step')
+    if clip_state is None:
+        check(lib().ct_sgd_step(table, len(items), float(momentum), float(dampening), int(bool(nesterov)),
+                                float(grad_scale), _stream()), 'ct_sgd_step')
+    else:
+        check(lib().ct_sgd_step_clipped(table, len(items), float(momentum), float(dampening), int(bool(nesterov)),
+                                        float(grad_scale), _clip_state(clip_state), _stream()), 'ct_sgd_step_clipped')
+
+
+CLIP_STATE_BYTES = C.sizeof(_lib.ClipState)
+
+
+def _clip_state(t):
+    if t.numel() != CLIP_STATE_BYTES:
+        raise _lib.CtdetError('clip state must hold %d bytes, got %d' % (CLIP_STATE_BYTES, t.numel()))
+    return _dev(t, 'clip_state', torch.uint8)
+
+
+def grad_table(grads):
+    """ctypes table of ct_grad_tensor for contiguous fp32 device tensors (an empty tensor passes a NULL pointer)."""
+    table = (_lib.GradTensor * max(len(grads), 1))()
+    for i, g in enumerate(grads):
+        table[i] = _lib.GradTensor(_dev(g, 'grad').value if g.numel() else None, g.numel())
+    return table
+
+
+def grad_norm_workspace_bytes(grads, table=None):
+    """Bytes of workspace grad_norm_clip needs for `grads` (`table`: their grad_table, when the caller has it)."""
+    return int(lib().ct_grad_norm_workspace_bytes(grad_table(grads) if table is None else table, len(grads)))
+
+
+def grad_norm_clip(grads, max_norm, grad_scale=1.0, state=None, workspace=None, table=None):
+    """ct_grad_norm_clip over `grads`: |grad_scale| * the 2-norm of all of them, and the clipping coefficient
+    min(1, max_norm / (norm + 1e-6)) -- 0 when the norm is not finite -- written to the 16-byte device tensor this
+    returns (uint8; `state` when given, else allocated zeroed).  No host synchronisation; read it with clip_info().
+    `workspace`: a uint8 device tensor of at least grad_norm_workspace_bytes(grads), allocated when None; `table`: the
+    grad_table of `grads` when the caller has built it already."""
+    if table is None:
+        table = grad_table(grads)
+    need = 0 if workspace is not None else int(lib().ct_grad_norm_workspace_bytes(table, len(grads)))
+    dev = state.device if state is not None else (grads[0].device if grads else torch.device('cuda'))
+    if state is None:
+        state = torch.zeros(CLIP_STATE_BYTES, device=dev, dtype=torch.uint8)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), device=dev, dtype=torch.uint8)
+    check(lib().ct_grad_norm_clip(table, len(grads), float(grad_scale), float(max_norm),
+                                  _dev(workspace, 'workspace', torch.uint8), workspace.numel(), _clip_state(state),
+                                  _stream()), 'ct_grad_norm_clip')
+    return state
+
+
+def clip_info(state):
+    """Synchronising read of a clip state -> {'norm', 'coef', 'finite', 'nonfinite'}."""
+    s = _lib.ClipState.from_buffer_copy(state.cpu().numpy().tobytes())
+    return {'norm': float(s.norm), 'coef': float(s.coef), 'finite': bool(s.finite), 'nonfinite': int(s.nonfinite)}
 
 
 # ------------------------------------------------------------------ NMS

@@ -7,6 +7,8 @@ lr = base_lr * warmup(iter) * gamma ** (#milestones <= iter), linear warmup from
 
 build_optimizer(..., fused=True), or CTDET_SGD_FUSED=1 in the environment, returns ctdet.optim.FusedSGD over the same
 groups: the whole update in one multi-tensor HIP call instead of three foreach launches per group.  Off by default.
+args.max_grad_norm (optional; a positive float, or math.inf for the non-finite guard alone) is FusedSGD's max_grad_norm:
+gradient-norm clipping and the skip of non-finite steps on the device.  Only the fused optimizer has it.
 """
 import os
 from bisect import bisect_right
@@ -28,9 +30,15 @@ def build_optimizer(args, model, fused=None):
               for name, p in model.named_parameters() if p.requires_grad]
     if fused is None:
         fused = os.environ.get('CTDET_SGD_FUSED', '0') == '1'
+    max_grad_norm = getattr(args, 'max_grad_norm', None)
     if fused:
         from ctdet.optim import FusedSGD
-        return FusedSGD(groups, args.lr, momentum=args.momentum)
+        if max_grad_norm is None:
+            return FusedSGD(groups, args.lr, momentum=args.momentum)
+        return FusedSGD(groups, args.lr, momentum=args.momentum, max_grad_norm=max_grad_norm)
+    if max_grad_norm is not None:
+        raise ValueError('args.max_grad_norm = %r needs the fused optimizer (fused=True or CTDET_SGD_FUSED=1): there is '
+                         'no torch path for it' % (max_grad_norm,))
     return torch.optim.SGD(groups, args.lr, momentum=args.momentum)
 
 

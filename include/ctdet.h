@@ -221,6 +221,57 @@ int ct_sgd_tensors_per_launch(void);
 int ct_sgd_step(const ct_sgd_tensor* items_host, int n, float momentum, float dampening,
                 int nesterov, float grad_scale, ct_stream_t stream);
 
+/* Gradient-norm clipping and the non-finite guard in front of ct_sgd_step: torch.nn.utils.clip_grad_norm_ (norm type 2,
+ * over ALL tensors of the call) without a pass that writes the gradients and without a host synchronisation -- the
+ * coefficient stays on the device, in a 16-byte ct_clip_state that ct_sgd_step_clipped reads.  Off unless called.
+ * ct_grad_norm_clip arithmetic:
+ *     S      = sum over every element of every tensor of (double)g * (double)g    (each product exact in binary64;
+ *              summed in binary64 in an order fixed by the table: the same table gives the same bits, run after run)
+ *     norm   = (float)( sqrt(S) * (double)|grad_scale| )                          one rounding to fp32
+ *     finite = isfinite(norm)
+ *     coef   = finite ? min(1.0f, max_norm / (norm + 1e-6f)) : 0.0f               fp32, each operation rounded once
+ *     state  = { norm, coef, finite, nonfinite + !finite }
+ * `nonfinite` counts the calls on this state that found a non-finite norm (the caller zeroes the state once).  A norm
+ * that overflows fp32 counts as non-finite, whatever the gradients hold.  max_norm = +inf is "guard only": coef is 1
+ * whenever the norm is finite.  n == 0 (or only empty tensors) gives norm 0.
+ * Reduction, two levels, deterministic (no floating-point atomics, no last-arriving-workgroup finish): every workgroup
+ * owns one 8192-element chunk of one tensor, found as in ct_sgd_step from a table of (grad, numel) that travels in the
+ * kernel arguments, ct_grad_norm_tensors_per_launch() (220) tensors per launch; it reads the chunk in 16-byte loads
+ * counted from the 16-byte line that holds element 0 (the first and the last group of a tensor element by element: no
+ * byte outside [grad, grad + numel) is read), sums the squares in double, lanes and waves in a fixed order, and stores
+ * one double to its own slot of `workspace`; a finishing launch of one workgroup sums the slots in a fixed order and
+ * writes `state_dev` with plain vector stores.  Every slot the finish reads is written by the same call: the workspace
+ * needs no clearing.  A call is ceil(tensors with numel > 0 / 220) + 1 launches; no allocation, no host
+ * synchronisation, asynchronous on `stream`; `items_host` is not read after the call returns.  Gradients are never
+ * written.  ct_grad_norm_workspace_bytes(items, n) is 8 bytes per chunk (at least 8; 0 for a table the call refuses).
+ * CT_ERR_INVALID (nothing launched): n < 0; numel < 0 or > 2^31-1; a non-empty tensor with a NULL grad or one that is
+ * not 4-byte aligned; max_norm <= 0 or NaN; a NULL state_dev; a NULL, misaligned (8 bytes) or too-small workspace.
+ *
+ * ct_sgd_step_clipped is ct_sgd_step with two differences:
+ *   state->finite == 0: the launch updates nothing, except that it stores +0 to the momentum buffer of every tensor
+ *       passed with first_step = 1, so that the buffer is defined state for the host.  A first step that was skipped
+ *       therefore continues with buf = momentum * 0 + (1 - dampening) * d, which differs from torch's buf = d only
+ *       when dampening != 0.
+ *   otherwise gs = grad_scale * state->coef is computed once (one fp32 rounding) and the unchanged recurrence runs
+ *       with gs in place of grad_scale; with coef == 1 the bits are those of ct_sgd_step.
+ * Same launch count and argument errors as ct_sgd_step, plus CT_ERR_INVALID for a NULL state_dev. */
+typedef struct ct_grad_tensor {
+    const float* grad;     /* dev, read only */
+    int64_t numel;         /* 0 .. 2^31-1    */
+} ct_grad_tensor;
+typedef struct ct_clip_state {
+    float norm;            /* |grad_scale| * 2-norm of all gradients of the last ct_grad_norm_clip  */
+    float coef;            /* what ct_sgd_step_clipped multiplies into grad_scale; 0 when !finite   */
+    int finite;            /* 1: the step runs, 0: it is skipped                                    */
+    int nonfinite;         /* calls on this state that found a non-finite norm                      */
+} ct_clip_state;
+int ct_grad_norm_tensors_per_launch(void);
+size_t ct_grad_norm_workspace_bytes(const ct_grad_tensor* items_host, int n);
+int ct_grad_norm_clip(const ct_grad_tensor* items_host, int n, float grad_scale, float max_norm,
+                      void* workspace, size_t workspace_bytes, ct_clip_state* state_dev, ct_stream_t stream);
+int ct_sgd_step_clipped(const ct_sgd_tensor* items_host, int n, float momentum, float dampening, int nesterov,
+                        float grad_scale, const ct_clip_state* state_dev, ct_stream_t stream);
+
 /* ---------------------------------------- batched test.py post-processing ---- */
 
 /* test.py:136-161 for a batch: per (image, class>=1) select score > conf_thresh, order by

@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
    python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
+                               [--clip-norm X] [--json]
    --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
    --wgrad-h2: CTDET_WGRAD_H2=1 for this run (the 1x1 weight gradients on ct_conv2d_wgrad_h2);
+   --clip-norm X: FusedSGD(max_grad_norm=X) (implies --fused-sgd; `inf` is the non-finite guard alone): the norm and the
+   clipping coefficient are computed on the device in front of the update, a non-finite step is skipped;
+   --json: one more line, JSON, with the step time and the optimizer's device time (always with --clip-norm, where it
+   also carries the last norm, coef and the number of skipped steps);
    --per-tensor-groups: the groups of utils/solver.py::build_optimizer (one per tensor) instead of a single group."""
-import argparse, os, sys, time, types
+import argparse, json, os, sys, time, types
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, 'context-transformer_amd')); sys.path.insert(0, REPO)
@@ -15,7 +20,10 @@ ap.add_argument('--sync', type=int, default=0)
 ap.add_argument('--phase', type=int, default=1); ap.add_argument('--setting', default='transfer')
 ap.add_argument('--fused-sgd', action='store_true'); ap.add_argument('--per-tensor-groups', action='store_true')
 ap.add_argument('--wgrad-h2', action='store_true')
+ap.add_argument('--clip-norm', type=float, default=None); ap.add_argument('--json', action='store_true')
 a = ap.parse_args()
+if a.clip_norm is not None:
+    a.fused_sgd = True
 if a.wgrad_h2:
     os.environ['CTDET_WGRAD_H2'] = '1'         # read once, when the TrainRuntime is built
 from ctdet import synth, dist as cdist
@@ -34,11 +42,11 @@ crit = MultiBoxLoss_combined(nout + 1, 0.5, True, 0, True, 3, 0.5, False)
 crit.sync_normalizer = world > 1
 if a.per_tensor_groups:
     from utils import solver
-    opt = solver.build_optimizer(types.SimpleNamespace(method='ours', phase=a.phase, lr=1e-4, momentum=0.9, weight_decay=5e-4),
-                                 net, fused=a.fused_sgd)
+    opt = solver.build_optimizer(types.SimpleNamespace(method='ours', phase=a.phase, lr=1e-4, momentum=0.9, weight_decay=5e-4,
+                                                       max_grad_norm=a.clip_norm), net, fused=a.fused_sgd)
 elif a.fused_sgd:
     from ctdet.optim import FusedSGD
-    opt = FusedSGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4)
+    opt = FusedSGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4, max_grad_norm=a.clip_norm)
 else:
     opt = torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4)
 x = synth.images(a.batch, a.size, 'randn', 1234 + rank).cuda()
@@ -57,7 +65,7 @@ def step():
 for _ in range(2):
     l = step()
 torch.cuda.synchronize()
-ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
 tf = tl = tb = to = 0.0
 cdist.barrier('cuda')
 t0 = time.perf_counter()
@@ -66,8 +74,9 @@ for _ in range(a.steps):
     ev[0].record(); out = net(x); ev[1].record()
     ld = crit(out, priors, tg); loss = sum(ld.values()); ev[2].record()
     loss.backward(); ev[3].record()
-    opt.step()
+    opt.step(); ev[4].record()
     torch.cuda.synchronize()
+    to += ev[3].elapsed_time(ev[4])
     tf += ev[0].elapsed_time(ev[1]); tl += ev[1].elapsed_time(ev[2]); tb += ev[2].elapsed_time(ev[3])
 cdist.barrier('cuda')
 dt = cdist.max_over_ranks((time.perf_counter() - t0) / a.steps, 'cuda')
@@ -76,3 +85,11 @@ if rank == 0:
     print('RFBNet-%d phase %d bs=%d x %d GPU(s)%s: %.1f ms/step = %.1f img/s | fwd %.1f  loss %.1f  bwd %.1f ms | loss %.4f'
           % (a.size, a.phase, a.batch, world, ' [%s, %d groups]' % (type(opt).__name__, len(opt.param_groups))
              if a.fused_sgd or a.per_tensor_groups else '', dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
+    if a.json or a.clip_norm is not None:
+        row = {'train_bench': 'RFBNet-%d phase %d' % (a.size, a.phase), 'batch': a.batch, 'gpus': world, 'steps': n,
+               'optimizer': type(opt).__name__, 'groups': len(opt.param_groups), 'ms_per_step': round(dt * 1e3, 3),
+               'fwd_ms': round(tf / n, 3), 'loss_ms': round(tl / n, 3), 'bwd_ms': round(tb / n, 3), 'opt_ms': round(to / n, 3),
+               'clip_norm': a.clip_norm, 'loss': float(loss)}
+        if a.clip_norm is not None:
+            row.update(opt.clip_info())                 # norm, coef, finite, nonfinite of the last step
+        print(json.dumps(row))
