@@ -74,7 +74,9 @@ __device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float
 // BM x BN = output pixels x output channels of a workgroup of NT threads: 128 x {64, 128} with four waves, 256 x 256
 // with eight (each wave 128 x 64: eight 32x32 accumulators; half the L2 -> LDS operand traffic per MFMA of 128 x 128,
 // which at 64 flop per byte asks for ~12 TB/s at the 0.75 PFLOP/s that tile tops out at)
-template <int BM, int BN, int BK, bool SMALL, int NT>
+// TAIL: Cin != cin_pad, some channel steps reach past Cin (an instantiation of its own, so that the layers whose channels fill
+// their steps -- every wide layer of the network -- carry none of the masking)
+template <int BM, int BN, int BK, bool SMALL, int NT, bool TAIL = false>
 __global__ __launch_bounds__(NT) void conv_bf16_nhwc(const Bf16Args a)
 {
     constexpr int SPR = BK / 8;                    // 16-byte segments per tile row
@@ -141,7 +143,13 @@ __global__ __launch_bounds__(NT) void conv_bf16_nhwc(const Bf16Args a)
     // profiles/r03_mfma_valu_overlap.txt).
     int ld_tap = 0, ld_kh = 0, ld_kw = 0, ld_cs = 0;       // non-SMALL: tap index, its (kh, kw), channel step within the tap
     int va[NA], va_tail[NA], vb[NB];
-    const bool has_tail = !SMALL && (a.Cin % BK) != 0;      // last channel step: segments at or past Cin read zeros
+    // Channel steps that reach past Cin (cin_pad is a multiple of 64: with BK = 32 the step in front of the last one can be one of
+    // them, Cin = 24 or 72, and the last one can lie past Cin altogether, Cin = 32): their segments at or past Cin read zeros, not
+    // the neighbouring channels of a wider buffer or the next pixel (a NaN or Inf there would survive the zero weights).  part_cs
+    // is the one step that straddles Cin, every later step of the tap loads nothing: va_tail holds the offsets of the steps from
+    // part_cs on -- masked per segment while the loader is at or in front of part_cs, all invalid once it is past it.
+    constexpr bool has_tail = !SMALL && TAIL;
+    const int part_cs = a.Cin / BK;
     auto tap_offsets = [&]() {
 #pragma unroll
         for (int q = 0; q < NA; ++q) {
@@ -149,7 +157,7 @@ __global__ __launch_bounds__(NT) void conv_bf16_nhwc(const Bf16Args a)
             const bool ok = pix_ok[q] && ld_tap < taps && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
             const int off = (((pix_n[q] * a.H + ih) * a.W + iw) * a.in_ctot + a.in_coff + sseg * 8) * 2;
             va[q] = ok ? off : kInvalidOff;
-            va_tail[q] = ok && (csteps - 1) * BK + sseg * 8 < a.Cin ? off : kInvalidOff;
+            va_tail[q] = ok && ld_cs <= part_cs && part_cs * BK + sseg * 8 < a.Cin ? off : kInvalidOff;
         }
     };
     if (!SMALL) {
@@ -189,7 +197,7 @@ __global__ __launch_bounds__(NT) void conv_bf16_nhwc(const Bf16Args a)
         }
         const int sa = ld_cs * BK * 2;                                      // bytes: channel step inside the pixel
         const int sb = (ld_tap * cgroups + ld_cs * SPR) * a.cout_pad * 16;   // bytes: (tap, channel group) plane
-        const bool tail = has_tail && ld_cs == csteps - 1;
+        const bool tail = has_tail && ld_cs >= part_cs;
         if constexpr (DMA) {
             typedef __attribute__((address_space(3))) void* lds_ptr;
             unsigned char* Ad = lds + dma_buf * (A_B + B_B) + wave * 1024;
@@ -217,6 +225,9 @@ __global__ __launch_bounds__(NT) void conv_bf16_nhwc(const Bf16Args a)
             ++ld_kw;
             if (ld_kw == a.KW) { ld_kw = 0; ++ld_kh; }
             tap_offsets();
+        } else if (has_tail && ld_cs == part_cs + 1) {                      // from here to the end of the tap: whole steps past Cin
+#pragma unroll
+            for (int q = 0; q < NA; ++q) va_tail[q] = kInvalidOff;
         }
     };
     auto store_step = [&](int buf) {
@@ -654,23 +665,83 @@ extern "C" int ct_maxpool2d_nhwc_bf16(const void* x, void* y, int batch, int cha
     return CT_OK;
 }
 
-extern "C" int ct_conv2d_bf16_fwd(const ct_conv_desc* d, ct_stream_t stream)
+// The descriptor checks of the launcher (and of the variant query, which refuses what the launcher refuses); `who` names the entry
+// point in the message.  Leaves the byte count of the input buffer in *in_bytes.
+static int bf16_check_desc(const ct_conv_desc* d, const char* who, long long* in_bytes)
 {
-    CT_REQUIRE(d && d->in && d->wpacked && d->scale && d->shift, "ct_conv2d_bf16_fwd: null tensor");
-    CT_REQUIRE(d->batch > 0 && d->cin > 0 && d->cout > 0 && !d->transposed, "ct_conv2d_bf16_fwd: bad shape");
+    CT_REQUIRE(d && d->in && d->wpacked && d->scale && d->shift, "%s: null tensor", who);
+    CT_REQUIRE(d->batch > 0 && d->cin > 0 && d->cout > 0 && !d->transposed, "%s: bad shape", who);
     CT_REQUIRE(d->in_coff % 8 == 0 && d->in_ctot % 8 == 0 && d->cin % 8 == 0,
-               "ct_conv2d_bf16_fwd: channel slices must be multiples of 8 (16-byte loads), got ctot %d coff %d cin %d",
+               "%s: channel slices must be multiples of 8 (16-byte loads), got ctot %d coff %d cin %d", who,
                d->in_ctot, d->in_coff, d->cin);
-    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "ct_conv2d_bf16_fwd: input slice");
+    CT_REQUIRE(d->in_coff >= 0 && d->in_coff + d->cin <= d->in_ctot, "%s: input slice", who);
     const int eoh = (d->h + 2 * d->pad_h - d->dil * (d->kh - 1) - 1) / d->stride + 1;
     const int eow = (d->w + 2 * d->pad_w - d->dil * (d->kw - 1) - 1) / d->stride + 1;
-    CT_REQUIRE(eoh == d->oh && eow == d->ow, "ct_conv2d_bf16_fwd: oh/ow mismatch");
+    CT_REQUIRE(eoh == d->oh && eow == d->ow, "%s: oh/ow mismatch", who);
     if (d->nseg == 0)
-        CT_REQUIRE(d->out && d->out_coff >= 0 && d->out_coff + d->cout <= d->out_ctot, "ct_conv2d_bf16_fwd: output slice");
+        CT_REQUIRE(d->out && d->out_coff >= 0 && d->out_coff + d->cout <= d->out_ctot, "%s: output slice", who);
     else
-        CT_REQUIRE(d->nseg <= 3 && !d->res, "ct_conv2d_bf16_fwd: segments");
-    const long long in_bytes = (long long)d->batch * d->h * d->w * d->in_ctot * 2;
-    CT_REQUIRE(in_bytes < kMaxBufBytes, "ct_conv2d_bf16_fwd: input above 2 GiB");
+        CT_REQUIRE(d->nseg <= 3 && !d->res, "%s: segments", who);
+    *in_bytes = (long long)d->batch * d->h * d->w * d->in_ctot * 2;
+    CT_REQUIRE(*in_bytes < kMaxBufBytes, "%s: input above 2 GiB", who);
+    return CT_OK;
+}
+
+// The seven variants of conv_bf16_nhwc the launcher picks among, and the rule that picks: a pure function of the (checked)
+// descriptor and of the three switches.
+enum Bf16Variant { V128x64k32s, V128x128k32s, V256x256k32, V128x64k32, V128x64k64, V128x128k32, V128x128k64 };
+static const char* const kBf16VariantName[] = {"bf16:128x64k32s", "bf16:128x128k32s", "bf16:256x256k32", "bf16:128x64k32",
+                                               "bf16:128x64k64",  "bf16:128x128k32",  "bf16:128x128k64"};
+struct Bf16Switches {
+    bool big_set;      // CTDET_BF16_BIG_MIN is set: its value alone decides (the fill-the-last-round rule is off)
+    int big_min;       // fewest 256 x 256 tiles for that variant (200 when unset)
+    bool shortk;       // CTDET_BF16_SHORTK != 0: 32-channel steps for narrow layers with cin <= 64
+    int wide_bk;       // CTDET_BF16_BK: 32 = the three-buffer ring for the wide tile, anything else 64
+};
+
+static Bf16Variant bf16_choose_variant(const ct_conv_desc* d, const Bf16Switches& sw)
+{
+    const int cin_pad = ct_conv_bf16_cin_pad(d->cin), cout_pad = ct_conv_bf16_cout_pad(d->cout);
+    const int npix = d->batch * d->oh * d->ow;
+    const int tn128 = (npix + 127) / 128;
+    const bool narrow = d->cout <= 64 || (long long)((d->cout + 127) / 128) * tn128 < 256;   // few tiles: finer ones
+    // 256 x 256 (eight waves): layers with >= 256 output channels whose 256-pixel tiles still give every CU a workgroup
+    const long long big_tiles = (long long)(cout_pad / 256) * ((npix + 255) / 256);
+    // one workgroup per CU: the tile count must fill its last round of 256 (362 tiles = 1.41 rounds lose to the 128-wide tiles)
+    const bool big = cin_pad != KSMALL && d->cout >= 256 && cout_pad % 256 == 0 && d->nseg == 0 && big_tiles >= sw.big_min &&
+                     (sw.big_set || big_tiles * 5 >= (big_tiles + 255) / 256 * 256 * 4);
+    if (cin_pad == KSMALL) return narrow ? V128x64k32s : V128x128k32s;
+    if (big) return V256x256k32;
+    // short reductions (conv1_2: 9 k-steps): the workgroup is prologue / epilogue bound, 32-channel steps halve
+    // its LDS footprint so that four instead of two of them share a CU
+    if (narrow && d->cin <= 64 && sw.shortk) return V128x64k32;
+    if (narrow) return V128x64k64;
+    return sw.wide_bk == 32 ? V128x128k32 : V128x128k64;
+}
+
+static Bf16Switches bf16_switches()
+{
+    Bf16Switches sw;
+    const char* big_env = getenv("CTDET_BF16_BIG_MIN");     // read per call: the tests force / forbid the variant
+    sw.big_set = big_env != nullptr;
+    sw.big_min = big_env ? atoi(big_env) : 200;
+    sw.shortk = !(getenv("CTDET_BF16_SHORTK") && atoi(getenv("CTDET_BF16_SHORTK")) == 0);      // read per call
+    static const int wide_bk = getenv("CTDET_BF16_BK") ? atoi(getenv("CTDET_BF16_BK")) : 64;   // read once.  32: the three-buffer ring (faster on conv6 / conv7 / 1x1, slower on the 3x3 trunk)
+    sw.wide_bk = wide_bk;
+    return sw;
+}
+
+extern "C" const char* ct_conv_bf16_variant_name(const ct_conv_desc* d)
+{
+    long long in_bytes;
+    if (bf16_check_desc(d, "ct_conv_bf16_variant_name", &in_bytes) != CT_OK) return nullptr;
+    return kBf16VariantName[bf16_choose_variant(d, bf16_switches())];
+}
+
+extern "C" int ct_conv2d_bf16_fwd(const ct_conv_desc* d, ct_stream_t stream)
+{
+    long long in_bytes;
+    if (int rc = bf16_check_desc(d, "ct_conv2d_bf16_fwd", &in_bytes)) return rc;
     Bf16Args a{};
     a.in = d->in; a.w = d->wpacked; a.scale = d->scale; a.shift = d->shift; a.lo = d->lo; a.res = d->res;
     a.out = d->out;
@@ -705,29 +776,15 @@ extern "C" int ct_conv2d_bf16_fwd(const ct_conv_desc* d, ct_stream_t stream)
         if (lds_err != hipSuccess) return;
         hipLaunchKernelGGL(kernel, dim3(a.tiles_m * tiles_n, a.ksplit), dim3(nt), smem, st, a);
     };
-    const int tn128 = (a.Npix + 127) / 128;
-    const bool narrow = d->cout <= 64 || (long long)((d->cout + 127) / 128) * tn128 < 256;   // few tiles: finer ones
-    // 256 x 256 (eight waves): layers with >= 256 output channels whose 256-pixel tiles still give every CU a workgroup
-    const char* big_env = getenv("CTDET_BF16_BIG_MIN");     // read per call: the tests force / forbid the variant
-    const int big_min = big_env ? atoi(big_env) : 200;
-    const long long big_tiles = (long long)(a.cout_pad / 256) * ((a.Npix + 255) / 256);
-    // one workgroup per CU: the tile count must fill its last round of 256 (362 tiles = 1.41 rounds lose to the 128-wide tiles)
-    const bool big = a.cin_pad != KSMALL && d->cout >= 256 && a.cout_pad % 256 == 0 && d->nseg == 0 && big_tiles >= big_min &&
-                     (big_env || big_tiles * 5 >= (big_tiles + 255) / 256 * 256 * 4);
-    static const int wide_bk = getenv("CTDET_BF16_BK") ? atoi(getenv("CTDET_BF16_BK")) : 64;   // 32: the three-buffer ring (faster on conv6 / conv7 / 1x1, slower on the 3x3 trunk)
-    if (a.cin_pad == KSMALL) {
-        if (narrow) go(conv_bf16_nhwc<128, 64, 32, true, 256>, 128, 64, 32, 256);
-        else go(conv_bf16_nhwc<128, 128, 32, true, 256>, 128, 128, 32, 256);
-    } else if (big) {
-        go(conv_bf16_nhwc<256, 256, 32, false, 512>, 256, 256, 32, 512);
-    } else if (narrow && d->cin <= 64 && !(getenv("CTDET_BF16_SHORTK") && atoi(getenv("CTDET_BF16_SHORTK")) == 0)) {
-        // short reductions (conv1_2: 9 k-steps): the workgroup is prologue / epilogue bound, 32-channel steps halve
-        // its LDS footprint so that four instead of two of them share a CU
-        go(conv_bf16_nhwc<128, 64, 32, false, 256>, 128, 64, 32, 256);
-    } else {
-        if (narrow) go(conv_bf16_nhwc<128, 64, 64, false, 256>, 128, 64, 64, 256);
-        else if (wide_bk == 32) go(conv_bf16_nhwc<128, 128, 32, false, 256>, 128, 128, 32, 256);
-        else go(conv_bf16_nhwc<128, 128, 64, false, 256>, 128, 128, 64, 256);
+    const bool tail = a.Cin != a.cin_pad;       // (the image layer masks by taps, not by channels: one instantiation)
+    switch (bf16_choose_variant(d, bf16_switches())) {
+    case V128x64k32s: go(conv_bf16_nhwc<128, 64, 32, true, 256>, 128, 64, 32, 256); break;
+    case V128x128k32s: go(conv_bf16_nhwc<128, 128, 32, true, 256>, 128, 128, 32, 256); break;
+    case V256x256k32: go(tail ? conv_bf16_nhwc<256, 256, 32, false, 512, true> : conv_bf16_nhwc<256, 256, 32, false, 512>, 256, 256, 32, 512); break;
+    case V128x64k32: go(tail ? conv_bf16_nhwc<128, 64, 32, false, 256, true> : conv_bf16_nhwc<128, 64, 32, false, 256>, 128, 64, 32, 256); break;
+    case V128x64k64: go(tail ? conv_bf16_nhwc<128, 64, 64, false, 256, true> : conv_bf16_nhwc<128, 64, 64, false, 256>, 128, 64, 64, 256); break;
+    case V128x128k32: go(tail ? conv_bf16_nhwc<128, 128, 32, false, 256, true> : conv_bf16_nhwc<128, 128, 32, false, 256>, 128, 128, 32, 256); break;
+    case V128x128k64: go(tail ? conv_bf16_nhwc<128, 128, 64, false, 256, true> : conv_bf16_nhwc<128, 128, 64, false, 256>, 128, 128, 64, 256); break;
     }
     if (lds_err != hipSuccess)
         return ctdet::fail(CT_ERR_HIP, "ct_conv2d_bf16_fwd: raising the LDS limit of conv_bf16_nhwc failed: %s", hipGetErrorString(lds_err));

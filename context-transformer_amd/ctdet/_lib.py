@@ -143,6 +143,7 @@ SIGNATURES = {
     'ct_nhwc_bf16_to_nchw_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     'ct_maxpool2d_nhwc_bf16': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'ct_conv2d_bf16_fwd': (_I, [C.POINTER(ConvDesc), _P]),
+    'ct_conv_bf16_variant_name': (C.c_char_p, [C.POINTER(ConvDesc)]),
     'ct_conv_bf16_wino_supported': (_I, [C.POINTER(ConvDesc)]),
     'ct_conv_bf16_wino_packed_bytes': (_Z, [_I, _I]),
     'ct_conv_pack_weights_bf16_wino': (_I, [_P, _P, _I, _I, _P, _P]),

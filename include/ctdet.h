@@ -744,6 +744,12 @@ size_t ct_conv_bf16_packed_elems(int cin, int cout, int kh, int kw);
 int ct_conv_pack_weights_bf16(const float* const* w, const int* cout, int nparts, int cin, int kh, int kw,
                               void* wpacked, ct_stream_t stream);
 int ct_conv2d_bf16_fwd(const ct_conv_desc* d, ct_stream_t stream);
+/* The kernel variant ct_conv2d_bf16_fwd launches for `d` under the current CTDET_BF16_BIG_MIN / CTDET_BF16_SHORTK (read per
+ * call) and CTDET_BF16_BK (read once per process): "bf16:<pixels>x<couts>k<channels per k-step>", a trailing "s" for the image
+ * layer (cin_pad == 8, a k-step of four taps) -- bf16:128x64k32s, bf16:128x128k32s, bf16:256x256k32, bf16:128x64k32 (short-K),
+ * bf16:128x64k64, bf16:128x128k32 (CTDET_BF16_BK=32, three-buffer ring), bf16:128x128k64.  Pure host code (no HIP call): the
+ * launcher picks by the same function.  NULL, with ct_last_error_string set, for a descriptor the launcher refuses. */
+const char* ct_conv_bf16_variant_name(const ct_conv_desc* d);
 /* x dev [batch][channels][hw] fp32 -> y dev [batch][hw][c_pad] bf16 (channels >= `channels` zero) and back
  * (channel slice [coff, coff+channels) of a ctot-channel NHWC buffer -> dense NCHW fp32) */
 int ct_nchw_f32_to_nhwc_bf16(const float* x, int batch, int channels, int hw, int c_pad, void* y, ct_stream_t stream);

@@ -1,5 +1,6 @@
-"""bf16 channels-last path (BASELINE.json configs[4]): ct_conv2d_bf16_fwd against torch-CPU fp32 convolutions of the
-bf16-rounded operands, and the whole RFBNet through HipBackendBF16 against the fp32 path on the same weights."""
+"""bf16 channels-last path (BASELINE.json configs[4]): ct_conv2d_bf16_fwd against float64 convolutions of the bf16-rounded
+operands under the bound of tests/conv_bf16_cases.py (the row table itself runs in tests/test_gpu_bf16_conv.py), and the whole
+RFBNet through HipBackendBF16 against the fp32 path on the same weights."""
 import ctypes as C
 import types
 
@@ -7,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_bf16_cases as T
 from ctdet import _lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -17,9 +19,33 @@ def _s():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class _Want:
+    """The float64 reference of a launch on the bf16-rounded operands and the accumulation term of the bound, per image."""
+
+    def __init__(self, r, y32, bf16=True):
+        self.r, self.y32, self.bf16 = r, y32, bf16
+        self.A = torch.tensor([T.accum_term_of(r[n], y32[n]) for n in range(r.shape[0])], dtype=torch.float64)
+
+    def seg(self, c0, c1):
+        """Channels [c0, c1) as the head buffers hold them: [B, oh * ow * channels], channels last."""
+        w = _Want.__new__(_Want)
+        B = self.r.shape[0]
+        w.r, w.y32, w.bf16, w.A = (self.r[:, c0:c1].permute(0, 2, 3, 1).reshape(B, -1), None, self.bf16, self.A)
+        return w
+
+
 def _close(got, want):
-    """One bf16 ulp (same products, fp32 accumulation in another order, one final rounding) plus the fp32
-    accumulation noise that survives where ReLU / cancellation leaves a result near zero."""
+    """The bound of tests/conv_bf16_cases.py: |g - r| <= h(r) + A per image against the float64 value r -- h half a bf16 ulp of r
+    (the one correct rounding; none for the fp32 head segments), A = max(8 e32, 2^-20) max|r| (fp32 accumulation in another
+    order; e32: torch-CPU fp32 against r on that image)."""
+    r = want.r
+    A = want.A.view(-1, *([1] * (r.dim() - 1)))
+    h = T.half_ulp(r) if want.bf16 else 0.0
+    return bool(((got.double() - r).abs() <= h + A).all())
+
+
+def _close_pair(got, want):
+    """Two device results of the same sums in another order: one bf16 ulp plus the accumulation noise near zero."""
     return ((got - want).abs() <= want.abs() * 2 ** -7 + 2e-5 * want.abs().max()).all()
 
 
@@ -73,15 +99,18 @@ def _conv_bf16(x, parts, stride, pad, dil, relu, res=None, res_scale=1.0, out_ct
     y = torch.empty(B, cout, OH, OW, device=DEV)
     _lib.check(lib.ct_nhwc_bf16_to_nchw_f32(yb.data_ptr(), B, cout, OH * OW, octot, out_coff, y.data_ptr(), _s()), 'back')
     torch.cuda.synchronize()
-    want = F.conv2d(x[:, cin_off:cin_off + cin].bfloat16().float(), torch.cat(parts).bfloat16().float(), None,
-                    stride, pad, dil) * scale.cpu().view(1, -1, 1, 1) + shift.cpu().view(1, -1, 1, 1)
-    if res is not None:
-        want = want * res_scale + res.bfloat16().float()
-    if relu:
-        want = F.relu(want)
+    xr, wr = x[:, cin_off:cin_off + cin].bfloat16().float(), torch.cat(parts).bfloat16().float()
+
+    def ref(dt):
+        y = F.conv2d(xr.to(dt), wr.to(dt), None, stride, pad, dil) * scale.cpu().to(dt).view(1, -1, 1, 1) + \
+            shift.cpu().to(dt).view(1, -1, 1, 1)
+        if res is not None:
+            y = y * torch.tensor(res_scale, dtype=torch.float32).to(dt) + res.bfloat16().to(dt)
+        return F.relu(y) if relu else y
+    want = _Want(ref(torch.float64), ref(torch.float32), bf16=not segs)
     if segs:
         return [f.cpu() for f in flats], want, yb
-    return y.cpu(), want.bfloat16().float(), yb
+    return y.cpu(), want, yb
 
 
 CASES = [  # B, ctot, H, W, couts, k, stride, pad, dil
@@ -99,7 +128,7 @@ def test_conv_bf16_vs_cpu(case):
     parts = [torch.randn(c, ctot, k, k, generator=g) * (2.0 / (ctot * k * k)) ** 0.5 for c in couts]
     got, want, _ = _conv_bf16(x, parts, stride, pad, dil, True)
     # same products, fp32 accumulation in another order, one final rounding to bf16: at most one bf16 ulp apart
-    assert _close(got, want), (got - want).abs().max()
+    assert _close(got, want), (got - want.r).abs().max()
 
 
 def test_conv_bf16_slices_and_residual():
@@ -134,7 +163,7 @@ def test_conv_bf16_256x256_tile(case, monkeypatch):
     res = torch.randn(B, cout, OH, OW, generator=g)
     monkeypatch.setenv('CTDET_BF16_BIG_MIN', '1')
     got, want, yb = _conv_bf16(x, [w], stride, pad, dil, True, res=res, res_scale=0.5, out_ctot=cout + 24, out_coff=8)
-    assert _close(got, want), (got - want).abs().max()
+    assert _close(got, want), (got - want.r).abs().max()
     full = yb.view(B, OH, OW, cout + 24)
     assert (full[..., :8] == 0x7FC0).all() and (full[..., 8 + cout:] == 0x7FC0).all()      # untouched channel slices
     monkeypatch.setenv('CTDET_BF16_BIG_MIN', '1000000000')
@@ -171,14 +200,14 @@ def test_conv_bf16_split_k_into_head_segments():
     unsplit, want, _ = _conv_bf16(x, parts, 1, 1, 1, False, segs=segs)
     split, _, _ = _conv_bf16(x, parts, 1, 1, 1, False, segs=segs, ksplit=3)
     again, _, _ = _conv_bf16(x, parts, 1, 1, 1, False, segs=segs, ksplit=3)
-    assert (want < 0).any()
+    assert (want.r < 0).any()
     for g_, (c0, c1, base, size) in enumerate(segs):
         cnt = H * W * (c1 - c0)
-        ref = want[:, c0:c1].permute(0, 2, 3, 1).reshape(B, -1)
+        ref = want.seg(c0, c1)
         for tag, flat in (('unsplit', unsplit[g_]), ('ksplit3', split[g_])):
             assert torch.isnan(flat[:, :base]).all() and torch.isnan(flat[:, base + cnt:]).all(), (tag, g_)
-            assert _close(flat[:, base:base + cnt], ref), (tag, g_, (flat[:, base:base + cnt] - ref).abs().max())
-        assert _close(split[g_][:, base:base + cnt], unsplit[g_][:, base:base + cnt]), g_
+            assert _close(flat[:, base:base + cnt], ref), (tag, g_, (flat[:, base:base + cnt] - ref.r).abs().max())
+        assert _close_pair(split[g_][:, base:base + cnt], unsplit[g_][:, base:base + cnt]), g_
         assert torch.equal(split[g_].view(torch.int32), again[g_].view(torch.int32)), 'split-K must be run-to-run deterministic'
 
 
