@@ -37,6 +37,7 @@ SOURCES = {
     'ct_conv_x3.hip': [],
     'ct_pool.hip': [],
     'ct_preproc.hip': ['-ffp-contract=off'],
+    'ct_aug_plan.hip': ['-ffp-contract=off'],
     'ct_attn.hip': [],
     'ct_attn_bwd.hip': [],
     'ct_train.hip': [],

@@ -1,0 +1,282 @@
+"""Host twin of csrc/ct_aug_plan.hip (`ct_aug_plan`): the augmentation DECISIONS and the box targets of
+data/data_augment.py `preproc.decide`, drawn from a counter-based generator instead of `random`.
+
+numpy, fp64, no device, no `random`.  The draw table below is the one include/ctdet.h documents; the device kernel
+evaluates the same expressions in the same order with contraction off, so both give the same bytes.
+
+Generator: Philox4x32-10, key = (seed lo, seed hi), counter = (sample_id lo, sample_id hi, slot, lane); one
+evaluation gives four 32-bit words w0..w3.  uniform(a, b) = a + (b - a) * (w * 2^-32), randrange(n) = (w * n) >> 32,
+coin = w >> 31.
+
+    slot           lane     w0                 w1                w2                  w3
+    0 (misc)       0        brightness coin    contrast coin     hue coin            saturation coin
+    0              1        beta U(-32,32)     alpha U(.5,1.5)   hue -18+rr(37)      sat U(.5,1.5)
+    0              2        expand u (> p: no) mirror coin       interp rr(5)        fallback interp rr(5)
+    0x100 + r      63       crop mode rr(7)
+    0x100 + r      0..49    scale U(.3,1)      ratio u           left rr(W - w)      top rr(H - h)
+    0x200 + r      0..63    scale U(1,4)       ratio u           left rr(w - cw + 1) top rr(h - ch + 1)
+
+Crop rounds r = 0..255, expand rounds r = 0..63; the lowest passing lane of the first round with one wins.
+"""
+import collections
+
+import numpy as np
+
+PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+_MASK = np.uint64(0xFFFFFFFF)
+
+SLOT_MISC, SLOT_CROP, SLOT_EXPAND = 0, 0x100, 0x200
+LANE_COINS, LANE_PARAMS, LANE_MISC, LANE_MODE = 0, 1, 2, 63
+CROP_TRIALS, CROP_ROUNDS, EXPAND_TRIALS, EXPAND_ROUNDS = 50, 256, 64, 64
+CROP_MIN_IOU = (None, 0.1, 0.3, 0.5, 0.7, 0.9, -np.inf)     # data_augment.py CROP_MODES; every upper bound is None
+STATUS_BAD_SAMPLE, STATUS_ROWS_DROPPED = 1, 2
+
+SAMPLE_DTYPE = np.dtype([('src_off', '<i8'), ('sample_id', '<u8'), ('H', '<i4'), ('W', '<i4'), ('box_begin', '<i4'),
+                         ('box_end', '<i4'), ('image', '<i4'), ('cls', '<i4'), ('weight', '<f4'), ('flags', '<i4')])
+PLAN_DTYPE = np.dtype([('src_off', '<i8'), ('H', '<i4'), ('W', '<i4'), ('crop', '<i4', (4,)), ('exp', '<i4', (4,)),
+                       ('mirror', '<i4'), ('interp', '<i4'), ('flags', '<i4'), ('hue', '<i4'), ('beta', '<f4'),
+                       ('alpha', '<f4'), ('sat', '<f4'), ('fill', '<f4', (3,)), ('pad', '<f4', (2,))])
+assert SAMPLE_DTYPE.itemsize == 48 and PLAN_DTYPE.itemsize == 96
+
+AugPlanResult = collections.namedtuple(
+    'AugPlanResult', 'plans truths gt_off status crop_rounds expand_rounds sample_rows info')
+
+
+def philox4x32(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10.  Counter words: scalars or arrays (broadcast); key words: scalars.  -> uint32 [..., 4]."""
+    c = np.broadcast_arrays(*[np.asarray(v, dtype=np.uint64) & _MASK for v in (c0, c1, c2, c3)])
+    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
+    m0, m1 = np.uint64(PHILOX_M[0]), np.uint64(PHILOX_M[1])
+    for _ in range(10):
+        p0, p1 = c[0] * m0, c[2] * m1
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & _MASK, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1),
+             p0 & _MASK]
+        k0, k1 = (k0 + PHILOX_W[0]) & 0xFFFFFFFF, (k1 + PHILOX_W[1]) & 0xFFFFFFFF
+    return np.stack(c, -1).astype(np.uint32)
+
+
+def draws(seed, sample_id, slot, lanes):
+    """The four words of every lane in `lanes` at (seed, sample_id, slot)."""
+    seed, sample_id = int(seed) & (2 ** 64 - 1), int(sample_id) & (2 ** 64 - 1)
+    return philox4x32(sample_id & 0xFFFFFFFF, sample_id >> 32, slot, lanes, seed & 0xFFFFFFFF, seed >> 32)
+
+
+def unit(w):
+    return np.asarray(w, dtype=np.float64) * 2.0 ** -32
+
+
+def uniform(a, b, w):
+    return a + (b - a) * unit(w)
+
+
+def randrange(n, w):
+    return ((np.asarray(w, dtype=np.uint64) * np.asarray(n, dtype=np.uint64)) >> np.uint64(32)).astype(np.int64)
+
+
+def _crop_trials(d, H, W, b, labels, min_iou, cls):
+    """The 50 trials of one crop round: d uint32 [50,4], b float64 [n,4]  ->  ok [50], (l, t, w, h) int64 [50]."""
+    scale = uniform(0.3, 1.0, d[:, 0])
+    lo, hi = np.maximum(0.5, scale * scale), np.minimum(2.0, 1.0 / scale / scale)
+    ratio = np.sqrt(lo + (hi - lo) * unit(d[:, 1]))
+    w, h = (scale * ratio * W).astype(np.int64), (scale / ratio * H).astype(np.int64)
+    ok = (w >= 1) & (h >= 1) & (w < W) & (h < H)
+    l = randrange(np.where(ok, W - w, 1), d[:, 2])
+    t = randrange(np.where(ok, H - h, 1), d[:, 3])
+    rl, rt, rr, rb = [v.astype(np.float64)[None, :] for v in (l, t, l + w, t + h)]
+    x1, y1, x2, y2 = [b[:, k, None] for k in range(4)]
+    ltx, lty, rbx, rby = np.maximum(x1, rl), np.maximum(y1, rt), np.minimum(x2, rr), np.minimum(y2, rb)
+    area_i = (rbx - ltx) * (rby - lty) * ((ltx < rbx) & (lty < rby))
+    area_a, area_b = (x2 - x1) * (y2 - y1), (rr - rl) * (rb - rt)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        iou = area_i / (area_a + area_b - area_i)
+    ok &= (min_iou <= iou.min(0)) & (iou.max(0) <= np.inf)
+    cx, cy = (x1 + x2) / 2, (y1 + y2) / 2
+    inside = (rl < cx) & (cx < rr) & (rt < cy) & (cy < rb)
+    ok &= inside.any(0)
+    if cls >= 0:
+        ok &= (inside & (labels[:, None] == float(cls + 1))).any(0)
+    return ok, l, t, w, h
+
+
+def _expand_trials(d, cw, ch):
+    scale = uniform(1.0, 4.0, d[:, 0])
+    lo, hi = np.maximum(0.5, 1.0 / scale / scale), np.minimum(2.0, scale * scale)
+    ratio = np.sqrt(lo + (hi - lo) * unit(d[:, 1]))
+    ws, hs = scale * ratio, scale / ratio
+    ok = ~((ws < 1) | (hs < 1))
+    w, h = (ws * cw).astype(np.int64), (hs * ch).astype(np.int64)
+    left = randrange(np.where(ok, w - cw + 1, 1), d[:, 2])
+    top = randrange(np.where(ok, h - ch + 1, 1), d[:, 3])
+    return ok, w, h, left, top
+
+
+def plan_sample(seed, sample_id, H, W, boxes, cls, p, interp_of_draw):
+    """One sample's decisions.  boxes float32 [n,5] pixel (x1,y1,x2,y2,label), cls -1 or the class constraint, p the
+    expand probability (a float32 value, like the C ABI's)  ->  dict(plan fields, rows float64 [k,5], rounds, ...)."""
+    H, W, cls = int(H), int(W), int(cls)
+    bl = np.asarray(boxes, dtype=np.float32).reshape(-1, 5).astype(np.float64)
+    b, labels, n = bl[:, :4], bl[:, 4], len(bl)
+    misc = draws(seed, sample_id, SLOT_MISC, np.arange(3))
+    out = dict(H=H, W=W, crop=(0, 0, W, H), exp=(W, H, 0, 0), mirror=0, interp=0, flags=0, hue=0, beta=0.0, alpha=1.0,
+               sat=1.0, crop_rounds=0, expand_rounds=0, crop_mode=0, crop_lane=-1, expand_lane=-1, cropped=False,
+               expanded=False, fallback=False)
+    # crop
+    l, t, w, h, cropped = 0, 0, W, H, False
+    if n > 0:
+        for r in range(CROP_ROUNDS):
+            d = draws(seed, sample_id, SLOT_CROP + r, np.arange(64))
+            out['crop_rounds'] = r + 1
+            mode = int(randrange(7, d[LANE_MODE, 0]))
+            out['crop_mode'] = mode
+            if mode == 0:
+                break
+            ok, tl, tt, tw, th = _crop_trials(d[:CROP_TRIALS], H, W, b, labels, CROP_MIN_IOU[mode], cls)
+            idx = np.flatnonzero(ok)
+            if len(idx):
+                k = int(idx[0])
+                l, t, w, h, cropped = int(tl[k]), int(tt[k]), int(tw[k]), int(th[k]), True
+                out['crop_lane'] = k
+                break
+    out['cropped'] = cropped
+    # distort
+    coins, prm = misc[LANE_COINS] >> 31, misc[LANE_PARAMS]
+    flags, beta, alpha, hue, sat = 0, 0.0, 1.0, 0, 1.0
+    if coins[0]:
+        flags, beta = flags | 1, float(uniform(-32.0, 32.0, prm[0]))
+    if coins[1]:
+        flags, alpha = flags | 2, float(uniform(0.5, 1.5, prm[1]))
+    if coins[2]:
+        flags, hue = flags | 4, -18 + int(randrange(37, prm[2]))
+    if coins[3]:
+        flags, sat = flags | 8, float(uniform(0.5, 1.5, prm[3]))
+    # expand
+    ew, eh, left, top, expanded = w, h, 0, 0, False
+    if not (float(unit(misc[LANE_MISC, 0])) > p):
+        for r in range(EXPAND_ROUNDS):
+            d = draws(seed, sample_id, SLOT_EXPAND + r, np.arange(EXPAND_TRIALS))
+            out['expand_rounds'] = r + 1
+            ok, xw, xh, xl, xt = _expand_trials(d, w, h)
+            idx = np.flatnonzero(ok)
+            if len(idx):
+                k = int(idx[0])
+                ew, eh, left, top, expanded = int(xw[k]), int(xh[k]), int(xl[k]), int(xt[k]), True
+                out['expand_lane'] = k
+                break
+    out['expanded'] = expanded
+    mirror = int(misc[LANE_MISC, 1] >> 31)
+    # targets
+    x1, y1, x2, y2 = [b[:, k].copy() for k in range(4)]
+    keep = np.ones(n, dtype=bool)
+    if cropped:
+        cx, cy = (x1 + x2) / 2, (y1 + y2) / 2
+        keep = (l < cx) & (cx < l + w) & (t < cy) & (cy < t + h)
+        x1, y1 = np.maximum(x1, float(l)) - l, np.maximum(y1, float(t)) - t
+        x2, y2 = np.minimum(x2, float(l + w)) - l, np.minimum(y2, float(t + h)) - t
+    if expanded:
+        x1, y1, x2, y2 = x1 + left, y1 + top, x2 + left, y2 + top
+    if mirror:
+        x1, x2 = ew - x2, ew - x1
+    x1, y1, x2, y2 = x1 / ew, y1 / eh, x2 / ew, y2 / eh
+    keep = keep & (np.minimum(x2 - x1, y2 - y1) > 0.01)
+    if not keep.any() or (cls >= 0 and not (labels[keep] == float(cls + 1)).any()):
+        out.update(fallback=True, interp=int(interp_of_draw[int(randrange(5, misc[LANE_MISC, 3]))]),
+                   rows=np.stack([b[:, 0] / W, b[:, 1] / H, b[:, 2] / W, b[:, 3] / H, labels], 1))
+        return out
+    out.update(crop=(l, t, w, h), exp=(ew, eh, left, top), mirror=mirror, flags=flags, beta=beta, alpha=alpha, hue=hue,
+               sat=sat, interp=int(interp_of_draw[int(randrange(5, misc[LANE_MISC, 2]))]),
+               rows=np.stack([x1, y1, x2, y2, labels], 1)[keep])
+    return out
+
+
+def _identity(plan, H, W):
+    plan['H'], plan['W'], plan['crop'], plan['exp'] = H, W, (0, 0, W, H), (W, H, 0, 0)
+    plan['mirror'] = plan['interp'] = plan['flags'] = plan['hue'] = 0
+    plan['beta'], plan['alpha'], plan['sat'] = 0.0, 1.0, 1.0
+
+
+def plan_batch(samples, boxes, num_images, max_gt, seed, p_expand, interp_of_draw, fill, truths_cap=None):
+    """What `ct_aug_plan` computes, safety rule included.  samples: SAMPLE_DTYPE array; boxes float32 [total,5].
+    -> AugPlanResult: plans (PLAN_DTYPE), truths float32 [min(rows, truths_cap), 6], gt_off int32 [num_images+1],
+    status int32 [4] = (bits, bad samples, dropped rows, rows before the cap), the crop / expand rounds each sample
+    used, each sample's rows, and plan_sample's dicts (None for a refused sample)."""
+    samples = np.asarray(samples, dtype=SAMPLE_DTYPE)
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 5)
+    total, n = len(boxes), len(samples)
+    p = float(np.float32(p_expand))
+    plans = np.zeros(n, dtype=PLAN_DTYPE)
+    plans['fill'] = np.asarray(fill, dtype=np.float32)
+    crop_rounds, expand_rounds = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    rows_of, image_of, info = [], [], []
+    prevmax, bad = -1, 0
+    for i, s in enumerate(samples):
+        H, W, img = int(s['H']), int(s['W']), int(s['image'])
+        plans[i]['src_off'] = s['src_off']
+        inrange = 0 <= img < num_images
+        refused = not inrange or H < 1 or W < 1 or img < prevmax
+        if inrange:
+            prevmax = max(prevmax, img)
+        if refused:
+            _identity(plans[i], max(H, 1), max(W, 1))
+            bad += 1
+            rows_of.append(np.zeros((0, 6), dtype=np.float32))
+            image_of.append(-1)
+            info.append(None)
+            continue
+        b0, b1 = min(max(int(s['box_begin']), 0), total), min(max(int(s['box_end']), 0), total)
+        cnt = min(max(b1 - b0, 0), int(max_gt))
+        r = plan_sample(seed, s['sample_id'], H, W, boxes[b0:b0 + cnt], s['cls'], p, interp_of_draw)
+        pl = plans[i]
+        pl['H'], pl['W'], pl['crop'], pl['exp'] = H, W, r['crop'], r['exp']
+        pl['mirror'], pl['interp'], pl['flags'], pl['hue'] = r['mirror'], r['interp'], r['flags'], r['hue']
+        pl['beta'], pl['alpha'], pl['sat'] = r['beta'], r['alpha'], r['sat']
+        crop_rounds[i], expand_rounds[i] = r['crop_rounds'], r['expand_rounds']
+        rows = np.zeros((len(r['rows']), 6), dtype=np.float64)
+        rows[:, :5] = r['rows']
+        flags = int(s['flags'])
+        if flags & 2:
+            rows[1:, 4] = -1
+        rows[:, 5] = float(s['weight'])
+        if flags & 1:
+            rows[rows[:, 4] == -1, 5] = 0
+        rows_of.append(rows.astype(np.float32))
+        image_of.append(img)
+        info.append(r)
+    counts = np.zeros(num_images, dtype=np.int64)
+    for img, rows in zip(image_of, rows_of):
+        if img >= 0:
+            counts[img] += len(rows)
+    all_rows = np.concatenate(rows_of, 0) if rows_of else np.zeros((0, 6), dtype=np.float32)
+    n_rows = len(all_rows)
+    cap = n_rows if truths_cap is None else int(truths_cap)
+    gt_off = np.minimum(np.concatenate([[0], np.cumsum(counts)]), cap).astype(np.int32)
+    dropped = max(n_rows - cap, 0)
+    status = np.array([(STATUS_BAD_SAMPLE if bad else 0) | (STATUS_ROWS_DROPPED if dropped else 0), bad, dropped, n_rows],
+                      dtype=np.int32)
+    return AugPlanResult(plans, all_rows[:cap], gt_off, status, crop_rounds, expand_rounds, rows_of, info)
+
+
+def plan_dict(plan):
+    """A PLAN_DTYPE record as the dict `ops.Augmenter` takes (data_augment.py `_plan`)."""
+    return dict(H=int(plan['H']), W=int(plan['W']), crop=tuple(int(v) for v in plan['crop']),
+                exp=tuple(int(v) for v in plan['exp']), mirror=int(plan['mirror']), interp=int(plan['interp']),
+                flags=int(plan['flags']), hue=int(plan['hue']), beta=float(plan['beta']), alpha=float(plan['alpha']),
+                sat=float(plan['sat']))
+
+
+def make_samples(shapes, targets, images=None, sample_ids=None, cls=-1, weights=None, flags=0):
+    """Pack per-sample (H, W) shapes and [G,5] target arrays into (SAMPLE_DTYPE array, float32 [total,5] boxes)."""
+    n = len(shapes)
+    s = np.zeros(n, dtype=SAMPLE_DTYPE)
+    pos, parts = 0, []
+    for i, (shape, tg) in enumerate(zip(shapes, targets)):
+        tg = np.asarray(tg, dtype=np.float32).reshape(-1, 5)
+        s[i]['H'], s[i]['W'], s[i]['box_begin'], s[i]['box_end'] = shape[0], shape[1], pos, pos + len(tg)
+        pos += len(tg)
+        parts.append(tg)
+    s['image'] = np.arange(n) if images is None else images
+    s['sample_id'] = np.arange(n, dtype=np.uint64) if sample_ids is None else np.asarray(sample_ids, dtype=np.uint64)
+    s['cls'], s['flags'] = cls, flags
+    s['weight'] = 1.0 if weights is None else weights
+    boxes = np.concatenate(parts, 0) if parts else np.zeros((0, 5), dtype=np.float32)
+    return s, np.ascontiguousarray(boxes, dtype=np.float32)

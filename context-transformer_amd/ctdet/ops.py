@@ -4,6 +4,7 @@ torch is plumbing here (device memory + the current HIP stream); every function 
 hand-written HIP kernels through ctypes and raises if the tensors are not on a HIP device --
 there is deliberately NO CPU / PyTorch fallback for these ops.
 """
+import collections
 import ctypes as C
 import functools
 
@@ -107,6 +108,32 @@ def match_batched(targets, priors, threshold, variances, want_overlap=False):
     ws_bytes = lib().ct_match_workspace_bytes(B, P, max_gt)
     ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
     check(lib().ct_match_batched(_dev(truths, 'truths'), _dev(off, 'gt_off', torch.int32), B, max_gt,
+                                 _dev(priors, 'priors'), P, float(threshold), float(variances[0]),
+                                 float(variances[1]), _dev(loc_t, 'loc_t'), _dev(conf_t, 'conf_t'),
+                                 _dev(obj_t, 'obj_t', torch.uint8), _opt(overlap, 'overlap'),
+                                 _dev(ws, 'ws', torch.uint8), ws_bytes, _stream()), 'ct_match_batched')
+    return (loc_t, conf_t, obj_t.bool(), overlap) if want_overlap else (loc_t, conf_t, obj_t.bool())
+
+
+# the device-resident form of a batch's target list: truths float32 [cap,6] and gt_off int32 [B+1] as ct_match_batched
+# reads them (what AugPlanner writes), max_gt the host-known upper bound of an image's row count
+PackedTargets = collections.namedtuple('PackedTargets', 'truths gt_off max_gt')
+
+
+def match_packed(truths, gt_off, batch, max_gt, priors, threshold, variances, want_overlap=False):
+    """match_batched on device-resident inputs: the same ct_match_batched call, no host-built offset table and no
+    copy.  max_gt: an upper bound of the rows of one image, e.g. the input box count of its samples."""
+    dev = priors.device
+    B, P, max_gt = int(batch), priors.shape[0], max(int(max_gt), 1)
+    if gt_off.numel() < B + 1:
+        raise ValueError('match_packed: gt_off has %d entries, batch %d needs %d' % (gt_off.numel(), B, B + 1))
+    loc_t = torch.empty(B, P, 4, device=dev)
+    conf_t = torch.empty(B, P, 2, device=dev)
+    obj_t = torch.empty(B, P, device=dev, dtype=torch.uint8)
+    overlap = torch.empty(B, P, device=dev) if want_overlap else None
+    ws_bytes = lib().ct_match_workspace_bytes(B, P, max_gt)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    check(lib().ct_match_batched(_dev(truths, 'truths'), _dev(gt_off, 'gt_off', torch.int32), B, max_gt,
                                  _dev(priors, 'priors'), P, float(threshold), float(variances[0]),
                                  float(variances[1]), _dev(loc_t, 'loc_t'), _dev(conf_t, 'conf_t'),
                                  _dev(obj_t, 'obj_t', torch.uint8), _opt(overlap, 'overlap'),
@@ -530,36 +557,23 @@ class Augmenter:
         n = len(images)
         if n == 0 or n > self.max_batch or len(plans) != n:
             raise ValueError('Augmenter: batch of %d images / %d plans (max %d)' % (n, len(plans), self.max_batch))
-        if self.copied is not None:
-            self.copied.synchronize()
-        need = sum(int(np.asarray(img).size) for img in images)
-        if need > self.cap:                 # any image size, like the reference (COCO is 640x480): grow, never refuse
-            self.cap = int(need * 1.25)
-            self.stage = torch.empty(self.cap, dtype=torch.uint8).pin_memory()
-            self.dev = torch.empty(self.cap, dtype=torch.uint8, device=self.device)
-        recs = (AugPlan * n)()
-        pos = 0
         for i, (img, p) in enumerate(zip(images, plans)):
-            a = np.ascontiguousarray(img)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or (a.shape[0], a.shape[1]) != (p['H'], p['W']):
-                raise ValueError('Augmenter: image %d is %s %s, plan says %dx%d' % (i, a.dtype, a.shape, p['H'], p['W']))
-            if pos + a.size > self.cap:
-                raise _lib.CtdetError('Augmenter: staging capacity %d bytes exceeded' % self.cap)
-            self.stage[pos:pos + a.size] = torch.from_numpy(a.reshape(-1))
+            if tuple(np.shape(img)[:2]) != (p['H'], p['W']):
+                raise ValueError('Augmenter: image %d is %s, plan says %dx%d' % (i, np.shape(img), p['H'], p['W']))
+        offs = self.upload(images)
+        recs = (AugPlan * n)()
+        for i, p in enumerate(plans):
             r = recs[i]
-            r.src_off, r.H, r.W = pos, p['H'], p['W']
+            r.src_off, r.H, r.W = int(offs[i]), p['H'], p['W']
             r.crop_l, r.crop_t, r.crop_w, r.crop_h = p['crop']
             r.exp_w, r.exp_h, r.exp_left, r.exp_top = p['exp']
             r.mirror, r.interp, r.flags, r.hue_delta = p['mirror'], p['interp'], p['flags'], p['hue']
             r.beta, r.alpha, r.sat_alpha = p['beta'], p['alpha'], p['sat']
             for c in range(3):
                 r.fill[c] = self.means_f[c]
-            pos += (a.size + 15) // 16 * 16
         self.plan_h[:n * 96] = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8)
-        self.dev[:pos].copy_(self.stage[:pos], non_blocking=True)
         self.plan_d[:n * 96].copy_(self.plan_h[:n * 96], non_blocking=True)
-        self.copied = torch.cuda.Event()
-        self.copied.record()
+        self.copied.record()                # the plan staging is free again after this copy too
         if out is None:
             out = torch.empty(n, 3, self.size, self.size, device=self.device, dtype=torch.float32)
         if not any(p['interp'] in INTERP_KIND for p in plans):
@@ -585,6 +599,127 @@ class Augmenter:
                                             _dev(self.tap_d, 'taps', torch.uint8), n, S, C.cast(self.means, C.c_void_p),
                                             _dev(out, 'out'), _stream()), 'ct_preproc_augment_taps')
         return out
+
+    def upload(self, images):
+        """Stage and upload the images: -> int64 [n] byte offsets of the images in the source buffer (AugPlan.src_off,
+        ct_aug_sample.src_off).  On its own for plans the device draws itself (AugPlanner, then `render`)."""
+        n = len(images)
+        if n == 0 or n > self.max_batch:
+            raise ValueError('Augmenter: batch of %d images (max %d)' % (n, self.max_batch))
+        if self.copied is not None:
+            self.copied.synchronize()
+        need = sum((int(np.asarray(img).size) + 15) // 16 * 16 for img in images)
+        if need > self.cap:                 # any image size, like the reference (COCO is 640x480): grow, never refuse
+            self.cap = int(need * 1.25)
+            self.stage = torch.empty(self.cap, dtype=torch.uint8).pin_memory()
+            self.dev = torch.empty(self.cap, dtype=torch.uint8, device=self.device)
+        offs = np.zeros(n, dtype=np.int64)
+        pos = 0
+        for i, img in enumerate(images):
+            a = np.ascontiguousarray(img)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError('Augmenter: image %d is %s %s, expected uint8 HxWx3' % (i, a.dtype, a.shape))
+            self.stage[pos:pos + a.size] = torch.from_numpy(a.reshape(-1))
+            offs[i] = pos
+            pos += (a.size + 15) // 16 * 16
+        self.dev[:pos].copy_(self.stage[:pos], non_blocking=True)
+        self.copied = torch.cuda.Event()
+        self.copied.record()
+        return offs
+
+    def render(self, plans_d, n, out=None):
+        """ct_preproc_augment over n device-resident plan records (uint8 [>= n*96]) whose src_off point into the
+        buffer `upload` filled.  The float filters only: tap tables are host decisions."""
+        if n == 0 or plans_d.numel() < n * 96:
+            raise ValueError('Augmenter.render: %d plans in a buffer of %d bytes' % (n, plans_d.numel()))
+        if out is None:
+            out = torch.empty(n, 3, self.size, self.size, device=self.device, dtype=torch.float32)
+        check(lib().ct_preproc_augment(_dev(self.dev, 'src', torch.uint8), _dev(plans_d, 'plans', torch.uint8), n,
+                                       self.size, C.cast(self.means, C.c_void_p), _dev(out, 'out'), _stream()),
+              'ct_preproc_augment')
+        return out
+
+
+AUG_SAMPLE_DTYPE = np.dtype([('src_off', '<i8'), ('sample_id', '<u8'), ('H', '<i4'), ('W', '<i4'), ('box_begin', '<i4'),
+                             ('box_end', '<i4'), ('image', '<i4'), ('cls', '<i4'), ('weight', '<f4'), ('flags', '<i4')])
+assert AUG_SAMPLE_DTYPE.itemsize == 48          # ct_aug_sample
+AUG_STATUS_BAD_SAMPLE, AUG_STATUS_ROWS_DROPPED = 1, 2
+
+
+class AugPlanner:
+    """The augmentation decisions and box targets of a batch on the device (ct_aug_plan, two launches): the host
+    hands over one ct_aug_sample per sample and the pixel boxes -- through one pinned staging buffer and one H2D copy,
+    as Augmenter stages its images -- and gets the plan records ct_preproc_augment reads and a PackedTargets that
+    ct_match_batched reads.  No host synchronisation unless `check()` is called."""
+
+    def __init__(self, device, seed, p_expand, interp_of_draw, fill, max_samples=64, max_boxes=4096):
+        self.device, self.seed, self.p_expand = torch.device(device), int(seed) & (2 ** 64 - 1), float(p_expand)
+        if len(interp_of_draw) != 5 or len(fill) != 3:
+            raise ValueError('AugPlanner: interp_of_draw has 5 entries and fill 3')
+        self.interp = (C.c_int * 5)(*[int(v) for v in interp_of_draw])
+        self.fill = (C.c_float * 3)(*[float(v) for v in fill])
+        self.cap_bytes = 0
+        self._reserve(max_samples, max_boxes)
+        self.copied = None
+        self.status = None                  # int32 [4] on the device, of the last call
+        self.upload_bytes = 0               # of the last call
+
+    def _reserve(self, n, total):
+        need = n * 48 + total * 20
+        if need > self.cap_bytes:
+            self.cap_bytes = need
+            self.stage = torch.empty(need, dtype=torch.uint8).pin_memory()
+            self.dev = torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    def __call__(self, samples, boxes, num_images, max_gt, truths_cap=None):
+        """samples: AUG_SAMPLE_DTYPE array [n]; boxes float32 [total,5]; max_gt: boxes per sample the kernel looks at.
+        -> (plans uint8 [n*96] on the device, PackedTargets).  truths_cap defaults to the input box count, which the
+        rows cannot exceed."""
+        samples = np.ascontiguousarray(samples, dtype=AUG_SAMPLE_DTYPE)
+        boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 5)
+        n, total, num_images, max_gt = len(samples), len(boxes), int(num_images), int(max_gt)
+        if n == 0 or num_images < 1 or max_gt < 1:
+            raise ValueError('AugPlanner: %d samples, %d images, max_gt %d' % (n, num_images, max_gt))
+        if self.copied is not None:
+            self.copied.synchronize()
+        self._reserve(n, total)
+        nb_s, nb = n * 48, n * 48 + total * 20
+        self.stage[:nb_s] = torch.from_numpy(samples.view(np.uint8).reshape(-1))
+        if total:
+            self.stage[nb_s:nb] = torch.from_numpy(boxes.view(np.uint8).reshape(-1))
+        self.dev[:nb].copy_(self.stage[:nb], non_blocking=True)
+        self.copied = torch.cuda.Event()
+        self.copied.record()
+        self.upload_bytes = nb
+        cap = max(total, 1) if truths_cap is None else int(truths_cap)
+        dev = self.device
+        plans = torch.empty(n * 96, dtype=torch.uint8, device=dev)
+        truths = torch.empty(max(cap, 1), 6, dtype=torch.float32, device=dev)
+        gt_off = torch.empty(num_images + 1, dtype=torch.int32, device=dev)
+        self.status = torch.empty(4, dtype=torch.int32, device=dev)
+        ws_bytes = lib().ct_aug_plan_workspace_bytes(n, max_gt)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(lib().ct_aug_plan(_dev(self.dev, 'samples', torch.uint8), n,
+                                C.c_void_p(self.dev.data_ptr() + nb_s), total, num_images, max_gt, self.seed,
+                                self.p_expand, self.interp, self.fill, _dev(plans, 'plans', torch.uint8),
+                                _dev(truths, 'truths'), cap, _dev(gt_off, 'gt_off', torch.int32),
+                                _dev(self.status, 'status', torch.int32), _dev(ws, 'workspace', torch.uint8),
+                                ws_bytes, _stream()), 'ct_aug_plan')
+        # host-known bound of an image's rows: the boxes its samples hand in (each capped at max_gt)
+        cnt = np.minimum(np.clip(samples['box_end'], 0, total) - np.clip(samples['box_begin'], 0, total), max_gt)
+        img = samples['image']
+        ok = (img >= 0) & (img < num_images)
+        per_image = np.bincount(img[ok], weights=np.maximum(cnt[ok], 0), minlength=1) if ok.any() else np.zeros(1)
+        return plans, PackedTargets(truths, gt_off, max(int(per_image.max()), 1))
+
+    def check(self):
+        """Read the status words of the last call (a host synchronisation) and raise when a sample was refused or a
+        row dropped."""
+        st = self.status.cpu().numpy()
+        if st[0]:
+            raise _lib.CtdetError('ct_aug_plan: status %d (%d samples refused, %d rows dropped of %d)'
+                                  % (st[0], st[1], st[2], st[3]))
+        return st
 
 
 def mixup_blend(img1, img2, lambd):

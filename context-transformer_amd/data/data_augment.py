@@ -60,9 +60,12 @@ def _plan(h, w):
 
 
 class preproc(object):
-    def __init__(self, resize, rgb_means, p, device='cuda', max_batch=32, rng=None, filters=None):
+    def __init__(self, resize, rgb_means, p, device='cuda', max_batch=32, rng=None, filters=None, decisions='host',
+                 seed=None):
         """filters: 'fast' or 'cv2' (INTERP_FILTERS); None reads CTDET_AUG_FILTERS, default 'fast'.  Either way the
-        random draws are the same in number and order."""
+        random draws are the same in number and order.
+        decisions: 'host' (the default) draws from `random` in the reference's order; 'device' adds `batch_device`,
+        which draws them on the device from the counter-based generator keyed by `seed` (ctdet/aug_plan_ref.py)."""
         if filters is None:
             filters = os.environ.get('CTDET_AUG_FILTERS', 'fast')
         if filters not in INTERP_FILTERS:
@@ -72,6 +75,13 @@ class preproc(object):
         self.device, self.max_batch = torch.device(device), max_batch
         self.rng = rng or random          # the reference uses the module-level generator
         self._aug = None
+        if decisions not in ('host', 'device'):
+            raise ValueError("preproc: decisions=%r (known: 'host', 'device')" % (decisions,))
+        if decisions == 'device' and filters == 'cv2':
+            raise ValueError("preproc: filters='cv2' needs host decisions: the bicubic / Lanczos4 tap tables depend on "
+                             "the canvas size, which decisions='device' never brings to the host")
+        self.decisions, self.seed = decisions, 0 if seed is None else int(seed)
+        self._planner = self._aug_dev = None
 
     # ------------------------------------------------------------------ decisions (host scalars, no pixels)
     def _crop(self, width, height, boxes, labels, cls):
@@ -189,6 +199,55 @@ class preproc(object):
     def __call__(self, image, targets, cls=None):
         imgs, touts = self.batch([image], [targets], cls)
         return imgs[0], touts[0]
+
+    # ------------------------------------------------------------------ decisions on the device
+    def batch_device(self, images, targets, sample_ids, cls=None, mix=None):
+        """decisions='device': lists of uint8 HxWx3 images and [G,5] pixel targets, one 64-bit sample id per image ->
+        (float32 [n,3,S,S], ops.PackedTargets(truths, gt_off, max_gt)), all on the device; no per-sample host work
+        beyond packing the inputs.  mix = (second images, second targets, lambdas): image i is blended with its
+        second image by lambdas[i] (data/voc0712.py:240-275); a lambda >= 1 means the first sample alone with weight
+        1.  A second sample draws with id sample_ids[i] + 2**63."""
+        if self.decisions != 'device':
+            raise ValueError("preproc.batch_device needs preproc(..., decisions='device')")
+        n = len(images)
+        if n == 0 or n > self.max_batch or len(targets) != n or len(sample_ids) != n:
+            raise ValueError('preproc.batch_device: %d images, %d targets, %d sample ids (max %d)'
+                             % (n, len(targets), len(sample_ids), self.max_batch))
+        if self._planner is None:
+            self._aug_dev = ops.Augmenter(self.resize, self.means, self.device, 2 * self.max_batch)
+            self._planner = ops.AugPlanner(self.device, self.seed, self.p, self.interp_of_draw, self.means,
+                                           2 * self.max_batch)
+        lam = [1.0] * n if mix is None else [float(v) for v in mix[2]]
+        imgs, tgs, rec = [], [], []           # samples in image order: first, then second where there is one
+        first, second = [], []
+        for i in range(n):
+            two = mix is not None and lam[i] < 1
+            first.append(len(imgs))
+            imgs.append(images[i]); tgs.append(targets[i])
+            rec.append((i, int(sample_ids[i]), np.float32(lam[i]) if two else np.float32(1)))
+            second.append(len(imgs) if two else first[-1])
+            if two:
+                imgs.append(mix[0][i]); tgs.append(mix[1][i])
+                rec.append((i, int(sample_ids[i]) + 2 ** 63, np.float32(1. - lam[i])))
+        offs = self._aug_dev.upload(imgs)
+        m = len(imgs)
+        samples = np.zeros(m, dtype=ops.AUG_SAMPLE_DTYPE)
+        parts, pos = [], 0
+        for k, (img, tg) in enumerate(zip(imgs, tgs)):
+            tg = np.asarray(tg, dtype=np.float32).reshape(-1, 5)
+            samples[k] = (offs[k], rec[k][1] % 2 ** 64, img.shape[0], img.shape[1], pos, pos + len(tg), rec[k][0],
+                          -1 if cls is None else cls, rec[k][2], 0)
+            pos += len(tg)
+            parts.append(tg)
+        boxes = np.concatenate(parts, 0) if pos else np.zeros((0, 5), dtype=np.float32)
+        max_gt = max(max(len(p) for p in parts), 1)
+        plans, packed = self._planner(samples, boxes, n, max_gt)
+        if mix is None:
+            return self._aug_dev.render(plans, n), packed
+        # the plans of the first samples, then of the second ones (a lambda >= 1 blends an image with itself)
+        order = torch.tensor(first + second, dtype=torch.int64).to(self.device, non_blocking=True)
+        x = self._aug_dev.render(plans.view(m, 96).index_select(0, order).reshape(-1), 2 * n)
+        return ops.mixup_blend(x[:n], x[n:], torch.tensor(lam, dtype=torch.float32).clamp(max=1.0).to(self.device)), packed
 
 
 def mixup_targets(target1, target2, lambd, ignore_minus1=False):

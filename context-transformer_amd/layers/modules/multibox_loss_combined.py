@@ -5,7 +5,8 @@ library (`ct_match_batched`) instead of a Python loop over images and ground tru
 arithmetic itself (smooth-L1, two cross-entropies, 3:1 hard-negative ranking) has two forms: torch ops on
 the device tensors with autograd (the default), or -- `fused=True` / CTDET_LOSS_FUSED=1 -- the library's
 ct_multibox_loss_fwd / _bwd (three launches forward, one backward, no sort) behind one autograd Function.
-targets: list of [G,6] tensors = [x1,y1,x2,y2,label,mixup_weight].
+targets: list of [G,6] tensors = [x1,y1,x2,y2,label,mixup_weight], or an ops.PackedTargets holding the same rows on
+the device (what preproc(decisions='device').batch_device returns).
 """
 import os
 
@@ -66,8 +67,13 @@ class MultiBoxLoss_combined(nn.Module):
         in place -- a training step captured as a hipGraph (bench.py --train) reads the same three tensors at every
         replay, the matching itself (a host-built offset table, an H2D copy) stays outside the graph."""
         dev = torch.device(device) if device is not None else priors.device
-        loc_t, conf_t, obj_t = ops.match_batched([t.to(dev) for t in targets], priors.to(dev).float().contiguous(),
-                                                 self.threshold, self.variance)
+        if isinstance(targets, ops.PackedTargets):      # device-resident truths / gt_off (ops.AugPlanner): no host table
+            loc_t, conf_t, obj_t = ops.match_packed(targets.truths, targets.gt_off, targets.gt_off.numel() - 1,
+                                                    targets.max_gt, priors.to(dev).float().contiguous(),
+                                                    self.threshold, self.variance)
+        else:
+            loc_t, conf_t, obj_t = ops.match_batched([t.to(dev) for t in targets], priors.to(dev).float().contiguous(),
+                                                     self.threshold, self.variance)
         if out is None:
             return MatchedTargets(loc_t, conf_t, obj_t)
         out.loc_t.copy_(loc_t); out.conf_t.copy_(conf_t); out.obj_t.copy_(obj_t)

@@ -953,6 +953,79 @@ int ct_preproc_augment_taps(const unsigned char* src, const void* plans, const c
 int ct_mixup_blend(const float* img1, const float* img2, const float* lambd, int batch, long per_image,
                    float* out, ct_stream_t stream);
 
+/* The augmentation DECISIONS and box targets of data/data_augment.py `preproc.decide` on the device
+ * (csrc/ct_aug_plan.hip; host twin ctdet/aug_plan_ref.py).  It writes the plan records ct_preproc_augment reads and the
+ * packed truths / gt_off pair ct_match_batched reads, so nothing per sample is left on the host.
+ *
+ * GENERATOR  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85),
+ *   key = (seed lo, seed hi), counter = (sample_id lo, sample_id hi, slot, lane); one evaluation gives words w0..w3.
+ *   A sample's decisions depend on (seed, sample_id, its H, W, boxes, cls) and nothing else.
+ * DRAW RULES  uniform(a,b) = a + (b-a) * (w * 2^-32) in fp64; randrange(n) = (w * n) >> 32 on a 64-bit product;
+ *   coin = w >> 31.  All decision arithmetic is fp64 with + - * / sqrt, comparisons, min/max and truncation only,
+ *   contraction off, so host twin and device round alike.
+ * DRAW TABLE
+ *   slot        lane    w0                  w1               w2                   w3
+ *   0           0       brightness coin     contrast coin    hue coin             saturation coin
+ *   0           1       beta U(-32,32)      alpha U(.5,1.5)  hue -18 + rr(37)     sat U(.5,1.5)
+ *   0           2       expand u            mirror coin      interp rr(5)         fallback interp rr(5)
+ *   0x100 + r   63      crop mode rr(7)
+ *   0x100 + r   0..49   scale U(.3,1)       ratio u          left rr(W - w)       top rr(H - h)
+ *   0x200 + r   0..63   scale U(1,4)        ratio u          left rr(w - cw + 1)  top rr(h - ch + 1)
+ * CROP (reference _crop)  no boxes: no crop.  Rounds r = 0..255: mode = CROP_MODES[rr(7)]; mode None ends the rounds
+ *   without a crop; else the 50 lanes are the round's trials: ratio = sqrt(U(max(.5, scale^2), min(2, 1/scale/scale))),
+ *   w = int(scale*ratio*W), h = int(scale/ratio*H).  A trial is rejected when w < 1, h < 1, w >= W or h >= H (the
+ *   reference raises there: the one defined departure), when the mode's IoU condition fails (matrix_iou, min and max
+ *   over the boxes), when no box centre lies strictly inside, or when cls >= 0 and no inside box is labelled cls + 1.
+ *   The lowest passing lane wins; none: next round; after 256 rounds no crop.  Same distribution as the reference's
+ *   sequential trials up to the cap's mass of at most (6/7)^256.
+ * DISTORT  a parameter is used only when its coin is set.  EXPAND (on the crop, cw x ch)  taken unless u > p; rounds
+ *   r = 0..63 of 64 trials: ratio = sqrt(U(max(.5, 1/scale/scale), min(2, scale^2))), ws = scale*ratio,
+ *   hs = scale/ratio, rejected when ws < 1 or hs < 1, canvas int(ws*cw) x int(hs*ch); after 64 rounds no expand.
+ * TARGETS  boxes whose centre is inside the crop, clipped to it and shifted; shifted by the canvas placement;
+ *   mirrored (x1' = width - x2, x2' = width - x1); divided by the canvas size; rows with min(w, h) > 0.01 are kept.
+ *   Nothing kept, or cls >= 0 and none of the kept rows labelled cls + 1: the identity plan, interp from the fallback
+ *   word, and the original boxes divided by (W, H), unfiltered.  Rows are float32 [x1,y1,x2,y2,label,weight].
+ *
+ * SAFETY RULE (this entry cannot inspect device tables): box_begin / box_end are clamped to [0, total_boxes]; boxes
+ * past max_gt of a sample are ignored; a sample whose image is outside [0, num_images) or below the largest in-range
+ * image index of the samples before it, or whose H or W is below 1, gets the identity plan (of max(H,1) x max(W,1),
+ * interp 0) and no rows, and sets status bit 1; rows past truths_cap are dropped (gt_off_out is capped with them) and
+ * set status bit 2.  status = {bits, refused samples, dropped rows, rows before the cap}.  Nothing is written outside
+ * the given sizes; every crop lies inside its image by construction.
+ * Two launches, no allocation, no host synchronisation, capturable.  An image's rows are those of its samples in
+ * sample order, in input order within a sample (what data_augment.mixup_targets gives). */
+typedef struct {
+    long long src_off;            /* byte offset of the sample's image in the Augmenter's source buffer; copied into the plan */
+    unsigned long long sample_id;
+    int H, W;
+    int box_begin, box_end;       /* rows of `boxes` that belong to this sample */
+    int image;                    /* the batch image its rows are appended to (non-decreasing over samples) */
+    int cls;                      /* -1 or the few-shot class constraint of preproc.__call__ */
+    float weight;                 /* column 6 of its rows (the mixup lambda, or 1) */
+    int flags;                    /* 1: rows labelled -1 get weight 0 (voc0712.py:271-273)
+                                     2: labels of the kept rows after the first become -1 (voc0712.py:237-238) */
+} ct_aug_sample;                  /* 48 bytes */
+
+size_t ct_aug_plan_workspace_bytes(int num_samples, int max_gt);
+int ct_aug_plan(const ct_aug_sample* samples,   /* device array [num_samples] */
+                int num_samples,
+                const float* boxes,             /* device, [total_boxes,5] pixel x1,y1,x2,y2,label (finite) */
+                int total_boxes,
+                int num_images,
+                int max_gt,                     /* boxes per sample the kernel looks at */
+                unsigned long long seed,
+                float p_expand,
+                const int* interp_of_draw5,     /* host array */
+                const float* fill3,             /* host array */
+                void* plans_out,                /* device, num_samples x 96 bytes: the AugPlan layout of csrc/ct_preproc.hip / ctdet/ops.py */
+                float* truths_out,              /* device, [truths_cap,6] */
+                int truths_cap,
+                int* gt_off_out,                /* device, [num_images+1] */
+                int* status,                    /* device, [4] */
+                void* workspace,
+                size_t workspace_bytes,
+                ct_stream_t stream);
+
 /* torch.nn.MaxPool2d of models/RFB_Net_vgg.py:328-330,338 (2x2 s2 [ceil], 3x3 s1 p1) on an NCHW
  * buffer: planes = batch*channels; windows are clipped to the input (ceil_mode semantics are
  * encoded in oh/ow by the caller). */
