@@ -7,6 +7,7 @@
 #include "ct_f16x2.h"
 #include "ct_wgrad_launch.h"
 #include <algorithm>
+#include <cstdint>
 
 namespace {
 
@@ -18,7 +19,8 @@ using ctdet::make_rsrc;
 // ------------------------------------------------------------------------------------------
 // weight gradient:  dW[co][ci][kh][kw] = sum_{n,oh,ow} dZ[n][co][oh][ow] * X[n][ci][ih][iw]
 // GEMM  M = cout, N = cin*kh*kw, K = batch*oh*ow (pixels), fp32 MFMA 32x32x2, 128x128 (or 64x64) tile,
-// split over pixel ranges across workgroups (fp32 atomicAdd into a zeroed dW).
+// split over pixel ranges across workgroups (fp32 atomicAdd into a zeroed dW; with WgradArgs::slab every split stores its
+// tile into its own [Cout][Ncols] slab instead, and ctdet::wgrad_slab_sum adds the slabs in order: ct_conv2d_wgrad_det).
 // Lanes run along pixels (coalesced rows of dZ and of the shifted X), tiles are staged to LDS
 // transposed ([pixel][row], stride 65) so the MFMA fragments read conflict-free.
 // ------------------------------------------------------------------------------------------
@@ -26,6 +28,7 @@ struct WgradArgs {
     const float* x;
     const float* dz;
     float* dw;
+    float* slab;             // null: atomics into dw.  Else slab blockIdx.y of [splits][Cout][Ncols], every element stored
     unsigned x_bytes, dz_bytes;
     int Cin, H, W, x_ctot, x_coff;
     int Cout, OW, OHW, dz_ctot, dz_coff;
@@ -230,7 +233,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(const WgradArgs a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm0 + 32 * i + ctdet::acc_row(r, hsel);
-                if (m < a.Cout) unsafeAtomicAdd(a.dw + (size_t)m * a.Ncols + col, acc[i][j][r] + acc2[i][j][r]);
+                if (m >= a.Cout) continue;
+                const float v = acc[i][j][r] + acc2[i][j][r];
+                if (a.slab) a.slab[((size_t)blockIdx.y * a.Cout + m) * a.Ncols + col] = v;
+                else unsafeAtomicAdd(a.dw + (size_t)m * a.Ncols + col, v);
             }
     }
 }
@@ -282,10 +288,11 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
 }
 
 // sliced variants (grid = channels x slices): block sums in double meet in `scratch` ([2][C] doubles, zeroed by the
-// host entry) through f64 atomics; a one-block-per-channel reduction leaves most of the chip idle on the RFB maps
+// host entry) through f64 atomics; a one-block-per-channel reduction leaves most of the chip idle on the RFB maps.
+// det: slice y STORES its two sums at scratch[y][2][C] instead (nothing zeroed), and the final kernel adds the slices in order.
 __global__ __launch_bounds__(256) void bn_stats_part_kernel(const float* __restrict__ z, int batch, int ctot,
                                                             int coff, int C, int HW, int per_slice,
-                                                            double* __restrict__ scratch)
+                                                            double* __restrict__ scratch, int det)
 {
     __shared__ double red[4];
     const int c = blockIdx.x;
@@ -300,19 +307,38 @@ __global__ __launch_bounds__(256) void bn_stats_part_kernel(const float* __restr
     s = block_sum(s, red);
     ss = block_sum(ss, red);
     if (threadIdx.x == 0) {
-        unsafeAtomicAdd(&scratch[c], s);
-        unsafeAtomicAdd(&scratch[C + c], ss);
+        if (det) {
+            scratch[(size_t)blockIdx.y * 2 * C + c] = s;
+            scratch[(size_t)blockIdx.y * 2 * C + C + c] = ss;
+        } else {
+            unsafeAtomicAdd(&scratch[c], s);
+            unsafeAtomicAdd(&scratch[C + c], ss);
+        }
     }
 }
 
-__global__ void bn_stats_final_kernel(const double* __restrict__ scratch, int C, double cnt,
+// the two sums of channel c over `slices` records [2][C] (one for the atomic path), in slice order
+__device__ __forceinline__ void slice_sums(const double* __restrict__ scratch, int C, int slices, int c, double& s0, double& s1)
+{
+    s0 = scratch[c];
+    s1 = scratch[C + c];
+#pragma unroll 4
+    for (int y = 1; y < slices; ++y) {
+        s0 += scratch[(size_t)y * 2 * C + c];
+        s1 += scratch[(size_t)y * 2 * C + C + c];
+    }
+}
+
+__global__ void bn_stats_final_kernel(const double* __restrict__ scratch, int slices, int C, double cnt,
                                       float* __restrict__ mean, float* __restrict__ var, float momentum,
                                       float unbias, float* __restrict__ rmean, float* __restrict__ rvar)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const double m = scratch[c] / cnt;
-    const float mf = (float)m, vf = (float)fmax(scratch[C + c] / cnt - m * m, 0.0);
+    double s, ss;
+    slice_sums(scratch, C, slices, c, s, ss);
+    const double m = s / cnt;
+    const float mf = (float)m, vf = (float)fmax(ss / cnt - m * m, 0.0);
     mean[c] = mf;
     var[c] = vf;
     if (rmean) {        // running statistics of nn.BatchNorm2d (momentum, unbiased variance), same launch
@@ -401,7 +427,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdArgs a)
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_reduce_part_kernel(const BnBwdArgs a, int per_slice,
-                                                                 double* __restrict__ scratch)
+                                                                 double* __restrict__ scratch, int det)
 {
     __shared__ double red[4];
     const int c = blockIdx.x;
@@ -417,18 +443,25 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_part_kernel(const BnBwdArgs
     sb = block_sum(sb, red);
     sg = block_sum(sg, red);
     if (threadIdx.x == 0) {
-        unsafeAtomicAdd(&scratch[c], sb);
-        unsafeAtomicAdd(&scratch[a.C + c], sg);
+        if (det) {
+            scratch[(size_t)blockIdx.y * 2 * a.C + c] = sb;
+            scratch[(size_t)blockIdx.y * 2 * a.C + a.C + c] = sg;
+        } else {
+            unsafeAtomicAdd(&scratch[c], sb);
+            unsafeAtomicAdd(&scratch[a.C + c], sg);
+        }
     }
 }
 
-__global__ void bn_bwd_reduce_final_kernel(const double* __restrict__ scratch, int C, float* __restrict__ dbeta,
+__global__ void bn_bwd_reduce_final_kernel(const double* __restrict__ scratch, int slices, int C, float* __restrict__ dbeta,
                                            float* __restrict__ dgamma)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    dbeta[c] = (float)scratch[c];
-    dgamma[c] = (float)scratch[C + c];
+    double sb, sg;
+    slice_sums(scratch, C, slices, c, sb, sg);
+    dbeta[c] = (float)sb;
+    dgamma[c] = (float)sg;
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a)
@@ -456,14 +489,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a)
 
 // y = act(conv + bias):  dz = dy * (y > 0 if relu),  dbias = sum dz   (VGG convs, heads)
 // grid (channel, slice): a slice is a contiguous range of the channel's batch*HW elements, so a 64-channel
-// 300x300 layer still fills the chip; per-slice sums meet in dbias through one float atomic per block.
+// 300x300 layer still fills the chip; per-slice sums meet in dbias through one float atomic per block -- or, with `slab`, are
+// stored as doubles at slab[slice][C] for dbias_slab_sum_kernel to add in order.
 __global__ __launch_bounds__(256) void bias_act_bwd_kernel(const float* __restrict__ dy, int dy_ctot,
                                                            int dy_coff, const float* __restrict__ y,
                                                            int y_ctot, int y_coff, int relu, int batch,
                                                            int C, int HW, float* __restrict__ dz,
                                                            int dz_ctot, int dz_coff,
                                                            float* __restrict__ dbias, int per_slice,
-                                                           unsigned* __restrict__ amax)
+                                                           unsigned* __restrict__ amax, double* __restrict__ slab)
 {
     __shared__ double red[4];
     const int c = blockIdx.x;
@@ -510,7 +544,22 @@ __global__ __launch_bounds__(256) void bias_act_bwd_kernel(const float* __restri
         ++n;
     }
     sb = block_sum(sb, red);
-    if (threadIdx.x == 0 && dbias) unsafeAtomicAdd(&dbias[c], (float)sb);
+    if (threadIdx.x == 0 && dbias) {
+        if (slab) slab[(size_t)blockIdx.y * C + c] = sb;
+        else unsafeAtomicAdd(&dbias[c], (float)sb);
+    }
+}
+
+// dbias[c] = the `nslabs` partial sums slab[.][C] of channel c added in slab order (bias + activation backward: one per
+// slice; fused pool backward: one per image)
+__global__ void dbias_slab_sum_kernel(const double* __restrict__ slab, int nslabs, int C, float* __restrict__ dbias)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double s = slab[c];
+#pragma unroll 8
+    for (int y = 1; y < nslabs; ++y) s += slab[(size_t)y * C + c];       // loads issued in groups, additions in slab order
+    dbias[c] = (float)s;
 }
 
 // max-pool backward (gather form): every input element collects dy of the windows whose FIRST
@@ -641,7 +690,7 @@ __global__ __launch_bounds__(256) void maxpool2x2_bias_relu_bwd_kernel(const flo
                                                                        const float* __restrict__ dy, int C, int H, int W,
                                                                        int OH, int OW, float* __restrict__ dz, int dz_ctot,
                                                                        int dz_coff, float* __restrict__ dbias,
-                                                                       unsigned* __restrict__ amax)
+                                                                       unsigned* __restrict__ amax, double* __restrict__ slab)
 {
     __shared__ double red[4];
     const int n = blockIdx.x / C, c = blockIdx.x - n * C;
@@ -677,7 +726,10 @@ __global__ __launch_bounds__(256) void maxpool2x2_bias_relu_bwd_kernel(const flo
     }
     if (amax) ctdet::h2::flush_absmax(amax, n, run);
     sb = block_sum(sb, red);
-    if (threadIdx.x == 0 && dbias) unsafeAtomicAdd(&dbias[c], (float)sb);
+    if (threadIdx.x == 0 && dbias) {
+        if (slab) slab[(size_t)n * C + c] = sb;         // one partial sum per image, added in image order
+        else unsafeAtomicAdd(&dbias[c], (float)sb);
+    }
 }
 
 // gradient of the channels-last head scatter: dz[n][co][pix] = dflat[n*img_stride + base + pix*ps + (co-co0)]
@@ -715,31 +767,31 @@ inline int grid_for(long total) { return (int)std::min<long>((total + 255) / 256
 
 }  // namespace
 
-// the images [b0, b0 + nb) of the batch; the first chunk zeroes dw
-static int wgrad_chunk(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, const ctdet::WgradLimits& lim,
-                       int b0, int nb, ct_stream_t stream)
+static bool wgrad_filter_built(const ct_conv_desc* d)
 {
-    WgradArgs a{};
-    ctdet::wgrad_fill(a, d, dz, dz_ctot, dz_coff, lim, b0, nb);
-    a.dw = dw;
-    a.H = d->h; a.W = d->w;
-    a.OW = d->ow; a.OHW = d->oh * d->ow;
-    a.stride = d->stride; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.dil = d->dil;
-    a.Npix = nb * a.OHW;
-    a.Ncols = d->cin * d->kh * d->kw;
+    return (d->kh == 3 && d->kw == 3) || (d->kh == 1 && d->kw == 1) || (d->kh == 1 && d->kw == 3) || (d->kh == 3 && d->kw == 1) ||
+           (d->kh == 4 && d->kw == 4);
+}
+
+// Tile edge and pixel splits of a launch over nb images: a pure function of the descriptor and the environment (host only).
+struct WgradPlan { int tb, tiles_m, tiles_n, splits, pix_per_split; };
+static WgradPlan wgrad_plan(const ct_conv_desc* d, int nb)
+{
+    WgradPlan p{};
+    const int Npix = nb * d->oh * d->ow, Ncols = d->cin * d->kh * d->kw;
     // the 128x128 variant (TB = 2) measured slower on the RFBNet shapes (fewer pixel splits in flight, the
     // 64 gathers per thread arrive in one burst); kept for experiments behind CTDET_WGRAD_TB=2
     static const int tb_env = getenv("CTDET_WGRAD_TB") ? atoi(getenv("CTDET_WGRAD_TB")) : 1;
-    const int tb = (tb_env == 2 && d->cout >= 96 && a.Ncols >= 96) ? 2 : 1;
-    const int bt = 64 * tb;
-    a.tiles_m = (d->cout + bt - 1) / bt;
-    a.tiles_n = (a.Ncols + bt - 1) / bt;
-    const int tiles = a.tiles_m * a.tiles_n;
+    p.tb = (tb_env == 2 && d->cout >= 96 && Ncols >= 96) ? 2 : 1;
+    const int bt = 64 * p.tb;
+    p.tiles_m = (d->cout + bt - 1) / bt;
+    p.tiles_n = (Ncols + bt - 1) / bt;
+    const int tiles = p.tiles_m * p.tiles_n;
     // Pixel splits: the chip holds `slots` workgroups at a time (2 per CU with the double-buffered LDS); take the
     // smallest split count whose last round is at least 92 % full -- one workgroup too many costs a whole round,
     // and every extra split pays the atomic epilogue again.
     static const int slots = getenv("CTDET_WGRAD_WGS") ? atoi(getenv("CTDET_WGRAD_WGS")) : 512;
-    const int smax = std::max(1, std::min((a.Npix + 255) / 256, (4 * slots) / tiles));
+    const int smax = std::max(1, std::min((Npix + 255) / 256, (4 * slots) / tiles));
     int splits = 1;
     double best = 0.0;
     for (int sp = 1; sp <= smax; ++sp) {
@@ -748,11 +800,34 @@ static int wgrad_chunk(const ct_conv_desc* d, const float* dz, int dz_ctot, int 
         if (eff > best + 1e-9) { best = eff; splits = sp; }
         if (eff >= 0.92) break;
     }
-    const ctdet::Split sp = ctdet::even_split((a.Npix + 63) / 64, splits);       // in blocks of 64 pixels
-    a.pix_per_split = sp.per_split * 64;
-    splits = sp.splits;
+    const ctdet::Split sp = ctdet::even_split((Npix + 63) / 64, splits);       // in blocks of 64 pixels: no split is empty
+    p.pix_per_split = sp.per_split * 64;
+    p.splits = sp.splits;
+    return p;
+}
+
+// the images [b0, b0 + nb) of the batch; the first chunk zeroes dw.  slab != null (ct_conv2d_wgrad_det): the chunk's splits
+// store into slab[0 .. splits) instead and dw is left to the caller's slab sum.
+static int wgrad_chunk(const char* who, const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
+                       const ctdet::WgradLimits& lim, int b0, int nb, const WgradPlan& plan, float* slab, ct_stream_t stream)
+{
+    WgradArgs a{};
+    ctdet::wgrad_fill(a, d, dz, dz_ctot, dz_coff, lim, b0, nb);
+    a.dw = dw;
+    a.slab = slab;
+    a.H = d->h; a.W = d->w;
+    a.OW = d->ow; a.OHW = d->oh * d->ow;
+    a.stride = d->stride; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.dil = d->dil;
+    a.Npix = nb * a.OHW;
+    a.Ncols = d->cin * d->kh * d->kw;
+    const int tb = plan.tb, bt = 64 * tb;
+    a.tiles_m = plan.tiles_m;
+    a.tiles_n = plan.tiles_n;
+    const int tiles = a.tiles_m * a.tiles_n;
+    a.pix_per_split = plan.pix_per_split;
+    const int splits = plan.splits;
     hipStream_t st = ctdet::as_stream(stream);
-    if (b0 == 0 && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dw, 0, (size_t)d->cout * a.Ncols * 4, st));
+    if (!slab && b0 == 0 && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dw, 0, (size_t)d->cout * a.Ncols * 4, st));
     const bool tapmajor = d->cin % bt == 0 && !(getenv("CTDET_WGRAD_GENERIC"));
     const bool tapmajor_for_smem = tapmajor;
     const dim3 grid(tiles, splits), block(256);
@@ -775,38 +850,109 @@ static int wgrad_chunk(const ct_conv_desc* d, const float* dz, int dz_ctot, int 
     else if (d->kh == 1 && d->kw == 3) CT_WGRAD_GO(1, 3);
     else if (d->kh == 3 && d->kw == 1) CT_WGRAD_GO(3, 1);
     else if (d->kh == 4 && d->kw == 4) CT_WGRAD_GO(4, 4);
-    else return ctdet::fail(CT_ERR_UNSUPPORTED, "ct_conv2d_wgrad: %dx%d filters not built", d->kh, d->kw);
+    else return ctdet::fail(CT_ERR_UNSUPPORTED, "%s: %dx%d filters not built", who, d->kh, d->kw);
 #undef CT_WGRAD_GO
     CT_HIP(le);
     CT_LAUNCH_CHECK("conv_wgrad_f32");
     return CT_OK;
 }
 
-extern "C" int ct_conv2d_wgrad(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff,
-                               float* dw, ct_stream_t stream)
+static bool wgrad_geometry_ok(const ct_conv_desc* d)
 {
-    const char* who = "ct_conv2d_wgrad";
-    if (int rc = ctdet::wgrad_check_pointers(d, dz, dw, ctdet::no_workspace(), who)) return rc;
-    if (int rc = ctdet::wgrad_check_slices(d, dz_ctot, dz_coff, who)) return rc;
+    if (d->stride < 1 || d->dil < 1 || d->kh < 1 || d->kw < 1) return false;
     const int eoh = (d->h + 2 * d->pad_h - d->dil * (d->kh - 1) - 1) / d->stride + 1;
     const int eow = (d->w + 2 * d->pad_w - d->dil * (d->kw - 1) - 1) / d->stride + 1;
-    CT_REQUIRE(eoh == d->oh && eow == d->ow, "%s: oh/ow mismatch", who);
-    // buffers above 2 GiB (32-bit buffer offsets): batch chunks accumulate into the same dw
+    return eoh == d->oh && eow == d->ow;
+}
+
+// slabs of all batch chunks of a launch, in chunk order (the count ct_conv2d_wgrad_det writes and sums)
+static int wgrad_total_splits(const ct_conv_desc* d, const ctdet::WgradLimits& lim)
+{
+    int total = 0;
+    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) total += wgrad_plan(d, std::min(lim.max_chunk, d->batch - b0)).splits;
+    return total;
+}
+
+// ws == null: ct_conv2d_wgrad (atomics); else ct_conv2d_wgrad_det with ws_bytes of slabs
+static int wgrad_impl(const char* who, const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, bool det, void* ws,
+                      size_t ws_bytes, ct_stream_t stream)
+{
+    if (int rc = ctdet::wgrad_check_pointers(d, dz, dw, det ? ws : ctdet::no_workspace(), who)) return rc;
+    if (int rc = ctdet::wgrad_check_slices(d, dz_ctot, dz_coff, who)) return rc;
+    CT_REQUIRE(wgrad_geometry_ok(d), "%s: oh/ow mismatch", who);
+    // buffers above 2 GiB (32-bit buffer offsets): batch chunks accumulate into the same dw (det: append their slabs)
     ctdet::WgradLimits lim;
     if (int rc = ctdet::wgrad_limits(d, dz_ctot, who, &lim, kMaxBufBytes - 1)) return rc;
-    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk)
-        if (int rc = wgrad_chunk(d, dz, dz_ctot, dz_coff, dw, lim, b0, std::min(lim.max_chunk, d->batch - b0), stream)) return rc;
+    const size_t n = (size_t)d->cout * d->cin * d->kh * d->kw;
+    int total = 0;
+    if (det) {
+        if (!wgrad_filter_built(d)) return ctdet::fail(CT_ERR_UNSUPPORTED, "%s: %dx%d filters not built", who, d->kh, d->kw);
+        if (int rc = ctdet::wgrad_check_det_workspace(ws, ws_bytes, (size_t)wgrad_total_splits(d, lim) * n * sizeof(float), who)) return rc;
+    }
+    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) {
+        const int nb = std::min(lim.max_chunk, d->batch - b0);
+        float* slab = det ? static_cast<float*>(ws) + (size_t)total * n : nullptr;
+        const WgradPlan plan = wgrad_plan(d, nb);
+        if (int rc = wgrad_chunk(who, d, dz, dz_ctot, dz_coff, dw, lim, b0, nb, plan, slab, stream)) return rc;
+        total += plan.splits;
+    }
+    if (det) {
+        if (int rc = ctdet::wgrad_slab_sum(static_cast<const float*>(ws), total, n, dw, ctdet::as_stream(stream))) return rc;
+    }
     return CT_OK;
 }
 
-extern "C" int ct_bn_train_stats(const float* z, int batch, int ctot, int coff, int channels, int hw,
-                                 float* mean, float* var, float momentum, float* running_mean,
-                                 float* running_var, void* scratch, ct_stream_t stream)
+extern "C" int ct_conv2d_wgrad(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff,
+                               float* dw, ct_stream_t stream)
 {
-    CT_REQUIRE(z && mean && var && batch > 0 && channels > 0 && hw > 0, "ct_bn_train_stats: bad arguments");
+    return wgrad_impl("ct_conv2d_wgrad", d, dz, dz_ctot, dz_coff, dw, false, nullptr, 0, stream);
+}
+
+extern "C" size_t ct_conv_wgrad_det_workspace_bytes(const ct_conv_desc* d, int* partials)
+{
+    if (partials) *partials = 0;
+    if (!d || d->batch <= 0 || d->cin <= 0 || d->cout <= 0 || d->oh <= 0 || d->ow <= 0 || !wgrad_geometry_ok(d) ||
+        !wgrad_filter_built(d))
+        return 0;
+    const ctdet::WgradLimits lim = ctdet::wgrad_sizes(d, d->cout, kMaxBufBytes - 1);      // dZ taken as dense
+    if (lim.img_x_bytes >= kMaxBufBytes || lim.img_z_bytes >= kMaxBufBytes) return 0;
+    const int total = wgrad_total_splits(d, lim);
+    if (partials) *partials = total;
+    return (size_t)total * d->cout * d->cin * d->kh * d->kw * sizeof(float);
+}
+
+extern "C" int ct_conv2d_wgrad_det(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, void* workspace,
+                                   size_t workspace_bytes, ct_stream_t stream)
+{
+    return wgrad_impl("ct_conv2d_wgrad_det", d, dz, dz_ctot, dz_coff, dw, true, workspace, workspace_bytes, stream);
+}
+
+// slices of a channel's batch*hw elements in the BatchNorm reductions (both passes)
+static int bn_slices(int batch, int channels, int hw)
+{
+    const long per_channel = (long)batch * hw;
+    return (int)std::max<long>(1, std::min<long>((1024 + channels - 1) / channels, per_channel / 2048));
+}
+
+// the scratch of a _det reduction: `slices` records of `per_slice_bytes`, 8-byte aligned
+static int det_scratch_check(const char* who, const void* scratch, size_t have, size_t need)
+{
+    CT_REQUIRE(scratch, "%s: scratch is null", who);
+    CT_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "%s: scratch must be 8-byte aligned", who);
+    if (have < need) return ctdet::fail(CT_ERR_WORKSPACE, "%s: scratch_bytes %zu, needs %zu", who, have, need);
+    return CT_OK;
+}
+
+static int bn_stats_impl(const char* who, const float* z, int batch, int ctot, int coff, int channels, int hw,
+                         float* mean, float* var, float momentum, float* running_mean,
+                         float* running_var, void* scratch, bool det, size_t scratch_bytes, ct_stream_t stream)
+{
+    CT_REQUIRE(z && mean && var && batch > 0 && channels > 0 && hw > 0, "%s: bad arguments", who);
     hipStream_t st = ctdet::as_stream(stream);
     const long per_channel = (long)batch * hw;
-    const int slices = (int)std::max<long>(1, std::min<long>((1024 + channels - 1) / channels, per_channel / 2048));
+    const int slices = bn_slices(batch, channels, hw);
+    if (det && slices > 1)
+        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)slices * 2 * channels * sizeof(double))) return rc;
     const bool run = running_mean && running_var;
     float* const rm = run ? running_mean : nullptr;
     float* const rv = run ? running_var : nullptr;
@@ -814,12 +960,12 @@ extern "C" int ct_bn_train_stats(const float* z, int batch, int ctot, int coff, 
     const float unbias = cntf > 1.f ? cntf / (cntf - 1.f) : 1.f;
     if (scratch && slices > 1) {
         const int per_slice = (int)((per_channel + slices - 1) / slices);
-        if (!ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(scratch, 0, (size_t)2 * channels * sizeof(double), st));
+        if (!det && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(scratch, 0, (size_t)2 * channels * sizeof(double), st));
         hipLaunchKernelGGL(bn_stats_part_kernel, dim3(channels, slices), dim3(256), 0, st, z, batch, ctot, coff,
-                           channels, hw, per_slice, (double*)scratch);
+                           channels, hw, per_slice, (double*)scratch, (int)det);
         CT_LAUNCH_CHECK("bn_stats_part_kernel");
         hipLaunchKernelGGL(bn_stats_final_kernel, dim3((channels + 255) / 256), dim3(256), 0, st,
-                           (const double*)scratch, channels, (double)per_channel, mean, var, momentum, unbias, rm, rv);
+                           (const double*)scratch, det ? slices : 1, channels, (double)per_channel, mean, var, momentum, unbias, rm, rv);
         CT_LAUNCH_CHECK("bn_stats_final_kernel");
     } else {
         hipLaunchKernelGGL(bn_stats_kernel, dim3(channels), dim3(256), 0, st, z, batch, ctot, coff, hw, mean, var,
@@ -827,6 +973,34 @@ extern "C" int ct_bn_train_stats(const float* z, int batch, int ctot, int coff, 
         CT_LAUNCH_CHECK("bn_stats_kernel");
     }
     return CT_OK;
+}
+
+extern "C" int ct_bn_train_stats(const float* z, int batch, int ctot, int coff, int channels, int hw,
+                                 float* mean, float* var, float momentum, float* running_mean,
+                                 float* running_var, void* scratch, ct_stream_t stream)
+{
+    return bn_stats_impl("ct_bn_train_stats", z, batch, ctot, coff, channels, hw, mean, var, momentum, running_mean, running_var,
+                         scratch, false, 0, stream);
+}
+
+extern "C" size_t ct_bn_det_scratch_bytes(int batch, int channels, int hw, int* partials)
+{
+    if (partials) *partials = 0;
+    if (batch <= 0 || channels <= 0 || hw <= 0) return 0;
+    if (partials) *partials = bn_slices(batch, channels, hw);
+    // slices * channels records of two doubles, bounded from above by an expression that grows with batch and with channels
+    // (slices * channels itself does not: 2 x 513 > 1 x 1024)
+    const long per_channel = (long)batch * hw;
+    const long records = std::max<long>(channels, std::min<long>(1023L + channels, (long)channels * std::max<long>(1, per_channel / 2048)));
+    return (size_t)records * 2 * sizeof(double);
+}
+
+extern "C" int ct_bn_train_stats_det(const float* z, int batch, int ctot, int coff, int channels, int hw,
+                                     float* mean, float* var, float momentum, float* running_mean,
+                                     float* running_var, void* scratch, size_t scratch_bytes, ct_stream_t stream)
+{
+    return bn_stats_impl("ct_bn_train_stats_det", z, batch, ctot, coff, channels, hw, mean, var, momentum, running_mean, running_var,
+                         scratch, true, scratch_bytes, stream);
 }
 
 extern "C" int ct_bn_train_apply(const float* z, const float* mean, const float* var, const float* gamma,
@@ -848,7 +1022,7 @@ extern "C" int ct_bn_train_apply(const float* z, const float* mean, const float*
     return CT_OK;
 }
 
-static int bn_backward_impl(int frozen, const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
+static int bn_backward_impl(const char* who, bool det, size_t scratch_bytes, int frozen, const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
                             int y_coff, const float* z, const float* mean, const float* var,
                             const float* gamma, float eps, int relu, const float* lo,
                             float res_scale, float* dres, int dres_ctot, int dres_coff,
@@ -856,9 +1030,9 @@ static int bn_backward_impl(int frozen, const float* dy, int dy_ctot, int dy_cof
                             int z_ctot, int z_coff, int batch, int channels, int hw,
                             void* scratch, ct_stream_t stream)
 {
-    CT_REQUIRE(dy && z && mean && var && gamma && dz && dgamma && dbeta, "ct_bn_train_backward: null pointer");
-    CT_REQUIRE(!(relu || lo) || y, "ct_bn_train_backward: ReLU mask needs the forward output");
-    CT_REQUIRE((long)batch * channels * hw <= kMaxLoopElems, "ct_bn_train_backward: too many elements (2^32 less one grid stride at most)");
+    CT_REQUIRE(dy && z && mean && var && gamma && dz && dgamma && dbeta, "%s: null pointer", who);
+    CT_REQUIRE(!(relu || lo) || y, "%s: ReLU mask needs the forward output", who);
+    CT_REQUIRE((long)batch * channels * hw <= kMaxLoopElems, "%s: too many elements (2^32 less one grid stride at most)", who);
     BnBwdArgs a{};
     a.dy = dy; a.y = y; a.z = z; a.mean = mean; a.var = var; a.gamma = gamma; a.lo = lo;
     a.dz = dz; a.dgamma = dgamma; a.dbeta = dbeta; a.dres = dres;
@@ -869,15 +1043,17 @@ static int bn_backward_impl(int frozen, const float* dy, int dy_ctot, int dy_cof
     a.frozen = frozen;
     hipStream_t st = ctdet::as_stream(stream);
     const long per_channel = (long)batch * hw;
-    const int slices = (int)std::max<long>(1, std::min<long>((1024 + channels - 1) / channels, per_channel / 2048));
+    const int slices = bn_slices(batch, channels, hw);
+    if (det && slices > 1)
+        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)slices * 2 * channels * sizeof(double))) return rc;
     if (scratch && slices > 1) {
         const int per_slice = (int)((per_channel + slices - 1) / slices);
-        if (!ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(scratch, 0, (size_t)2 * channels * sizeof(double), st));
+        if (!det && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(scratch, 0, (size_t)2 * channels * sizeof(double), st));
         hipLaunchKernelGGL(bn_bwd_reduce_part_kernel, dim3(channels, slices), dim3(256), 0, st, a, per_slice,
-                           (double*)scratch);
+                           (double*)scratch, (int)det);
         CT_LAUNCH_CHECK("bn_bwd_reduce_part_kernel");
         hipLaunchKernelGGL(bn_bwd_reduce_final_kernel, dim3((channels + 255) / 256), dim3(256), 0, st,
-                           (const double*)scratch, channels, dbeta, dgamma);
+                           (const double*)scratch, det ? slices : 1, channels, dbeta, dgamma);
         CT_LAUNCH_CHECK("bn_bwd_reduce_final_kernel");
     } else {
         hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(channels), dim3(256), 0, st, a);
@@ -896,7 +1072,7 @@ extern "C" int ct_bn_train_backward(const float* dy, int dy_ctot, int dy_coff, c
                                     int z_ctot, int z_coff, int batch, int channels, int hw,
                                     void* scratch, ct_stream_t stream)
 {
-    return bn_backward_impl(0, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, mean, var, gamma, eps, relu, lo, res_scale,
+    return bn_backward_impl("ct_bn_train_backward", false, 0, 0, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, mean, var, gamma, eps, relu, lo, res_scale,
                             dres, dres_ctot, dres_coff, dres_accumulate, dz, dgamma, dbeta, z_ctot, z_coff, batch,
                             channels, hw, scratch, stream);
 }
@@ -909,29 +1085,104 @@ extern "C" int ct_bn_eval_backward(const float* dy, int dy_ctot, int dy_coff, co
                                    int z_ctot, int z_coff, int batch, int channels, int hw,
                                    void* scratch, ct_stream_t stream)
 {
-    return bn_backward_impl(1, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, running_mean, running_var, gamma, eps, relu,
+    return bn_backward_impl("ct_bn_train_backward", false, 0, 1, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, running_mean, running_var, gamma, eps, relu,
                             lo, res_scale, dres, dres_ctot, dres_coff, dres_accumulate, dz, dgamma, dbeta, z_ctot,
                             z_coff, batch, channels, hw, scratch, stream);
 }
 
-extern "C" int ct_bias_act_backward_amax(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
-                                         int y_coff, int relu, int batch, int channels, int hw, float* dz,
-                                         int dz_ctot, int dz_coff, float* dbias, unsigned* dz_absmax, ct_stream_t stream)
+extern "C" int ct_bn_train_backward_det(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
+                                        int y_coff, const float* z, const float* mean, const float* var,
+                                        const float* gamma, float eps, int relu, const float* lo,
+                                        float res_scale, float* dres, int dres_ctot, int dres_coff,
+                                        int dres_accumulate, float* dz, float* dgamma, float* dbeta,
+                                        int z_ctot, int z_coff, int batch, int channels, int hw,
+                                        void* scratch, size_t scratch_bytes, ct_stream_t stream)
 {
-    CT_REQUIRE(dy && dz && (!relu || y), "ct_bias_act_backward: null pointer");
-    CT_REQUIRE(batch > 0 && channels > 0 && hw > 0, "ct_bias_act_backward: bad shape");
-    hipStream_t st = ctdet::as_stream(stream);
+    return bn_backward_impl("ct_bn_train_backward_det", true, scratch_bytes, 0, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, mean, var, gamma,
+                            eps, relu, lo, res_scale, dres, dres_ctot, dres_coff, dres_accumulate, dz, dgamma, dbeta, z_ctot, z_coff,
+                            batch, channels, hw, scratch, stream);
+}
+
+extern "C" int ct_bn_eval_backward_det(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
+                                       int y_coff, const float* z, const float* running_mean, const float* running_var,
+                                       const float* gamma, float eps, int relu, const float* lo,
+                                       float res_scale, float* dres, int dres_ctot, int dres_coff,
+                                       int dres_accumulate, float* dz, float* dgamma, float* dbeta,
+                                       int z_ctot, int z_coff, int batch, int channels, int hw,
+                                       void* scratch, size_t scratch_bytes, ct_stream_t stream)
+{
+    return bn_backward_impl("ct_bn_eval_backward_det", true, scratch_bytes, 1, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, running_mean,
+                            running_var, gamma, eps, relu, lo, res_scale, dres, dres_ctot, dres_coff, dres_accumulate, dz, dgamma,
+                            dbeta, z_ctot, z_coff, batch, channels, hw, scratch, stream);
+}
+
+// slices of a channel's batch*hw elements in the bias + activation backward, and the elements of one
+struct BiasSlices { int slices, per_slice; };
+static BiasSlices bias_slices(int batch, int channels, int hw)
+{
     const long per_channel = (long)batch * hw;
     int slices = (int)std::max<long>(1, std::min<long>((2048 + channels - 1) / channels, (per_channel + 4095) / 4096));
     slices = std::min(slices, 65535);
     int per_slice = (int)((per_channel + slices - 1) / slices);
     per_slice = (per_slice + 3) / 4 * 4;
     slices = (int)((per_channel + per_slice - 1) / per_slice);
-    if (dbias && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dbias, 0, (size_t)channels * 4, st));
-    hipLaunchKernelGGL(bias_act_bwd_kernel, dim3(channels, slices), dim3(256), 0, st, dy, dy_ctot, dy_coff, y,
-                       y_ctot, y_coff, relu, batch, channels, hw, dz, dz_ctot, dz_coff, dbias, per_slice, dz_absmax);
-    CT_LAUNCH_CHECK("bias_act_bwd_kernel");
+    return {slices, per_slice};
+}
+
+static int dbias_slab_sum(const double* slab, int nslabs, int channels, float* dbias, hipStream_t st)
+{
+    hipLaunchKernelGGL(dbias_slab_sum_kernel, dim3((channels + 255) / 256), dim3(256), 0, st, slab, nslabs, channels, dbias);
+    CT_LAUNCH_CHECK("dbias_slab_sum_kernel");
     return CT_OK;
+}
+
+static int bias_act_backward_impl(const char* who, const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
+                                  int y_coff, int relu, int batch, int channels, int hw, float* dz,
+                                  int dz_ctot, int dz_coff, float* dbias, unsigned* dz_absmax, bool det, void* scratch,
+                                  size_t scratch_bytes, ct_stream_t stream)
+{
+    CT_REQUIRE(dy && dz && (!relu || y), "%s: null pointer", who);
+    CT_REQUIRE(batch > 0 && channels > 0 && hw > 0, "%s: bad shape", who);
+    hipStream_t st = ctdet::as_stream(stream);
+    const BiasSlices sl = bias_slices(batch, channels, hw);
+    double* slab = nullptr;
+    if (det && dbias) {
+        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)sl.slices * channels * sizeof(double))) return rc;
+        slab = static_cast<double*>(scratch);
+    }
+    if (dbias && !slab && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dbias, 0, (size_t)channels * 4, st));
+    hipLaunchKernelGGL(bias_act_bwd_kernel, dim3(channels, sl.slices), dim3(256), 0, st, dy, dy_ctot, dy_coff, y,
+                       y_ctot, y_coff, relu, batch, channels, hw, dz, dz_ctot, dz_coff, dbias, sl.per_slice, dz_absmax, slab);
+    CT_LAUNCH_CHECK("bias_act_bwd_kernel");
+    return slab ? dbias_slab_sum(slab, sl.slices, channels, dbias, st) : CT_OK;
+}
+
+extern "C" int ct_bias_act_backward_amax(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
+                                         int y_coff, int relu, int batch, int channels, int hw, float* dz,
+                                         int dz_ctot, int dz_coff, float* dbias, unsigned* dz_absmax, ct_stream_t stream)
+{
+    return bias_act_backward_impl("ct_bias_act_backward", dy, dy_ctot, dy_coff, y, y_ctot, y_coff, relu, batch, channels, hw, dz, dz_ctot,
+                                  dz_coff, dbias, dz_absmax, false, nullptr, 0, stream);
+}
+
+extern "C" size_t ct_bias_det_scratch_bytes(int batch, int channels, int hw, int* partials)
+{
+    if (partials) *partials = 0;
+    if (batch <= 0 || channels <= 0 || hw <= 0) return 0;
+    if (partials) *partials = bias_slices(batch, channels, hw).slices;
+    // slices * channels doubles, bounded from above by an expression that grows with batch and with channels
+    const long per_channel = (long)batch * hw;
+    const long records = std::max<long>(channels, std::min<long>(2047L + channels, (long)channels * ((per_channel + 4095) / 4096)));
+    return (size_t)records * sizeof(double);
+}
+
+extern "C" int ct_bias_act_backward_det(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
+                                        int y_coff, int relu, int batch, int channels, int hw, float* dz,
+                                        int dz_ctot, int dz_coff, float* dbias, unsigned* dz_absmax, void* scratch,
+                                        size_t scratch_bytes, ct_stream_t stream)
+{
+    return bias_act_backward_impl("ct_bias_act_backward_det", dy, dy_ctot, dy_coff, y, y_ctot, y_coff, relu, batch, channels, hw, dz,
+                                  dz_ctot, dz_coff, dbias, dz_absmax, true, scratch, scratch_bytes, stream);
 }
 
 extern "C" int ct_bias_act_backward(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
@@ -966,21 +1217,50 @@ extern "C" int ct_maxpool2d_bwd(const float* x, const float* dy, float* dx, long
     return CT_OK;
 }
 
+static int maxpool2x2_bias_relu_bwd_impl(const char* who, const float* y, int y_ctot, int y_coff, const float* dy, int batch, int channels,
+                                        int h, int w, int oh, int ow, float* dz, int dz_ctot, int dz_coff, float* dbias,
+                                        unsigned* dz_absmax, bool det, void* scratch, size_t scratch_bytes, ct_stream_t stream)
+{
+    CT_REQUIRE(y && dy && dz && batch > 0 && channels > 0 && h > 0 && w > 0, "%s: bad arguments", who);
+    CT_REQUIRE(oh <= (h + 1) / 2 && ow <= (w + 1) / 2 && oh >= h / 2 && ow >= w / 2, "%s: %dx%d is not a 2x2 / stride 2 "
+               "pooling of %dx%d", who, oh, ow, h, w);
+    CT_REQUIRE(y_coff >= 0 && y_coff + channels <= y_ctot && dz_coff >= 0 && dz_coff + channels <= dz_ctot, "%s: channel slice", who);
+    CT_REQUIRE((long)batch * channels <= 0x7FFFFFFFL, "%s: too many planes", who);
+    hipStream_t st = ctdet::as_stream(stream);
+    double* slab = nullptr;
+    if (det && dbias) {
+        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)batch * channels * sizeof(double))) return rc;
+        slab = static_cast<double*>(scratch);
+    }
+    if (dbias && !slab && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dbias, 0, (size_t)channels * 4, st));
+    hipLaunchKernelGGL(maxpool2x2_bias_relu_bwd_kernel, dim3((unsigned)(batch * channels)), dim3(256), 0, st, y, y_ctot, y_coff, dy,
+                       channels, h, w, oh, ow, dz, dz_ctot, dz_coff, dbias, dz_absmax, slab);
+    CT_LAUNCH_CHECK("maxpool2x2_bias_relu_bwd_kernel");
+    return slab ? dbias_slab_sum(slab, batch, channels, dbias, st) : CT_OK;
+}
+
 extern "C" int ct_maxpool2x2_bias_relu_bwd(const float* y, int y_ctot, int y_coff, const float* dy, int batch, int channels, int h,
                                            int w, int oh, int ow, float* dz, int dz_ctot, int dz_coff, float* dbias,
                                            unsigned* dz_absmax, ct_stream_t stream)
 {
-    CT_REQUIRE(y && dy && dz && batch > 0 && channels > 0 && h > 0 && w > 0, "ct_maxpool2x2_bias_relu_bwd: bad arguments");
-    CT_REQUIRE(oh <= (h + 1) / 2 && ow <= (w + 1) / 2 && oh >= h / 2 && ow >= w / 2, "ct_maxpool2x2_bias_relu_bwd: %dx%d is not a 2x2 / stride 2 "
-               "pooling of %dx%d", oh, ow, h, w);
-    CT_REQUIRE(y_coff >= 0 && y_coff + channels <= y_ctot && dz_coff >= 0 && dz_coff + channels <= dz_ctot, "ct_maxpool2x2_bias_relu_bwd: channel slice");
-    CT_REQUIRE((long)batch * channels <= 0x7FFFFFFFL, "ct_maxpool2x2_bias_relu_bwd: too many planes");
-    hipStream_t st = ctdet::as_stream(stream);
-    if (dbias && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dbias, 0, (size_t)channels * 4, st));
-    hipLaunchKernelGGL(maxpool2x2_bias_relu_bwd_kernel, dim3((unsigned)(batch * channels)), dim3(256), 0, st, y, y_ctot, y_coff, dy,
-                       channels, h, w, oh, ow, dz, dz_ctot, dz_coff, dbias, dz_absmax);
-    CT_LAUNCH_CHECK("maxpool2x2_bias_relu_bwd_kernel");
-    return CT_OK;
+    return maxpool2x2_bias_relu_bwd_impl("ct_maxpool2x2_bias_relu_bwd", y, y_ctot, y_coff, dy, batch, channels, h, w, oh, ow, dz, dz_ctot,
+                                         dz_coff, dbias, dz_absmax, false, nullptr, 0, stream);
+}
+
+extern "C" size_t ct_maxpool2x2_bias_relu_bwd_det_scratch_bytes(int batch, int channels, int* partials)
+{
+    if (partials) *partials = 0;
+    if (batch <= 0 || channels <= 0) return 0;
+    if (partials) *partials = batch;            // one workgroup, one partial sum per (image, channel) plane
+    return (size_t)batch * channels * sizeof(double);
+}
+
+extern "C" int ct_maxpool2x2_bias_relu_bwd_det(const float* y, int y_ctot, int y_coff, const float* dy, int batch, int channels, int h,
+                                               int w, int oh, int ow, float* dz, int dz_ctot, int dz_coff, float* dbias,
+                                               unsigned* dz_absmax, void* scratch, size_t scratch_bytes, ct_stream_t stream)
+{
+    return maxpool2x2_bias_relu_bwd_impl("ct_maxpool2x2_bias_relu_bwd_det", y, y_ctot, y_coff, dy, batch, channels, h, w, oh, ow, dz,
+                                         dz_ctot, dz_coff, dbias, dz_absmax, true, scratch, scratch_bytes, stream);
 }
 
 extern "C" int ct_head_grad_gather(const ct_out_segment* segs, int nseg, int batch, int channels, int hw,

@@ -8,6 +8,7 @@
 #include "ct_common.h"
 #include "ct_device.h"
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 
 namespace ctdet {
@@ -76,6 +77,35 @@ inline Split even_split(int units, int want)
     return {(units + per_split - 1) / per_split, per_split};
 }
 
+// The slab workspace of a deterministic (_det) entry: every split stores its partial result in a slab of its own and a finishing
+// kernel adds the slabs in slab-index order.  The producers write every element of every slab the finish reads, so the workspace
+// may hold anything on entry and ct_scratch_prezeroed has no bearing on it.
+inline int wgrad_check_det_workspace(const void* workspace, size_t have, size_t need, const char* who)
+{
+    CT_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    if (have < need) return fail(CT_ERR_WORKSPACE, "%s: workspace_bytes %zu, needs %zu", who, have, need);
+    return CT_OK;
+}
+
+// out[i] = slab 0 [i] + slab 1 [i] + ... of `nslabs` slabs of n floats, in slab-index order: one thread per element, so the order
+// is the loop's (the loads of four slabs are issued together, the additions stay in order).  out may be slab 0 itself.
+__global__ static __launch_bounds__(256) void wgrad_slab_sum_kernel(const float* slabs, int nslabs, size_t n, float* out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float v = slabs[i];
+#pragma unroll 4
+    for (int s = 1; s < nslabs; ++s) v += slabs[(size_t)s * n + i];
+    out[i] = v;
+}
+
+inline int wgrad_slab_sum(const float* slabs, int nslabs, size_t n, float* out, hipStream_t st)
+{
+    hipLaunchKernelGGL(wgrad_slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slabs, nslabs, n, out);
+    CT_LAUNCH_CHECK("wgrad_slab_sum_kernel");
+    return CT_OK;
+}
+
 // ---- the two fused Winograd kernels: F(3x3, 2x2) of ct_wino_wgrad.hip and F(3x3, 4x4) of ct_wino4_wgrad.hip
 inline bool wgrad_wino_ok(const ct_conv_desc* d)
 {
@@ -89,15 +119,54 @@ struct WinoWgradForm {
     int tile, points;           // output tile edge, transform points = (tile + 2)^2
     int block, threads;         // channels per workgroup side, threads per workgroup
     int lds_bytes;
-    int wgs;                    // workgroups to aim at (one round of the chip), unless the environment variable wgs_env says
-    const char* wgs_env;
+    int (*wgs)();               // workgroups to aim at (one round of the chip, or what the form's environment variable says): read
+                                // once per kernel and process, by the form's own function
+    bool det;                   // the _det entry: one dU slab per split, summed in order ahead of `finish`, in place of the atomics
 };
+
+// The tile-range splits of a launch over nb images: a pure function of the descriptor and the environment (host only).
+struct WinoWgradPlan { int TY, TX, NT, chunks, cblocks, blocks; Split sp; };
+inline WinoWgradPlan wgrad_wino_plan(const WinoWgradForm& f, const ct_conv_desc* d, int nb)
+{
+    WinoWgradPlan p{};
+    const int kblocks = (d->cout + f.block - 1) / f.block;
+    p.cblocks = (d->cin + f.block - 1) / f.block;
+    p.blocks = kblocks * p.cblocks;
+    const int wgs = f.wgs();
+    p.TY = (d->h + f.tile - 1) / f.tile; p.TX = (d->w + f.tile - 1) / f.tile;
+    p.NT = nb * p.TY * p.TX;
+    p.chunks = (p.NT + 7) / 8;                     // TT = 8 tiles per chunk in both kernels
+    p.sp = even_split(p.chunks, std::min(65535, std::max(1, std::min(p.chunks, wgs / p.blocks))));
+    return p;
+}
+
+// splits of all batch chunks of a launch, in chunk order: the dU slabs of a _det entry
+inline int wgrad_wino_total_splits(const WinoWgradForm& f, const ct_conv_desc* d, const WgradLimits& lim)
+{
+    int total = 0;
+    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) total += wgrad_wino_plan(f, d, std::min(lim.max_chunk, d->batch - b0)).sp.splits;
+    return total;
+}
+
+// bytes of the slab workspace of a _det entry (dZ taken as dense), 0 for a descriptor the form does not take; *partials = slabs
+inline size_t wgrad_wino_det_bytes(const WinoWgradForm& f, const ct_conv_desc* d, int* partials)
+{
+    if (partials) *partials = 0;
+    if (!d || !wgrad_wino_ok(d) || d->batch <= 0) return 0;
+    const WgradLimits lim = wgrad_sizes(d, d->cout);
+    if (lim.img_x_bytes >= kMaxBufBytes || lim.img_z_bytes >= kMaxBufBytes) return 0;
+    const int total = wgrad_wino_total_splits(f, d, lim);
+    if (partials) *partials = total;
+    return (size_t)total * f.points * d->cout * d->cin * sizeof(float);
+}
 
 // Workgroup = block x block channels x all transform points over a range of tile chunks; the ranges are split over
 // blockIdx.y, partial sums meet in the workspace dU[points][cout][cin] through f32 atomics, `finish` applies G^T . G into dw.
+// f.det: split s of the launch stores slab s of dU[splits][points][cout][cin] (workspace_bytes of them; nothing is zeroed),
+// wgrad_slab_sum adds the slabs in order into slab 0, and `finish` runs on that.
 template <typename Args>
 int launch_wgrad_wino(const WinoWgradForm& f, void (*kernel)(Args), void (*finish)(const float*, float*, int), const ct_conv_desc* d,
-                      const float* dz, int dz_ctot, int dz_coff, float* dw, void* workspace, ct_stream_t stream)
+                      const float* dz, int dz_ctot, int dz_coff, float* dw, void* workspace, size_t workspace_bytes, ct_stream_t stream)
 {
     if (int rc = wgrad_check_pointers(d, dz, dw, workspace, f.who)) return rc;
     if (!wgrad_wino_ok(d))
@@ -106,29 +175,35 @@ int launch_wgrad_wino(const WinoWgradForm& f, void (*kernel)(Args), void (*finis
     if (int rc = wgrad_check_slices(d, dz_ctot, dz_coff, f.who)) return rc;
     WgradLimits lim;
     if (int rc = wgrad_limits(d, dz_ctot, f.who, &lim)) return rc;
+    const int KC = d->cout * d->cin;
+    const size_t slab = (size_t)f.points * KC;          // floats
+    if (f.det)
+        if (int rc = wgrad_check_det_workspace(workspace, workspace_bytes, wgrad_wino_total_splits(f, d, lim) * slab * sizeof(float), f.who))
+            return rc;
     hipStream_t st = as_stream(stream);
     CT_HIP(raise_lds_limit((const void*)kernel, f.lds_bytes));
     float* dU = static_cast<float*>(workspace);
-    const int KC = d->cout * d->cin;
-    if (!scratch_prezeroed()) CT_HIP(hipMemsetAsync(dU, 0, (size_t)f.points * KC * 4, st));
-    const int kblocks = (d->cout + f.block - 1) / f.block, cblocks = (d->cin + f.block - 1) / f.block;
-    const int blocks = kblocks * cblocks;
-    static const int wgs = getenv(f.wgs_env) ? atoi(getenv(f.wgs_env)) : f.wgs;        // one per Args, that is per kernel
+    if (!f.det && !scratch_prezeroed()) CT_HIP(hipMemsetAsync(dU, 0, slab * 4, st));
+    int slabs = 0;
     for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) {
         const int nb = std::min(lim.max_chunk, d->batch - b0);
+        const WinoWgradPlan p = wgrad_wino_plan(f, d, nb);
         Args a{};
         wgrad_fill(a, d, dz, dz_ctot, dz_coff, lim, b0, nb);
         a.dU = dU;
+        a.slab = f.det ? dU + slabs * slab : nullptr;
         a.H = d->h; a.W = d->w;
-        a.TY = (d->h + f.tile - 1) / f.tile; a.TX = (d->w + f.tile - 1) / f.tile;
-        a.NT = nb * a.TY * a.TX;
-        a.chunks = (a.NT + 7) / 8;                 // TT = 8 tiles per chunk in both kernels
-        a.cblocks = cblocks;
-        const Split sp = even_split(a.chunks, std::min(65535, std::max(1, std::min(a.chunks, wgs / blocks))));
-        a.chunks_per_split = sp.per_split;
-        hipLaunchKernelGGL(kernel, dim3(blocks, sp.splits), dim3(f.threads), f.lds_bytes, st, a);
+        a.TY = p.TY; a.TX = p.TX;
+        a.NT = p.NT;
+        a.chunks = p.chunks;
+        a.cblocks = p.cblocks;
+        a.chunks_per_split = p.sp.per_split;
+        hipLaunchKernelGGL(kernel, dim3(p.blocks, p.sp.splits), dim3(f.threads), f.lds_bytes, st, a);
         CT_LAUNCH_CHECK(f.kernel_name);
+        slabs += p.sp.splits;
     }
+    if (f.det && slabs > 1)
+        if (int rc = wgrad_slab_sum(dU, slabs, slab, dU, st)) return rc;
     hipLaunchKernelGGL(finish, dim3((KC + 255) / 256), dim3(256), 0, st, dU, dw, KC);
     CT_LAUNCH_CHECK(f.finish_name);
     return CT_OK;

@@ -51,6 +51,7 @@ struct W4WArgs {
     const float* x;
     const float* dz;
     float* dU;               // [36][Cout][Cin]
+    float* slab;             // null: atomics into dU.  Else the first slab of this launch in [splits][36][Cout][Cin]: stores
     unsigned x_bytes, dz_bytes;
     int Cin, Cout, H, W, x_ctot, x_coff, dz_ctot, dz_coff;
     int TY, TX, NT, chunks, chunks_per_split, cblocks;
@@ -226,12 +227,14 @@ __global__ __launch_bounds__(256, 2) void wino4_wgrad_f32(const W4WArgs a)
     // ---- partial sums -> dU[xi][k][c]
 #pragma unroll
     for (int x = 0; x < 9; ++x) {
-        float* U = a.dU + (size_t)(9 * wave + x) * a.Cout * a.Cin;
+        float* U = (a.slab ? a.slab + (size_t)blockIdx.y * 36 * a.Cout * a.Cin : a.dU) + (size_t)(9 * wave + x) * a.Cout * a.Cin;
         const int cc = c0 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int k = k0 + 8 * (r >> 2) + 4 * hi + (r & 3);
-            if (k < a.Cout && cc < a.Cin) unsafeAtomicAdd(U + (size_t)k * a.Cin + cc, acc[x][r]);
+            if (k >= a.Cout || cc >= a.Cin) continue;
+            if (a.slab) U[(size_t)k * a.Cin + cc] = acc[x][r];
+            else unsafeAtomicAdd(U + (size_t)k * a.Cin + cc, acc[x][r]);
         }
     }
 }
@@ -264,8 +267,15 @@ __global__ __launch_bounds__(256) void wino4_wgrad_finish(const float* __restric
 }
 
 // two workgroups per CU, one round
-const ctdet::WinoWgradForm kForm = {"ct_conv2d_wgrad_wino4", "wino4_wgrad_f32", "wino4_wgrad_finish", 4, 36, CB, 256, W4W_LDS_BYTES, 512,
-                                    "CTDET_W4W_WGS"};
+int w4w_wgs()
+{
+    static const int wgs = getenv("CTDET_W4W_WGS") ? atoi(getenv("CTDET_W4W_WGS")) : 512;
+    return wgs;
+}
+const ctdet::WinoWgradForm kForm = {"ct_conv2d_wgrad_wino4", "wino4_wgrad_f32", "wino4_wgrad_finish", 4, 36, CB, 256, W4W_LDS_BYTES, w4w_wgs,
+                                    false};
+const ctdet::WinoWgradForm kFormDet = {"ct_conv2d_wgrad_wino4_det", "wino4_wgrad_f32", "wino4_wgrad_finish", 4, 36, CB, 256, W4W_LDS_BYTES,
+                                       w4w_wgs, true};
 
 }  // namespace
 
@@ -279,5 +289,17 @@ extern "C" size_t ct_conv_wgrad_wino4_workspace_bytes(const ct_conv_desc* d)
 extern "C" int ct_conv2d_wgrad_wino4(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
                                      void* workspace, ct_stream_t stream)
 {
-    return ctdet::launch_wgrad_wino(kForm, wino4_wgrad_f32, wino4_wgrad_finish, d, dz, dz_ctot, dz_coff, dw, workspace, stream);
+    return ctdet::launch_wgrad_wino(kForm, wino4_wgrad_f32, wino4_wgrad_finish, d, dz, dz_ctot, dz_coff, dw, workspace, 0, stream);
+}
+
+extern "C" size_t ct_conv_wgrad_wino4_det_workspace_bytes(const ct_conv_desc* d, int* partials)
+{
+    return ctdet::wgrad_wino_det_bytes(kFormDet, d, partials);
+}
+
+extern "C" int ct_conv2d_wgrad_wino4_det(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, void* workspace,
+                                         size_t workspace_bytes, ct_stream_t stream)
+{
+    return ctdet::launch_wgrad_wino(kFormDet, wino4_wgrad_f32, wino4_wgrad_finish, d, dz, dz_ctot, dz_coff, dw, workspace,
+                                    workspace_bytes, stream);
 }

@@ -47,6 +47,7 @@ struct WWArgs {
     const float* x;
     const float* dz;
     float* dU;               // [16][Cout][Cin]
+    float* slab;             // null: atomics into dU.  Else the first slab of this launch in [splits][16][Cout][Cin]: stores
     unsigned x_bytes, dz_bytes;
     int Cin, Cout, H, W, x_ctot, x_coff, dz_ctot, dz_coff;
     int TY, TX, NT, chunks, chunks_per_split, cblocks;
@@ -238,7 +239,7 @@ __global__ __launch_bounds__(512) void wino_wgrad_f32(const WWArgs a)
     // ---- partial sums -> dU[xi][k][c]
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
-        float* U = a.dU + (size_t)(2 * wave + x) * a.Cout * a.Cin;
+        float* U = (a.slab ? a.slab + (size_t)blockIdx.y * 16 * a.Cout * a.Cin : a.dU) + (size_t)(2 * wave + x) * a.Cout * a.Cin;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -247,7 +248,9 @@ __global__ __launch_bounds__(512) void wino_wgrad_f32(const WWArgs a)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int k = k0 + 32 * i + 8 * (r >> 2) + 4 * hi + (r & 3);
-                    if (k < a.Cout && cc < a.Cin) unsafeAtomicAdd(U + (size_t)k * a.Cin + cc, acc[x][i][jj][r]);
+                    if (k >= a.Cout || cc >= a.Cin) continue;
+                    if (a.slab) U[(size_t)k * a.Cin + cc] = acc[x][i][jj][r];
+                    else unsafeAtomicAdd(U + (size_t)k * a.Cin + cc, acc[x][i][jj][r]);
                 }
             }
     }
@@ -281,8 +284,15 @@ __global__ __launch_bounds__(256) void wino_wgrad_finish(const float* __restrict
 
 // one workgroup per CU (128 KB of LDS each), ONE round: every extra split pays the 64K-atomic epilogue again (target 768
 // measured 7-25 % slower than 256 on the RFBNet shapes)
-const ctdet::WinoWgradForm kForm = {"ct_conv2d_wgrad_wino", "wino_wgrad_f32", "wino_wgrad_finish", 2, 16, 64, 512, WW_LDS_BYTES, 256,
-                                    "CTDET_WW_WGS"};
+int ww_wgs()
+{
+    static const int wgs = getenv("CTDET_WW_WGS") ? atoi(getenv("CTDET_WW_WGS")) : 256;
+    return wgs;
+}
+const ctdet::WinoWgradForm kForm = {"ct_conv2d_wgrad_wino", "wino_wgrad_f32", "wino_wgrad_finish", 2, 16, 64, 512, WW_LDS_BYTES, ww_wgs,
+                                    false};
+const ctdet::WinoWgradForm kFormDet = {"ct_conv2d_wgrad_wino_det", "wino_wgrad_f32", "wino_wgrad_finish", 2, 16, 64, 512, WW_LDS_BYTES,
+                                       ww_wgs, true};
 
 } // namespace
 
@@ -296,5 +306,17 @@ extern "C" size_t ct_conv_wgrad_wino_workspace_bytes(const ct_conv_desc* d)
 extern "C" int ct_conv2d_wgrad_wino(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
                                     void* workspace, ct_stream_t stream)
 {
-    return ctdet::launch_wgrad_wino(kForm, wino_wgrad_f32, wino_wgrad_finish, d, dz, dz_ctot, dz_coff, dw, workspace, stream);
+    return ctdet::launch_wgrad_wino(kForm, wino_wgrad_f32, wino_wgrad_finish, d, dz, dz_ctot, dz_coff, dw, workspace, 0, stream);
+}
+
+extern "C" size_t ct_conv_wgrad_wino_det_workspace_bytes(const ct_conv_desc* d, int* partials)
+{
+    return ctdet::wgrad_wino_det_bytes(kFormDet, d, partials);
+}
+
+extern "C" int ct_conv2d_wgrad_wino_det(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, void* workspace,
+                                        size_t workspace_bytes, ct_stream_t stream)
+{
+    return ctdet::launch_wgrad_wino(kFormDet, wino_wgrad_f32, wino_wgrad_finish, d, dz, dz_ctot, dz_coff, dw, workspace,
+                                    workspace_bytes, stream);
 }

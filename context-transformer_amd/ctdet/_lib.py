@@ -162,6 +162,22 @@ SIGNATURES = {
     'ct_conv_wgrad_h2_supported': (_I, [C.POINTER(ConvDesc)]),
     'ct_conv_wgrad_h2_workspace_bytes': (_Z, [C.POINTER(ConvDesc)]),
     'ct_conv2d_wgrad_h2': (_I, [C.POINTER(ConvDesc), _P, _I, _I, _P, _P, _P, _Z, _P]),
+    'ct_conv_wgrad_det_workspace_bytes': (_Z, [C.POINTER(ConvDesc), C.POINTER(_I)]),
+    'ct_conv2d_wgrad_det': (_I, [C.POINTER(ConvDesc), _P, _I, _I, _P, _P, _Z, _P]),
+    'ct_conv_wgrad_wino_det_workspace_bytes': (_Z, [C.POINTER(ConvDesc), C.POINTER(_I)]),
+    'ct_conv2d_wgrad_wino_det': (_I, [C.POINTER(ConvDesc), _P, _I, _I, _P, _P, _Z, _P]),
+    'ct_conv_wgrad_wino4_det_workspace_bytes': (_Z, [C.POINTER(ConvDesc), C.POINTER(_I)]),
+    'ct_conv2d_wgrad_wino4_det': (_I, [C.POINTER(ConvDesc), _P, _I, _I, _P, _P, _Z, _P]),
+    'ct_bn_det_scratch_bytes': (_Z, [_I, _I, _I, C.POINTER(_I)]),
+    'ct_bn_train_stats_det': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _Z, _P]),
+    'ct_bn_train_backward_det': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _I, _P, _F, _P, _I, _I, _I,
+                                      _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    'ct_bn_eval_backward_det': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _I, _P, _F, _P, _I, _I, _I,
+                                     _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    'ct_bias_det_scratch_bytes': (_Z, [_I, _I, _I, C.POINTER(_I)]),
+    'ct_bias_act_backward_det': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _Z, _P]),
+    'ct_maxpool2x2_bias_relu_bwd_det_scratch_bytes': (_Z, [_I, _I, C.POINTER(_I)]),
+    'ct_maxpool2x2_bias_relu_bwd_det': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _Z, _P]),
     'ct_bn_train_stats': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P]),
     'ct_bn_train_apply': (_I, [_P, _P, _P, _P, _P, _F, _I, _P, _P, _I, _I, _F, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'ct_bn_train_backward': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _I, _P, _F, _P, _I, _I, _I,

@@ -17,6 +17,10 @@ What the reference gets from autograd + cuDNN in `train.py:222-229` (`model(data
             (ops.CtxTrainer), producing the gradient of the raw conf logits the head backward consumes.
 
 Buffers are owned by the runtime and reused every step (call backward before the next forward).
+
+CTDET_TRAIN_DETERMINISTIC=1 (opt-in): the weight gradients, BatchNorm reductions and bias sums run their `_det` twins (one slab
+per split, added in order, in place of floating-point atomics: include/ctdet.h), so the convolutional step repeats bit for bit;
+the Context-Transformer block is refused under it.
 """
 import ctypes as C
 import os
@@ -70,6 +74,9 @@ class LayerState:
     wgrad_ws: object = None
     dw: object = None
     dz_amax: object = None      # maxima of |dZ|: the slot ct_bias_act_backward_amax fills (_wire_absmax)
+    # deterministic mode, per part: the slice of TrainRuntime.det_scratch its BatchNorm reductions (both passes) resp. its dbias
+    # sum (the fused pool backward's included) store their partial sums in
+    det_scratch: list = field(default_factory=list)
 
 
 @dataclass(frozen=True)
@@ -80,12 +87,13 @@ class TrainSwitches:
     fuse_pool_bwd: bool     # CTDET_TRAIN_FUSE_POOL_BWD=0: pool backward and bias / ReLU backward as two kernels
     streams: int            # CTDET_TRAIN_STREAMS=1: weight gradients on the caller's stream
     ksplit: int             # CTDET_KSPLIT=0: no split-K slabs for the data gradients
+    deterministic: bool = False     # CTDET_TRAIN_DETERMINISTIC=1: ordered slab sums in place of the floating-point atomics
 
     @classmethod
     def of(cls, env):
         return cls(env.get('CTDET_PACK_BATCH', '1') != '0', env.get('CTDET_PREZERO', '1') != '0',
                    env.get('CTDET_TRAIN_FUSE_POOL_BWD', '1') != '0', int(env.get('CTDET_TRAIN_STREAMS', '2')),
-                   int(env.get('CTDET_KSPLIT', '1')))
+                   int(env.get('CTDET_KSPLIT', '1')), env.get('CTDET_TRAIN_DETERMINISTIC', '0') not in ('', '0'))
 
 
 class PackList:
@@ -123,7 +131,8 @@ class TrainRuntime:
         self._pack_table, self._pack_ptrs, self._pack_counts, self._recording = None, None, (0, 0), False
         self._x3_list, self._h2_list = PackList(self.lib, 'ct_conv_x3_pack'), PackList(self.lib, 'ct_conv_wino_h2_pack')
         self.bucketer, self.generation, self.used_ctx, self.amax_slots, self._wired_epoch = None, 0, False, {}, None
-        self.wgrad_wsh2 = self.wgrad_ws_all = self.bn_scratch = None
+        self.wgrad_wsh2 = self.wgrad_ws_all = self.bn_scratch = self.wgrad_wsdet = self.det_scratch = None
+        self.det = self.switches.deterministic
         self.params, self._pindex, self.ctx = [], {}, None      # params: ordered parameters that receive gradients
         if self.plan.ctx:
             C_ = net.num_classes
@@ -155,6 +164,8 @@ class TrainRuntime:
         backend.ws_rebuild([self.state[st.name].fwd for st in self.plan.steps if st.kind == 'conv'])
         self._wire_absmax()
         self._pool_bwd = self._find_fused_pool_bwd() if self.switches.fuse_pool_bwd else {}
+        if self.det:
+            self._alloc_det_scratch()
         # weight gradients beside the data-gradient chain (CTDET_TRAIN_STREAMS=1 keeps everything on the caller's stream).  The
         # stream is the forward pass's side stream: the two are never busy at the same time, and a training step with ONE side
         # stream can be captured as a hipGraph (a second one crashes hipStreamEndCapture on ROCm 7.2)
@@ -258,7 +269,7 @@ class TrainRuntime:
         w.cout = st.cout
         w.kh, w.kw, w.stride, w.pad_h, w.pad_w, w.dil = st.kh, st.kw, st.stride, st.ph, st.pw, st.dil
         w.oh, w.ow = st.oh, st.ow
-        r = s.wgrad_route = wgrad_routes.choose(self.lib, st, w, st.cout, os.environ)
+        r = s.wgrad_route = wgrad_routes.choose(self.lib, st, w, st.cout, os.environ, deterministic=self.det)
         s.wgrad_ws_bytes = r.workspace_bytes(self.lib, w)
         self._ws_need[r.ws] = max(self._ws_need.get(r.ws, 0), s.wgrad_ws_bytes)
 
@@ -273,6 +284,8 @@ class TrainRuntime:
         self.wgrad_ws4s = torch.empty(max(need.get('wgrad_ws4s', 0), 1), device=dev, dtype=torch.uint8)
         if self.wgrad_h2:
             self.wgrad_wsh2 = torch.empty(max(need.get('wgrad_wsh2', 0), 1), device=dev, dtype=torch.uint8)
+        if self.det:                            # the slabs of the largest deterministic weight gradient
+            self.wgrad_wsdet = torch.empty(max(need.get('wgrad_wsdet', 0), 1), device=dev, dtype=torch.uint8)
         if not self.prezero:
             return
         al, states = self.be.alloc, list(self.state.values())
@@ -288,6 +301,29 @@ class TrainRuntime:
         for s, n in sizes:
             s.wgrad_ws = self.wgrad_ws_all[o:o + n]
             o += (n + 63) // 64 * 64
+
+    def _alloc_det_scratch(self):
+        """Deterministic mode: ONE float64 arena; every BatchNorm part and every bias sum owns a slice of it, sized by the library's
+        queries (a fused pool producer's slice also holds that launch's per-image sums).  Nothing zeroes it: the reductions store
+        every partial sum they later add."""
+        lib, B = self.lib, self.batch
+        fused = {pr.name for pr in self._pool_bwd.values()}
+        sizes = []
+        for st, s in self._convs():
+            for p in st.parts:
+                hw = st.oh * st.ow
+                if s.is_bn:
+                    n = lib.ct_bn_det_scratch_bytes(B, p.cout, hw, None)
+                else:
+                    n = lib.ct_bias_det_scratch_bytes(B, p.cout, hw, None)
+                    if st.name in fused:
+                        n = max(n, lib.ct_maxpool2x2_bias_relu_bwd_det_scratch_bytes(B, p.cout, None))
+                sizes.append((s, (int(n) + 15) // 16 * 2))          # doubles, slices 16-byte aligned
+        self.det_scratch = self.be.alloc((max(sum(n for _, n in sizes), 1),), torch.float64)
+        o = 0
+        for s, n in sizes:
+            s.det_scratch.append(self.det_scratch[o:o + n])
+            o += n
 
     def _find_fused_pool_bwd(self):
         """MaxPool2d(2, 2) whose input only the pool reads, under a convolution with bias + ReLU and no BatchNorm (conv1_2, conv2_2,
@@ -509,6 +545,10 @@ class TrainRuntime:
 
     def forward(self, x, use_ctx=True):
         lib, B = self.lib, self.batch
+        if self.det and use_ctx and self.ctx is not None:
+            raise _lib.CtdetError('CTDET_TRAIN_DETERMINISTIC=1 does not cover the Context-Transformer block: ct_ctx_attention_bwd '
+                                  'sums through floating-point atomics (csrc/ct_attn_bwd.hip); unset the switch for a phase-2 '
+                                  "'ours' network")
         self.generation += 1                        # saved activations belong to THIS forward
         self.used_ctx = bool(use_ctx and self.ctx is not None)
         if tuple(x.shape) != tuple(self.bufs['x'].shape):
@@ -563,9 +603,9 @@ class TrainRuntime:
                 mean_t, var_t = bn.running_mean, bn.running_var
             else:
                 mean_t, var_t = s.mean[i], s.var[i]
-                _lib.check(lib.ct_bn_train_stats(z.data_ptr(), B, z.shape[1], off, p.cout, hw, mean_t.data_ptr(), var_t.data_ptr(),
-                                                 float(bn.momentum), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                                 s.scratch[i].data_ptr(), self._s()), st.name + ' bn stats')
+                _lib.check((lib.ct_bn_train_stats_det if self.det else lib.ct_bn_train_stats)(
+                    z.data_ptr(), B, z.shape[1], off, p.cout, hw, mean_t.data_ptr(), var_t.data_ptr(), float(bn.momentum),
+                    bn.running_mean.data_ptr(), bn.running_var.data_ptr(), *self._scratch(s, i), self._s()), st.name + ' bn stats')
             res = self.bufs[st.res] if st.res is not None else None
             _lib.check(lib.ct_bn_train_apply(
                 z.data_ptr(), mean_t.data_ptr(), var_t.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps),
@@ -573,6 +613,26 @@ class TrainRuntime:
                 st.res_coff, float(st.res_scale), dst.data_ptr(), dst.shape[1], st.dst_coff + off, z.shape[1], off, B, p.cout, hw,
                 self._s()), st.name + ' bn apply')
             off += p.cout
+
+    def _scratch(self, s, i):
+        """The scratch arguments of part i's reduction: the BatchNorm scratch, or in deterministic mode the part's slab slice and
+        its size in bytes."""
+        if not self.det:
+            return (s.scratch[i].data_ptr(),)
+        t = s.det_scratch[i]
+        return t.data_ptr(), t.numel() * 8
+
+    def policy_record(self):
+        """What shaped this runtime's training launches, resolved to what is in force (tools/train_bench.py prints it as `policy`):
+        the deterministic mode, the weight-gradient routes by layer count, the bytes of the mode's workspaces."""
+        routes = {}
+        for s in self.state.values():
+            routes[s.wgrad_route.name] = routes.get(s.wgrad_route.name, 0) + 1
+        return {
+            'deterministic': self.det,
+            'wgrad_routes': dict(sorted(routes.items())),
+            'det_workspace_bytes': {'wgrad_wsdet': self.wgrad_wsdet.numel(), 'det_scratch': self.det_scratch.numel() * 8} if self.det else None,
+        }
 
     # ------------------------------------------------------------------ backward
     def backward(self, dloc, dconf, dobj):
@@ -656,9 +716,10 @@ class TrainRuntime:
             pr = self._pool_bwd[st.name]
             sp = self.state[pr.name]
             y = self.bufs[pr.dst]
-            _lib.check(lib.ct_maxpool2x2_bias_relu_bwd(y.data_ptr(), y.shape[1], pr.dst_coff, self.grads[st.dst].data_ptr(), B, st.ch,
-                                                       st.h, st.w, st.oh, st.ow, sp.dz.data_ptr(), sp.zc, 0, sp.dbias[0].data_ptr(),
-                                                       sp.dz_amax, self._s()), st.name + ' + ' + pr.name + ' bias bwd')
+            _lib.check((lib.ct_maxpool2x2_bias_relu_bwd_det if self.det else lib.ct_maxpool2x2_bias_relu_bwd)(
+                y.data_ptr(), y.shape[1], pr.dst_coff, self.grads[st.dst].data_ptr(), B, st.ch, st.h, st.w, st.oh, st.ow,
+                sp.dz.data_ptr(), sp.zc, 0, sp.dbias[0].data_ptr(), sp.dz_amax, *(self._scratch(sp, 0) if self.det else ()), self._s()),
+                st.name + ' + ' + pr.name + ' bias bwd')
             sp.dz_from_pool = True
             return
         _lib.check(lib.ct_maxpool2d_bwd(self.bufs[st.src].data_ptr(), self.grads[st.dst].data_ptr(), self.grads[st.src].data_ptr(),
@@ -681,8 +742,13 @@ class TrainRuntime:
                        st.name + ' head gather')
             off = 0
             for i, p in enumerate(st.parts):
-                _lib.check(lib.ct_bias_act_backward(s.dz.data_ptr(), ctot, off, None, 0, 0, 0, B, p.cout, hw, s.dz.data_ptr(), ctot, off,
-                                                    s.dbias[i].data_ptr(), self._s()), st.name + ' bias bwd')
+                if self.det:
+                    _lib.check(lib.ct_bias_act_backward_det(s.dz.data_ptr(), ctot, off, None, 0, 0, 0, B, p.cout, hw, s.dz.data_ptr(), ctot,
+                                                            off, s.dbias[i].data_ptr(), None, *self._scratch(s, i), self._s()),
+                               st.name + ' bias bwd')
+                else:
+                    _lib.check(lib.ct_bias_act_backward(s.dz.data_ptr(), ctot, off, None, 0, 0, 0, B, p.cout, hw, s.dz.data_ptr(), ctot,
+                                                        off, s.dbias[i].data_ptr(), self._s()), st.name + ' bias bwd')
                 put(p.bias, s.dbias[i])
                 off += p.cout
             return
@@ -699,21 +765,22 @@ class TrainRuntime:
                     written.setdefault(st.res, []).append((st.res_coff, st.res_coff + p.cout))
                 frozen = s.frozen[i]
                 mean_t, var_t = (p.bn.running_mean, p.bn.running_var) if frozen else (s.mean[i], s.var[i])
-                _lib.check((lib.ct_bn_eval_backward if frozen else lib.ct_bn_train_backward)(
+                fn = 'ct_bn_eval_backward' if frozen else 'ct_bn_train_backward'
+                _lib.check(getattr(lib, fn + '_det' if self.det else fn)(
                     gy.data_ptr(), gy.shape[1], st.dst_coff + off, y.data_ptr(), y.shape[1], st.dst_coff + off, z.data_ptr(),
                     mean_t.data_ptr(), var_t.data_ptr(), p.bn.weight.data_ptr(), float(p.bn.eps), int(p.relu), None,
                     float(st.res_scale), dres, dres_ctot, st.res_coff, dres_acc, s.dz.data_ptr(), s.dgamma[i].data_ptr(),
-                    s.dbeta[i].data_ptr(), ctot, off, B, p.cout, hw, s.scratch[i].data_ptr(), self._s()), st.name + ' bn bwd')
+                    s.dbeta[i].data_ptr(), ctot, off, B, p.cout, hw, *self._scratch(s, i), self._s()), st.name + ' bn bwd')
                 put(p.bn.weight, s.dgamma[i])
                 put(p.bn.bias, s.dbeta[i])
             else:
                 if s.dz_from_pool:
                     s.dz_from_pool = False          # dZ and dbias came from the pool's fused backward (_pool_backward)
                 else:
-                    _lib.check(lib.ct_bias_act_backward_amax(
+                    _lib.check((lib.ct_bias_act_backward_det if self.det else lib.ct_bias_act_backward_amax)(
                         gy.data_ptr(), gy.shape[1], st.dst_coff + off, y.data_ptr(), y.shape[1], st.dst_coff + off, int(p.relu), B,
                         p.cout, hw, s.dz.data_ptr(), ctot, off, s.dbias[i].data_ptr() if p.bias is not None else None, s.dz_amax,
-                        self._s()), st.name + ' bias bwd')
+                        *(self._scratch(s, i) if self.det else ()), self._s()), st.name + ' bias bwd')
                 if p.bias is not None:
                     put(p.bias, s.dbias[i])
             off += p.cout

@@ -6,6 +6,8 @@ launch (the forward and data-gradient launches have ctdet/wino_forms.py).
   wino4    Winograd F(3x3, 4x4) fused on the fp32 MFMA (csrc/ct_wino4_wgrad.hip)
   wino4s   F(3x3, 4x4) as transform kernels + the bf16x3 GEMM, also the dilated 3x3 layers (csrc/ct_wino4s.hip)
   h2       the 1x1 layers on the f16 matrix pipe, f16x2 operand form, opt-in (csrc/ct_wgrad_h2.hip)
+  direct_det, wino2_det, wino4_det   the deterministic twins of the first three: the same kernels with one slab per split in
+           place of the atomics, the slabs added in order (CTDET_TRAIN_DETERMINISTIC=1; include/ctdet.h)
 
 A route's workspace is one of three kinds: none; the accumulating float dU workspace (`zeroed`: TrainRuntime.wgrad_ws, or under
 CTDET_PREZERO a slice of wgrad_ws_all per layer, zeroed once per step); a byte workspace shared by all layers of the route
@@ -25,9 +27,12 @@ class Route:
     ws: Optional[str] = None            # TrainRuntime attribute of the shared workspace (None: no workspace)
     zeroed: bool = False                # the float dU workspace, passed without a size
     dz_amax: bool = False               # takes dZ's per-image maxima (and X's, through desc.in_absmax)
+    partials: bool = False              # the size query also reports the partial sums per output (a second argument)
 
     def workspace_bytes(self, lib, desc):
-        return int(getattr(lib, self.size)(C.byref(desc))) if self.size else 0
+        if not self.size:
+            return 0
+        return int(getattr(lib, self.size)(C.byref(desc), *((None,) if self.partials else ())))
 
     def run(self, lib, desc, dz, ctot, dw, ws, dz_amax, stream):
         """Launch on desc: dZ = channels [0, ctot) of tensor dz, dw dense; ws = the workspace tensor of this layer (None: none)."""
@@ -48,6 +53,14 @@ ROUTES = {r.name: r for r in (
     Route('h2', 'ct_conv2d_wgrad_h2', ' wgrad (f16x2)', 'ct_conv_wgrad_h2_supported', 'ct_conv_wgrad_h2_workspace_bytes', 'wgrad_wsh2',
           dz_amax=True),
 )}
+# deterministic twins, by the name of the route they replace; ONE slab workspace for the three (weight gradients run in stream order)
+DET_ROUTES = {r.name[:-4]: r for r in (
+    Route('direct_det', 'ct_conv2d_wgrad_det', ' wgrad (det)', None, 'ct_conv_wgrad_det_workspace_bytes', 'wgrad_wsdet', partials=True),
+    Route('wino2_det', 'ct_conv2d_wgrad_wino_det', ' wgrad (winograd, det)', 'ct_conv_wgrad_wino_supported',
+          'ct_conv_wgrad_wino_det_workspace_bytes', 'wgrad_wsdet', partials=True),
+    Route('wino4_det', 'ct_conv2d_wgrad_wino4_det', ' wgrad (winograd, det)', 'ct_conv_wgrad_wino4_supported',
+          'ct_conv_wgrad_wino4_det_workspace_bytes', 'wgrad_wsdet', partials=True),
+)}
 
 
 def h2_enabled(env):
@@ -56,8 +69,10 @@ def h2_enabled(env):
     return env.get('CTDET_WGRAD_H2', '0') not in ('', '0')
 
 
-def choose(lib, st, desc, ctot, env):
-    """The route of plan step st (a fused conv of ctot output channels) with weight-gradient descriptor desc."""
+def choose(lib, st, desc, ctot, env, deterministic=False):
+    """The route of plan step st (a fused conv of ctot output channels) with weight-gradient descriptor desc.  deterministic
+    (TrainSwitches.deterministic): the same choice, then direct / wino2 / wino4 become their slab twins; wino4s and h2 have no
+    atomics and stay."""
     def ok(route):
         return bool(getattr(lib, route.supported)(C.byref(desc)))
     hw = st.oh * st.ow
@@ -89,4 +104,6 @@ def choose(lib, st, desc, ctot, env):
     # maxima passes a BatchNorm layer's dZ needs cost 10 us) stay on ct_conv2d_wgrad.
     if route.name == 'direct' and h2_enabled(env) and st.stride == 1 and hw >= 361 and ok(ROUTES['h2']):
         route = ROUTES['h2']
+    if deterministic:
+        route = DET_ROUTES.get(route.name, route)
     return route

@@ -845,6 +845,84 @@ size_t ct_conv_wgrad_h2_workspace_bytes(const ct_conv_desc* d);
 int ct_conv2d_wgrad_h2(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, const unsigned* dz_absmax, float* dw,
                        void* workspace, size_t workspace_bytes, ct_stream_t stream);
 
+/* ---- deterministic twins (`_det`): ordered sums in place of atomics --------------------------------------------------
+ * ct_conv2d_wgrad, ct_conv2d_wgrad_wino, ct_conv2d_wgrad_wino4, the sliced BatchNorm reductions and the two dbias sums let
+ * the partial results of several workgroups meet through floating-point atomics, so the order in which they land decides
+ * the last bits.  A `_det` twin runs the SAME kernels over the SAME partition, but every workgroup STORES its partial result
+ * into a slab of its own in a caller-provided workspace, and a finishing kernel adds the slabs of each output element in
+ * slab-index order: same build, same environment, same inputs => same bits, whatever the scheduling.  Every slab element the
+ * finish reads is written by its producer, so the workspace may hold anything on entry, nothing is memset, and
+ * ct_scratch_prezeroed() has no bearing on these entries: the output is always OVERWRITTEN.  The partition stays a pure
+ * function of the descriptor and the environment; the size queries are host code (no device needed) and return through
+ * `partials` (may be NULL) how many partial sums meet in one output element of that launch.
+ *
+ * Arguments, result layout and refusals are those of the plain entry (the message names the `_det` entry), plus: a
+ * workspace that is NULL or not 16-byte aligned (scratch: 8-byte) is CT_ERR_INVALID, one smaller than the launch needs is
+ * CT_ERR_WORKSPACE.
+ *
+ * Direct kernel.  One launch per batch chunk of max_chunk images (all of them unless X or dZ exceeds 2 GiB).  For a chunk
+ * of nb images, with Npix = nb*oh*ow, Ncols = cin*kh*kw, tiles = ceil(cout/64) * ceil(Ncols/64) and slots = 512
+ * (CTDET_WGRAD_WGS; tile edge 128 under CTDET_WGRAD_TB=2 where cout >= 96 and Ncols >= 96):
+ *     smax   = max(1, min(ceil(Npix/256), 4*slots / tiles))
+ *     want   = the first sp in 1..smax whose fill  tiles*sp / (ceil(tiles*sp / slots) * slots)  reaches 0.92,
+ *              else the sp of the largest fill (the smallest such sp)
+ *     per    = ceil(ceil(Npix/64) / want)        blocks of 64 pixels per split
+ *     splits = ceil(ceil(Npix/64) / per)
+ * Workspace: slabs [splits][cout][Ncols] floats per chunk, the chunks' slabs appended in chunk order; partials = the sum of
+ * `splits` over the chunks; bytes = partials * cout * Ncols * 4.  The queries take dZ as dense (dz_ctot == cout) when they
+ * count batch chunks; the entry checks workspace_bytes against the dz_ctot it is given.  0 / partials 0: a NULL or
+ * non-positive descriptor, an oh/ow that does not follow from the geometry, a filter size that is not built. */
+size_t ct_conv_wgrad_det_workspace_bytes(const ct_conv_desc* d, int* partials);
+int ct_conv2d_wgrad_det(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
+                        void* workspace, size_t workspace_bytes, ct_stream_t stream);
+/* Winograd twins.  Per chunk of nb images, with tile = 2 / 4, points = 16 / 36, block = 64 / 32 channels per workgroup side,
+ * wgs = 256 / 512 (CTDET_WW_WGS / CTDET_W4W_WGS) for F(3x3, 2x2) / F(3x3, 4x4):
+ *     chunks = ceil(nb * ceil(h/tile) * ceil(w/tile) / 8),   blocks = ceil(cout/block) * ceil(cin/block)
+ *     want   = min(65535, max(1, min(chunks, wgs / blocks))),  per = ceil(chunks / want),  splits = ceil(chunks / per)
+ * Workspace: slabs [splits][points][cout][cin] floats, appended in chunk order; the finish adds them in order and then applies
+ * G^T . G.  bytes = partials * points * cout * cin * 4; 0 / partials 0 where ct_conv_wgrad_wino_supported() is 0. */
+size_t ct_conv_wgrad_wino_det_workspace_bytes(const ct_conv_desc* d, int* partials);
+int ct_conv2d_wgrad_wino_det(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
+                             void* workspace, size_t workspace_bytes, ct_stream_t stream);
+size_t ct_conv_wgrad_wino4_det_workspace_bytes(const ct_conv_desc* d, int* partials);
+int ct_conv2d_wgrad_wino4_det(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
+                              void* workspace, size_t workspace_bytes, ct_stream_t stream);
+/* BatchNorm twins: slices = max(1, min(ceil(1024/channels), batch*hw / 2048)) (= partials), slice y stores its two sums as
+ * doubles at scratch[y][2][channels] and the final kernel adds the slices in order.  With one slice the one-workgroup
+ * reduction runs and scratch is not looked at.  The query returns 16 * max(channels, min(1023 + channels, channels *
+ * max(1, batch*hw / 2048))) bytes: at least slices * 2 * channels doubles, and growing with batch and with channels (which
+ * slices * channels does not).  0 for a non-positive argument.  Arguments as the plain entries, `scratch` followed by its size. */
+size_t ct_bn_det_scratch_bytes(int batch, int channels, int hw, int* partials);
+int ct_bn_train_stats_det(const float* z, int batch, int ctot, int coff, int channels, int hw,
+                          float* mean, float* var, float momentum, float* running_mean, float* running_var,
+                          void* scratch, size_t scratch_bytes, ct_stream_t stream);
+int ct_bn_train_backward_det(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot, int y_coff,
+                             const float* z, const float* mean, const float* var, const float* gamma,
+                             float eps, int relu, const float* lo, float res_scale,
+                             float* dres, int dres_ctot, int dres_coff, int dres_accumulate,
+                             float* dz, float* dgamma, float* dbeta, int z_ctot, int z_coff,
+                             int batch, int channels, int hw, void* scratch, size_t scratch_bytes, ct_stream_t stream);
+int ct_bn_eval_backward_det(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot, int y_coff,
+                            const float* z, const float* running_mean, const float* running_var, const float* gamma,
+                            float eps, int relu, const float* lo, float res_scale,
+                            float* dres, int dres_ctot, int dres_coff, int dres_accumulate,
+                            float* dz, float* dgamma, float* dbeta, int z_ctot, int z_coff,
+                            int batch, int channels, int hw, void* scratch, size_t scratch_bytes, ct_stream_t stream);
+/* dbias twins (arguments of ct_bias_act_backward_amax resp. ct_maxpool2x2_bias_relu_bwd, then scratch and its size; scratch is
+ * looked at only where dbias is given).  Bias + activation: s0 = min(65535, max(1, min(ceil(2048/channels),
+ * ceil(batch*hw / 4096)))), per = ceil(batch*hw / s0) rounded up to a multiple of 4, slices = ceil(batch*hw / per) (=
+ * partials); slice y stores its sum as a double at scratch[y][channels].  The query returns 8 * max(channels, min(2047 +
+ * channels, channels * ceil(batch*hw / 4096))) bytes (the same kind of bound as above).  Fused pool: one workgroup per
+ * (image, channel) plane, so partials = batch and scratch holds [batch][channels] doubles, added in image order. */
+size_t ct_bias_det_scratch_bytes(int batch, int channels, int hw, int* partials);
+int ct_bias_act_backward_det(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot, int y_coff,
+                             int relu, int batch, int channels, int hw, float* dz, int dz_ctot, int dz_coff,
+                             float* dbias, unsigned* dz_absmax, void* scratch, size_t scratch_bytes, ct_stream_t stream);
+size_t ct_maxpool2x2_bias_relu_bwd_det_scratch_bytes(int batch, int channels, int* partials);
+int ct_maxpool2x2_bias_relu_bwd_det(const float* y, int y_ctot, int y_coff, const float* dy, int batch, int channels, int h, int w,
+                                    int oh, int ow, float* dz, int dz_ctot, int dz_coff, float* dbias, unsigned* dz_absmax,
+                                    void* scratch, size_t scratch_bytes, ct_stream_t stream);
+
 /* nn.BatchNorm2d(eps 1e-5, momentum 0.01) in training mode (models/RFB_Net_vgg.py:13,19), split in
  * three launches around the conv output z (channel slice [z_coff, z_coff+channels) of an NCHW buffer
  * with z_ctot channels; dz uses the same slicing):

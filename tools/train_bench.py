@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
    python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
-                               [--clip-norm X] [--json]
+                               [--clip-norm X] [--deterministic] [--json]
    --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
    --wgrad-h2: CTDET_WGRAD_H2=1 for this run (the 1x1 weight gradients on ct_conv2d_wgrad_h2);
    --clip-norm X: FusedSGD(max_grad_norm=X) (implies --fused-sgd; `inf` is the non-finite guard alone): the norm and the
    clipping coefficient are computed on the device in front of the update, a non-finite step is skipped;
-   --json: one more line, JSON, with the step time and the optimizer's device time (always with --clip-norm, where it
+   --deterministic: CTDET_TRAIN_DETERMINISTIC=1 for this run (ordered slab sums in place of the floating-point atomics of the
+   convolutional training step); after the timing line it prints `deterministic_repeat`: whether two runs
+   of the same step from the same state gave the same gradient bits, and with --fused-sgd under CTDET_LOSS_FUSED=1 the same
+   for the parameters after two steps (reported, not asserted);
+   --json: one more line, JSON, with the step time, the optimizer's device time and the training runtime's `policy` record
+   (always with --clip-norm and --deterministic; with --clip-norm it
    also carries the last norm, coef and the number of skipped steps);
    --per-tensor-groups: the groups of utils/solver.py::build_optimizer (one per tensor) instead of a single group."""
 import argparse, json, os, sys, time, types
@@ -19,13 +24,15 @@ ap.add_argument('--classes', type=int, default=20); ap.add_argument('--steps', t
 ap.add_argument('--sync', type=int, default=0)
 ap.add_argument('--phase', type=int, default=1); ap.add_argument('--setting', default='transfer')
 ap.add_argument('--fused-sgd', action='store_true'); ap.add_argument('--per-tensor-groups', action='store_true')
-ap.add_argument('--wgrad-h2', action='store_true')
+ap.add_argument('--wgrad-h2', action='store_true'); ap.add_argument('--deterministic', action='store_true')
 ap.add_argument('--clip-norm', type=float, default=None); ap.add_argument('--json', action='store_true')
 a = ap.parse_args()
 if a.clip_norm is not None:
     a.fused_sgd = True
 if a.wgrad_h2:
     os.environ['CTDET_WGRAD_H2'] = '1'         # read once, when the TrainRuntime is built
+if a.deterministic:
+    os.environ['CTDET_TRAIN_DETERMINISTIC'] = '1'      # the same
 from ctdet import synth, dist as cdist
 from models.RFB_Net_vgg import build_net
 from layers.functions import PriorBox
@@ -40,15 +47,16 @@ priors = PriorBox(getattr(cfgs, 'VOC_%d' % a.size)).forward().cuda()
 nout = a.classes if a.phase == 1 else net.OBJ_Target.weight.shape[0] + (a.classes if a.setting == 'incre' else 0)
 crit = MultiBoxLoss_combined(nout + 1, 0.5, True, 0, True, 3, 0.5, False)
 crit.sync_normalizer = world > 1
-if a.per_tensor_groups:
-    from utils import solver
-    opt = solver.build_optimizer(types.SimpleNamespace(method='ours', phase=a.phase, lr=1e-4, momentum=0.9, weight_decay=5e-4,
-                                                       max_grad_norm=a.clip_norm), net, fused=a.fused_sgd)
-elif a.fused_sgd:
-    from ctdet.optim import FusedSGD
-    opt = FusedSGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4, max_grad_norm=a.clip_norm)
-else:
-    opt = torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4)
+def make_opt():
+    if a.per_tensor_groups:
+        from utils import solver
+        return solver.build_optimizer(types.SimpleNamespace(method='ours', phase=a.phase, lr=1e-4, momentum=0.9, weight_decay=5e-4,
+                                                            max_grad_norm=a.clip_norm), net, fused=a.fused_sgd)
+    if a.fused_sgd:
+        from ctdet.optim import FusedSGD
+        return FusedSGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4, max_grad_norm=a.clip_norm)
+    return torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4)
+opt = make_opt()
 x = synth.images(a.batch, a.size, 'randn', 1234 + rank).cuda()
 tg = [t.cuda() for t in synth.targets(a.batch, nout + 1, 99 + rank)]
 trt = net.train_runtime(a.batch)
@@ -85,11 +93,32 @@ if rank == 0:
     print('RFBNet-%d phase %d bs=%d x %d GPU(s)%s: %.1f ms/step = %.1f img/s | fwd %.1f  loss %.1f  bwd %.1f ms | loss %.4f'
           % (a.size, a.phase, a.batch, world, ' [%s, %d groups]' % (type(opt).__name__, len(opt.param_groups))
              if a.fused_sgd or a.per_tensor_groups else '', dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
-    if a.json or a.clip_norm is not None:
+    if a.json or a.clip_norm is not None or a.deterministic:
         row = {'train_bench': 'RFBNet-%d phase %d' % (a.size, a.phase), 'batch': a.batch, 'gpus': world, 'steps': n,
                'optimizer': type(opt).__name__, 'groups': len(opt.param_groups), 'ms_per_step': round(dt * 1e3, 3),
                'fwd_ms': round(tf / n, 3), 'loss_ms': round(tl / n, 3), 'bwd_ms': round(tb / n, 3), 'opt_ms': round(to / n, 3),
                'clip_norm': a.clip_norm, 'loss': float(loss)}
         if a.clip_norm is not None:
             row.update(opt.clip_info())                 # norm, coef, finite, nonfinite of the last step
+        row['policy'] = trt.policy_record()             # deterministic: true / false, the weight-gradient routes
         print(json.dumps(row))
+if a.deterministic:
+    # two runs of the same step from the same state: parameters, BatchNorm buffers and a fresh optimizer each time
+    state0 = {k: v.clone() for k, v in net.state_dict().items()}
+    def rerun(steps):
+        global opt
+        net.load_state_dict(state0)
+        opt = make_opt()
+        for _ in range(steps):
+            step()
+        torch.cuda.synchronize()
+        return [None if p.grad is None else p.grad.clone() for p in net.parameters()], [p.detach().clone() for p in net.parameters()]
+    def same(u, v):
+        return all((x is None and y is None) or torch.equal(x, y) for x, y in zip(u, v))
+    (g1, _), (g2, _) = rerun(1), rerun(1)
+    rep = {'deterministic_repeat': same(g1, g2)}
+    if a.fused_sgd and os.environ.get('CTDET_LOSS_FUSED', '0') not in ('', '0'):
+        (_, p1), (_, p2) = rerun(2), rerun(2)
+        rep['deterministic_repeat_params_2_steps'] = same(p1, p2)
+    if rank == 0:
+        print(json.dumps(rep))
