@@ -15,6 +15,13 @@
 //                         over blockIdx.z, partial sums meet in dK/dV through float atomics)
 //   ctx_linear_bwd_kernel  y = Lin(x)+x: dx (+)= dy + dy W, dW += dy^T x, db += sum dy
 //   ctx_pool_bwd_kernel    max-pool backward of the context pooling (first maximum per window)
+// Partial sums of several workgroups meet in dK / dV (the query split), in dWz / dOBJ (one partial per workgroup of the output
+// pass) and in every linear's dW / db (the same): ct_ctx_attention_bwd adds them with float atomics into zeroed outputs.
+// ct_ctx_attention_bwd_det launches the same kernels over the same grids in their storing instantiations (template parameters
+// STORE / DET): every workgroup stores its partial into a slab of its own behind the plain workspace carve, nothing is memset, and
+//   ctx_kv_finish_kernel     adds the key side's slabs in slab order into dV, then (the dK launch reuses the area) into dK
+//   ctx_small_finish_kernel  ONE launch for dWz, dOBJ and every dW / db: a fixed tree in double, rounded once (include/ctdet.h)
+// so two calls on the same inputs give the same bits.
 #include "ct_common.h"
 #include "ct_attn_common.h"
 #include <mutex>
@@ -37,13 +44,16 @@ struct OutBwdArgs {
     float* dconf;           // [B][P][d]   (written)
     float* dDs;             // [B][P_pad][64] swizzled
     float* delta;           // [B][P_pad]
-    float* dwz;             // [d]    (atomics)
-    float* dobj;            // [T][d] (atomics)
+    float* dwz;             // [d]    (atomics; DET: the slabs [workgroup][(T + 1) d], a slab = dwz [d] then dobj [T][d])
+    float* dobj;            // [T][d] (atomics; DET: dwz + d)
     int P, P_pad, d, T, ostride, ooff, chunks;
     float scale;
 };
 
 // 256 threads = 64 rows x 4 feature quarters (16 features each); a block walks `chunks` 64-row chunks.
+// DET (ct_ctx_attention_bwd_det): the 64 rows' dwz sums meet in row order instead of through LDS atomics, and the block's totals
+// are STORED to slab blockIdx.y * gridDim.x + blockIdx.x for ctx_small_finish_kernel.
+template <bool DET>
 __global__ __launch_bounds__(256) void ctx_out_bwd_kernel(const OutBwdArgs a)
 {
     __shared__ float objw[32 * DP];          // [t][i]
@@ -134,15 +144,34 @@ __global__ __launch_bounds__(256) void ctx_out_bwd_kernel(const OutBwdArgs a)
         }
         __syncthreads();
     }
-    // block totals -> global (atomics)
+    if constexpr (DET) {
+        // block totals -> this block's slab (stores).  Ns is free after the last chunk's barrier: row rl's sums go through it and
+        // one thread per feature adds the 64 rows in row order
 #pragma unroll
-    for (int j = 0; j < 16; ++j) atomicAdd(&red[f0 + j], dwz_acc[j]);
-    __syncthreads();
-    if (tid < a.d) atomic_add_f32(&a.dwz[tid], red[tid]);
+        for (int j = 0; j < 16; ++j) Ns[rl * (DP + 1) + f0 + j] = dwz_acc[j];
+        __syncthreads();
+        const size_t slab = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (size_t)((a.T + 1) * a.d);
+        if (tid < a.d) {
+            float acc = 0.f;
+            for (int r = 0; r < 64; ++r) acc += Ns[r * (DP + 1) + tid];
+            a.dwz[slab + tid] = acc;
+        }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int e = tid + 256 * j, t = e >> 6, i = e & 63;
-        if (t < a.T && i < a.d) atomic_add_f32(&a.dobj[t * a.d + i], dobj_acc[j] * a.scale);
+        for (int j = 0; j < 8; ++j) {
+            const int e = tid + 256 * j, t = e >> 6, i = e & 63;
+            if (t < a.T && i < a.d) a.dobj[slab + t * a.d + i] = dobj_acc[j] * a.scale;
+        }
+    } else {
+        // block totals -> global (atomics)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) atomicAdd(&red[f0 + j], dwz_acc[j]);
+        __syncthreads();
+        if (tid < a.d) atomic_add_f32(&a.dwz[tid], red[tid]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int e = tid + 256 * j, t = e >> 6, i = e & 63;
+            if (t < a.T && i < a.d) atomic_add_f32(&a.dobj[t * a.d + i], dobj_acc[j] * a.scale);
+        }
     }
 }
 
@@ -331,7 +360,8 @@ struct BwdKVx3Args {
     const unsigned char *Qx1, *dDx1;        // 32-query tiles, mode 1 (contraction over features: S, dA)
     const unsigned char *Qx2, *dDx2;        // 32-query tiles, mode 2 (contraction over queries: dK, dV)
     const float *lse, *delta;
-    float *dK, *dV;                         // [B][M_pad][64] natural feature order, accumulated with atomics
+    float *dK, *dV;                         // [B][M_pad][64] natural feature order, accumulated with atomics; STORE: the
+                                            // slabs [split][B][M_pad][64] (split == 1: dK / dV themselves)
     int P_pad, M, M_pad, split;
 };
 // One kernel for both gradients needs 351 registers and 96 KB of LDS (one wave per SIMD: 4.4 ms at 512 bs 8); as two
@@ -344,7 +374,9 @@ struct KvCfg {
     static constexpr int LDS_BYTES = 2 * BUF_BYTES;
 };
 
-template <bool WANT_K>
+// STORE (ct_ctx_attention_bwd_det): the workgroup stores its accumulators into slab blockIdx.z instead of adding them into dK / dV;
+// a template parameter, so that the atomic instantiations keep their code (the kernel sits at its register limit).
+template <bool WANT_K, bool STORE = false>
 __global__ __launch_bounds__(256, 2) void ctx_attn_bwd_kv(const BwdKVx3Args a)
 {
     constexpr int NTILE = KvCfg<WANT_K>::NTILE, BUF_BYTES = KvCfg<WANT_K>::BUF_BYTES;
@@ -487,12 +519,37 @@ __global__ __launch_bounds__(256, 2) void ctx_attn_bwd_kv(const BwdKVx3Args a)
         __syncthreads();
     }
     // accumulator row r = feature acc_row(r, h) (g0) and 32 + that (g1)
-    float* orow = (WANT_K ? a.dK : a.dV) + ((size_t)b * a.M_pad + key) * DP;
+    if constexpr (STORE) {
+        float* orow = (WANT_K ? a.dK : a.dV) + (((size_t)blockIdx.z * gridDim.y + b) * a.M_pad + key) * DP;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int i = acc_row(r, h);
-        atomic_add_f32(&orow[i], g0[r]);
-        atomic_add_f32(&orow[32 + i], g1[r]);
+        for (int r = 0; r < 16; ++r) {
+            const int i = acc_row(r, h);
+            orow[i] = g0[r];
+            orow[32 + i] = g1[r];
+        }
+    } else {
+        float* orow = (WANT_K ? a.dK : a.dV) + ((size_t)b * a.M_pad + key) * DP;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = acc_row(r, h);
+            atomic_add_f32(&orow[i], g0[r]);
+            atomic_add_f32(&orow[32 + i], g1[r]);
+        }
+    }
+}
+
+// dK / dV of ct_ctx_attention_bwd_det: element e of the output = slab 0 + slab 1 + ... in slab order (fp32, as the atomics add,
+// but in ONE order); four elements per thread.
+__global__ __launch_bounds__(256) void ctx_kv_finish_kernel(const float4* __restrict__ slabs, int nslabs, size_t quads,
+                                                            float4* __restrict__ out)
+{
+    for (size_t e = blockIdx.x * (size_t)256 + threadIdx.x; e < quads; e += (size_t)gridDim.x * 256) {
+        float4 s = slabs[e];
+        for (int k = 1; k < nslabs; ++k) {
+            const float4 v = slabs[(size_t)k * quads + e];
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        out[e] = s;
     }
 }
 
@@ -505,12 +562,14 @@ struct LinBwdArgs {
     const float* x;
     const float* W;          // [d][d] (out, in)
     float* dx;               // [B][rows][d]
-    float* dW;               // [d][d] atomics
-    float* db;               // [d]    atomics
+    float* dW;               // [d][d] atomics (DET: the slabs [workgroup][(d + 1) d], a slab = dW [d][d] then db [d])
+    float* db;               // [d]    atomics (DET: dW + d d)
     long long dy_batch_stride;
     int rows, d, dy_stride, accumulate, chunks;
 };
 
+// DET (ct_ctx_attention_bwd_det): the block's dW / db totals are STORED to slab blockIdx.y * gridDim.x + blockIdx.x.
+template <bool DET>
 __global__ __launch_bounds__(256) void ctx_linear_bwd_kernel(const LinBwdArgs a)
 {
     __shared__ float Ws[DP * (DP + 1)];      // W[o][i]
@@ -573,12 +632,64 @@ __global__ __launch_bounds__(256) void ctx_linear_bwd_kernel(const LinBwdArgs a)
         }
     }
     const int o = rl;
-    if (o < a.d) {
+    if constexpr (DET) {
+        const size_t slab = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (size_t)((a.d + 1) * a.d);
+        if (o < a.d) {
 #pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (f0 + j < a.d) atomic_add_f32(&a.dW[o * a.d + f0 + j], dw_acc[j]);
+            for (int j = 0; j < 16; ++j)
+                if (f0 + j < a.d) a.dW[slab + o * a.d + f0 + j] = dw_acc[j];
+        }
+        if (tid < a.d) a.db[slab + tid] = db_acc;
+    } else {
+        if (o < a.d) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (f0 + j < a.d) atomic_add_f32(&a.dW[o * a.d + f0 + j], dw_acc[j]);
+        }
+        if (tid < a.d) atomic_add_f32(&a.db[tid], db_acc);
     }
-    if (tid < a.d) atomic_add_f32(&a.db[tid], db_acc);
+}
+
+// The small parameter gradients of ct_ctx_attention_bwd_det (dwz / dobj and every linear's dW / db) from their slabs, ONE launch:
+// blockIdx.y = the job, a block = 32 outputs x 8 image lanes.  Output e of a job whose slabs are [B][nx][n] floats, in double:
+//     s(b) = slab[b][0][e] + slab[b][1][e] + ... + slab[b][nx-1][e]        the slabs of image b in index order
+//     t(l) = s(l) + s(l + 8) + s(l + 16) + ...                             the images of lane l = b mod 8, ascending
+//     out  = float(t(0) + t(1) + ... + t(7))                               the lanes in order; rounded once
+// a fixed tree that depends on (B, nx) alone.  Outputs [0, n0) go to dst0, [n0, n) to dst1.
+struct SmallJob {
+    const float* slab;
+    float *dst0, *dst1;
+    int n0, n, nx;
+};
+struct SmallFinishArgs {
+    SmallJob job[5];
+    int B;
+};
+
+__global__ __launch_bounds__(256) void ctx_small_finish_kernel(const SmallFinishArgs a)
+{
+    __shared__ double part[8][32];
+    const SmallJob j = a.job[blockIdx.y];
+    if ((int)blockIdx.x * 32 >= j.n) return;
+    const int o = threadIdx.x & 31, l = threadIdx.x >> 5;
+    const int e = blockIdx.x * 32 + o;
+    double t = 0.0;
+    if (e < j.n)
+        for (int b = l; b < a.B; b += 8) {
+            const float* p = j.slab + (size_t)b * j.nx * j.n + e;
+            double s = 0.0;
+            for (int x = 0; x < j.nx; ++x) s += (double)p[(size_t)x * j.n];
+            t += s;
+        }
+    part[l][o] = t;
+    __syncthreads();
+    if (l == 0 && e < j.n) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += part[k][o];
+        if (e < j.n0) j.dst0[e] = (float)s;
+        else j.dst1[e - j.n0] = (float)s;
+    }
 }
 
 // channels-last max-pool backward, kernel = stride = k, ceil_mode: every input cell belongs to one
@@ -649,6 +760,45 @@ BwdWs carve_bwd(char* base, int batch, int P, int M)
     return w;
 }
 
+// workgroups the query tiles of one key block are spread over: enough to fill 256 CUs twice over
+int kv_split_of(int batch, int P_pad, int M_pad)
+{
+    const int kv_blocks = (M_pad / QB) * batch;
+    return std::max(1, std::min(P_pad / (8 * KT), (1024 + kv_blocks - 1) / kv_blocks));
+}
+
+// The slabs of ct_ctx_attention_bwd_det, behind the plain carve (include/ctdet.h has the formulas).  Sizes in floats, each area
+// rounded up to 256 bytes: kv = ONE area for the dV launch and then the dK launch (none with one split), out = dwz / dobj,
+// lin_q = theta (and as much again for fc_base), lin_k = phi and g each.
+struct DetSlabs {
+    int partials[4];
+    size_t kv, out, lin_q, lin_k;
+    int nlin_q;
+    size_t bytes;
+};
+
+DetSlabs det_slabs(int batch, int P, int M, int d, int t, int incre)
+{
+    DetSlabs s{};
+    const int P_pad = (P + QB - 1) / QB * QB, M_pad = (M + QB - 1) / QB * QB;
+    s.partials[0] = (P_pad + 255) / 256 * batch;
+    s.partials[1] = kv_split_of(batch, P_pad, M_pad);
+    s.partials[2] = (P + 255) / 256 * batch;
+    s.partials[3] = (M + 255) / 256 * batch;
+    s.kv = s.partials[1] > 1 ? (size_t)s.partials[1] * batch * M_pad * DP : 0;
+    s.out = (size_t)s.partials[0] * (t + 1) * d;
+    s.lin_q = (size_t)s.partials[2] * (d + 1) * d;
+    s.lin_k = (size_t)s.partials[3] * (d + 1) * d;
+    s.nlin_q = incre ? 2 : 1;
+    auto b = [](size_t floats) { return ctdet::align_up(floats * 4, 256); };
+    s.bytes = b(s.kv) + b(s.out) + s.nlin_q * b(s.lin_q) + 2 * b(s.lin_k);
+    return s;
+}
+
+int ctx_bwd_run(const char* who, bool det, const float* conf, const float* pool, int batch, int num_priors, int num_ctx,
+                const ct_ctx_params* prm, const void* saved, const float* dout, float* dconf, float* dpool,
+                const ct_ctx_grads* grads, void* workspace, size_t workspace_bytes, ct_stream_t stream);
+
 }  // namespace
 
 extern "C" size_t ct_ctx_attention_bwd_workspace_bytes(int batch, int num_priors, int num_ctx)
@@ -656,23 +806,75 @@ extern "C" size_t ct_ctx_attention_bwd_workspace_bytes(int batch, int num_priors
     return carve_bwd(nullptr, batch, num_priors, num_ctx).total;
 }
 
+extern "C" size_t ct_ctx_attention_bwd_det_workspace_bytes(int batch, int num_priors, int num_ctx, int d, int t, int incre,
+                                                           int partials[4])
+{
+    const bool ok = batch > 0 && num_priors > 0 && num_ctx > 0 && d >= 1 && d <= DP && t >= 1 && t <= 32;
+    const DetSlabs s = ok ? det_slabs(batch, num_priors, num_ctx, d, t, incre) : DetSlabs{};
+    if (partials)
+        for (int i = 0; i < 4; ++i) partials[i] = s.partials[i];
+    return ok ? carve_bwd(nullptr, batch, num_priors, num_ctx).total + s.bytes : 0;
+}
+
 extern "C" int ct_ctx_attention_bwd(const float* conf, const float* pool, int batch, int num_priors,
                                     int num_ctx, const ct_ctx_params* prm, const void* saved,
                                     const float* dout, float* dconf, float* dpool, const ct_ctx_grads* grads,
                                     void* workspace, size_t workspace_bytes, ct_stream_t stream)
 {
-    CT_REQUIRE(conf && pool && prm && saved && dout && dconf && dpool && grads && workspace,
-               "ct_ctx_attention_bwd: null pointer");
-    CT_REQUIRE(batch > 0 && num_priors > 0 && num_ctx > 0, "ct_ctx_attention_bwd: bad sizes");
-    CT_REQUIRE(prm->d >= 1 && prm->d <= DP && prm->t >= 1 && prm->t <= 32, "ct_ctx_attention_bwd: d=%d t=%d",
-               prm->d, prm->t);
+    return ctx_bwd_run("ct_ctx_attention_bwd", false, conf, pool, batch, num_priors, num_ctx, prm, saved, dout, dconf, dpool,
+                       grads, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ct_ctx_attention_bwd_det(const float* conf, const float* pool, int batch, int num_priors,
+                                        int num_ctx, const ct_ctx_params* prm, const void* saved,
+                                        const float* dout, float* dconf, float* dpool, const ct_ctx_grads* grads,
+                                        void* workspace, size_t workspace_bytes, ct_stream_t stream)
+{
+    return ctx_bwd_run("ct_ctx_attention_bwd_det", true, conf, pool, batch, num_priors, num_ctx, prm, saved, dout, dconf, dpool,
+                       grads, workspace, workspace_bytes, stream);
+}
+
+namespace {
+
+// det = 0: the launches of ct_ctx_attention_bwd (memsets, atomics).  det = 1: the same kernels over the same partition in their
+// storing instantiations, the slabs behind the plain carve, two finishing kernels, no memset.
+int ctx_bwd_run(const char* who, bool det, const float* conf, const float* pool, int batch, int num_priors, int num_ctx,
+                const ct_ctx_params* prm, const void* saved, const float* dout, float* dconf, float* dpool,
+                const ct_ctx_grads* grads, void* workspace, size_t workspace_bytes, ct_stream_t stream)
+{
+    CT_REQUIRE(conf && pool && prm && saved && dout && dconf && dpool && grads && (det || workspace), "%s: null pointer", who);
+    CT_REQUIRE(batch > 0 && num_priors > 0 && num_ctx > 0, "%s: bad sizes", who);
+    CT_REQUIRE(prm->d >= 1 && prm->d <= DP && prm->t >= 1 && prm->t <= 32, "%s: d=%d t=%d", who, prm->d, prm->t);
     CT_REQUIRE(grads->theta_w && grads->theta_b && grads->phi_w && grads->phi_b && grads->g_w && grads->g_b &&
-                   grads->wz && grads->obj_w, "ct_ctx_attention_bwd: null gradient buffer");
-    CT_REQUIRE(!prm->fc_w || (grads->fc_w && grads->fc_b && prm->fc_b), "ct_ctx_attention_bwd: fc gradient missing");
-    const size_t need = ct_ctx_attention_bwd_workspace_bytes(batch, num_priors, num_ctx);
-    if (workspace_bytes < need)
-        return ctdet::fail(CT_ERR_WORKSPACE, "ct_ctx_attention_bwd: workspace %zu < %zu", workspace_bytes, need);
+                   grads->wz && grads->obj_w, "%s: null gradient buffer", who);
+    CT_REQUIRE(!prm->fc_w || (grads->fc_w && grads->fc_b && prm->fc_b), "%s: fc gradient missing", who);
+    const size_t plain_need = ct_ctx_attention_bwd_workspace_bytes(batch, num_priors, num_ctx);
+    DetSlabs ds{};
+    if (det) {
+        CT_REQUIRE(workspace, "%s: workspace is null", who);
+        CT_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+        ds = det_slabs(batch, num_priors, num_ctx, prm->d, prm->t, prm->fc_w != nullptr);
+        if (workspace_bytes < plain_need + ds.bytes)
+            return ctdet::fail(CT_ERR_WORKSPACE, "%s: workspace_bytes %zu, needs %zu", who, workspace_bytes,
+                               plain_need + ds.bytes);
+    } else if (workspace_bytes < plain_need) {
+        return ctdet::fail(CT_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, plain_need);
+    }
     BwdWs w = carve_bwd((char*)workspace, batch, num_priors, num_ctx);
+    // det: the slab areas, in the order of det_slabs
+    float *slab_kv = nullptr, *slab_out = nullptr, *slab_theta = nullptr, *slab_fc = nullptr, *slab_phi = nullptr,
+          *slab_g = nullptr;
+    if (det) {
+        char* p = (char*)workspace + w.total;
+        auto take = [&](size_t floats) {
+            float* r = (float*)p;
+            p += ctdet::align_up(floats * 4, 256);
+            return r;
+        };
+        slab_kv = take(ds.kv); slab_out = take(ds.out); slab_theta = take(ds.lin_q);
+        if (prm->fc_w) slab_fc = take(ds.lin_q);
+        slab_phi = take(ds.lin_k); slab_g = take(ds.lin_k);
+    }
     hipStream_t st = ctdet::as_stream(stream);
     const int d = prm->d, T = prm->t;
     const int ostride = (prm->fc_w ? d : 0) + T;
@@ -681,20 +883,22 @@ extern "C" int ct_ctx_attention_bwd(const float* conf, const float* pool, int ba
     const float* save_d = (const float*)saved;
     const float* save_lse = save_d + (size_t)batch * w.P_pad * DP;
 
-    // zero the accumulated outputs
-    CT_HIP(hipMemsetAsync(grads->theta_w, 0, (size_t)d * d * 4, st));
-    CT_HIP(hipMemsetAsync(grads->phi_w, 0, (size_t)d * d * 4, st));
-    CT_HIP(hipMemsetAsync(grads->g_w, 0, (size_t)d * d * 4, st));
-    CT_HIP(hipMemsetAsync(grads->theta_b, 0, (size_t)d * 4, st));
-    CT_HIP(hipMemsetAsync(grads->phi_b, 0, (size_t)d * 4, st));
-    CT_HIP(hipMemsetAsync(grads->g_b, 0, (size_t)d * 4, st));
-    CT_HIP(hipMemsetAsync(grads->wz, 0, (size_t)d * 4, st));
-    CT_HIP(hipMemsetAsync(grads->obj_w, 0, (size_t)T * d * 4, st));
-    if (prm->fc_w) {
-        CT_HIP(hipMemsetAsync(grads->fc_w, 0, (size_t)d * d * 4, st));
-        CT_HIP(hipMemsetAsync(grads->fc_b, 0, (size_t)d * 4, st));
+    // zero the accumulated outputs (det: every output and every slab element is stored by its producer)
+    if (!det) {
+        CT_HIP(hipMemsetAsync(grads->theta_w, 0, (size_t)d * d * 4, st));
+        CT_HIP(hipMemsetAsync(grads->phi_w, 0, (size_t)d * d * 4, st));
+        CT_HIP(hipMemsetAsync(grads->g_w, 0, (size_t)d * d * 4, st));
+        CT_HIP(hipMemsetAsync(grads->theta_b, 0, (size_t)d * 4, st));
+        CT_HIP(hipMemsetAsync(grads->phi_b, 0, (size_t)d * 4, st));
+        CT_HIP(hipMemsetAsync(grads->g_b, 0, (size_t)d * 4, st));
+        CT_HIP(hipMemsetAsync(grads->wz, 0, (size_t)d * 4, st));
+        CT_HIP(hipMemsetAsync(grads->obj_w, 0, (size_t)T * d * 4, st));
+        if (prm->fc_w) {
+            CT_HIP(hipMemsetAsync(grads->fc_w, 0, (size_t)d * d * 4, st));
+            CT_HIP(hipMemsetAsync(grads->fc_b, 0, (size_t)d * 4, st));
+        }
+        CT_HIP(hipMemsetAsync(w.dK, 0, ((char*)w.dV - (char*)w.dK) + (size_t)batch * w.M_pad * DP * 4, st));
     }
-    CT_HIP(hipMemsetAsync(w.dK, 0, ((char*)w.dV - (char*)w.dK) + (size_t)batch * w.M_pad * DP * 4, st));
 
     // recompute the projections in the operand layouts of the two MFMA kernels
     hipLaunchKernelGGL(ctx_project_kernel, dim3(w.P_pad / 64, batch), blk, 0, st, conf, num_priors, w.P_pad, d,
@@ -710,15 +914,15 @@ extern "C" int ct_ctx_attention_bwd(const float* conf, const float* pool, int ba
     OutBwdArgs oa{};
     oa.conf = conf; oa.D = save_d; oa.dout = dout; oa.wz = prm->wz; oa.obj_w = prm->obj_w;
     oa.dconf = dconf; oa.dDs = w.dDs; oa.delta = w.delta;
-    oa.dwz = grads->wz; oa.dobj = grads->obj_w;
+    oa.dwz = det ? slab_out : grads->wz; oa.dobj = det ? slab_out + d : grads->obj_w;
     oa.P = num_priors; oa.P_pad = w.P_pad; oa.d = d; oa.T = T; oa.ostride = ostride;
     oa.ooff = prm->fc_w ? d : 0; oa.chunks = 4; oa.scale = prm->scale;
-    hipLaunchKernelGGL(ctx_out_bwd_kernel, dim3((w.P_pad / 64 + oa.chunks - 1) / oa.chunks, batch), blk, 0, st, oa);
+    const dim3 out_grid((w.P_pad / 64 + oa.chunks - 1) / oa.chunks, batch);
+    if (det) hipLaunchKernelGGL(ctx_out_bwd_kernel<true>, out_grid, blk, 0, st, oa);
+    else hipLaunchKernelGGL(ctx_out_bwd_kernel<false>, out_grid, blk, 0, st, oa);
     CT_LAUNCH_CHECK("ctx_out_bwd_kernel");
 
-    // enough workgroups to fill 256 CUs twice over
-    const int kv_blocks = (w.M_pad / QB) * batch;
-    const int kv_split = std::max(1, std::min(w.P_pad / (8 * KT), (1024 + kv_blocks - 1) / kv_blocks));
+    const int kv_split = kv_split_of(batch, w.P_pad, w.M_pad);
     {
         auto to_x3 = [&](const float* src, int rows_pad, unsigned char* dst, int mode) {
             hipLaunchKernelGGL(ctx_rows_to_x3_kernel, dim3(rows_pad / 64, batch), blk, 0, st, src, rows_pad,
@@ -765,10 +969,43 @@ extern "C" int ct_ctx_attention_bwd(const float* conf, const float* pool, int ba
         ka.Kx0 = w.Kx0; ka.Vx0 = w.Vx0; ka.Qx1 = w.Qx1; ka.dDx1 = w.dDx1; ka.Qx2 = w.Qx2; ka.dDx2 = w.dDx2;
         ka.lse = save_lse; ka.delta = w.delta; ka.dK = w.dK; ka.dV = w.dV;
         ka.P_pad = w.P_pad; ka.M = num_ctx; ka.M_pad = w.M_pad; ka.split = kv_split;
-        hipLaunchKernelGGL(ctx_attn_bwd_kv<false>, dim3(w.M_pad / QB, batch, kv_split), blk, KvCfg<false>::LDS_BYTES, st, ka);
-        CT_LAUNCH_CHECK("ctx_attn_bwd_kv<dV>");
-        hipLaunchKernelGGL(ctx_attn_bwd_kv<true>, dim3(w.M_pad / QB, batch, kv_split), blk, KvCfg<true>::LDS_BYTES, st, ka);
-        CT_LAUNCH_CHECK("ctx_attn_bwd_kv<dK>");
+        const dim3 kv_grid(w.M_pad / QB, batch, kv_split);
+        if (!det) {
+            hipLaunchKernelGGL(ctx_attn_bwd_kv<false>, kv_grid, blk, KvCfg<false>::LDS_BYTES, st, ka);
+            CT_LAUNCH_CHECK("ctx_attn_bwd_kv<dV>");
+            hipLaunchKernelGGL(ctx_attn_bwd_kv<true>, kv_grid, blk, KvCfg<true>::LDS_BYTES, st, ka);
+            CT_LAUNCH_CHECK("ctx_attn_bwd_kv<dK>");
+        } else {
+            static std::once_flag once_det;
+            static hipError_t attr_det = hipSuccess;
+            std::call_once(once_det, [] {
+                attr_det = hipFuncSetAttribute((const void*)ctx_attn_bwd_kv<true, true>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, KvCfg<true>::LDS_BYTES);
+                if (attr_det == hipSuccess)
+                    attr_det = hipFuncSetAttribute((const void*)ctx_attn_bwd_kv<false, true>,
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, KvCfg<false>::LDS_BYTES);
+            });
+            CT_HIP(attr_det);
+            // one split: the workgroups store straight into dV / dK.  More: into the slab area, which the dV launch's finish has
+            // read (stream order) before the dK launch writes it
+            const size_t quads = (size_t)batch * w.M_pad * DP / 4;
+            const dim3 fin_grid((unsigned)std::min<size_t>((quads + 255) / 256, 4096));
+            if (kv_split > 1) ka.dK = ka.dV = slab_kv;
+            hipLaunchKernelGGL((ctx_attn_bwd_kv<false, true>), kv_grid, blk, KvCfg<false>::LDS_BYTES, st, ka);
+            CT_LAUNCH_CHECK("ctx_attn_bwd_kv<dV, store>");
+            if (kv_split > 1) {
+                hipLaunchKernelGGL(ctx_kv_finish_kernel, fin_grid, blk, 0, st, (const float4*)slab_kv, kv_split, quads,
+                                   (float4*)w.dV);
+                CT_LAUNCH_CHECK("ctx_kv_finish_kernel(dV)");
+            }
+            hipLaunchKernelGGL((ctx_attn_bwd_kv<true, true>), kv_grid, blk, KvCfg<true>::LDS_BYTES, st, ka);
+            CT_LAUNCH_CHECK("ctx_attn_bwd_kv<dK, store>");
+            if (kv_split > 1) {
+                hipLaunchKernelGGL(ctx_kv_finish_kernel, fin_grid, blk, 0, st, (const float4*)slab_kv, kv_split, quads,
+                                   (float4*)w.dK);
+                CT_LAUNCH_CHECK("ctx_kv_finish_kernel(dK)");
+            }
+        }
     }
 
     // projections backward
@@ -778,22 +1015,47 @@ extern "C" int ct_ctx_attention_bwd(const float* conf, const float* pool, int ba
         la.dy = dy; la.x = x; la.W = W; la.dx = dx; la.dW = dW; la.db = db;
         la.dy_batch_stride = dy_bs; la.rows = rows; la.d = d; la.dy_stride = dy_stride;
         la.accumulate = accumulate; la.chunks = 4;
-        hipLaunchKernelGGL(ctx_linear_bwd_kernel, dim3((rows + 64 * la.chunks - 1) / (64 * la.chunks), batch), blk,
-                           0, st, la);
+        const dim3 grid((rows + 64 * la.chunks - 1) / (64 * la.chunks), batch);
+        if (det) hipLaunchKernelGGL(ctx_linear_bwd_kernel<true>, grid, blk, 0, st, la);
+        else hipLaunchKernelGGL(ctx_linear_bwd_kernel<false>, grid, blk, 0, st, la);
         CT_LAUNCH_CHECK(name);
         return CT_OK;
     };
+    // det: dW / db of a linear = its slab area (a slab = dW [d][d] then db [d])
+    auto dW_of = [&](float* slab, float* g) { return det ? slab : g; };
+    auto db_of = [&](float* slab, float* g) { return det ? slab + d * d : g; };
     if (int rc = linear(w.dQ, (long long)w.P_pad * DP, DP, conf, num_priors, prm->theta_w, dconf, 1,
-                        grads->theta_w, grads->theta_b, "ctx_linear_bwd_kernel(theta)")) return rc;
+                        dW_of(slab_theta, grads->theta_w), db_of(slab_theta, grads->theta_b),
+                        "ctx_linear_bwd_kernel(theta)")) return rc;
     if (prm->fc_w)
         if (int rc = linear(dout, (long long)num_priors * ostride, ostride, conf, num_priors, prm->fc_w, dconf, 1,
-                            grads->fc_w, grads->fc_b, "ctx_linear_bwd_kernel(fc_base)")) return rc;
-    if (int rc = linear(w.dK, (long long)w.M_pad * DP, DP, pool, num_ctx, prm->phi_w, dpool, 0, grads->phi_w,
-                        grads->phi_b, "ctx_linear_bwd_kernel(phi)")) return rc;
-    if (int rc = linear(w.dV, (long long)w.M_pad * DP, DP, pool, num_ctx, prm->g_w, dpool, 1, grads->g_w,
-                        grads->g_b, "ctx_linear_bwd_kernel(g)")) return rc;
+                            dW_of(slab_fc, grads->fc_w), db_of(slab_fc, grads->fc_b), "ctx_linear_bwd_kernel(fc_base)"))
+            return rc;
+    if (int rc = linear(w.dK, (long long)w.M_pad * DP, DP, pool, num_ctx, prm->phi_w, dpool, 0,
+                        dW_of(slab_phi, grads->phi_w), db_of(slab_phi, grads->phi_b), "ctx_linear_bwd_kernel(phi)")) return rc;
+    if (int rc = linear(w.dV, (long long)w.M_pad * DP, DP, pool, num_ctx, prm->g_w, dpool, 1,
+                        dW_of(slab_g, grads->g_w), db_of(slab_g, grads->g_b), "ctx_linear_bwd_kernel(g)")) return rc;
+    if (det) {
+        // every small parameter gradient from its slabs, one launch
+        SmallFinishArgs fa{};
+        int nj = 0, nmax = 0;
+        auto job = [&](const float* slab, float* dst0, float* dst1, int n0, int n, int per_image) {
+            fa.job[nj++] = SmallJob{slab, dst0, dst1, n0, n, per_image};
+            nmax = std::max(nmax, n);
+        };
+        job(slab_out, grads->wz, grads->obj_w, d, (T + 1) * d, ds.partials[0] / batch);
+        job(slab_theta, grads->theta_w, grads->theta_b, d * d, (d + 1) * d, ds.partials[2] / batch);
+        if (prm->fc_w) job(slab_fc, grads->fc_w, grads->fc_b, d * d, (d + 1) * d, ds.partials[2] / batch);
+        job(slab_phi, grads->phi_w, grads->phi_b, d * d, (d + 1) * d, ds.partials[3] / batch);
+        job(slab_g, grads->g_w, grads->g_b, d * d, (d + 1) * d, ds.partials[3] / batch);
+        fa.B = batch;
+        hipLaunchKernelGGL(ctx_small_finish_kernel, dim3((nmax + 31) / 32, nj), blk, 0, st, fa);
+        CT_LAUNCH_CHECK("ctx_small_finish_kernel");
+    }
     return CT_OK;
 }
+
+}  // namespace
 
 extern "C" int ct_ctx_pool_bwd(const float* in, long long in_img_stride, const float* dpool,
                                long long dpool_img_stride, float* din, long long din_img_stride, int batch,

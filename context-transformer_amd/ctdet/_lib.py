@@ -266,6 +266,9 @@ SIGNATURES = {
     'ct_ctx_attention_bwd_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_ctx_attention_bwd': (_I, [_P, _P, _I, _I, _I, C.POINTER(CtxParams), _P, _P, _P, _P, C.POINTER(CtxGrads),
                                   _P, _Z, _P]),
+    'ct_ctx_attention_bwd_det_workspace_bytes': (_Z, [_I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    'ct_ctx_attention_bwd_det': (_I, [_P, _P, _I, _I, _I, C.POINTER(CtxParams), _P, _P, _P, _P, C.POINTER(CtxGrads),
+                                      _P, _Z, _P]),
     'ct_ctx_pool_bwd': (_I, [_P, _LL, _P, _LL, _P, _LL, _I, _I, _I, _I, _I, _P]),
 }
 

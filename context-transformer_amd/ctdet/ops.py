@@ -790,15 +790,22 @@ def ctx_attention_buffers(B, P, M, d, T, setting_incre, device):
 class CtxTrainer:
     """Forward-with-saved-rows + backward of the Context-Transformer block for one (B, P, M, d, T)
     (train.py:222-229 differentiates models/RFB_Net_vgg.py:253-271 through autograd).  Owns the
-    workspaces; gradients come back in fresh tensors keyed like `params`."""
+    workspaces; gradients come back in fresh tensors keyed like `params`.  deterministic=True: the backward is
+    ct_ctx_attention_bwd_det (slabs added in a fixed order in place of floating-point atomics; the workspace holds them too)."""
     KEYS = ('theta_w', 'theta_b', 'phi_w', 'phi_b', 'g_w', 'g_b', 'wz', 'obj_w')
 
-    def __init__(self, B, P, M, d, T, incre, device):
+    def __init__(self, B, P, M, d, T, incre, device, deterministic=False):
         self.B, self.P, self.M, self.d, self.T, self.incre = B, P, M, d, T, bool(incre)
         self.device = torch.device(device)
+        self.deterministic = bool(deterministic)
         L = lib()
-        self.ws_bytes = max(L.ct_ctx_attention_workspace_bytes(B, P, M, d),
-                            L.ct_ctx_attention_bwd_workspace_bytes(B, P, M))
+        self.bwd_entry = 'ct_ctx_attention_bwd_det' if self.deterministic else 'ct_ctx_attention_bwd'
+        if self.deterministic:
+            bwd_bytes = L.ct_ctx_attention_bwd_det_workspace_bytes(B, P, M, d, T, int(self.incre), None)
+            self.slab_bytes = bwd_bytes - L.ct_ctx_attention_bwd_workspace_bytes(B, P, M)
+        else:
+            bwd_bytes, self.slab_bytes = L.ct_ctx_attention_bwd_workspace_bytes(B, P, M), 0
+        self.ws_bytes = max(L.ct_ctx_attention_workspace_bytes(B, P, M, d), bwd_bytes)
         self.ws = torch.empty(self.ws_bytes, device=self.device, dtype=torch.uint8)
         self.saved_bytes = L.ct_ctx_attention_saved_bytes(B, P)
         self.saved = torch.empty(self.saved_bytes, device=self.device, dtype=torch.uint8)
@@ -822,11 +829,11 @@ class CtxTrainer:
         g = _lib.CtxGrads()
         for k in self.keys:
             setattr(g, k, _dev(grads[k], 'd' + k).value)
-        check(lib().ct_ctx_attention_bwd(_dev(conf, 'conf'), _dev(pool, 'pool'), self.B, self.P, self.M, C.byref(prm),
-                                         _dev(self.saved, 'saved', torch.uint8), _dev(dout, 'dout'),
-                                         _dev(self.dconf, 'dconf'), _dev(self.dpool, 'dpool'), C.byref(g),
-                                         _dev(self.ws, 'ws', torch.uint8), self.ws_bytes, _stream()),
-              'ct_ctx_attention_bwd')
+        check(getattr(lib(), self.bwd_entry)(_dev(conf, 'conf'), _dev(pool, 'pool'), self.B, self.P, self.M, C.byref(prm),
+                                             _dev(self.saved, 'saved', torch.uint8), _dev(dout, 'dout'),
+                                             _dev(self.dconf, 'dconf'), _dev(self.dpool, 'dpool'), C.byref(g),
+                                             _dev(self.ws, 'ws', torch.uint8), self.ws_bytes, _stream()),
+              self.bwd_entry)
         return self.dconf, self.dpool, grads
 
 

@@ -20,7 +20,9 @@ Buffers are owned by the runtime and reused every step (call backward before the
 
 CTDET_TRAIN_DETERMINISTIC=1 (opt-in): the weight gradients, BatchNorm reductions and bias sums run their `_det` twins (one slab
 per split, added in order, in place of floating-point atomics: include/ctdet.h), so the convolutional step repeats bit for bit;
-the Context-Transformer block is refused under it.
+the Context-Transformer block is refused under it.  CTDET_TRAIN_DETERMINISTIC=2: all of that, and the block's backward runs
+ct_ctx_attention_bwd_det (ops.CtxTrainer(deterministic=True)), so forward(use_ctx=True) is accepted and a whole phase-2 step
+repeats bit for bit.
 """
 import ctypes as C
 import os
@@ -87,13 +89,15 @@ class TrainSwitches:
     fuse_pool_bwd: bool     # CTDET_TRAIN_FUSE_POOL_BWD=0: pool backward and bias / ReLU backward as two kernels
     streams: int            # CTDET_TRAIN_STREAMS=1: weight gradients on the caller's stream
     ksplit: int             # CTDET_KSPLIT=0: no split-K slabs for the data gradients
-    deterministic: bool = False     # CTDET_TRAIN_DETERMINISTIC=1: ordered slab sums in place of the floating-point atomics
+    deterministic: bool = False     # CTDET_TRAIN_DETERMINISTIC=1 or 2: ordered slab sums in place of the floating-point atomics
+    deterministic_ctx: bool = False     # CTDET_TRAIN_DETERMINISTIC=2: the Context-Transformer block's backward too
 
     @classmethod
     def of(cls, env):
+        det = env.get('CTDET_TRAIN_DETERMINISTIC', '0')
         return cls(env.get('CTDET_PACK_BATCH', '1') != '0', env.get('CTDET_PREZERO', '1') != '0',
                    env.get('CTDET_TRAIN_FUSE_POOL_BWD', '1') != '0', int(env.get('CTDET_TRAIN_STREAMS', '2')),
-                   int(env.get('CTDET_KSPLIT', '1')), env.get('CTDET_TRAIN_DETERMINISTIC', '0') not in ('', '0'))
+                   int(env.get('CTDET_KSPLIT', '1')), det not in ('', '0'), det == '2')
 
 
 class PackList:
@@ -132,13 +136,13 @@ class TrainRuntime:
         self._x3_list, self._h2_list = PackList(self.lib, 'ct_conv_x3_pack'), PackList(self.lib, 'ct_conv_wino_h2_pack')
         self.bucketer, self.generation, self.used_ctx, self.amax_slots, self._wired_epoch = None, 0, False, {}, None
         self.wgrad_wsh2 = self.wgrad_ws_all = self.bn_scratch = self.wgrad_wsdet = self.det_scratch = None
-        self.det = self.switches.deterministic
+        self.det, self.det_ctx = self.switches.deterministic, self.switches.deterministic_ctx
         self.params, self._pindex, self.ctx = [], {}, None      # params: ordered parameters that receive gradients
         if self.plan.ctx:
             C_ = net.num_classes
             self.P = self.bufs['conf'].shape[1] // C_
             self.ctx = ops.CtxTrainer(batch, self.P, self.plan.M, C_, net.OBJ_Target.weight.shape[0],
-                                      net.setting == 'incre', backend.device)
+                                      net.setting == 'incre', backend.device, deterministic=self.det_ctx)
             self.ctx_params = dict(obj_w=net.OBJ_Target.weight, wz=net.Wz, theta_w=net.theta.weight, theta_b=net.theta.bias,
                                    phi_w=net.phi.weight, phi_b=net.phi.bias, g_w=net.g.weight, g_b=net.g.bias)
             if net.setting == 'incre':
@@ -545,10 +549,10 @@ class TrainRuntime:
 
     def forward(self, x, use_ctx=True):
         lib, B = self.lib, self.batch
-        if self.det and use_ctx and self.ctx is not None:
+        if self.det and not self.det_ctx and use_ctx and self.ctx is not None:
             raise _lib.CtdetError('CTDET_TRAIN_DETERMINISTIC=1 does not cover the Context-Transformer block: ct_ctx_attention_bwd '
-                                  'sums through floating-point atomics (csrc/ct_attn_bwd.hip); unset the switch for a phase-2 '
-                                  "'ours' network")
+                                  'sums through floating-point atomics (csrc/ct_attn_bwd.hip); set the switch to 2 '
+                                  "(ct_ctx_attention_bwd_det) or unset it for a phase-2 'ours' network")
         self.generation += 1                        # saved activations belong to THIS forward
         self.used_ctx = bool(use_ctx and self.ctx is not None)
         if tuple(x.shape) != tuple(self.bufs['x'].shape):
@@ -628,10 +632,16 @@ class TrainRuntime:
         routes = {}
         for s in self.state.values():
             routes[s.wgrad_route.name] = routes.get(s.wgrad_route.name, 0) + 1
+        det_bytes = None
+        if self.det:
+            det_bytes = {'wgrad_wsdet': self.wgrad_wsdet.numel(), 'det_scratch': self.det_scratch.numel() * 8}
+            if self.det_ctx and self.ctx is not None:
+                det_bytes['ctx_slabs'] = self.ctx.slab_bytes        # behind the plain carve of the block's workspace
         return {
             'deterministic': self.det,
+            'deterministic_ctx': self.det_ctx,
             'wgrad_routes': dict(sorted(routes.items())),
-            'det_workspace_bytes': {'wgrad_wsdet': self.wgrad_wsdet.numel(), 'det_scratch': self.det_scratch.numel() * 8} if self.det else None,
+            'det_workspace_bytes': det_bytes,
         }
 
     # ------------------------------------------------------------------ backward

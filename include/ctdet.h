@@ -1166,6 +1166,33 @@ int ct_ctx_attention_bwd(const float* conf, const float* pool, int batch, int nu
                          const ct_ctx_params* prm, const void* saved, const float* dout, float* dconf,
                          float* dpool, const ct_ctx_grads* grads, void* workspace,
                          size_t workspace_bytes, ct_stream_t stream);
+/* The deterministic twin of ct_ctx_attention_bwd (the `_det` rules above: same kernels, same partition, stores in place of
+ * atomics, the workspace may hold anything on entry, nothing is memset, every output is overwritten).  Arguments, results and
+ * refusals are those of ct_ctx_attention_bwd; a workspace that is NULL or not 16-byte aligned is CT_ERR_INVALID, one smaller than
+ * the query's answer CT_ERR_WORKSPACE.  With P_pad / M_pad = num_priors / num_ctx rounded up to 128, partial sums meet at four
+ * sites; partials[] (may be NULL) reports how many per output element:
+ *     [0] = ceil(P_pad / 256) * batch        the output pass: dwz [d], dobj [t][d]        (one per workgroup, 256 query rows)
+ *     [1] = max(1, min(P_pad / 256, ceil(1024 / ((M_pad / 128) * batch))))                 the key side: dK, dV (kv_split)
+ *     [2] = ceil(num_priors / 256) * batch   the query-side linears: theta, fc_base        (dW [d][d], db [d] per workgroup)
+ *     [3] = ceil(num_ctx / 256) * batch      the key-side linears: phi, g
+ * Workspace: the carve of ct_ctx_attention_bwd_workspace_bytes, then fp32 slabs, each area rounded up to 256 bytes:
+ *     [partials[1]][batch][M_pad][64]        dV's slabs, then (stream order) dK's in the same area; absent when partials[1] == 1,
+ *                                            the workgroups then store straight into dK / dV
+ *     [partials[0]][(t + 1) * d]             dwz, dobj
+ *     [partials[2]][(d + 1) * d]             theta; once more for fc_base when incre != 0
+ *     [partials[3]][(d + 1) * d]             phi, and once more for g
+ * Inside the output pass the 64 rows of a workgroup add their dwz terms in row order (no LDS atomics).  Order of the sums: dK / dV
+ * element = slab 0 + slab 1 + ... in fp32, in slab order.  A small gradient whose slabs are [batch][nx] (workgroup x of image b
+ * writes slab b * nx + x), in double, rounded once to fp32:
+ *     s(b) = slab[b][0] + slab[b][1] + ... + slab[b][nx-1];   t(l) = s(l) + s(l + 8) + s(l + 16) + ...  (l = 0 .. 7);
+ *     out  = t(0) + t(1) + ... + t(7)
+ * -- a fixed tree that depends on (batch, nx) alone.  The query is host code; 0 (partials all 0) for a non-positive size, d outside
+ * 1 .. 64 or t outside 1 .. 32. */
+size_t ct_ctx_attention_bwd_det_workspace_bytes(int batch, int num_priors, int num_ctx, int d, int t, int incre, int partials[4]);
+int ct_ctx_attention_bwd_det(const float* conf, const float* pool, int batch, int num_priors, int num_ctx,
+                             const ct_ctx_params* prm, const void* saved, const float* dout, float* dconf,
+                             float* dpool, const ct_ctx_grads* grads, void* workspace,
+                             size_t workspace_bytes, ct_stream_t stream);
 /* Backward of ct_ctx_pool_fwd (max_pool2d, kernel = stride = k, ceil_mode, channels-last): adds the
  * window gradient dpool to din at the first maximum of each window (torch's tie rule). */
 int ct_ctx_pool_bwd(const float* in, long long in_img_stride, const float* dpool,

@@ -2,14 +2,17 @@
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
    python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
                                [--clip-norm X] [--deterministic] [--json]
+   --classes: classes of the conf head; default 20, with --phase 2 the width of the Context-Transformer block (60 for 'transfer',
+   15 for 'incre': the head feeds the block);
    --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
    --wgrad-h2: CTDET_WGRAD_H2=1 for this run (the 1x1 weight gradients on ct_conv2d_wgrad_h2);
    --clip-norm X: FusedSGD(max_grad_norm=X) (implies --fused-sgd; `inf` is the non-finite guard alone): the norm and the
    clipping coefficient are computed on the device in front of the update, a non-finite step is skipped;
    --deterministic: CTDET_TRAIN_DETERMINISTIC=1 for this run (ordered slab sums in place of the floating-point atomics of the
-   convolutional training step); after the timing line it prints `deterministic_repeat`: whether two runs
-   of the same step from the same state gave the same gradient bits, and with --fused-sgd under CTDET_LOSS_FUSED=1 the same
-   for the parameters after two steps (reported, not asserted);
+   convolutional training step, DESIGN.md section 6; with --phase 2 level 2, which adds the Context-Transformer block's backward);
+   after the timing line it prints `deterministic_repeat`: whether two runs of the same step from the same state gave the same
+   gradient bits (every parameter of the network, at phase 2 the block's included), and with --fused-sgd under CTDET_LOSS_FUSED=1
+   the same for the parameters after two steps (reported, not asserted);
    --json: one more line, JSON, with the step time, the optimizer's device time and the training runtime's `policy` record
    (always with --clip-norm and --deterministic; with --clip-norm it
    also carries the last norm, coef and the number of skipped steps);
@@ -20,7 +23,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, 'context-transformer_amd')); sys.path.insert(0, REPO)
 ap = argparse.ArgumentParser()
 ap.add_argument('--size', type=int, default=300); ap.add_argument('--batch', type=int, default=32)
-ap.add_argument('--classes', type=int, default=20); ap.add_argument('--steps', type=int, default=5)
+ap.add_argument('--classes', type=int, default=None); ap.add_argument('--steps', type=int, default=5)
 ap.add_argument('--sync', type=int, default=0)
 ap.add_argument('--phase', type=int, default=1); ap.add_argument('--setting', default='transfer')
 ap.add_argument('--fused-sgd', action='store_true'); ap.add_argument('--per-tensor-groups', action='store_true')
@@ -32,14 +35,18 @@ if a.clip_norm is not None:
 if a.wgrad_h2:
     os.environ['CTDET_WGRAD_H2'] = '1'         # read once, when the TrainRuntime is built
 if a.deterministic:
-    os.environ['CTDET_TRAIN_DETERMINISTIC'] = '1'      # the same
+    os.environ['CTDET_TRAIN_DETERMINISTIC'] = '2' if a.phase == 2 else '1'      # the same; 2 = the Context-Transformer block too
 from ctdet import synth, dist as cdist
-from models.RFB_Net_vgg import build_net
+from models.RFB_Net_vgg import build_net, _CTX_DIMS
 from layers.functions import PriorBox
 from layers.modules.multibox_loss_combined import MultiBoxLoss_combined
 import data as cfgs
 rank, local, world = cdist.init('nccl')
 torch.cuda.set_device(local)
+if a.classes is None:
+    # phase 2: the width the Context-Transformer block's parameters are built for (60 base classes for 'transfer').  With any
+    # other width the block's gradient tensors are only partly written, and their tails are whatever the allocator left there
+    a.classes = _CTX_DIMS[a.setting][0] if a.phase == 2 else 20
 net = build_net(types.SimpleNamespace(method='ours', phase=a.phase, setting=a.setting), a.size, a.classes)
 net.load_state_dict(synth.fill_state_dict(net.state_dict()))
 net = net.cuda().train(); net.device = 'cuda'
