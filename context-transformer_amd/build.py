@@ -46,6 +46,7 @@ SOURCES = {
     'ct_loss.hip': ['-ffp-contract=off'],
     'ct_optim.hip': ['-ffp-contract=off'],
     'ct_nms.hip': ['-ffp-contract=off'],
+    'ct_soft_nms.hip': ['-ffp-contract=off'],
     'ct_post.hip': ['-ffp-contract=off'],
     'ct_eval.hip': ['-ffp-contract=off'],
     'ct_coco_eval.hip': ['-ffp-contract=off'],

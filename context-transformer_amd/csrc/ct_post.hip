@@ -23,6 +23,10 @@
 namespace ctdet {
 int nms_launch_strided(const float* dets, const int* seg_len, int seg_stride, int nseg, float thresh,
                        int ge, int* keep, int* keep_count, hipStream_t st);
+// ct_soft_nms.hip
+int soft_nms_launch_strided(float* dets, const int* seg_len, int seg_stride, int nseg, int method, float sigma, float Nt,
+                            float score_threshold, int max_emit, float* cur_ws, int* keep, int* keep_count, hipStream_t st);
+int soft_nms_check_params(const char* who, int method, float sigma);
 }
 
 namespace {
@@ -645,6 +649,70 @@ extern "C" int ct_postprocess_batched(const float* boxes, const float* scores, i
     } else {
         rc = ctdet::nms_launch_strided(w.dets_sorted, w.seg_count, num_priors, S, nms_thresh, ge, w.keep, w.keep_count, st);
     }
+    if (rc != CT_OK) return rc;
+    { CT_PROF("topk_kernel", st); hipLaunchKernelGGL(topk_kernel, dim3(batch), dim3(256), 0, st, w.dets_sorted, w.keep, w.keep_count,
+                       num_priors, num_fg, max_per_image, out_cap, out_count, overflow); }
+    CT_LAUNCH_CHECK("topk_kernel");
+    { CT_PROF("gather_kernel", st); hipLaunchKernelGGL(gather_kernel, dim3(S), dim3(256), 0, st, w.dets_sorted, w.sorted_idx, w.keep,
+                       out_count, num_priors, out_cap, out_dets, out_index); }
+    CT_LAUNCH_CHECK("gather_kernel");
+    return CT_OK;
+}
+
+// ---- the same pipeline with soft-NMS (ct_soft_nms.hip) ----
+// Score decay is not prefix-consistent in the hard path's sense (a candidate far down a segment can end above the image's
+// cut or below it depending on everything in front of it), so neither the partial sort nor the prefix cut is used: every
+// candidate is sorted, and each segment stops after max_per_image emissions (plus ties with the last one) -- later rows of a
+// segment can reach the image's output only through such a tie.  The soft kernel writes the decayed scores into
+// dets_sorted's own score column and the emitted positions into keep[], which is the layout topk_kernel / gather_kernel
+// read; its current scores of long segments live in the key buffer, which is free once the rows are sorted.
+extern "C" size_t ct_postprocess_soft_workspace_bytes(int batch, int num_priors, int num_fg)
+{
+    return carve(nullptr, batch, num_priors, num_fg).total;
+}
+
+extern "C" int ct_postprocess_batched_soft(const float* boxes, const float* scores, int batch, int num_priors, int num_fg,
+                                           float conf_thresh, int method, float sigma, float Nt, float score_threshold,
+                                           int max_per_image, int out_cap, float* out_dets, int* out_count, int* out_index,
+                                           int* overflow, void* workspace, size_t workspace_bytes, ct_stream_t stream)
+{
+    CT_REQUIRE(boxes && scores && out_dets && out_count && overflow, "ct_postprocess_batched_soft: null pointer");
+    CT_REQUIRE(batch > 0 && num_priors > 0 && num_fg > 0 && out_cap > 0 && max_per_image >= 0,
+               "ct_postprocess_batched_soft: bad sizes");
+    CT_REQUIRE(conf_thresh >= 0.f, "ct_postprocess_batched_soft: conf_thresh must be >= 0 (scores are compared as unsigned bit patterns)");
+    CT_REQUIRE(score_threshold >= 0.f, "ct_postprocess_batched_soft: score_threshold must be >= 0 (the top-k rule compares score bits)");
+    int rc = ctdet::soft_nms_check_params("ct_postprocess_batched_soft", method, sigma);
+    if (rc != CT_OK) return rc;
+    if (!workspace) return ctdet::fail(CT_ERR_WORKSPACE, "ct_postprocess_batched_soft: workspace is NULL");
+    const size_t need = ct_postprocess_soft_workspace_bytes(batch, num_priors, num_fg);
+    if (workspace_bytes < need)
+        return ctdet::fail(CT_ERR_WORKSPACE, "ct_postprocess_batched_soft: workspace %zu < %zu", workspace_bytes, need);
+    PostWs w = carve((char*)workspace, batch, num_priors, num_fg);
+    const int S = batch * num_fg;
+    const int np2 = std::max(next_pow2(num_priors), 2);
+    hipStream_t st = ctdet::as_stream(stream);
+    CT_HIP(hipMemsetAsync(overflow, 0, sizeof(int), st));
+    constexpr size_t kLds4k = 4096 * 8 + 64, kLds8k = 8192 * 8 + 64;
+    const dim3 sort_grid(8 * ((batch + 7) / 8) * num_fg);
+    {
+        CT_PROF("select_sort_kernel", st);
+        if (num_priors > 16384) {
+            static hipError_t attr8k = hipFuncSetAttribute((const void*)select_sort_kernel<8192, false>,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLds8k);
+            CT_HIP(attr8k);
+            hipLaunchKernelGGL((select_sort_kernel<8192, false>), sort_grid, dim3(kSortThreads), kLds8k, st, boxes, scores, batch, num_priors,
+                               num_fg, conf_thresh, np2, w.keys, w.dets_sorted, w.sorted_idx, w.seg_count, w.seg_sorted, (const int*)nullptr);
+        } else {
+            static hipError_t attr4k = hipFuncSetAttribute((const void*)select_sort_kernel<4096, false>,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLds4k);
+            CT_HIP(attr4k);
+            hipLaunchKernelGGL((select_sort_kernel<4096, false>), sort_grid, dim3(kSortThreads), kLds4k, st, boxes, scores, batch, num_priors,
+                               num_fg, conf_thresh, np2, w.keys, w.dets_sorted, w.sorted_idx, w.seg_count, w.seg_sorted, (const int*)nullptr);
+        }
+    }
+    CT_LAUNCH_CHECK("select_sort_kernel");
+    rc = ctdet::soft_nms_launch_strided(w.dets_sorted, w.seg_count, num_priors, S, method, sigma, Nt, score_threshold,
+                                        max_per_image, reinterpret_cast<float*>(w.keys), w.keep, w.keep_count, st);
     if (rc != CT_OK) return rc;
     { CT_PROF("topk_kernel", st); hipLaunchKernelGGL(topk_kernel, dim3(batch), dim3(256), 0, st, w.dets_sorted, w.keep, w.keep_count,
                        num_priors, num_fg, max_per_image, out_cap, out_count, overflow); }

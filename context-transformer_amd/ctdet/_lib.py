@@ -105,6 +105,9 @@ SIGNATURES = {
     'ct_nms_batched_dev': (_I, [_P, _P, _I, _I, _F, _I, _P, _P, _P, _Z, _P]),
     'ct_cpu_nms': (_I, [_P, _I, _F, _I, _P, _P]),
     'ct_cpu_soft_nms': (_I, [_P, _I, _F, _F, _F, C.c_uint, _P]),
+    'ct_soft_nms_lds_rows': (_I, []),
+    'ct_soft_nms_batched_workspace_bytes': (_Z, [_I, _I]),
+    'ct_soft_nms_batched_dev': (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P, _Z, _P]),
     'ct_decode': (_I, [_P, _P, _I, _I, _F, _F, _P, _I, _P, _P]),
     'ct_encode': (_I, [_P, _P, _I, _F, _F, _P, _P]),
     'ct_detect_fused': (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _I, _P, _P, _P]),
@@ -123,6 +126,8 @@ SIGNATURES = {
     'ct_sgd_step_clipped': (_I, [C.POINTER(SgdTensor), _I, _F, _F, _I, _F, _P, _P]),
     'ct_postprocess_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    'ct_postprocess_soft_workspace_bytes': (_Z, [_I, _I, _I]),
+    'ct_postprocess_batched_soft': (_I, [_P, _P, _I, _I, _I, _F, _I, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_voc_match': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _D, _P, _P, _I, _P, _P]),
     'ct_voc_pr': (_I, [_P, _P, _LL, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     'ct_coco_match': (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P,

@@ -292,6 +292,46 @@ def nms_batched(dets, seg_off, thresh, ge=False, max_seg_len=None):
     return keep, cnt
 
 
+SOFT_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}
+
+
+def soft_method(method):
+    """'hard' / 'linear' / 'gaussian' (or the reference's 0 / 1 / 2) -> the library's method number."""
+    if isinstance(method, str):
+        if method not in SOFT_METHODS:
+            raise ValueError('nms_method %r is not one of %s' % (method, sorted(SOFT_METHODS)))
+        return SOFT_METHODS[method]
+    m = int(method)
+    if m not in (0, 1, 2):
+        raise ValueError('soft-NMS method %r is not 0, 1 or 2' % (method,))
+    return m
+
+
+def soft_nms_batched(dets, seg_off, method=1, sigma=0.5, Nt=0.3, score_threshold=0.001, max_emit=0, max_seg_len=None,
+                     out=None, workspace=None):
+    """Soft-NMS of every segment (the device form of cpu_soft_nms): dets dev [total,5] (segments in descending score
+    order), seg_off dev int32 [S+1] -> (out_rows [total,5], out_pos [total], out_count [S]); segment s emitted
+    out_rows[seg_off[s] : seg_off[s] + out_count[s]] in that order, out_pos are their positions inside the segment.
+    out: the three tensors to write into; workspace: uint8 tensor of ct_soft_nms_batched_workspace_bytes."""
+    S = seg_off.numel() - 1
+    total = dets.shape[0]
+    if out is None:
+        out = (torch.empty(max(total, 1), 5, device=dets.device), torch.empty(max(total, 1), device=dets.device,
+                                                                              dtype=torch.int32),
+               torch.empty(S, device=dets.device, dtype=torch.int32))
+    rows, pos, cnt = out
+    need = lib().ct_soft_nms_batched_workspace_bytes(total, S)
+    if workspace is None:
+        workspace = torch.empty(need, device=dets.device, dtype=torch.uint8)
+    check(lib().ct_soft_nms_batched_dev(_dev(dets, 'dets'), _dev(seg_off, 'seg_off', torch.int32), S,
+                                        int(total if max_seg_len is None else max_seg_len), soft_method(method),
+                                        float(sigma), float(Nt), float(score_threshold), int(max_emit),
+                                        _dev(rows, 'out_rows'), _dev(pos, 'out_pos', torch.int32),
+                                        _dev(cnt, 'out_count', torch.int32), _dev(workspace, 'workspace', torch.uint8),
+                                        workspace.numel(), _stream()), 'ct_soft_nms_batched_dev')
+    return rows, pos, cnt
+
+
 def cpu_nms(dets, thresh, ge=True):
     """utils/nms/cpu_nms.pyx:17-68 on a host numpy array (the reference's --cpu path)."""
     d = np.ascontiguousarray(dets, dtype=np.float32)
@@ -326,8 +366,26 @@ class PostProcessor:
         self.out_count = torch.zeros(batch, num_fg, device=device, dtype=torch.int32)
         self.out_index = torch.zeros(batch, num_fg, self.cap, device=device, dtype=torch.int32)
         self.overflow = torch.zeros(1, device=device, dtype=torch.int32)
+        self.soft_ws = None             # the soft-NMS entry's workspace, allocated by the first run that needs it
 
-    def run(self, boxes, scores, conf_thresh=0.01, nms_thresh=0.45, ge=False, max_per_image=200):
+    def run(self, boxes, scores, conf_thresh=0.01, nms_thresh=0.45, ge=False, max_per_image=200, nms_method='hard',
+            soft_sigma=0.5, soft_score_threshold=0.001):
+        """nms_method 'hard': greedy NMS (suppress IoU > nms_thresh, or >= with ge).  'linear' / 'gaussian': soft-NMS
+        (cpu_soft_nms methods 1 / 2) with Nt = nms_thresh, sigma = soft_sigma, rows below soft_score_threshold dropped;
+        `ge` does not apply to them."""
+        method = soft_method(nms_method)
+        if method != 0:
+            if self.soft_ws is None:
+                nbytes = lib().ct_postprocess_soft_workspace_bytes(self.B, self.P, self.T)
+                self.soft_ws = torch.empty(nbytes, device=self.out_dets.device, dtype=torch.uint8)
+            check(lib().ct_postprocess_batched_soft(
+                _dev(boxes, 'boxes'), _dev(scores, 'scores'), self.B, self.P, self.T, float(conf_thresh), method,
+                float(soft_sigma), float(nms_thresh), float(soft_score_threshold), int(max_per_image), self.cap,
+                _dev(self.out_dets, 'out_dets'), _dev(self.out_count, 'out_count', torch.int32),
+                _dev(self.out_index, 'out_index', torch.int32), _dev(self.overflow, 'overflow', torch.int32),
+                _dev(self.soft_ws, 'soft_ws', torch.uint8), self.soft_ws.numel(), _stream()),
+                'ct_postprocess_batched_soft')
+            return self.out_dets, self.out_count
         check(lib().ct_postprocess_batched(
             _dev(boxes, 'boxes'), _dev(scores, 'scores'), self.B, self.P, self.T, float(conf_thresh),
             float(nms_thresh), int(bool(ge)), int(max_per_image), self.cap, _dev(self.out_dets, 'out_dets'),

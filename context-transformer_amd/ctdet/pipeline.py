@@ -23,7 +23,10 @@ from . import ops
 
 class DetectionPipeline:
     def __init__(self, net, priors, batch, num_fg, image_wh=(500, 375), conf_thresh=0.01, nms_thresh=0.45,
-                 max_per_image=200, force_cpu_rule=False, variance=(0.1, 0.2), out_cap=None, graph=None):
+                 max_per_image=200, force_cpu_rule=False, variance=(0.1, 0.2), out_cap=None, graph=None,
+                 nms_method='hard', soft_sigma=0.5, soft_score_threshold=0.001):
+        """nms_method 'hard' (default), 'linear' or 'gaussian': the last two run soft-NMS (cpu_soft_nms methods 1 / 2,
+        Nt = nms_thresh, sigma = soft_sigma, rows below soft_score_threshold dropped) in place of hard NMS."""
         self.net = net
         self.device = net._device()
         self.priors = priors.to(self.device, torch.float32).contiguous()
@@ -32,6 +35,8 @@ class DetectionPipeline:
         self.variance = variance
         self.conf_thresh, self.nms_thresh, self.max_per_image = conf_thresh, nms_thresh, max_per_image
         self.ge = bool(force_cpu_rule)
+        ops.soft_method(nms_method)                 # a misspelt method fails here, not in the first step
+        self.nms_method, self.soft_sigma, self.soft_score_threshold = nms_method, soft_sigma, soft_score_threshold
         self.scale = None
         self.set_image_wh(image_wh)
         self.rt = net.runtime(batch, self.device)
@@ -72,12 +77,20 @@ class DetectionPipeline:
             key += tuple(v.data_ptr() if isinstance(v, torch.Tensor) else v for _, v in sorted(prm.items()))
         return key
 
+    def _post_key(self):
+        """The post-processing arguments a captured step froze."""
+        key = (self.conf_thresh, self.nms_thresh, self.ge, self.max_per_image)
+        if self.nms_method != 'hard':
+            key += (ops.soft_method(self.nms_method), float(self.soft_sigma), float(self.soft_score_threshold))
+        return key
+
     def _step(self):
         """The launches of one step on the current stream; reads rt.bufs['x'] (already filled)."""
         loc, conf, obj = self.net.forward_raw(None, _input_loaded=True, _batch=self.batch)
         ops.detect_fused(loc, conf.contiguous(), obj, self.priors, self.variance, True, self.scale,
                          out=(self.boxes, self.scores))
-        self.post.run(self.boxes, self.scores, self.conf_thresh, self.nms_thresh, self.ge, self.max_per_image)
+        self.post.run(self.boxes, self.scores, self.conf_thresh, self.nms_thresh, self.ge, self.max_per_image,
+                      self.nms_method, self.soft_sigma, self.soft_score_threshold)
 
     def _capture(self):
         g = torch.cuda.CUDAGraph()
@@ -106,8 +119,8 @@ class DetectionPipeline:
         be = rt.backend
         # (kernel_epoch: a step changed kernels; ws_generation: a three-kernel-Winograd workspace was re-allocated -- either way
         # a captured graph holds stale launches / pointers)
-        key = (self.conf_thresh, self.nms_thresh, self.ge, self.max_per_image, rt.event_log is None,
-               getattr(be, 'kernel_epoch', 0), getattr(be, 'ws_generation', 0)) + self._net_key()
+        key = self._post_key() + (rt.event_log is None, getattr(be, 'kernel_epoch', 0),
+                                  getattr(be, 'ws_generation', 0)) + self._net_key()
         if self.use_graph and rt.event_log is None:
             if self._graph is not None and self._graph_key == key:
                 self._graph.replay()

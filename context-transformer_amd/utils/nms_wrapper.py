@@ -12,6 +12,7 @@ from .nms import cpu_nms as _host
 from .nms import gpu_nms as _device
 
 cpu_nms, cpu_soft_nms, gpu_nms = _host.cpu_nms, _host.cpu_soft_nms, _device.gpu_nms
+gpu_soft_nms = _device.gpu_soft_nms         # cpu_soft_nms's device twin (the reference has none)
 _RULES = {False: gpu_nms, True: cpu_nms}
 
 

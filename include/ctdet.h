@@ -115,6 +115,25 @@ int ct_cpu_nms(const float* dets_host, int n, float thresh, int ge, int* keep_ou
 int ct_cpu_soft_nms(float* boxes_host, int n, float sigma, float Nt, float threshold,
                     unsigned method, int* n_out);
 
+/* Soft-NMS on the device (the device form of `cpu_soft_nms`), one workgroup per segment.  Segments as for
+ * ct_nms_batched_dev: dets dev [total,5], each segment in descending score order (lower prior index first on ties).
+ *   method 0 hard (ov > Nt removes), 1 linear (score *= 1 - ov when ov > Nt), 2 Gaussian (score *= exp(-ov^2 / sigma));
+ *   a row whose decayed score falls below score_threshold is removed (reference default 0.001);
+ *   max_emit > 0: a segment stops after max_emit rows, except for further rows that tie with the last one; 0: no limit.
+ *   out_rows  dev [total,5]  out_rows[seg_off[s] + i], i < out_count[s]: the emitted rows (box, decayed score) in
+ *                            emission order = non-increasing score
+ *   out_pos   dev [total]    position of each emitted row relative to its segment
+ *   out_count dev [S]        rows emitted; -1: the workspace does not cover segment s (queried with too few rows)
+ * Nothing is written past out_count[s] rows of a segment.  Methods 0 and 1 equal ct_cpu_soft_nms bit for bit on tie-free
+ * input; method 2 makes the same decisions with scores within an ulp of the weight per decay (the double-precision exp is
+ * another libm's).  Segments of at most ct_soft_nms_lds_rows() rows keep their state in LDS, longer ones in the workspace. */
+int ct_soft_nms_lds_rows(void);
+size_t ct_soft_nms_batched_workspace_bytes(int total_rows, int num_segments);
+int ct_soft_nms_batched_dev(const float* dets, const int* seg_off, int num_segments, int max_seg_len,
+                            int method, float sigma, float Nt, float score_threshold, int max_emit,
+                            float* out_rows, int* out_pos, int* out_count,
+                            void* workspace, size_t workspace_bytes, ct_stream_t stream);
+
 /* ----------------------------------------------------- boxes / detection ---- */
 
 /* utils/box_utils.py:184-202 `decode(loc, priors, variances)`, batched over images:
@@ -290,6 +309,15 @@ int ct_postprocess_batched(const float* boxes, const float* scores, int batch, i
                            int max_per_image, int out_cap, float* out_dets, int* out_count,
                            int* out_index, int* overflow,
                            void* workspace, size_t workspace_bytes, ct_stream_t stream);
+/* The same with soft-NMS (ct_soft_nms_batched_dev's method / sigma / Nt / score_threshold) in place of hard NMS: every
+ * candidate is selected and sorted, each segment emits at most max_per_image rows (plus ties with the last one), then the
+ * same top-k rule and gather.  Same outputs, same overflow rule; rows carry their decayed scores. */
+size_t ct_postprocess_soft_workspace_bytes(int batch, int num_priors, int num_fg);
+int ct_postprocess_batched_soft(const float* boxes, const float* scores, int batch, int num_priors,
+                                int num_fg, float conf_thresh, int method, float sigma, float Nt,
+                                float score_threshold, int max_per_image, int out_cap, float* out_dets,
+                                int* out_count, int* out_index, int* overflow,
+                                void* workspace, size_t workspace_bytes, ct_stream_t stream);
 
 /* ------------------------------------------------- PASCAL VOC evaluation ---- */
 
