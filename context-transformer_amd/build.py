@@ -48,6 +48,7 @@ SOURCES = {
     'ct_nms.hip': ['-ffp-contract=off'],
     'ct_soft_nms.hip': ['-ffp-contract=off'],
     'ct_post.hip': ['-ffp-contract=off'],
+    'ct_tta.hip': ['-ffp-contract=off'],
     'ct_eval.hip': ['-ffp-contract=off'],
     'ct_coco_eval.hip': ['-ffp-contract=off'],
     'ct_cpu_nms.cpp': ['-ffp-contract=off'],

@@ -98,3 +98,40 @@ extern "C" int ct_cpu_soft_nms(float* boxes, int n, float sigma, float Nt, float
     *n_out = N;
     return CT_OK;
 }
+
+// The host twin of box_vote_kernel (ct_tta.hip) on one (image, class) segment: every output row's box becomes the
+// weight-weighted mean of the candidates that overlap it by at least vote_thresh.  The fp32 IoU expression of ct_cpu_nms,
+// float64 sums taken sequentially in candidate order, one float64 division, one rounding to fp32; a row without a member
+// keeps its bits, and so does every score.
+extern "C" int ct_cpu_box_vote(const float* cand_boxes, const float* weights, int n, float vote_thresh, float* rows, int m)
+{
+    CT_REQUIRE(n >= 0 && m >= 0 && (n == 0 || (cand_boxes && weights)) && (m == 0 || rows), "ct_cpu_box_vote: bad arguments");
+    CT_REQUIRE(vote_thresh > 0.f && vote_thresh <= 1.f, "ct_cpu_box_vote: vote_thresh %g is outside (0, 1]", (double)vote_thresh);
+    for (int r = 0; r < m; ++r) {
+        float* t = rows + (size_t)r * 5;
+        const float tx1 = t[0], ty1 = t[1], tx2 = t[2], ty2 = t[3];
+        const float tarea = (tx2 - tx1 + 1.0f) * (ty2 - ty1 + 1.0f);
+        double sw = 0.0, s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int j = 0; j < n; ++j) {
+            const float* b = cand_boxes + (size_t)j * 4;
+            const float xx1 = tx1 >= b[0] ? tx1 : b[0];
+            const float yy1 = ty1 >= b[1] ? ty1 : b[1];
+            const float xx2 = tx2 <= b[2] ? tx2 : b[2];
+            const float yy2 = ty2 <= b[3] ? ty2 : b[3];
+            const float w0 = xx2 - xx1 + 1.0f, h0 = yy2 - yy1 + 1.0f;
+            const float w = 0.0f >= w0 ? 0.0f : w0;
+            const float h = 0.0f >= h0 ? 0.0f : h0;
+            const float inter = w * h;
+            const float area = (b[2] - b[0] + 1.0f) * (b[3] - b[1] + 1.0f);
+            const float ovr = inter / (tarea + area - inter);
+            if (ovr >= vote_thresh) {
+                const double wq = (double)weights[j];
+                sw += wq;
+                for (int c = 0; c < 4; ++c) s[c] += wq * (double)b[c];
+            }
+        }
+        if (sw > 0.0)
+            for (int c = 0; c < 4; ++c) t[c] = (float)(s[c] / sw);
+    }
+    return CT_OK;
+}

@@ -128,6 +128,12 @@ SIGNATURES = {
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_postprocess_soft_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_postprocess_batched_soft': (_I, [_P, _P, _I, _I, _I, _F, _I, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    'ct_hflip_f32': (_I, [_P, _P, _L, _I, _I, _P]),
+    'ct_tta_merge': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    'ct_box_vote_lds_rows': (_I, []),
+    'ct_box_vote_workspace_bytes': (_Z, [_I, _I, _I, _I]),
+    'ct_box_vote_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _Z, _P]),
+    'ct_cpu_box_vote': (_I, [_P, _P, _I, _F, _P, _I]),
     'ct_voc_match': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _D, _P, _P, _I, _P, _P]),
     'ct_voc_pr': (_I, [_P, _P, _LL, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     'ct_coco_match': (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P,

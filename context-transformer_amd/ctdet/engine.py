@@ -1201,6 +1201,11 @@ class Runtime:
         if tuple(x.shape) != want:
             raise _lib.CtdetError('plan was built for input %s, got %s' % (want, tuple(x.shape)))
         self.refresh_weights()
+        self.copy_input(x)
+
+    def copy_input(self, x):
+        """The copy of load_input alone (x already checked, weights already fresh): one launch, capturable -- a
+        DetectionPipeline's second test-time-augmentation pass loads its mirrored batch with it inside the step."""
         if hasattr(self.backend, 'load_input'):       # bf16 path: NCHW fp32 image -> NHWC bf16
             self.backend.load_input(self.bufs['x'], x)
         else:

@@ -354,6 +354,95 @@ def cpu_soft_nms(boxes, sigma=0.5, Nt=0.3, threshold=0.001, method=0):
     return n_out.value
 
 
+TTA_MODES = (None, 'hflip')
+
+
+def tta_mode(name):
+    """None / 'hflip' -> the number of passes of that test-time augmentation (1 / 2)."""
+    if name is not None and not isinstance(name, str) or name not in TTA_MODES:
+        raise ValueError('tta %r is not one of %s' % (name, list(TTA_MODES)))
+    return 1 if name is None else 2
+
+
+def vote_threshold(box_vote):
+    """None (no voting) or the IoU threshold of box voting, a number in (0, 1]."""
+    if box_vote is None:
+        return None
+    if isinstance(box_vote, bool) or not isinstance(box_vote, (int, float, np.floating)) or not 0.0 < float(box_vote) <= 1.0:
+        raise ValueError('box_vote %r is not None or a number in (0, 1]' % (box_vote,))
+    return float(box_vote)
+
+
+def hflip(x, out=None):
+    """x [..., H, W] mirrored along W into `out` (a different tensor; allocated when None)."""
+    if out is None:
+        out = torch.empty_like(x)
+    if out.shape != x.shape or out.data_ptr() == x.data_ptr():
+        raise ValueError('hflip is out of place: `out` must be another tensor of the same shape')
+    h, w = x.shape[-2], x.shape[-1]
+    check(lib().ct_hflip_f32(_dev(x, 'x'), _dev(out, 'out'), x.numel() // (h * w), h, w, _stream()), 'ct_hflip_f32')
+    return out
+
+
+def tta_merge(boxes_k, scores_k, k, num_passes, mirror, scale, out):
+    """Pass k's boxes [B,P,4] / scores [B,P,C] into rows [k*P, (k+1)*P) of out = (boxes [B,K*P,4], scores [B,K*P,C]);
+    mirror: the pass saw the mirrored image, x1' = W_b - x2 and x2' = W_b - x1 with W_b from scale ([4] or [B,4])."""
+    B, P, Cn = scores_k.shape
+    boxes_m, scores_m = out
+    if tuple(boxes_m.shape) != (B, num_passes * P, 4) or tuple(scores_m.shape) != (B, num_passes * P, Cn):
+        raise ValueError('tta_merge: merged buffers %s / %s do not hold %d passes of %s'
+                         % (tuple(boxes_m.shape), tuple(scores_m.shape), num_passes, tuple(scores_k.shape)))
+    per_image = int(scale is not None and scale.dim() == 2)
+    check(lib().ct_tta_merge(_dev(boxes_k, 'boxes_k'), _dev(scores_k, 'scores_k'), B, P, Cn, int(num_passes), int(k),
+                             int(bool(mirror)), _opt(scale, 'scale'), per_image, _dev(boxes_m, 'boxes_merged'),
+                             _dev(scores_m, 'scores_merged'), _stream()), 'ct_tta_merge')
+    return out
+
+
+def box_vote_workspace_bytes(batch, num_rows, num_fg, out_cap):
+    return lib().ct_box_vote_workspace_bytes(batch, num_rows, num_fg, out_cap)
+
+
+def box_vote(boxes, scores, out_dets, out_count, conf_thresh, vote_thresh, workspace=None):
+    """Box voting on a post-processing result, in place: every row r < out_count[b,c] of out_dets [B,T,cap,5] gets the
+    score-weighted mean box of the rows q of boxes [B,N,4] with scores[b,q,1+c] > conf_thresh that overlap it by at least
+    vote_thresh (include/ctdet.h).  Scores, counts and order are untouched.  workspace: uint8 tensor of
+    box_vote_workspace_bytes (allocated when None)."""
+    B, N = boxes.shape[0], boxes.shape[1]
+    T, cap = out_dets.shape[1], out_dets.shape[2]
+    if tuple(scores.shape) != (B, N, T + 1) or tuple(out_count.shape) != (B, T):
+        raise ValueError('box_vote: scores %s / out_count %s do not match boxes %s and out_dets %s'
+                         % (tuple(scores.shape), tuple(out_count.shape), tuple(boxes.shape), tuple(out_dets.shape)))
+    thr = vote_threshold(vote_thresh)
+    if thr is None:
+        raise ValueError('box_vote needs a threshold in (0, 1]')
+    if workspace is None:
+        workspace = torch.empty(box_vote_workspace_bytes(B, N, T, cap), device=boxes.device, dtype=torch.uint8)
+    check(lib().ct_box_vote_batched(_dev(boxes, 'boxes'), _dev(scores, 'scores'), B, N, T, float(conf_thresh), thr, cap,
+                                    _dev(out_dets, 'out_dets'), _dev(out_count, 'out_count', torch.int32),
+                                    _dev(workspace, 'workspace', torch.uint8), workspace.numel(), _stream()),
+          'ct_box_vote_batched')
+    return out_dets
+
+
+def cpu_box_vote(cand_boxes, weights, rows, vote_thresh):
+    """The host twin on one segment: cand_boxes float32 [n,4] and weights float32 [n] in merged-index order; `rows`
+    (float32 [m,5], C-contiguous) is updated in place, its score column untouched."""
+    thr = vote_threshold(vote_thresh)
+    if thr is None:
+        raise ValueError('cpu_box_vote needs a threshold in (0, 1]')
+    if not (isinstance(rows, np.ndarray) and rows.dtype == np.float32 and rows.flags['C_CONTIGUOUS'] and rows.ndim == 2
+            and rows.shape[1] == 5):
+        raise ValueError('cpu_box_vote needs C-contiguous float32 rows [m,5] (they are updated in place)')
+    cb = np.ascontiguousarray(cand_boxes, dtype=np.float32).reshape(-1, 4)
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if len(w) != len(cb):
+        raise ValueError('cpu_box_vote: %d boxes, %d weights' % (len(cb), len(w)))
+    check(lib().ct_cpu_box_vote(cb.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), len(cb), thr,
+                                rows.ctypes.data_as(C.c_void_p), rows.shape[0]), 'ct_cpu_box_vote')
+    return rows
+
+
 class PostProcessor:
     """Batched test.py:136-161 on the device with persistent buffers."""
 
@@ -367,13 +456,16 @@ class PostProcessor:
         self.out_index = torch.zeros(batch, num_fg, self.cap, device=device, dtype=torch.int32)
         self.overflow = torch.zeros(1, device=device, dtype=torch.int32)
         self.soft_ws = None             # the soft-NMS entry's workspace, allocated by the first run that needs it
+        self.vote_ws = None             # box voting's workspace, likewise
 
     def run(self, boxes, scores, conf_thresh=0.01, nms_thresh=0.45, ge=False, max_per_image=200, nms_method='hard',
-            soft_sigma=0.5, soft_score_threshold=0.001):
+            soft_sigma=0.5, soft_score_threshold=0.001, box_vote=None):
         """nms_method 'hard': greedy NMS (suppress IoU > nms_thresh, or >= with ge).  'linear' / 'gaussian': soft-NMS
         (cpu_soft_nms methods 1 / 2) with Nt = nms_thresh, sigma = soft_sigma, rows below soft_score_threshold dropped;
-        `ge` does not apply to them."""
+        `ge` does not apply to them.  box_vote (a float in (0, 1]): after the top-k cut every row's box is replaced by the
+        score-weighted mean of the candidates of its class that overlap it by at least that IoU (ops.box_vote)."""
         method = soft_method(nms_method)
+        vote = vote_threshold(box_vote)
         if method != 0:
             if self.soft_ws is None:
                 nbytes = lib().ct_postprocess_soft_workspace_bytes(self.B, self.P, self.T)
@@ -385,13 +477,21 @@ class PostProcessor:
                 _dev(self.out_index, 'out_index', torch.int32), _dev(self.overflow, 'overflow', torch.int32),
                 _dev(self.soft_ws, 'soft_ws', torch.uint8), self.soft_ws.numel(), _stream()),
                 'ct_postprocess_batched_soft')
-            return self.out_dets, self.out_count
+            return self._vote(boxes, scores, conf_thresh, vote)
         check(lib().ct_postprocess_batched(
             _dev(boxes, 'boxes'), _dev(scores, 'scores'), self.B, self.P, self.T, float(conf_thresh),
             float(nms_thresh), int(bool(ge)), int(max_per_image), self.cap, _dev(self.out_dets, 'out_dets'),
             _dev(self.out_count, 'out_count', torch.int32), _dev(self.out_index, 'out_index', torch.int32),
             _dev(self.overflow, 'overflow', torch.int32), _dev(self.ws, 'ws', torch.uint8), self.ws_bytes,
             _stream()), 'ct_postprocess_batched')
+        return self._vote(boxes, scores, conf_thresh, vote)
+
+    def _vote(self, boxes, scores, conf_thresh, vote):
+        if vote is not None:
+            if self.vote_ws is None:
+                nbytes = box_vote_workspace_bytes(self.B, self.P, self.T, self.cap)
+                self.vote_ws = torch.empty(nbytes, device=self.out_dets.device, dtype=torch.uint8)
+            box_vote(boxes, scores, self.out_dets, self.out_count, conf_thresh, vote, self.vote_ws)
         return self.out_dets, self.out_count
 
     def to_all_boxes(self):

@@ -5,6 +5,9 @@ one image per step to a whole batch with every stage on the device.
   -> fused eval-softmax + decode + score fusion + `boxes *= scale`
   -> per (image, class): score > 0.01, descending-score order, NMS 0.45
   -> per image: keep score >= 200-th largest
+  [-> box voting: every kept box becomes the score-weighted mean of the candidates of its class that overlap it]
+With tta='hflip' the network also runs on the batch mirrored along W; that pass's boxes are mirrored back in pixels and both
+candidate sets are pooled per image (2P rows) in front of the post-processing.
 Results equal the reference's sequential per-image / per-class loop on the same
 (loc, conf, obj): all_boxes[img][cls] = float32 [k,5] rows in descending score order.
 
@@ -22,11 +25,18 @@ from . import ops
 
 
 class DetectionPipeline:
+    tta, passes, box_vote = None, 1, None           # the defaults: one pass, no voting
+
     def __init__(self, net, priors, batch, num_fg, image_wh=(500, 375), conf_thresh=0.01, nms_thresh=0.45,
                  max_per_image=200, force_cpu_rule=False, variance=(0.1, 0.2), out_cap=None, graph=None,
-                 nms_method='hard', soft_sigma=0.5, soft_score_threshold=0.001):
+                 nms_method='hard', soft_sigma=0.5, soft_score_threshold=0.001, tta=None, box_vote=None):
         """nms_method 'hard' (default), 'linear' or 'gaussian': the last two run soft-NMS (cpu_soft_nms methods 1 / 2,
-        Nt = nms_thresh, sigma = soft_sigma, rows below soft_score_threshold dropped) in place of hard NMS."""
+        Nt = nms_thresh, sigma = soft_sigma, rows below soft_score_threshold dropped) in place of hard NMS.
+        tta 'hflip': two passes, the second on the mirrored batch; self.boxes / self.scores are then the merged [B,2P,...]
+        buffers (pass 0's P rows, then pass 1's mirrored back: x1' = W - x2, x2' = W - x1), the post-processor works on 2P
+        rows and out_index holds merged indices k*P + p (pass k, prior p).
+        box_vote (a float in (0, 1]): ops.box_vote with that IoU threshold after the top-k cut; may be changed between
+        runs.  Both default to off, and the step then makes exactly the calls it makes without them."""
         self.net = net
         self.device = net._device()
         self.priors = priors.to(self.device, torch.float32).contiguous()
@@ -37,12 +47,22 @@ class DetectionPipeline:
         self.ge = bool(force_cpu_rule)
         ops.soft_method(nms_method)                 # a misspelt method fails here, not in the first step
         self.nms_method, self.soft_sigma, self.soft_score_threshold = nms_method, soft_sigma, soft_score_threshold
+        self.tta, self.passes = tta, ops.tta_mode(tta)
+        ops.vote_threshold(box_vote)
+        self.box_vote = box_vote
         self.scale = None
         self.set_image_wh(image_wh)
         self.rt = net.runtime(batch, self.device)
-        self.post = ops.PostProcessor(batch, self.P, num_fg, self.device, out_cap)
-        self.boxes = torch.empty(batch, self.P, 4, device=self.device)
-        self.scores = torch.empty(batch, self.P, num_fg + 1, device=self.device)
+        rows = self.passes * self.P
+        self.post = ops.PostProcessor(batch, rows, num_fg, self.device, out_cap)
+        self.boxes = torch.empty(batch, rows, 4, device=self.device)
+        self.scores = torch.empty(batch, rows, num_fg + 1, device=self.device)
+        self.stage = self.x_flip = None
+        if self.passes > 1:
+            # one pass's ct_detect_fused output (both passes use it in turn) and the mirrored batch
+            self.stage = (torch.empty(batch, self.P, 4, device=self.device),
+                          torch.empty(batch, self.P, num_fg + 1, device=self.device))
+            self.x_flip = torch.empty((batch,) + tuple(self.rt.plan.buf_shapes['x']), device=self.device)
         self.use_graph = (os.environ.get('CTDET_GRAPH', '1') != '0') if graph is None else bool(graph)
         if len(getattr(self.rt, 'sides', None) or []) > 1:
             # more than one side stream (CTDET_STREAMS > 2): ROCm 7.2 crashes in hipStreamEndCapture on that fork/join
@@ -82,15 +102,30 @@ class DetectionPipeline:
         key = (self.conf_thresh, self.nms_thresh, self.ge, self.max_per_image)
         if self.nms_method != 'hard':
             key += (ops.soft_method(self.nms_method), float(self.soft_sigma), float(self.soft_score_threshold))
+        if self.tta is not None or self.box_vote is not None:
+            key += (self.tta, ops.vote_threshold(self.box_vote))
         return key
 
-    def _step(self):
-        """The launches of one step on the current stream; reads rt.bufs['x'] (already filled)."""
+    def _detect(self, out):
+        """The network on rt.bufs['x'] and the fused decode into out = (boxes [B,P,4], scores [B,P,T+1])."""
         loc, conf, obj = self.net.forward_raw(None, _input_loaded=True, _batch=self.batch)
-        ops.detect_fused(loc, conf.contiguous(), obj, self.priors, self.variance, True, self.scale,
-                         out=(self.boxes, self.scores))
+        ops.detect_fused(loc, conf.contiguous(), obj, self.priors, self.variance, True, self.scale, out=out)
+
+    def _step(self):
+        """The launches of one step on the current stream; reads rt.bufs['x'] (already filled) and, for the second
+        pass of tta='hflip', self.x_flip."""
+        merged = (self.boxes, self.scores)
+        if self.passes == 1:
+            self._detect(merged)
+        else:
+            self._detect(self.stage)
+            ops.tta_merge(self.stage[0], self.stage[1], 0, self.passes, False, self.scale, merged)
+            self.rt.copy_input(self.x_flip)
+            self._detect(self.stage)
+            ops.tta_merge(self.stage[0], self.stage[1], 1, self.passes, True, self.scale, merged)
+        vote = () if self.box_vote is None else (self.box_vote,)
         self.post.run(self.boxes, self.scores, self.conf_thresh, self.nms_thresh, self.ge, self.max_per_image,
-                      self.nms_method, self.soft_sigma, self.soft_score_threshold)
+                      self.nms_method, self.soft_sigma, self.soft_score_threshold, *vote)
 
     def _capture(self):
         g = torch.cuda.CUDAGraph()
@@ -114,6 +149,8 @@ class DetectionPipeline:
             self.set_image_wh(image_wh)
         rt = self.rt
         rt.load_input(x)                            # shape check, weight refresh, copy into the plan's input buffer
+        if self.passes > 1:
+            ops.hflip(x, out=self.x_flip)           # reads the caller's tensor: outside the captured step, like the copy above
         if hasattr(rt, 'ensure_wired'):
             rt.ensure_wired()
         be = rt.backend

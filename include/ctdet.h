@@ -319,6 +319,39 @@ int ct_postprocess_batched_soft(const float* boxes, const float* scores, int bat
                                 int* out_count, int* out_index, int* overflow,
                                 void* workspace, size_t workspace_bytes, ct_stream_t stream);
 
+/* ------------------------- flip test-time augmentation and box voting ---- */
+
+/* Out-of-place mirror of NCHW rows: out[plane][y][j] = in[plane][y][w-1-j], planes = B*C.  in != out. */
+int ct_hflip_f32(const float* in, float* out, long planes, int h, int w, ct_stream_t stream);
+/* Pass k of num_passes (ct_detect_fused's boxes_k dev [B,P,4] in pixels, scores_k dev [B,P,num_cls_cols]) -> rows
+ * [k*P, (k+1)*P) of every image of boxes_merged dev [B,num_passes*P,4] / scores_merged dev [B,num_passes*P,num_cls_cols].
+ * mirror != 0: the pass ran on the image mirrored along W, its boxes are mirrored back in fp32: x1' = W_b - x2,
+ * x2' = W_b - x1, y unchanged, W_b = scale4[0] (scale_per_image: scale4[b*4]), the image's width.  Scores are copied.
+ * Post-processing the merged buffers as one image with num_passes*P priors pools the passes before NMS; its out_index
+ * then holds merged indices k*P + p.  Box pointers must be 16-byte aligned. */
+int ct_tta_merge(const float* boxes_k, const float* scores_k, int batch, int num_priors, int num_cls_cols,
+                 int num_passes, int k, int mirror, const float* scale4, int scale_per_image,
+                 float* boxes_merged, float* scores_merged, ct_stream_t stream);
+/* Box voting (Detectron's box_voting, scoring method ID) on the post-processing's output, in place: the box of row r <
+ * out_count[b,c] of out_dets dev [B,T,out_cap,5] becomes, per coordinate, sum(w_q x_q) / sum(w_q) over the members q of
+ * (b, c): every row q < num_rows of the image with w_q = scores[b,q,1+c] > conf_thresh and IoU(row r, boxes[b,q]) >=
+ * vote_thresh.  The IoU is the +1 pixel expression of the NMS (w = max(min(x2) - max(x1) + 1, 0), ovr = inter /
+ * (Sa + Sb - inter)) in fp32 with the IEEE quotient; products and sums are float64, one float64 division, one rounding to
+ * fp32.  A row's own source candidate is a member (IoU 1); a row without a member keeps its bits.  Scores, out_count,
+ * out_index and the row order are untouched, nothing behind out_count rows is written.  boxes dev [B,num_rows,4]
+ * (16-byte aligned), scores dev [B,num_rows,1+T]: the buffers the post-processing read.  0 < vote_thresh <= 1.
+ * Against ct_cpu_box_vote (sequential sums): |dev - host| <= 2^-23 |host| + 2^-30 max|coordinate of the segment|; two
+ * runs give the same bits.  Candidates are staged in LDS in chunks of ct_box_vote_lds_rows(); the workspace holds the
+ * running sums of longer segments (not needed, and may be NULL, when num_rows <= ct_box_vote_lds_rows()). */
+int ct_box_vote_lds_rows(void);
+size_t ct_box_vote_workspace_bytes(int batch, int num_rows, int num_fg, int out_cap);
+int ct_box_vote_batched(const float* boxes, const float* scores, int batch, int num_rows, int num_fg,
+                        float conf_thresh, float vote_thresh, int out_cap, float* out_dets, const int* out_count,
+                        void* workspace, size_t workspace_bytes, ct_stream_t stream);
+/* Host twin on one (image, class) segment: cand_boxes host [n,4] and weights host [n] in merged-index order, rows host
+ * [m,5] updated in place (column 4 untouched).  Same fp32 IoU expression, float64 sums in candidate order. */
+int ct_cpu_box_vote(const float* cand_boxes, const float* weights, int n, float vote_thresh, float* rows, int m);
+
 /* ------------------------------------------------- PASCAL VOC evaluation ---- */
 
 /* data/voc0712.py:339-426 (`_do_python_eval`) + data/voc_eval.py:134-203 (`voc_eval`) on the device, fed from the
