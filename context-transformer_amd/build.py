@@ -45,6 +45,7 @@ SOURCES = {
     'ct_box.hip': ['-ffp-contract=off'],
     'ct_loss.hip': ['-ffp-contract=off'],
     'ct_optim.hip': ['-ffp-contract=off'],
+    'ct_ema.hip': ['-ffp-contract=off'],
     'ct_nms.hip': ['-ffp-contract=off'],
     'ct_soft_nms.hip': ['-ffp-contract=off'],
     'ct_post.hip': ['-ffp-contract=off'],

@@ -23,20 +23,16 @@
 // state (two scalar loads), multiplies coef into grad_scale once, or -- when the norm was not finite -- leaves
 // everything alone except the momentum buffers of first-step tensors, which it sets to +0.
 #include "ct_common.h"
+#include "ct_multi_tensor.h"
 
 #include <climits>
 #include <cstdint>
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int CHUNK = 8192;                 // elements per workgroup: 8 dwordx4 groups per lane, issued 4 at a time
-constexpr int GROUPS = CHUNK / 4;           // 16-byte groups per chunk
-constexpr int UNROLL = 4;
-constexpr int TENSORS_PER_LAUNCH = 80;      // 80 * 40 B + 81 * 4 B + scalars = 3548 B of the 4096 B a launch may carry
-constexpr int64_t MAX_NUMEL = 2147483647;
+using namespace ctdet::mt;                  // chunk geometry, update(), owner_of(), line_offset(): shared with ct_ema.hip
 
-enum { F_FIRST = 1, F_VEC = 2, F_SHIFT = 4 /* bits 2-3: elements between the 16-byte line and element 0 */ };
+constexpr int TENSORS_PER_LAUNCH = 80;      // 80 * 40 B + 81 * 4 B + scalars = 3548 B of the 4096 B a launch may carry
 
 struct Tensor {
     float* p;
@@ -57,45 +53,6 @@ struct Launch {
 };
 static_assert(sizeof(Tensor) == 40, "kernel-argument budget");
 static_assert(sizeof(Launch) <= 4096, "kernel arguments are limited to 4 KiB");
-
-struct Hyper {
-    float lr, wd, momentum, omd, gs;
-    bool first, nesterov;
-};
-
-// include/ctdet.h, ct_sgd_step: one rounding per line
-__device__ inline void update(float& p, float g, float& b, const Hyper& h)
-{
-    g = __fmul_rn(g, h.gs);
-    float d = g;
-    if (h.wd != 0.f) d = __fadd_rn(g, __fmul_rn(h.wd, p));
-    float step = d;
-    if (h.momentum != 0.f) {
-        b = h.first ? d : __fadd_rn(__fmul_rn(h.momentum, b), __fmul_rn(h.omd, d));
-        step = h.nesterov ? __fadd_rn(d, __fmul_rn(h.momentum, b)) : b;
-    }
-    p = __fsub_rn(p, __fmul_rn(h.lr, step));
-}
-
-__device__ inline void update4(float4& p, float4 g, float4& b, const Hyper& h)
-{
-    update(p.x, g.x, b.x, h);
-    update(p.y, g.y, b.y, h);
-    update(p.z, g.z, b.z, h);
-    update(p.w, g.w, b.w, h);
-}
-
-// The tensor that owns workgroup `blk`: the last entry whose first workgroup is <= blk
-template <int N>
-__device__ inline int owner_of(const int (&first_block)[N], int n, int blk)
-{
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (blk >= first_block[mid]) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // CLIP = false is ct_sgd_step.  CLIP = true (ct_sgd_step_clipped) reads the state ct_grad_norm_clip left on the
 // device: coef goes into grad_scale once, and a non-finite norm skips the update.
@@ -313,8 +270,6 @@ __global__ __launch_bounds__(FINISH_THREADS) void grad_norm_finish_kernel(const 
         state->nonfinite = bad;
     }
 }
-
-inline int line_offset(const void* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3); }
 
 inline int64_t grad_chunks(const ct_grad_tensor& it)
 {

@@ -75,6 +75,23 @@ class ClipState(C.Structure):
     _fields_ = [('norm', C.c_float), ('coef', C.c_float), ('finite', C.c_int), ('nonfinite', C.c_int)]
 
 
+class EmaState(C.Structure):
+    """ct_ema_state: what ct_ema_begin leaves on the device for ct_sgd_step_ema / ct_ema_update."""
+    _fields_ = [('updates', C.c_int), ('decay', C.c_float), ('one_minus', C.c_float), ('applied', C.c_int)]
+
+
+class SgdEmaTensor(C.Structure):
+    _fields_ = SgdTensor._fields_ + [('ema', C.c_void_p)]
+
+
+class EmaTensor(C.Structure):
+    _fields_ = [('ema', C.c_void_p), ('src', C.c_void_p), ('numel', C.c_int64)]
+
+
+class SwapTensor(C.Structure):
+    _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('numel', C.c_int64)]
+
+
 class ResizeTap(C.Structure):
     """ct_resize_tap: first source index (unclamped) and the 11-bit coefficients of one output coordinate."""
     _fields_ = [('first', C.c_int), ('c', C.c_short * 8)]
@@ -124,6 +141,11 @@ SIGNATURES = {
     'ct_grad_norm_workspace_bytes': (_Z, [C.POINTER(GradTensor), _I]),
     'ct_grad_norm_clip': (_I, [C.POINTER(GradTensor), _I, _F, _F, _P, _Z, _P, _P]),
     'ct_sgd_step_clipped': (_I, [C.POINTER(SgdTensor), _I, _F, _F, _I, _F, _P, _P]),
+    'ct_ema_begin': (_I, [_P, _F, _F, _P, _P]),
+    'ct_sgd_ema_tensors_per_launch': (_I, []),
+    'ct_sgd_step_ema': (_I, [C.POINTER(SgdEmaTensor), _I, _F, _F, _I, _F, _P, _P, _P]),
+    'ct_ema_update': (_I, [C.POINTER(EmaTensor), _I, _P, _P]),
+    'ct_tensor_swap': (_I, [C.POINTER(SwapTensor), _I, _P]),
     'ct_postprocess_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_postprocess_soft_workspace_bytes': (_Z, [_I, _I, _I]),

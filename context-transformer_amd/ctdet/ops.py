@@ -265,6 +265,86 @@ def clip_info(state):
     return {'norm': float(s.norm), 'coef': float(s.coef), 'finite': bool(s.finite), 'nonfinite': int(s.nonfinite)}
 
 
+# ------------------------------------------------------------------ weight averaging
+EMA_STATE_BYTES = C.sizeof(_lib.EmaState)
+
+
+def _ema_state(t):
+    if not isinstance(t, torch.Tensor) or t.numel() != EMA_STATE_BYTES:
+        raise _lib.CtdetError('ema state must be a uint8 tensor of %d bytes, got %s'
+                              % (EMA_STATE_BYTES, t.numel() if isinstance(t, torch.Tensor) else type(t)))
+    return _dev(t, 'ema_state', torch.uint8)
+
+
+def ema_begin(state, decay, warmup=0.0, clip_state=None):
+    """ct_ema_begin on the 16-byte device tensor `state` (uint8, zeroed once by the caller): opens one update with the
+    decay min(decay, (1 + n) / (warmup + n)) (warmup 0: `decay`), or -- when `clip_state` (what grad_norm_clip
+    returned) says the step is skipped -- marks it as not applied and leaves the count alone.  No synchronisation."""
+    check(lib().ct_ema_begin(_ema_state(state), float(decay), float(warmup),
+                             None if clip_state is None else _clip_state(clip_state), _stream()), 'ct_ema_begin')
+    return state
+
+
+def sgd_ema_table(items):
+    """ctypes table of ct_sgd_ema_tensor for `items` = [(param, grad, momentum_buf or None, lr, weight_decay,
+    first_step, ema)], as sgd_table."""
+    table = (_lib.SgdEmaTensor * max(len(items), 1))()
+    for i, (p, g, buf, lr, wd, first, ema) in enumerate(items):
+        n = p.numel()
+        if g.numel() != n or (buf is not None and buf.numel() != n) or ema.numel() != n:
+            raise _lib.CtdetError('sgd_step_ema: tensor %d has %d elements, its grad %d, its momentum buffer %s, its '
+                                  'average %d' % (i, n, g.numel(), None if buf is None else buf.numel(), ema.numel()))
+        table[i] = _lib.SgdEmaTensor(_dev(p, 'param').value, _dev(g, 'grad').value, _opt(buf, 'momentum_buf').value, n,
+                                     lr, wd, int(bool(first)), _dev(ema, 'ema').value)
+    return table
+
+
+def sgd_step_ema(items, momentum, dampening, nesterov, grad_scale, ema_state, clip_state=None):
+    """sgd_step over `items` (see sgd_ema_table) that also moves each tensor's average towards the new parameter value
+    in the same pass (ct_sgd_step_ema), with the decay ema_begin left in `ema_state`.  A step `clip_state` skips, or
+    one ema_begin did not open, leaves the averages alone."""
+    if not items:
+        return
+    check(lib().ct_sgd_step_ema(sgd_ema_table(items), len(items), float(momentum), float(dampening),
+                                int(bool(nesterov)), float(grad_scale),
+                                None if clip_state is None else _clip_state(clip_state), _ema_state(ema_state),
+                                _stream()), 'ct_sgd_step_ema')
+
+
+def _pair_table(struct, pairs, what):
+    table = (struct * max(len(pairs), 1))()
+    for i, (a, b) in enumerate(pairs):
+        if a.numel() != b.numel():
+            raise _lib.CtdetError('%s: pair %d has %d and %d elements' % (what, i, a.numel(), b.numel()))
+        if a.numel():                           # an empty tensor passes NULL pointers, as in grad_table
+            table[i] = struct(_dev(a, what + ' tensor').value, _dev(b, what + ' tensor').value, a.numel())
+    return table
+
+
+def ema_update(pairs, ema_state):
+    """ema := d * ema + (1 - d) * src for every (ema, src) of `pairs` (ct_ema_update), contiguous fp32 device tensors,
+    with the decay ema_begin left in `ema_state`; nothing is written when that update was not opened."""
+    if not pairs:
+        return
+    check(lib().ct_ema_update(_pair_table(_lib.EmaTensor, pairs, 'ema_update'), len(pairs), _ema_state(ema_state),
+                              _stream()), 'ct_ema_update')
+
+
+def tensor_swap(pairs):
+    """Exchanges the contents of a and b for every (a, b) of `pairs` in place (ct_tensor_swap).  The tensors' version
+    counters are the caller's business (torch.autograd.graph.increment_version)."""
+    if not pairs:
+        return
+    check(lib().ct_tensor_swap(_pair_table(_lib.SwapTensor, pairs, 'tensor_swap'), len(pairs), _stream()),
+          'ct_tensor_swap')
+
+
+def ema_info(state):
+    """Synchronising read of an ema state -> {'updates', 'decay', 'applied'}."""
+    s = _lib.EmaState.from_buffer_copy(state.cpu().numpy().tobytes())
+    return {'updates': int(s.updates), 'decay': float(s.decay), 'applied': bool(s.applied)}
+
+
 # ------------------------------------------------------------------ NMS
 def nms_sorted_host(dets_sorted, thresh, ge=False, device_id=0, plain_iou=False):
     """The `_nms` contract (utils/nms/nms_kernel.cu:91-144): host numpy [n,dim>=4] sorted by

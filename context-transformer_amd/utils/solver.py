@@ -9,6 +9,8 @@ build_optimizer(..., fused=True), or CTDET_SGD_FUSED=1 in the environment, retur
 groups: the whole update in one multi-tensor HIP call instead of three foreach launches per group.  Off by default.
 args.max_grad_norm (optional; a positive float, or math.inf for the non-finite guard alone) is FusedSGD's max_grad_norm:
 gradient-norm clipping and the skip of non-finite steps on the device.  Only the fused optimizer has it.
+args.ema_decay (optional, with args.ema_warmup) attaches a ctdet.optim.WeightEMA of the model as `optimizer.ema`: the
+weights are averaged inside the fused update; evaluate under `with optimizer.ema.swapped():`.  Fused only as well.
 """
 import os
 from bisect import bisect_right
@@ -31,6 +33,15 @@ def build_optimizer(args, model, fused=None):
     if fused is None:
         fused = os.environ.get('CTDET_SGD_FUSED', '0') == '1'
     max_grad_norm = getattr(args, 'max_grad_norm', None)
+    ema_decay = getattr(args, 'ema_decay', None)
+    if ema_decay is not None:
+        if not fused:
+            raise ValueError('args.ema_decay = %r needs the fused optimizer (fused=True or CTDET_SGD_FUSED=1): with '
+                             'torch.optim.SGD call ctdet.optim.WeightEMA(model).update() after step()' % (ema_decay,))
+        from ctdet.optim import FusedSGD, WeightEMA
+        warmup = getattr(args, 'ema_warmup', None)
+        ema = WeightEMA(model, ema_decay) if warmup is None else WeightEMA(model, ema_decay, warmup)
+        return FusedSGD(groups, args.lr, momentum=args.momentum, max_grad_norm=max_grad_norm, ema=ema)
     if fused:
         from ctdet.optim import FusedSGD
         if max_grad_norm is None:

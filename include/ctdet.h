@@ -291,6 +291,81 @@ int ct_grad_norm_clip(const ct_grad_tensor* items_host, int n, float grad_scale,
 int ct_sgd_step_clipped(const ct_sgd_tensor* items_host, int n, float momentum, float dampening, int nesterov,
                         float grad_scale, const ct_clip_state* state_dev, ct_stream_t stream);
 
+/* Exponential moving average of the weights ("model averaging") riding on the fused step (csrc/ct_ema.hip).  Off unless
+ * called.  The update count, the decay of the step and the decision whether the step is averaged at all live in a
+ * 16-byte ct_ema_state on the device, next to ct_clip_state: nothing is synchronised to the host.
+ * ct_ema_begin opens one update; one launch of one thread, plain loads and stores of the 16 bytes, no atomics:
+ *     n       = state->updates
+ *     applied = clip ? clip->finite : 1
+ *     if applied:
+ *         nf  = (float)n
+ *         a   = 1.0f + nf
+ *         b   = warmup + nf
+ *         q   = a / b
+ *         d   = (warmup == 0) ? decay : min(decay, q)
+ *         om  = 1.0f - d
+ *         state = { n == INT_MAX ? n : n + 1, d, om, 1 }
+ *     else:
+ *         state->applied = 0                                    nothing else is written
+ * every line one fp32 rounding.  With warmup = 10 the first updates use d = 1/10, 2/11, 3/12, ... until that passes
+ * `decay`; a step the non-finite guard skipped does not advance n.  The caller zeroes the state once.
+ * CT_ERR_INVALID (nothing launched): a NULL or misaligned (4 bytes) state; decay outside [0, 1) or NaN; warmup other
+ * than 0 or a finite value >= 1; a misaligned clip state.
+ *
+ * ct_sgd_step_ema is ct_sgd_step (clip NULL) or ct_sgd_step_clipped (clip given) -- the same recurrence, the same bits
+ * in param and momentum_buf, the same skipped step -- and then, iff the step ran and ema_dev->applied != 0, on the new
+ * parameter value still in its register:
+ *     t   = d * ema
+ *     u   = om * p
+ *     ema = t + u
+ * with d = ema_dev->decay and om = ema_dev->one_minus, three fp32 roundings, no FMA.  A skipped step, or applied == 0,
+ * writes nothing to ema.  The dwordx4 path needs all four pointers (three without momentum) at one offset inside the
+ * 16-byte line; any other tensor moves one dword per lane.  The table travels in the kernel arguments,
+ * ct_sgd_ema_tensors_per_launch() (77) tensors per launch, no limit on n: ceil(tensors with numel > 0 / 77) launches.
+ * Argument errors as ct_sgd_step, plus a NULL ema of a non-empty tensor and a NULL or misaligned ema_dev.
+ *
+ * ct_ema_update runs the same three lines with src in place of p, for tensors the optimizer did not touch: parameters
+ * without a gradient this step, floating-point buffers such as the BatchNorm running statistics, or every tensor when
+ * the optimizer is torch's.  It writes nothing when applied == 0.  ema and src must not alias.
+ * ct_tensor_swap exchanges a and b element by element, to evaluate with the averaged weights in place and to put the
+ * live ones back; a == b or overlapping ranges are refused on the host.
+ * All three read and write no byte outside [ptr, ptr + numel), take numel == 0 with any pointers, validate the whole
+ * table before any device work, allocate nothing and never synchronise; items_host is not read after the call
+ * returns.  ct_ema_update and ct_tensor_swap carry 140 tensors per launch. */
+typedef struct ct_ema_state {
+    int updates;           /* updates applied so far (saturates at INT_MAX)                                */
+    float decay;           /* d of the last applied update                                                 */
+    float one_minus;       /* 1.0f - d, rounded once                                                       */
+    int applied;           /* 1: the last ct_ema_begin opened an update, 0: it was a skipped step           */
+} ct_ema_state;
+typedef struct ct_sgd_ema_tensor {
+    float* param;          /* as ct_sgd_tensor, field for field                   */
+    const float* grad;
+    float* momentum_buf;
+    int64_t numel;
+    float lr, weight_decay;
+    int first_step;
+    float* ema;            /* dev, updated in place; must not alias the others    */
+} ct_sgd_ema_tensor;
+typedef struct ct_ema_tensor {
+    float* ema;            /* dev, updated in place */
+    const float* src;      /* dev, read only        */
+    int64_t numel;         /* 0 .. 2^31-1           */
+} ct_ema_tensor;
+typedef struct ct_swap_tensor {
+    float* a;
+    float* b;
+    int64_t numel;         /* 0 .. 2^31-1           */
+} ct_swap_tensor;
+int ct_ema_begin(ct_ema_state* state_dev, float decay, float warmup, const ct_clip_state* clip_dev_or_null,
+                 ct_stream_t stream);
+int ct_sgd_ema_tensors_per_launch(void);
+int ct_sgd_step_ema(const ct_sgd_ema_tensor* items_host, int n, float momentum, float dampening, int nesterov,
+                    float grad_scale, const ct_clip_state* clip_dev_or_null, const ct_ema_state* ema_dev,
+                    ct_stream_t stream);
+int ct_ema_update(const ct_ema_tensor* items_host, int n, const ct_ema_state* ema_dev, ct_stream_t stream);
+int ct_tensor_swap(const ct_swap_tensor* items_host, int n, ct_stream_t stream);
+
 /* ---------------------------------------- batched test.py post-processing ---- */
 
 /* test.py:136-161 for a batch: per (image, class>=1) select score > conf_thresh, order by

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
    python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
-                               [--clip-norm X] [--deterministic] [--json]
+                               [--clip-norm X] [--ema DECAY] [--deterministic] [--json]
    --classes: classes of the conf head; default 20, with --phase 2 the width of the Context-Transformer block (60 for 'transfer',
    15 for 'incre': the head feeds the block);
    --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
    --wgrad-h2: CTDET_WGRAD_H2=1 for this run (the 1x1 weight gradients on ct_conv2d_wgrad_h2);
    --clip-norm X: FusedSGD(max_grad_norm=X) (implies --fused-sgd; `inf` is the non-finite guard alone): the norm and the
    clipping coefficient are computed on the device in front of the update, a non-finite step is skipped;
+   --ema DECAY: FusedSGD(ema=WeightEMA(net, DECAY)) (implies --fused-sgd): the weights are averaged inside the fused update and
+   the JSON line (always printed) carries the average's device state (`ema_info`: updates, decay, applied);
    --deterministic: CTDET_TRAIN_DETERMINISTIC=1 for this run (ordered slab sums in place of the floating-point atomics of the
    convolutional training step; with --phase 2 level 2, which adds the Context-Transformer block's backward);
    after the timing line it prints `deterministic_repeat`: whether two runs of the same step from the same state gave the same
@@ -29,8 +31,9 @@ ap.add_argument('--phase', type=int, default=1); ap.add_argument('--setting', de
 ap.add_argument('--fused-sgd', action='store_true'); ap.add_argument('--per-tensor-groups', action='store_true')
 ap.add_argument('--wgrad-h2', action='store_true'); ap.add_argument('--deterministic', action='store_true')
 ap.add_argument('--clip-norm', type=float, default=None); ap.add_argument('--json', action='store_true')
+ap.add_argument('--ema', type=float, default=None)
 a = ap.parse_args()
-if a.clip_norm is not None:
+if a.clip_norm is not None or a.ema is not None:
     a.fused_sgd = True
 if a.wgrad_h2:
     os.environ['CTDET_WGRAD_H2'] = '1'         # read once, when the TrainRuntime is built
@@ -58,10 +61,11 @@ def make_opt():
     if a.per_tensor_groups:
         from utils import solver
         return solver.build_optimizer(types.SimpleNamespace(method='ours', phase=a.phase, lr=1e-4, momentum=0.9, weight_decay=5e-4,
-                                                            max_grad_norm=a.clip_norm), net, fused=a.fused_sgd)
+                                                            max_grad_norm=a.clip_norm, ema_decay=a.ema), net, fused=a.fused_sgd)
     if a.fused_sgd:
-        from ctdet.optim import FusedSGD
-        return FusedSGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4, max_grad_norm=a.clip_norm)
+        from ctdet.optim import FusedSGD, WeightEMA
+        return FusedSGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4, max_grad_norm=a.clip_norm,
+                        ema=None if a.ema is None else WeightEMA(net, a.ema))
     return torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4)
 opt = make_opt()
 x = synth.images(a.batch, a.size, 'randn', 1234 + rank).cuda()
@@ -100,13 +104,15 @@ if rank == 0:
     print('RFBNet-%d phase %d bs=%d x %d GPU(s)%s: %.1f ms/step = %.1f img/s | fwd %.1f  loss %.1f  bwd %.1f ms | loss %.4f'
           % (a.size, a.phase, a.batch, world, ' [%s, %d groups]' % (type(opt).__name__, len(opt.param_groups))
              if a.fused_sgd or a.per_tensor_groups else '', dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
-    if a.json or a.clip_norm is not None or a.deterministic:
+    if a.json or a.clip_norm is not None or a.ema is not None or a.deterministic:
         row = {'train_bench': 'RFBNet-%d phase %d' % (a.size, a.phase), 'batch': a.batch, 'gpus': world, 'steps': n,
                'optimizer': type(opt).__name__, 'groups': len(opt.param_groups), 'ms_per_step': round(dt * 1e3, 3),
                'fwd_ms': round(tf / n, 3), 'loss_ms': round(tl / n, 3), 'bwd_ms': round(tb / n, 3), 'opt_ms': round(to / n, 3),
                'clip_norm': a.clip_norm, 'loss': float(loss)}
         if a.clip_norm is not None:
             row.update(opt.clip_info())                 # norm, coef, finite, nonfinite of the last step
+        if a.ema is not None:
+            row.update(ema_decay=a.ema, ema_info=opt.ema.info())
         row['policy'] = trt.policy_record()             # deterministic: true / false, the weight-gradient routes
         print(json.dumps(row))
 if a.deterministic:
