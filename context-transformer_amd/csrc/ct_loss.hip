@@ -4,7 +4,12 @@
 // the image's keys (held in LDS) finds the num_neg-th largest.  Every reduction runs in a fixed order -- no float
 // atomics in this file -- so results are bit-identical from run to run and an image's selection does not depend on
 // its batch mates.  Compiled with -ffp-contract=off.
+// The localisation term is smooth-L1 on the encoded offsets or, in the IOU instantiations of the two per-prior kernels
+// (ct_multibox_loss_fwd_loc / _bwd_loc), one of the IoU-family terms of ct_iou_loss.h on the decoded boxes.
 #include "ct_common.h"
+#include "ct_iou_loss.h"
+
+#include <cmath>
 
 #include <algorithm>
 #include <cstdint>
@@ -62,15 +67,25 @@ __device__ inline float smooth_l1(float d)
     return a < 1.f ? 0.5f * d * d : a - 0.5f;
 }
 
+// What the IOU instantiations need beyond the smooth-L1 arguments; the others ignore it.
+struct LocArgs {
+    const float4* priors;   // [P] centre form
+    int num_priors;
+    int kind;               // CT_LOC_*
+    float var0, var1;
+};
+
 // ---------------------------------------------------------------------------------------------------- per prior
-// ws[row] = (smooth-L1 sum, objectness CE, mining key, class CE).  The class CE is taken on the fused logits
+// ws[row] = (localisation term, objectness CE, mining key, class CE).  The localisation term is the smooth-L1 sum of
+// every row or, with IOU, the IoU-family term of a positive row of non-zero weight and 0 of any other row, whose loc,
+// loc_t and prior are then not read (kind is uniform over the launch).  The class CE is taken on the fused logits
 // z = [o0 + lse(conf), o1 + conf_1 ..]; since logsumexp(z) = lse(conf) + logsumexp(o0, o1), it is
 // CE_obj(0) for target 0 and (lse(conf) - conf_t) + CE_obj(1) for a foreground target.
-template <int G, bool VEC>
+template <int G, bool VEC, bool IOU>
 __global__ __launch_bounds__(ROW_THREADS) void loss_prior_kernel(
     const float4* __restrict__ loc, const float* __restrict__ conf, const float2* __restrict__ obj,
     const float4* __restrict__ loc_t, const float2* __restrict__ conf_t, const uint8_t* __restrict__ obj_t,
-    long long rows, int nfg, float4* __restrict__ ws)
+    long long rows, int nfg, float4* __restrict__ ws, LocArgs la)
 {
     const int sub = threadIdx.x % G;
     const long long row = (long long)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
@@ -83,8 +98,14 @@ __global__ __launch_bounds__(ROW_THREADS) void loss_prior_kernel(
     row_max_sumexp<G, VEC>(crow, sub, items, v0, m, s);
     if (sub != 0 || !live) return;
 
-    const float4 a = loc[r], b = loc_t[r];
-    const float l1 = (smooth_l1(a.x - b.x) + smooth_l1(a.y - b.y)) + (smooth_l1(a.z - b.z) + smooth_l1(a.w - b.w));
+    const float2 ct = conf_t[r];
+    float l1 = 0.f;
+    if (!IOU) {
+        const float4 a = loc[r], b = loc_t[r];
+        l1 = (smooth_l1(a.x - b.x) + smooth_l1(a.y - b.y)) + (smooth_l1(a.z - b.z) + smooth_l1(a.w - b.w));
+    } else if (ct.x > 0.f && ct.y != 0.f) {
+        l1 = ctdet::iou_row_forward(loc[r], loc_t[r], la.priors[r % la.num_priors], la.var0, la.var1, la.kind).loss;
+    }
     const float2 o = obj[r];
     const float om = fmaxf(o.x, o.y);
     const float olse = logf(expf(o.x - om) + expf(o.y - om));
@@ -92,7 +113,7 @@ __global__ __launch_bounds__(ROW_THREADS) void loss_prior_kernel(
     const bool ot = obj_t[r] != 0;
     const float ce_obj = ot ? ce1 : ce0;
     const float key = (!ot && ce_obj > 0.f) ? ce_obj : 0.f;            // never -0 or NaN: the select orders bit patterns
-    const int t = class_target(conf_t[r].x, nfg);
+    const int t = class_target(ct.x, nfg);
     float ce_cls = ce0;
     if (t > 0) ce_cls = ((m + logf(s)) - crow[t - 1]) + ce1;
     ws[r] = make_float4(l1, ce_obj, key, ce_cls);
@@ -264,12 +285,12 @@ __global__ void loss_finish_kernel(const double* __restrict__ partial, const lon
 // With p = softmax(fused logits), s = softmax(obj), q = softmax(conf): p_0 = s_0 and p_k = s_1 q_k, so
 //   d cls / d conf_k = [t >= 1] q_k - [t = k],   d cls / d obj = s - onehot(t >= 1),   d obj-loss / d obj = s - onehot(obj_t).
 // A row with w = 0 (then weight * pos = 0 too) is written as zeros without looking at its logits.
-template <int G, bool VEC>
+template <int G, bool VEC, bool IOU>
 __global__ __launch_bounds__(ROW_THREADS) void loss_bwd_kernel(
     const float4* __restrict__ loc, const float* __restrict__ conf, const float2* __restrict__ obj,
     const float4* __restrict__ loc_t, const float2* __restrict__ conf_t, const uint8_t* __restrict__ obj_t,
     const float* __restrict__ w, const float* __restrict__ g, long long rows, int nfg,
-    float4* __restrict__ dloc, float* __restrict__ dconf, float2* __restrict__ dobj)
+    float4* __restrict__ dloc, float* __restrict__ dconf, float2* __restrict__ dobj, LocArgs la)
 {
     const int sub = threadIdx.x % G;
     const long long row = (long long)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
@@ -312,10 +333,16 @@ __global__ __launch_bounds__(ROW_THREADS) void loss_bwd_kernel(
     if (ct.x > 0.f && ct.y != 0.f) {
         const float4 a = loc[row], b = loc_t[row];
         const float gl = g0 * ct.y;
-        dl.x = gl * fminf(fmaxf(a.x - b.x, -1.f), 1.f);
-        dl.y = gl * fminf(fmaxf(a.y - b.y, -1.f), 1.f);
-        dl.z = gl * fminf(fmaxf(a.z - b.z, -1.f), 1.f);
-        dl.w = gl * fminf(fmaxf(a.w - b.w, -1.f), 1.f);
+        if (!IOU) {
+            dl.x = gl * fminf(fmaxf(a.x - b.x, -1.f), 1.f);
+            dl.y = gl * fminf(fmaxf(a.y - b.y, -1.f), 1.f);
+            dl.z = gl * fminf(fmaxf(a.z - b.z, -1.f), 1.f);
+            dl.w = gl * fminf(fmaxf(a.w - b.w, -1.f), 1.f);
+        } else {
+            const float4 p = la.priors[row % la.num_priors];
+            const ctdet::IouRow ir = ctdet::iou_row_forward(a, b, p, la.var0, la.var1, la.kind);
+            ctdet::iou_row_backward(ir, p, la.var0, la.var1, la.kind, gl, dl.x, dl.y, dl.z, dl.w);
+        }
     }
     dloc[row] = dl;
 
@@ -347,49 +374,69 @@ extern "C" size_t ct_multibox_loss_workspace_bytes(int batch, int num_priors, in
     return ws_rows_bytes(batch, num_priors) + ctdet::align_up((size_t)batch * 3 * sizeof(double), 256);
 }
 
-// launch KERNEL<G, VEC> for the row length nfg; `vec` (16-byte loads allowed), `rows`, `nfg`, `st` come from the caller
-#define CT_LOSS_DISPATCH(KERNEL, ...)                                                                            \
+// launch KERNEL<G, VEC, IOU> for the row length nfg; `vec` (16-byte loads allowed), `rows`, `nfg`, `st` come from the caller
+#define CT_LOSS_DISPATCH(KERNEL, IOU, ...)                                                                       \
     do {                                                                                                         \
         const int G = group_for(vec ? nfg / 4 : nfg);                                                            \
         const long long nblk = (rows + ROW_THREADS / G - 1) / (ROW_THREADS / G);                                 \
         CT_REQUIRE(nblk < 0x7FFFFFFFLL, "%s: too many priors", #KERNEL);                                         \
         const dim3 grid((unsigned)nblk), block(ROW_THREADS);                                                     \
         if (vec) {                                                                                               \
-            if (G == 4) hipLaunchKernelGGL((KERNEL<4, true>), grid, block, 0, st, __VA_ARGS__);                  \
-            else if (G == 8) hipLaunchKernelGGL((KERNEL<8, true>), grid, block, 0, st, __VA_ARGS__);             \
-            else if (G == 16) hipLaunchKernelGGL((KERNEL<16, true>), grid, block, 0, st, __VA_ARGS__);           \
-            else hipLaunchKernelGGL((KERNEL<64, true>), grid, block, 0, st, __VA_ARGS__);                        \
+            if (G == 4) hipLaunchKernelGGL((KERNEL<4, true, IOU>), grid, block, 0, st, __VA_ARGS__);             \
+            else if (G == 8) hipLaunchKernelGGL((KERNEL<8, true, IOU>), grid, block, 0, st, __VA_ARGS__);        \
+            else if (G == 16) hipLaunchKernelGGL((KERNEL<16, true, IOU>), grid, block, 0, st, __VA_ARGS__);      \
+            else hipLaunchKernelGGL((KERNEL<64, true, IOU>), grid, block, 0, st, __VA_ARGS__);                   \
         } else {                                                                                                 \
-            if (G == 4) hipLaunchKernelGGL((KERNEL<4, false>), grid, block, 0, st, __VA_ARGS__);                 \
-            else if (G == 8) hipLaunchKernelGGL((KERNEL<8, false>), grid, block, 0, st, __VA_ARGS__);            \
-            else if (G == 16) hipLaunchKernelGGL((KERNEL<16, false>), grid, block, 0, st, __VA_ARGS__);          \
-            else hipLaunchKernelGGL((KERNEL<64, false>), grid, block, 0, st, __VA_ARGS__);                       \
+            if (G == 4) hipLaunchKernelGGL((KERNEL<4, false, IOU>), grid, block, 0, st, __VA_ARGS__);            \
+            else if (G == 8) hipLaunchKernelGGL((KERNEL<8, false, IOU>), grid, block, 0, st, __VA_ARGS__);       \
+            else if (G == 16) hipLaunchKernelGGL((KERNEL<16, false, IOU>), grid, block, 0, st, __VA_ARGS__);     \
+            else hipLaunchKernelGGL((KERNEL<64, false, IOU>), grid, block, 0, st, __VA_ARGS__);                  \
         }                                                                                                        \
         CT_LAUNCH_CHECK(#KERNEL);                                                                                \
     } while (0)
 
-extern "C" int ct_multibox_loss_fwd(const float* loc, const float* conf, const float* obj, const float* loc_t,
-                                    const float* conf_t, const uint8_t* obj_t, int batch, int num_priors,
-                                    int num_classes, int negpos_ratio, float* sums, long long* num_pos, long long* n,
-                                    float* w, void* ws, size_t ws_bytes, ct_stream_t stream)
+namespace {
+
+// the checks of the _loc entries, before any HIP call; `fn` names the entry in the message
+int check_loc_args(const char* fn, const float* priors, int loc_loss, float var0, float var1)
 {
-    CT_REQUIRE(loc && conf && obj && loc_t && conf_t && obj_t && sums && num_pos && n && w && ws,
-               "ct_multibox_loss_fwd: null pointer");
-    CT_REQUIRE(batch > 0 && num_priors > 0, "ct_multibox_loss_fwd: batch=%d num_priors=%d", batch, num_priors);
-    CT_REQUIRE(num_classes >= 2, "ct_multibox_loss_fwd: num_classes=%d (at least background and one class)", num_classes);
-    CT_REQUIRE(negpos_ratio >= 0, "ct_multibox_loss_fwd: negpos_ratio=%d", negpos_ratio);
+    CT_REQUIRE(loc_loss >= CT_LOC_SMOOTH_L1 && loc_loss <= CT_LOC_CIOU,
+               "%s: loc_loss=%d (0 smooth-L1, 1 iou, 2 giou, 3 diou, 4 ciou)", fn, loc_loss);
+    CT_REQUIRE(std::isfinite(var0) && std::isfinite(var1) && var0 > 0.f && var1 > 0.f,
+               "%s: variances (%g, %g) must be positive and finite", fn, (double)var0, (double)var1);
+    if (loc_loss != CT_LOC_SMOOTH_L1) {
+        CT_REQUIRE(priors != nullptr, "%s: loc_loss=%d needs priors (null pointer)", fn, loc_loss);
+        CT_REQUIRE((reinterpret_cast<uintptr_t>(priors) & 15) == 0, "%s: priors must be 16-byte aligned", fn);
+    }
+    return CT_OK;
+}
+
+// the shared launcher of ct_multibox_loss_fwd and _fwd_loc: the same three launches whatever la.kind
+int loss_fwd(const char* fn, const float* loc, const float* conf, const float* obj, const float* loc_t,
+             const float* conf_t, const uint8_t* obj_t, int batch, int num_priors, int num_classes, int negpos_ratio,
+             float* sums, long long* num_pos, long long* n, float* w, void* ws, size_t ws_bytes, ct_stream_t stream,
+             LocArgs la)
+{
+    CT_REQUIRE(loc && conf && obj && loc_t && conf_t && obj_t && sums && num_pos && n && w && ws, "%s: null pointer", fn);
+    CT_REQUIRE(batch > 0 && num_priors > 0, "%s: batch=%d num_priors=%d", fn, batch, num_priors);
+    CT_REQUIRE(num_classes >= 2, "%s: num_classes=%d (at least background and one class)", fn, num_classes);
+    CT_REQUIRE(negpos_ratio >= 0, "%s: negpos_ratio=%d", fn, negpos_ratio);
     const size_t need = ct_multibox_loss_workspace_bytes(batch, num_priors, num_classes);
-    if (ws_bytes < need)
-        return ctdet::fail(CT_ERR_WORKSPACE, "ct_multibox_loss_fwd: workspace %zu < %zu", ws_bytes, need);
+    if (ws_bytes < need) return ctdet::fail(CT_ERR_WORKSPACE, "%s: workspace %zu < %zu", fn, ws_bytes, need);
     hipStream_t st = ctdet::as_stream(stream);
     const long long rows = (long long)batch * num_priors;
     const int nfg = num_classes - 1;
     float4* rows_ws = (float4*)ws;
     double* partial = (double*)((char*)ws + ws_rows_bytes(batch, num_priors));
+    la.num_priors = num_priors;
 
     const bool vec = nfg % 4 == 0 && (reinterpret_cast<uintptr_t>(conf) & 15) == 0;
-    CT_LOSS_DISPATCH(loss_prior_kernel, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
-                     (const float2*)conf_t, obj_t, rows, nfg, rows_ws);
+    if (la.kind == CT_LOC_SMOOTH_L1)
+        CT_LOSS_DISPATCH(loss_prior_kernel, false, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                         (const float2*)conf_t, obj_t, rows, nfg, rows_ws, la);
+    else
+        CT_LOSS_DISPATCH(loss_prior_kernel, true, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                         (const float2*)conf_t, obj_t, rows, nfg, rows_ws, la);
 
     if (num_priors <= LDS_MAX_KEYS) {
         const size_t lds = (size_t)num_priors * sizeof(unsigned);
@@ -413,20 +460,70 @@ extern "C" int ct_multibox_loss_fwd(const float* loc, const float* conf, const f
     return CT_OK;
 }
 
+int loss_bwd(const char* fn, const float* loc, const float* conf, const float* obj, const float* loc_t,
+             const float* conf_t, const uint8_t* obj_t, const float* w, const float* g, int batch, int num_priors,
+             int num_classes, float* dloc, float* dconf, float* dobj, ct_stream_t stream, LocArgs la)
+{
+    CT_REQUIRE(loc && conf && obj && loc_t && conf_t && obj_t && w && g && dloc && dconf && dobj, "%s: null pointer", fn);
+    CT_REQUIRE(batch > 0 && num_priors > 0, "%s: batch=%d num_priors=%d", fn, batch, num_priors);
+    CT_REQUIRE(num_classes >= 2, "%s: num_classes=%d (at least background and one class)", fn, num_classes);
+    hipStream_t st = ctdet::as_stream(stream);
+    const long long rows = (long long)batch * num_priors;
+    const int nfg = num_classes - 1;
+    la.num_priors = num_priors;
+    const bool vec = nfg % 4 == 0 && ((reinterpret_cast<uintptr_t>(conf) | reinterpret_cast<uintptr_t>(dconf)) & 15) == 0;
+    if (la.kind == CT_LOC_SMOOTH_L1)
+        CT_LOSS_DISPATCH(loss_bwd_kernel, false, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                         (const float2*)conf_t, obj_t, w, g, rows, nfg, (float4*)dloc, dconf, (float2*)dobj, la);
+    else
+        CT_LOSS_DISPATCH(loss_bwd_kernel, true, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                         (const float2*)conf_t, obj_t, w, g, rows, nfg, (float4*)dloc, dconf, (float2*)dobj, la);
+    return CT_OK;
+}
+
+const LocArgs SMOOTH_L1_ARGS = {nullptr, 0, CT_LOC_SMOOTH_L1, 0.f, 0.f};
+
+}  // namespace
+
+extern "C" int ct_multibox_loss_fwd(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                                    const float* conf_t, const uint8_t* obj_t, int batch, int num_priors,
+                                    int num_classes, int negpos_ratio, float* sums, long long* num_pos, long long* n,
+                                    float* w, void* ws, size_t ws_bytes, ct_stream_t stream)
+{
+    return loss_fwd("ct_multibox_loss_fwd", loc, conf, obj, loc_t, conf_t, obj_t, batch, num_priors, num_classes,
+                    negpos_ratio, sums, num_pos, n, w, ws, ws_bytes, stream, SMOOTH_L1_ARGS);
+}
+
 extern "C" int ct_multibox_loss_bwd(const float* loc, const float* conf, const float* obj, const float* loc_t,
                                     const float* conf_t, const uint8_t* obj_t, const float* w, const float* g,
                                     int batch, int num_priors, int num_classes, float* dloc, float* dconf,
                                     float* dobj, ct_stream_t stream)
 {
-    CT_REQUIRE(loc && conf && obj && loc_t && conf_t && obj_t && w && g && dloc && dconf && dobj,
-               "ct_multibox_loss_bwd: null pointer");
-    CT_REQUIRE(batch > 0 && num_priors > 0, "ct_multibox_loss_bwd: batch=%d num_priors=%d", batch, num_priors);
-    CT_REQUIRE(num_classes >= 2, "ct_multibox_loss_bwd: num_classes=%d (at least background and one class)", num_classes);
-    hipStream_t st = ctdet::as_stream(stream);
-    const long long rows = (long long)batch * num_priors;
-    const int nfg = num_classes - 1;
-    const bool vec = nfg % 4 == 0 && ((reinterpret_cast<uintptr_t>(conf) | reinterpret_cast<uintptr_t>(dconf)) & 15) == 0;
-    CT_LOSS_DISPATCH(loss_bwd_kernel, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
-                     (const float2*)conf_t, obj_t, w, g, rows, nfg, (float4*)dloc, dconf, (float2*)dobj);
-    return CT_OK;
+    return loss_bwd("ct_multibox_loss_bwd", loc, conf, obj, loc_t, conf_t, obj_t, w, g, batch, num_priors, num_classes,
+                    dloc, dconf, dobj, stream, SMOOTH_L1_ARGS);
 }
+
+extern "C" int ct_multibox_loss_fwd_loc(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                                        const float* conf_t, const uint8_t* obj_t, int batch, int num_priors,
+                                        int num_classes, int negpos_ratio, float* sums, long long* num_pos, long long* n,
+                                        float* w, void* ws, size_t ws_bytes, ct_stream_t stream, const float* priors,
+                                        int loc_loss, float var0, float var1)
+{
+    if (const int rc = check_loc_args("ct_multibox_loss_fwd_loc", priors, loc_loss, var0, var1)) return rc;
+    const LocArgs la = {loc_loss == CT_LOC_SMOOTH_L1 ? nullptr : (const float4*)priors, 0, loc_loss, var0, var1};
+    return loss_fwd("ct_multibox_loss_fwd_loc", loc, conf, obj, loc_t, conf_t, obj_t, batch, num_priors, num_classes,
+                    negpos_ratio, sums, num_pos, n, w, ws, ws_bytes, stream, la);
+}
+
+extern "C" int ct_multibox_loss_bwd_loc(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                                        const float* conf_t, const uint8_t* obj_t, const float* w, const float* g,
+                                        int batch, int num_priors, int num_classes, float* dloc, float* dconf,
+                                        float* dobj, ct_stream_t stream, const float* priors, int loc_loss, float var0,
+                                        float var1)
+{
+    if (const int rc = check_loc_args("ct_multibox_loss_bwd_loc", priors, loc_loss, var0, var1)) return rc;
+    const LocArgs la = {loc_loss == CT_LOC_SMOOTH_L1 ? nullptr : (const float4*)priors, 0, loc_loss, var0, var1};
+    return loss_bwd("ct_multibox_loss_bwd_loc", loc, conf, obj, loc_t, conf_t, obj_t, w, g, batch, num_priors,
+                    num_classes, dloc, dconf, dobj, stream, la);
+}
+

@@ -10,6 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CTDET_LIB') or os.path.join(os.path.dirname(_HERE), 'lib', 'libctdet.so')
 
 CT_OK = 0
+# CT_LOC_*: the localisation term of ct_multibox_loss_fwd_loc / _bwd_loc, by position
+LOC_LOSSES = ('smooth_l1', 'iou', 'giou', 'diou', 'ciou')
 
 
 class CtdetError(RuntimeError):
@@ -135,6 +137,8 @@ SIGNATURES = {
     'ct_multibox_loss_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_multibox_loss_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_multibox_loss_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'ct_multibox_loss_fwd_loc': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _F, _F]),
+    'ct_multibox_loss_bwd_loc': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, _F]),
     'ct_sgd_tensors_per_launch': (_I, []),
     'ct_sgd_step': (_I, [C.POINTER(SgdTensor), _I, _F, _F, _I, _F, _P]),
     'ct_grad_norm_tensors_per_launch': (_I, []),

@@ -149,9 +149,26 @@ def _u8(t, name):
     return _dev(t, name, torch.uint8)
 
 
-def multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio):
+def _loc_args(priors, loc_loss, variances, num_priors):
+    """The trailing (priors, loc_loss, var0, var1) of the _loc entries, or None for the entries without them: the default
+    term with no priors given."""
+    if loc_loss not in _lib.LOC_LOSSES:
+        raise ValueError('loc_loss must be one of %s, got %r' % (', '.join(_lib.LOC_LOSSES), loc_loss))
+    if priors is None:
+        if loc_loss != 'smooth_l1':
+            raise _lib.CtdetError('loc_loss=%r needs the priors the targets were matched against' % (loc_loss,))
+        return None
+    if tuple(priors.shape) != (num_priors, 4):
+        raise _lib.CtdetError('priors must be [%d,4], got %s' % (num_priors, tuple(priors.shape)))
+    return (_dev(priors, 'priors'), _lib.LOC_LOSSES.index(loc_loss), float(variances[0]), float(variances[1]))
+
+
+def multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio, priors=None, loc_loss='smooth_l1',
+                  variances=(0.1, 0.2)):
     """layers/modules/multibox_loss_combined.py:76-122 fused (ct_multibox_loss_fwd) -> sums [3] = un-normalised
-    (loc, cls, obj) losses, n int64 [1], num_pos int64 [B], w [B,P] = weight * (pos | hard negative)."""
+    (loc, cls, obj) losses, n int64 [1], num_pos int64 [B], w [B,P] = weight * (pos | hard negative).
+    loc_loss: 'smooth_l1' or one of 'iou', 'giou', 'diou', 'ciou' on the boxes decoded with `priors` [P,4] (centre form)
+    and `variances` (include/ctdet.h, ct_multibox_loss_fwd_loc, which is called whenever priors are given)."""
     _dev(loc, 'loc')
     dev = loc.device
     B, P = loc.shape[0], loc.shape[1]
@@ -161,28 +178,38 @@ def multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_rati
             raise _lib.CtdetError('%s must be [%d,%d,%d], got %s' % (name, B, P, last, tuple(t.shape)))
     if tuple(obj_t.shape) != (B, P):
         raise _lib.CtdetError('obj_t must be [%d,%d], got %s' % (B, P, tuple(obj_t.shape)))
+    extra = _loc_args(priors, loc_loss, variances, P)
     sums = torch.empty(3, device=dev)
     n = torch.empty(1, device=dev, dtype=torch.int64)
     num_pos = torch.empty(B, device=dev, dtype=torch.int64)
     w = torch.empty(B, P, device=dev)
     ws_bytes = lib().ct_multibox_loss_workspace_bytes(B, P, int(num_classes))
     ws = torch.empty(max(ws_bytes, 1), device=dev, dtype=torch.uint8)
-    check(lib().ct_multibox_loss_fwd(_dev(loc, 'loc'), _dev(conf, 'conf'), _dev(obj, 'obj'), _dev(loc_t, 'loc_t'),
-                                     _dev(conf_t, 'conf_t'), _u8(obj_t, 'obj_t'), B, P, int(num_classes),
-                                     int(negpos_ratio), _dev(sums, 'sums'), _dev(num_pos, 'num_pos', torch.int64),
-                                     _dev(n, 'n', torch.int64), _dev(w, 'w'), _dev(ws, 'ws', torch.uint8), ws_bytes,
-                                     _stream()), 'ct_multibox_loss_fwd')
+    args = (_dev(loc, 'loc'), _dev(conf, 'conf'), _dev(obj, 'obj'), _dev(loc_t, 'loc_t'), _dev(conf_t, 'conf_t'),
+            _u8(obj_t, 'obj_t'), B, P, int(num_classes), int(negpos_ratio), _dev(sums, 'sums'),
+            _dev(num_pos, 'num_pos', torch.int64), _dev(n, 'n', torch.int64), _dev(w, 'w'), _dev(ws, 'ws', torch.uint8),
+            ws_bytes, _stream())
+    if extra is None:
+        check(lib().ct_multibox_loss_fwd(*args), 'ct_multibox_loss_fwd')
+    else:
+        check(lib().ct_multibox_loss_fwd_loc(*args, *extra), 'ct_multibox_loss_fwd_loc')
     return sums, n, num_pos, w
 
 
-def multibox_loss_backward(loc, conf, obj, loc_t, conf_t, obj_t, w, g, num_classes):
-    """Gradients of (g * sums).sum() w.r.t. (loc, conf, obj); g is a DEVICE [3] tensor (ct_multibox_loss_bwd)."""
+def multibox_loss_backward(loc, conf, obj, loc_t, conf_t, obj_t, w, g, num_classes, priors=None, loc_loss='smooth_l1',
+                           variances=(0.1, 0.2)):
+    """Gradients of (g * sums).sum() w.r.t. (loc, conf, obj); g is a DEVICE [3] tensor (ct_multibox_loss_bwd, or
+    ct_multibox_loss_bwd_loc when priors are given -- the same priors, loc_loss and variances as in the forward)."""
     B, P = loc.shape[0], loc.shape[1]
+    extra = _loc_args(priors, loc_loss, variances, P)
     dloc, dconf, dobj = torch.empty_like(loc), torch.empty_like(conf), torch.empty_like(obj)
-    check(lib().ct_multibox_loss_bwd(_dev(loc, 'loc'), _dev(conf, 'conf'), _dev(obj, 'obj'), _dev(loc_t, 'loc_t'),
-                                     _dev(conf_t, 'conf_t'), _u8(obj_t, 'obj_t'), _dev(w, 'w'), _dev(g, 'g'),
-                                     B, P, int(num_classes), _dev(dloc, 'dloc'), _dev(dconf, 'dconf'),
-                                     _dev(dobj, 'dobj'), _stream()), 'ct_multibox_loss_bwd')
+    args = (_dev(loc, 'loc'), _dev(conf, 'conf'), _dev(obj, 'obj'), _dev(loc_t, 'loc_t'), _dev(conf_t, 'conf_t'),
+            _u8(obj_t, 'obj_t'), _dev(w, 'w'), _dev(g, 'g'), B, P, int(num_classes), _dev(dloc, 'dloc'),
+            _dev(dconf, 'dconf'), _dev(dobj, 'dobj'), _stream())
+    if extra is None:
+        check(lib().ct_multibox_loss_bwd(*args), 'ct_multibox_loss_bwd')
+    else:
+        check(lib().ct_multibox_loss_bwd_loc(*args, *extra), 'ct_multibox_loss_bwd_loc')
     return dloc, dconf, dobj
 
 

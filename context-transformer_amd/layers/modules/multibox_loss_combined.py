@@ -5,9 +5,13 @@ library (`ct_match_batched`) instead of a Python loop over images and ground tru
 arithmetic itself (smooth-L1, two cross-entropies, 3:1 hard-negative ranking) has two forms: torch ops on
 the device tensors with autograd (the default), or -- `fused=True` / CTDET_LOSS_FUSED=1 -- the library's
 ct_multibox_loss_fwd / _bwd (three launches forward, one backward, no sort) behind one autograd Function.
+The localisation term is the reference's smooth-L1 on the encoded offsets (the default) or -- `loc_loss=` /
+CTDET_LOC_LOSS -- 1 - IoU, GIoU, DIoU or CIoU between the decoded prediction and the decoded target of every positive
+prior (defined in include/ctdet.h at ct_multibox_loss_fwd_loc), in both forms; `loc_weight` multiplies loss_box_reg.
 targets: list of [G,6] tensors = [x1,y1,x2,y2,label,mixup_weight], or an ops.PackedTargets holding the same rows on
 the device (what preproc(decisions='device').batch_device returns).
 """
+import math
 import os
 
 import torch
@@ -28,24 +32,91 @@ class FusedMultiBoxLoss(torch.autograd.Function):
     backward kernel as a device pointer, so a normaliser applied outside (`sums / n`) scales it for free."""
 
     @staticmethod
-    def forward(ctx, loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio):
-        sums, n, num_pos, w = ops.multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio)
+    def forward(ctx, loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio, priors=None, loc_loss='smooth_l1',
+                variances=(0.1, 0.2)):
+        sums, n, num_pos, w = ops.multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio,
+                                                priors=priors, loc_loss=loc_loss, variances=variances)
         ctx.save_for_backward(loc, conf, obj, loc_t, conf_t, obj_t, w)
         ctx.num_classes = num_classes
+        ctx.loc = (priors, loc_loss, tuple(variances))
         ctx.mark_non_differentiable(n, num_pos, w)
         return sums, n, num_pos, w
 
     @staticmethod
     def backward(ctx, g, *unused):
         loc, conf, obj, loc_t, conf_t, obj_t, w = ctx.saved_tensors
+        priors, loc_loss, variances = ctx.loc
         dloc, dconf, dobj = ops.multibox_loss_backward(loc, conf, obj, loc_t, conf_t, obj_t, w,
-                                                       g.to(torch.float32).contiguous(), ctx.num_classes)
-        return dloc, dconf, dobj, None, None, None, None, None
+                                                       g.to(torch.float32).contiguous(), ctx.num_classes,
+                                                       priors=priors, loc_loss=loc_loss, variances=variances)
+        return dloc, dconf, dobj, None, None, None, None, None, None, None, None
+
+
+LOC_LOSSES = _lib.LOC_LOSSES        # 'smooth_l1' and the four IoU kinds
+
+
+class _ScaleGrad(torch.autograd.Function):
+    """x in the forward, grad * weight in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.weight = weight
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.weight, None
+
+
+class _ScaleValue(torch.autograd.Function):
+    """x * weight in the forward, the gradient passed through unchanged: the other half of _ScaleGrad."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        return x * weight
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def _decode_rows(l, priors, variance):
+    """utils/box_utils.py:184 on [B,P,4] offsets: -> x1, y1, x2, y2, cx, cy, w, h, each [B,P]."""
+    cx = priors[:, 0] + l[..., 0] * variance[0] * priors[:, 2]
+    cy = priors[:, 1] + l[..., 1] * variance[0] * priors[:, 3]
+    w = priors[:, 2] * torch.exp(l[..., 2] * variance[1])
+    h = priors[:, 3] * torch.exp(l[..., 3] * variance[1])
+    return cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2, cx, cy, w, h
+
+
+def iou_loss_rows(kind, loc, loc_t, priors, variance):
+    """The IoU-family term of every row, [B,P] (torch ops with autograd; include/ctdet.h has the definition)."""
+    ax1, ay1, ax2, ay2, acx, acy, aw, ah = _decode_rows(loc, priors, variance)
+    tx1, ty1, tx2, ty2, tcx, tcy, tw, th = _decode_rows(loc_t, priors, variance)
+    iw = (torch.minimum(ax2, tx2) - torch.maximum(ax1, tx1)).clamp_min(0)
+    ih = (torch.minimum(ay2, ty2) - torch.maximum(ay1, ty1)).clamp_min(0)
+    inter = iw * ih
+    union = aw * ah + tw * th - inter
+    iou = inter / union
+    loss = 1 - iou
+    if kind == 'iou':
+        return loss
+    cw = torch.maximum(ax2, tx2) - torch.minimum(ax1, tx1)
+    ch = torch.maximum(ay2, ty2) - torch.minimum(ay1, ty1)
+    if kind == 'giou':
+        return loss + (cw * ch - union) / (cw * ch)
+    loss = loss + ((acx - tcx) ** 2 + (acy - tcy) ** 2) / (cw ** 2 + ch ** 2)
+    if kind == 'diou':
+        return loss
+    v = (4 / math.pi ** 2) * (torch.atan(tw / th) - torch.atan(aw / ah)) ** 2
+    with torch.no_grad():               # alpha is a constant in the backward pass; 0 where v = 0 (never 0 / 0)
+        alpha = torch.where(v > 0, v / ((1 - iou) + v).masked_fill(v <= 0, 1.0), torch.zeros_like(v))
+    return loss + alpha * v
 
 
 class MultiBoxLoss_combined(nn.Module):
     def __init__(self, num_classes, overlap_thresh, prior_for_matching, bkg_label, neg_mining, neg_pos,
-                 neg_overlap, encode_target, fused=None):
+                 neg_overlap, encode_target, fused=None, loc_loss=None, loc_weight=1.0):
         super().__init__()
         # fused: the HIP loss kernels instead of the torch ops below; None reads CTDET_LOSS_FUSED (default off)
         self.fused = os.environ.get('CTDET_LOSS_FUSED', '0') == '1' if fused is None else bool(fused)
@@ -58,6 +129,13 @@ class MultiBoxLoss_combined(nn.Module):
         self.negpos_ratio = neg_pos
         self.neg_overlap = neg_overlap
         self.variance = [0.1, 0.2]
+        # loc_loss: the localisation term, one of LOC_LOSSES; None reads CTDET_LOC_LOSS (unset or empty: smooth_l1)
+        if loc_loss is None:
+            loc_loss = os.environ.get('CTDET_LOC_LOSS', '') or 'smooth_l1'
+        if loc_loss not in LOC_LOSSES:
+            raise ValueError('loc_loss must be one of %s, got %r' % (', '.join(LOC_LOSSES), loc_loss))
+        self.loc_loss = loc_loss
+        self.loc_weight = float(loc_weight)   # multiplies loss_box_reg (published GIoU-style recipes use 2-5)
         self.sync_normalizer = False      # set True under multi-process data parallelism
 
     @torch.no_grad()
@@ -88,7 +166,7 @@ class MultiBoxLoss_combined(nn.Module):
         else:
             loc_t, conf_t, obj_t = self.match(priors, targets, dev)
         if self.fused:
-            return self._forward_fused(loc_data, conf_data, obj_data, loc_t, conf_t, obj_t)
+            return self._forward_fused(loc_data, conf_data, obj_data, loc_t, conf_t, obj_t, priors)
         labels, weights = conf_t[:, :, 0], conf_t[:, :, 1]
         pos = labels > 0
         num_pos = (weights * pos.float()).sum(1, keepdim=True).long()
@@ -98,8 +176,22 @@ class MultiBoxLoss_combined(nn.Module):
         # host keeps issuing the backward pass while the forward still runs (tools/train_bench.py at small batches).
 
         # localisation: smooth-L1 on positives, weighted by the mixup weight (:81-85)
-        l1 = F.smooth_l1_loss(loc_data, loc_t, reduction='none').sum(2)
-        loss_l = (l1 * (weights * pos.float())).sum()
+        if self.loc_weight != 1.0:
+            # loc_weight in the torch form: the value is multiplied once at the end (_ScaleValue) and the gradient once where
+            # it reaches loc_data, so both are the unweighted run's times loc_weight to one rounding, element for element
+            loc_data = _ScaleGrad.apply(loc_data, self.loc_weight)
+        if self.loc_loss == 'smooth_l1':
+            l1 = F.smooth_l1_loss(loc_data, loc_t, reduction='none').sum(2)
+            loss_l = (l1 * (weights * pos.float())).sum()
+        else:
+            # an IoU-family term between the decoded boxes.  A row that is not positive or carries weight 0 is evaluated
+            # on zero offsets (prediction = target = its prior: finite, L = 0) so that whatever it holds reaches neither
+            # the value nor the gradient
+            live = (pos & (weights != 0)).unsqueeze(2)
+            zero = torch.zeros((), dtype=loc_data.dtype, device=dev)
+            rows = iou_loss_rows(self.loc_loss, torch.where(live, loc_data, zero), torch.where(live, loc_t, zero),
+                                 priors.to(dev), self.variance)
+            loss_l = (rows * (weights * pos.float())).sum()
 
         # hard negatives ranked by objectness loss, 3:1 (:88-96)
         obj_flat = obj_data.reshape(-1, 2)
@@ -130,19 +222,27 @@ class MultiBoxLoss_combined(nn.Module):
         if self.sync_normalizer:          # data-parallel: N over the global batch (see ctdet.dist)
             from ctdet.dist import global_normalizer
             n = global_normalizer(n, dev)
-        return {'loss_box_reg': loss_l / n, 'loss_cls': loss_c / n, 'loss_obj': loss_obj / n}
+        loss_l = loss_l / n
+        if self.loc_weight != 1.0:
+            loss_l = _ScaleValue.apply(loss_l, self.loc_weight)
+        return {'loss_box_reg': loss_l, 'loss_cls': loss_c / n, 'loss_obj': loss_obj / n}
 
-    def _forward_fused(self, loc_data, conf_data, obj_data, loc_t, conf_t, obj_t):
+    def _forward_fused(self, loc_data, conf_data, obj_data, loc_t, conf_t, obj_t, priors):
         for t in (loc_data, conf_data, obj_data, loc_t, conf_t, obj_t):
             if not t.is_cuda:
                 raise _lib.CtdetError('MultiBoxLoss_combined(fused=True) needs tensors on the HIP device (got %s); '
                                       'there is no CPU form of the fused loss -- use fused=False' % t.device)
-        sums, n, _, _ = FusedMultiBoxLoss.apply(loc_data.contiguous(), conf_data.contiguous(), obj_data.contiguous(),
-                                                loc_t.contiguous(), conf_t.contiguous(), obj_t.contiguous(),
-                                                self.num_classes, int(self.negpos_ratio))
+        args = (loc_data.contiguous(), conf_data.contiguous(), obj_data.contiguous(), loc_t.contiguous(),
+                conf_t.contiguous(), obj_t.contiguous(), self.num_classes, int(self.negpos_ratio))
+        if self.loc_loss != 'smooth_l1':
+            args += (priors.to(loc_data.device, torch.float32).contiguous(), self.loc_loss, tuple(self.variance))
+        sums, n, _, _ = FusedMultiBoxLoss.apply(*args)
         n = n[0]
         if self.sync_normalizer:
             from ctdet.dist import global_normalizer
             n = global_normalizer(n, loc_data.device)
         losses = sums / n                 # the one torch op: autograd hands g / n to the backward kernel
-        return {'loss_box_reg': losses[0], 'loss_cls': losses[1], 'loss_obj': losses[2]}
+        loss_l = losses[0]
+        if self.loc_weight != 1.0:        # reaches the backward kernel through g[0]: no launch of its own in the backward
+            loss_l = loss_l * self.loc_weight
+        return {'loss_box_reg': loss_l, 'loss_cls': losses[1], 'loss_obj': losses[2]}

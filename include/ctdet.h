@@ -205,6 +205,44 @@ int ct_multibox_loss_bwd(const float* loc, const float* conf, const float* obj, 
                          int batch, int num_priors, int num_classes, float* dloc, float* dconf, float* dobj,
                          ct_stream_t stream);
 
+/* The same loss with a choice of localisation term (no counterpart in the reference, whose only term is smooth-L1):
+ * loc_loss = CT_LOC_SMOOTH_L1 is ct_multibox_loss_fwd / _bwd launch for launch and bit for bit (priors may be NULL);
+ * the IoU kinds replace the smooth-L1 term of every positive row (label > 0) by L below.  Selection, mining, w, num_pos,
+ * n, sums[1], sums[2], dconf and dobj do not depend on loc_loss.  Same workspace query, same launch counts.
+ *   priors dev [P,4] centre form (pcx, pcy, pw, ph), the priors the matcher encoded loc_t against; var0, var1 its variances.
+ * Definition.  D(l, p) is utils/box_utils.py:184 `decode`: cx = pcx + l0 var0 pw, cy = pcy + l1 var0 ph, w = pw exp(l2 var1),
+ * h = ph exp(l3 var1), box (cx - w/2, cy - h/2, cx + w/2, cy + h/2).  A = D(loc, p) is the prediction, T = D(loc_t, p) the
+ * matched box (it recovers the ground truth up to rounding, and it is the definition here: no new matcher output).
+ *   iw = max(0, min(A.x2, T.x2) - max(A.x1, T.x1)), ih likewise; inter = iw ih; union = A.w A.h + T.w T.h - inter;
+ *   IoU = inter / union; cw = max(A.x2, T.x2) - min(A.x1, T.x1), ch likewise;
+ *   CT_LOC_IOU:  L = 1 - IoU
+ *   CT_LOC_GIOU: L = 1 - IoU + (cw ch - union) / (cw ch)
+ *   CT_LOC_DIOU: L = 1 - IoU + rho2 / c2,  rho2 = squared distance of the two centres, c2 = cw^2 + ch^2
+ *   CT_LOC_CIOU: L = DIoU's + alpha v,  v = (4 / pi^2) (atan(T.w / T.h) - atan(A.w / A.h))^2, alpha = v / ((1 - IoU) + v),
+ *                alpha = 0 when v = 0; alpha is a CONSTANT in the backward pass (as in the published implementations).
+ * sums[0] = sum over positives of L * weight, in the fixed-order fp64 accumulation of the smooth-L1 term.
+ * A row that is not positive, or whose weight is 0, contributes 0 and gets dloc = 0 exactly: its loc, loc_t and prior are not
+ * read.  The exponent is not clamped: non-finite inputs on a positive row give non-finite outputs.  At a kink (two equal
+ * arguments of a min / max, iw or ih exactly 0) the gradient is one of the one-sided derivatives.
+ * CT_ERR_INVALID before any HIP call: an unknown loc_loss, NULL priors with an IoU kind, a variance that is not a
+ * positive finite number. */
+enum {
+    CT_LOC_SMOOTH_L1 = 0,
+    CT_LOC_IOU = 1,
+    CT_LOC_GIOU = 2,
+    CT_LOC_DIOU = 3,
+    CT_LOC_CIOU = 4
+};
+int ct_multibox_loss_fwd_loc(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                             const float* conf_t, const uint8_t* obj_t, int batch, int num_priors, int num_classes,
+                             int negpos_ratio, float* sums, long long* num_pos, long long* n, float* w,
+                             void* workspace, size_t workspace_bytes, ct_stream_t stream,
+                             const float* priors, int loc_loss, float var0, float var1);
+int ct_multibox_loss_bwd_loc(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                             const float* conf_t, const uint8_t* obj_t, const float* w, const float* g,
+                             int batch, int num_priors, int num_classes, float* dloc, float* dconf, float* dobj,
+                             ct_stream_t stream, const float* priors, int loc_loss, float var0, float var1);
+
 /* train.py `optimizer.step()` over the parameter groups of utils/solver.py:6-33 (torch.optim.SGD, one group per
  * tensor, maximize=False): weight decay, momentum, dampening, Nesterov and the update fused into one pass over
  * (param, grad, momentum_buf) for ALL tensors of a call (csrc/ct_optim.hip).  lr and weight_decay are per tensor (the

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """MultiBoxLoss forward + gradients w.r.t. the three predictions: the torch path against the fused HIP kernels.
 
-    python tools/loss_probe.py [--reps 30] [--warmup 5]
+    python tools/loss_probe.py [--reps 30] [--warmup 5] [--loc-loss NAME ...]
 
 Both forms run on the same prematched batch in the same process, alternating, with HIP events around
 loss forward + torch.autograd.grad; medians over --reps after --warmup, at (300^2, bs 32), (300^2, bs 4) and
-(512^2, bs 8, C = 61).  Prints one JSON line; `spread_us` is the inter-quartile range of each form's samples."""
+(512^2, bs 8, C = 61).  Prints one JSON line; `spread_us` is the inter-quartile range of each form's samples.
+--loc-loss: the IoU-family localisation terms to time next to the two smooth-L1 forms (default: all four); each adds a
+`loc` row per shape with the fused and the torch form's medians and spreads (`--loc-loss none`: the smooth-L1 rows alone)."""
 import argparse
 import json
 import os
@@ -24,9 +26,10 @@ from layers.modules.multibox_loss_combined import MultiBoxLoss_combined  # noqa:
 import data as cfgs  # noqa: E402
 
 SHAPES = (('rfb300_bs32', 300, 32, 21), ('rfb300_bs4', 300, 4, 21), ('rfb512_bs8_c61', 512, 8, 61))
+LOC_KINDS = ('iou', 'giou', 'diou', 'ciou')
 
 
-def probe(size, batch, ncls, reps, warmup):
+def probe(size, batch, ncls, reps, warmup, kinds=()):
     dev = 'cuda'
     priors = PriorBox(cfgs.VOC_300 if size == 300 else cfgs.VOC_512).forward().to(dev)
     P = priors.shape[0]
@@ -36,6 +39,10 @@ def probe(size, batch, ncls, reps, warmup):
                                                       torch.randn(batch, P, 2, generator=g))]
     crits = {name: MultiBoxLoss_combined(ncls, 0.5, True, 0, True, 3, 0.5, False, fused=f)
              for name, f in (('torch', False), ('fused', True))}
+    for kind in kinds:
+        for name, f in (('torch', False), ('fused', True)):
+            crits['%s_%s' % (name, kind)] = MultiBoxLoss_combined(ncls, 0.5, True, 0, True, 3, 0.5, False, fused=f,
+                                                                  loc_loss=kind)
     matched = crits['torch'].match(priors, [t.to(dev) for t in synth.targets(batch, ncls, 99)])
 
     def step(crit):
@@ -56,12 +63,21 @@ def probe(size, batch, ncls, reps, warmup):
             b.synchronize()
             if it >= warmup:
                 samples[name].append(a.elapsed_time(b) * 1e3)
-    res = {'num_priors': P, 'batch': batch, 'num_classes': ncls, 'loss': values}
+    res = {'num_priors': P, 'batch': batch, 'num_classes': ncls, 'positives': int((matched.conf_t[:, :, 0] > 0).sum()),
+           'loss': {k: values[k] for k in ('torch', 'fused')}}
+    stat = {}
     for name, s in samples.items():
         q = statistics.quantiles(s, n=4)
-        res[name + '_us'] = round(statistics.median(s), 1)
-        res[name + '_spread_us'] = round(q[2] - q[0], 1)
+        stat[name] = (round(statistics.median(s), 1), round(q[2] - q[0], 1))
+    for name in ('torch', 'fused'):
+        res[name + '_us'], res[name + '_spread_us'] = stat[name]
     res['speedup'] = round(res['torch_us'] / res['fused_us'], 2)
+    if kinds:       # one row per kind, next to the smooth-L1 figures above
+        res['loc'] = {kind: {'fused_us': stat['fused_' + kind][0], 'fused_spread_us': stat['fused_' + kind][1],
+                             'torch_us': stat['torch_' + kind][0], 'torch_spread_us': stat['torch_' + kind][1],
+                             'fused_minus_smooth_l1_us': round(stat['fused_' + kind][0] - stat['fused'][0], 1),
+                             'loss_box_reg': {f: values['%s_%s' % (f, kind)]['loss_box_reg'] for f in ('torch', 'fused')}}
+                      for kind in kinds}
     return res
 
 
@@ -69,11 +85,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--loc-loss', nargs='+', default=list(LOC_KINDS), choices=LOC_KINDS + ('none',))
     a = ap.parse_args()
+    kinds = tuple(k for k in LOC_KINDS if k in a.loc_loss)
     assert a.reps >= 20, 'medians of at least 20 samples'
     assert torch.cuda.is_available(), 'loss_probe needs a HIP device'
     out = {'probe': 'multibox_loss fwd + grad, HIP events, median us', 'device': torch.cuda.get_device_name(0),
-           'reps': a.reps, 'shapes': {name: probe(size, b, c, a.reps, a.warmup) for name, size, b, c in SHAPES}}
+           'reps': a.reps, 'loc_loss': list(kinds),
+           'shapes': {name: probe(size, b, c, a.reps, a.warmup, kinds) for name, size, b, c in SHAPES}}
     print(json.dumps(out))
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
    python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
-                               [--clip-norm X] [--ema DECAY] [--deterministic] [--json]
+                               [--clip-norm X] [--ema DECAY] [--deterministic] [--loc-loss NAME] [--loc-weight X] [--json]
    --classes: classes of the conf head; default 20, with --phase 2 the width of the Context-Transformer block (60 for 'transfer',
    15 for 'incre': the head feeds the block);
    --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
@@ -15,6 +15,8 @@
    after the timing line it prints `deterministic_repeat`: whether two runs of the same step from the same state gave the same
    gradient bits (every parameter of the network, at phase 2 the block's included), and with --fused-sgd under CTDET_LOSS_FUSED=1
    the same for the parameters after two steps (reported, not asserted);
+   --loc-loss NAME, --loc-weight X: the criterion's localisation term (smooth_l1, iou, giou, diou, ciou; default: what CTDET_LOC_LOSS
+   says, else smooth_l1) and the factor on loss_box_reg; both are reported on the JSON line, which is then always printed;
    --json: one more line, JSON, with the step time, the optimizer's device time and the training runtime's `policy` record
    (always with --clip-norm and --deterministic; with --clip-norm it
    also carries the last norm, coef and the number of skipped steps);
@@ -32,6 +34,7 @@ ap.add_argument('--fused-sgd', action='store_true'); ap.add_argument('--per-tens
 ap.add_argument('--wgrad-h2', action='store_true'); ap.add_argument('--deterministic', action='store_true')
 ap.add_argument('--clip-norm', type=float, default=None); ap.add_argument('--json', action='store_true')
 ap.add_argument('--ema', type=float, default=None)
+ap.add_argument('--loc-loss', default=None); ap.add_argument('--loc-weight', type=float, default=1.0)
 a = ap.parse_args()
 if a.clip_norm is not None or a.ema is not None:
     a.fused_sgd = True
@@ -55,7 +58,7 @@ net.load_state_dict(synth.fill_state_dict(net.state_dict()))
 net = net.cuda().train(); net.device = 'cuda'
 priors = PriorBox(getattr(cfgs, 'VOC_%d' % a.size)).forward().cuda()
 nout = a.classes if a.phase == 1 else net.OBJ_Target.weight.shape[0] + (a.classes if a.setting == 'incre' else 0)
-crit = MultiBoxLoss_combined(nout + 1, 0.5, True, 0, True, 3, 0.5, False)
+crit = MultiBoxLoss_combined(nout + 1, 0.5, True, 0, True, 3, 0.5, False, loc_loss=a.loc_loss, loc_weight=a.loc_weight)
 crit.sync_normalizer = world > 1
 def make_opt():
     if a.per_tensor_groups:
@@ -104,11 +107,12 @@ if rank == 0:
     print('RFBNet-%d phase %d bs=%d x %d GPU(s)%s: %.1f ms/step = %.1f img/s | fwd %.1f  loss %.1f  bwd %.1f ms | loss %.4f'
           % (a.size, a.phase, a.batch, world, ' [%s, %d groups]' % (type(opt).__name__, len(opt.param_groups))
              if a.fused_sgd or a.per_tensor_groups else '', dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
-    if a.json or a.clip_norm is not None or a.ema is not None or a.deterministic:
+    if a.json or a.clip_norm is not None or a.ema is not None or a.deterministic or a.loc_loss is not None or a.loc_weight != 1.0:
         row = {'train_bench': 'RFBNet-%d phase %d' % (a.size, a.phase), 'batch': a.batch, 'gpus': world, 'steps': n,
                'optimizer': type(opt).__name__, 'groups': len(opt.param_groups), 'ms_per_step': round(dt * 1e3, 3),
                'fwd_ms': round(tf / n, 3), 'loss_ms': round(tl / n, 3), 'bwd_ms': round(tb / n, 3), 'opt_ms': round(to / n, 3),
-               'clip_norm': a.clip_norm, 'loss': float(loss)}
+               'clip_norm': a.clip_norm, 'loss': float(loss), 'loc_loss': crit.loc_loss, 'loc_weight': crit.loc_weight,
+               'loss_fused': crit.fused}
         if a.clip_norm is not None:
             row.update(opt.clip_info())                 # norm, coef, finite, nonfinite of the last step
         if a.ema is not None:
