@@ -1,38 +1,35 @@
 // Fused multi-tensor SGD step (train.py's `optimizer.step()` over the groups of utils/solver.py:6-33): weight decay,
 // momentum, dampening, Nesterov and the parameter update of torch.optim.SGD in ONE pass over (param, grad, buf), for
-// any number of tensors per call.  The tensor table and the first workgroup of every tensor travel in the kernel
-// arguments (no device table, no staging copy, nothing read from the caller's array after the call returns), so a
-// call is ceil(non-empty tensors / TENSORS_PER_LAUNCH) launches whatever the tensor sizes; a workgroup finds its
-// tensor by a binary search over the prefix sums, which are scalar loads from the kernel-argument segment.
-//
-// Each workgroup owns one CHUNK of one tensor.  A tensor whose three pointers share their offset inside a 16-byte
-// line is walked in 16-byte groups counted from the line that holds element 0: every whole group is a dwordx4 load /
-// store, and only the first and the last group of the tensor can be partial (scalar, bounds-checked per element).
-// Tensors whose pointers disagree are walked one dword per lane, still coalesced.  No byte outside
-// [ptr, ptr + numel) is read or written; plain stores only.
+// any number of tensors per call -- ct_sgd_step, ct_sgd_step_clipped -- and, with one more array, the weight average
+// updated from the new parameter value while it is still in a register (ct_sgd_step_ema: 7 array passes instead of
+// 5 + 3).  A call is ceil(non-empty tensors / tensors per launch) launches whatever the tensor sizes.  The walk over a
+// tensor, the launch-record packing and the argument checks are those of ct_multi_tensor.h; this file holds the two
+// launch records, the one kernel both are walked by, and the gradient norm.
 //
 // Every operation is rounded separately to fp32 (__fmul_rn / __fadd_rn / __fsub_rn, and -ffp-contract=off for the
 // file), in the order include/ctdet.h states, so a NumPy float32 restatement reproduces the result bit for bit.
 //
-// Gradient-norm clipping and the non-finite guard (ct_grad_norm_clip, ct_sgd_step_clipped) sit in front of the same
-// update.  grad_norm_kernel walks the gradients in the same chunks, found by the same prefix-sum search: every
-// workgroup squares and sums its chunk in binary64 (each product of two fp32 values is exact there), reduces across
-// lanes and waves in a fixed order and stores ONE double to its own workspace slot; grad_norm_finish_kernel (one
-// workgroup) sums the slots in a fixed order and writes {norm, coef, finite, nonfinite} to a 16-byte device state.
-// No atomics, no "last workgroup finishes": the same table gives the same bits.  sgd_multi_kernel<true> reads that
-// state (two scalar loads), multiplies coef into grad_scale once, or -- when the norm was not finite -- leaves
-// everything alone except the momentum buffers of first-step tensors, which it sets to +0.
+// Gradient-norm clipping and the non-finite guard (ct_grad_norm_clip) sit in front of the same update.
+// grad_norm_kernel is a reduction, not a map, so it keeps a read-only walk of its own over the same chunks, found by the
+// same prefix-sum search: every workgroup squares and sums its chunk in binary64 (each product of two fp32 values is
+// exact there), reduces across lanes and waves in a fixed order and stores ONE double to its own workspace slot;
+// grad_norm_finish_kernel (one workgroup) sums the slots in a fixed order and writes {norm, coef, finite, nonfinite}
+// to a 16-byte device state.  No atomics, no "last workgroup finishes": the same table gives the same bits.
+// sgd_multi_kernel<., true> reads that state (two scalar loads), multiplies coef into grad_scale once, or -- when the
+// norm was not finite -- leaves everything alone except the momentum buffers of first-step tensors, which it sets to +0.
 #include "ct_common.h"
 #include "ct_multi_tensor.h"
 
-#include <climits>
 #include <cstdint>
+#include <cstdio>
+#include <type_traits>
 
 namespace {
 
-using namespace ctdet::mt;                  // chunk geometry, update(), owner_of(), line_offset(): shared with ct_ema.hip
+using namespace ctdet::mt;
 
 constexpr int TENSORS_PER_LAUNCH = 80;      // 80 * 40 B + 81 * 4 B + scalars = 3548 B of the 4096 B a launch may carry
+constexpr int SGD_EMA_PER_LAUNCH = 77;      // 77 * 48 B + 78 * 4 B + scalars = 4048 B
 
 struct Tensor {
     float* p;
@@ -49,125 +46,112 @@ struct Launch {
     int n;
     float momentum, one_minus_damp, grad_scale;
     int nesterov;
-    const ct_clip_state* clip;              // sgd_multi_kernel<true> only; appended, so the other offsets stay
+    const ct_clip_state* clip;              // CLIP only; appended, so the other offsets stay
 };
 static_assert(sizeof(Tensor) == 40, "kernel-argument budget");
 static_assert(sizeof(Launch) <= 4096, "kernel arguments are limited to 4 KiB");
 
-// CLIP = false is ct_sgd_step.  CLIP = true (ct_sgd_step_clipped) reads the state ct_grad_norm_clip left on the
-// device: coef goes into grad_scale once, and a non-finite norm skips the update.
-template <bool CLIP>
-__global__ __launch_bounds__(THREADS) void sgd_multi_kernel(const Launch L)
+struct SgdEmaTensor {
+    float* p;
+    const float* g;
+    float* b;
+    float* e;
+    int numel;
+    float lr, wd;
+    int flags;
+};
+
+struct SgdEmaLaunch {
+    SgdEmaTensor t[SGD_EMA_PER_LAUNCH];
+    int first_block[SGD_EMA_PER_LAUNCH + 1];
+    int n;
+    float momentum, one_minus_damp, grad_scale;
+    int nesterov;
+    const ct_clip_state* clip;              // CLIP only
+    const ct_ema_state* ema;
+};
+static_assert(sizeof(SgdEmaTensor) == 48, "kernel-argument budget");
+static_assert(sizeof(SgdEmaLaunch) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// The update of one element or one 16-byte group for walk().  EMA = false never touches E, averaged, d or om.
+template <bool EMA>
+struct SgdOp {
+    float* __restrict__ P;
+    const float* __restrict__ G;
+    float* __restrict__ B;
+    float* __restrict__ E;
+    Hyper h;
+    bool has_buf, averaged;
+    float d, om;
+    template <class V> struct Regs { V p, g, b, e; };
+
+    template <class V> __device__ Regs<V> load(int64_t j) const
+    {
+        Regs<V> r;
+        r.p = ld<V>(P + j);
+        r.g = ld<V>(G + j);
+        r.b = has_buf ? ld<V>(B + j) : zero<V>();
+        if constexpr (EMA) r.e = averaged ? ld<V>(E + j) : zero<V>();
+        else r.e = zero<V>();
+        return r;
+    }
+    template <class V> __device__ void apply(Regs<V>& r) const
+    {
+        update(r.p, r.g, r.b, h);
+        if constexpr (EMA) r.e = ema_of(r.e, r.p, d, om);
+    }
+    template <class V> __device__ void store(int64_t j, const Regs<V>& r) const
+    {
+        st(P + j, r.p);
+        if (has_buf) st(B + j, r.b);
+        if constexpr (EMA) {
+            if (averaged) st(E + j, r.e);
+        }
+    }
+};
+
+// LaunchT = Launch is ct_sgd_step; SgdEmaLaunch is ct_sgd_step_ema, where the average moves iff the step ran and
+// ct_ema_begin opened an update.  CLIP reads the state ct_grad_norm_clip left on the device: coef goes into grad_scale
+// once, and a non-finite norm skips the update.
+template <class LaunchT, bool CLIP>
+__global__ __launch_bounds__(THREADS) void sgd_multi_kernel(const LaunchT L)
 {
+    constexpr bool EMA = std::is_same<LaunchT, SgdEmaLaunch>::value;
     const int blk = blockIdx.x;
     const int lo = owner_of(L.first_block, L.n, blk);
-    const Tensor& T = L.t[lo];
+    const auto& T = L.t[lo];
     const int chunk = blk - L.first_block[lo];
     const int flags = T.flags;
     const int numel = T.numel;
-    float* __restrict__ P = T.p;
-    const float* __restrict__ G = T.g;
-    float* __restrict__ B = T.b;
-    Hyper h;
-    h.lr = T.lr; h.wd = T.wd; h.momentum = L.momentum; h.omd = L.one_minus_damp; h.gs = L.grad_scale;
-    h.first = flags & F_FIRST; h.nesterov = L.nesterov != 0;
-    const bool has_buf = L.momentum != 0.f;
     const int tid = threadIdx.x;
+    SgdOp<EMA> op;
+    op.P = T.p; op.G = T.g; op.B = T.b;
+    op.h.lr = T.lr; op.h.wd = T.wd; op.h.momentum = L.momentum; op.h.omd = L.one_minus_damp; op.h.gs = L.grad_scale;
+    op.h.first = flags & F_FIRST; op.h.nesterov = L.nesterov != 0;
+    op.has_buf = L.momentum != 0.f;
 
     if (CLIP) {
         if (L.clip->finite == 0) {
             // Skipped step.  A first-step buffer is uninitialised memory the host is about to adopt as state: +0 to
             // the elements of this chunk (dword stores: the path is rare), nothing else is written.
-            if (has_buf && h.first) {
+            if (op.has_buf && op.h.first) {
                 const int shift = (flags & F_VEC) ? (flags >> 2) & 3 : 0;
-                const int64_t s0 = (int64_t)chunk * CHUNK;              // shifted coordinates, as below
+                const int64_t s0 = (int64_t)chunk * CHUNK;              // shifted coordinates, as in walk()
                 const int64_t j0 = s0 > shift ? s0 - shift : 0;
                 const int64_t j1 = s0 + CHUNK - shift < numel ? s0 + CHUNK - shift : numel;
-                for (int64_t j = j0 + tid; j < j1; j += THREADS) B[j] = 0.f;
+                for (int64_t j = j0 + tid; j < j1; j += THREADS) op.B[j] = 0.f;
             }
             return;
         }
-        h.gs = __fmul_rn(L.grad_scale, L.clip->coef);
+        op.h.gs = __fmul_rn(L.grad_scale, L.clip->coef);
     }
-
-    if (!(flags & F_VEC)) {
-        // pointers disagree inside the 16-byte line: one dword per lane
-        const int64_t base = (int64_t)chunk * CHUNK;
-        for (int k = 0; k < CHUNK / THREADS; k += UNROLL) {
-            float p[UNROLL], g[UNROLL], b[UNROLL];
-            int64_t j[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                j[u] = base + (int64_t)(k + u) * THREADS + tid;
-                if (j[u] < numel) {
-                    p[u] = P[j[u]];
-                    g[u] = G[j[u]];
-                    b[u] = has_buf ? B[j[u]] : 0.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                if (j[u] < numel) {
-                    update(p[u], g[u], b[u], h);
-                    P[j[u]] = p[u];
-                    if (has_buf) B[j[u]] = b[u];
-                }
-            }
-        }
-        return;
+    if constexpr (EMA) {
+        op.E = T.e;
+        op.averaged = L.ema->applied != 0;
+        op.d = L.ema->decay;
+        op.om = L.ema->one_minus;
     }
-
-    // Shifted coordinates: s = element index + shift, so s % 4 == 0 sits on a 16-byte line of all three arrays.
-    // The tensor occupies s in [shift, end); group q covers s in [4q, 4q + 4).
-    const int shift = (flags >> 2) & 3;
-    const int64_t end = (int64_t)numel + shift;
-    const int64_t q0 = (int64_t)chunk * GROUPS;
-    const bool whole = (q0 * 4 >= shift) && ((q0 + GROUPS) * 4 <= end);
-    if (whole) {
-        for (int k = 0; k < GROUPS / THREADS; k += UNROLL) {
-            float4 p[UNROLL], g[UNROLL], b[UNROLL];
-            int64_t j[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                j[u] = (q0 + (int64_t)(k + u) * THREADS + tid) * 4 - shift;
-                p[u] = *reinterpret_cast<const float4*>(P + j[u]);
-                g[u] = *reinterpret_cast<const float4*>(G + j[u]);
-                b[u] = has_buf ? *reinterpret_cast<const float4*>(B + j[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                update4(p[u], g[u], b[u], h);
-                *reinterpret_cast<float4*>(P + j[u]) = p[u];
-                if (has_buf) *reinterpret_cast<float4*>(B + j[u]) = b[u];
-            }
-        }
-        return;
-    }
-    // first / last chunk of the tensor: whole groups stay 16-byte wide, a partial group goes element by element
-    for (int k = 0; k < GROUPS / THREADS; ++k) {
-        const int64_t s = (q0 + (int64_t)k * THREADS + tid) * 4;
-        if (s >= end) break;
-        if (s >= shift && s + 4 <= end) {
-            const int64_t j = s - shift;
-            float4 p = *reinterpret_cast<const float4*>(P + j);
-            const float4 g = *reinterpret_cast<const float4*>(G + j);
-            float4 b = has_buf ? *reinterpret_cast<const float4*>(B + j) : make_float4(0.f, 0.f, 0.f, 0.f);
-            update4(p, g, b, h);
-            *reinterpret_cast<float4*>(P + j) = p;
-            if (has_buf) *reinterpret_cast<float4*>(B + j) = b;
-        } else {
-            for (int e = 0; e < 4; ++e) {
-                const int64_t se = s + e;
-                if (se < shift || se >= end) continue;
-                const int64_t j = se - shift;
-                float p = P[j];
-                float b = has_buf ? B[j] : 0.f;
-                update(p, G[j], b, h);
-                P[j] = p;
-                if (has_buf) B[j] = b;
-            }
-        }
-    }
+    walk(op, chunk, numel, flags, tid);
 }
 
 // ------------------------------------------------------------------------------------------------ gradient norm
@@ -216,8 +200,8 @@ __global__ __launch_bounds__(THREADS) void grad_norm_kernel(const NormLaunch L)
     const int numel = L.numel[lo];
     const float* __restrict__ G = L.g[lo];
     const int tid = threadIdx.x;
-    // Shifted coordinates as in sgd_multi_kernel: s = element index + shift, s % 4 == 0 on a 16-byte line.  With one
-    // array there is always such a shift.
+    // Shifted coordinates as in walk(): s = element index + shift, s % 4 == 0 on a 16-byte line.  With one array there
+    // is always such a shift.
     const int shift = (int)((reinterpret_cast<uintptr_t>(G) >> 2) & 3);
     const int64_t end = (int64_t)numel + shift;
     const int64_t q0 = (int64_t)chunk * GROUPS;
@@ -271,97 +255,89 @@ __global__ __launch_bounds__(FINISH_THREADS) void grad_norm_finish_kernel(const 
     }
 }
 
+// one array: it is always walked in 16-byte groups
 inline int64_t grad_chunks(const ct_grad_tensor& it)
 {
-    return ctdet::ceil_div<int64_t>(it.numel + line_offset(it.grad), CHUNK);
+    const void* const ptrs[1] = {it.grad};
+    return it.numel ? chunks_of(it.numel, vec_flags(ptrs)) : 0;
 }
 
-// The argument checks both norm entry points share; -> CT_OK or the recorded failure
+// The argument checks both norm entry points share; *slots = the workgroups, and workspace slots, of the call
 int check_grads(const char* who, const ct_grad_tensor* items, int n, int64_t* slots)
 {
-    CT_REQUIRE(n >= 0, "%s: n = %d is negative", who, n);
-    CT_REQUIRE(n == 0 || items != nullptr, "%s: items is NULL with n = %d", who, n);
+    if (const int rc = check_table(who, items, n)) return rc;
     int64_t total = 0;
     for (int i = 0; i < n; ++i) {
-        const ct_grad_tensor& it = items[i];
-        CT_REQUIRE(it.numel >= 0 && it.numel <= MAX_NUMEL, "%s: tensor %d has numel %lld (0 .. 2^31-1)", who, i,
-                   (long long)it.numel);
-        if (it.numel == 0) continue;        // an empty tensor may have no pointer
-        CT_REQUIRE(it.grad, "%s: tensor %d has a NULL grad", who, i);
-        CT_REQUIRE((reinterpret_cast<uintptr_t>(it.grad) & 3) == 0, "%s: tensor %d has a grad that is not 4-byte aligned",
-                   who, i);
-        total += grad_chunks(it);
+        const Ptr ptrs[] = {{items[i].grad, "grad", false}};
+        if (const int rc = check_tensor(who, i, items[i].numel, ptrs)) return rc;
+        total += grad_chunks(items[i]);
     }
-    CT_REQUIRE(total <= INT_MAX, "%s: %lld chunks of %d elements are more than a call takes", who, (long long)total, CHUNK);
     *slots = total;
-    return CT_OK;
+    return check_chunks(who, total);
 }
 
-// ct_sgd_step (clip == nullptr) and ct_sgd_step_clipped; `who` names the entry point in the messages
-int sgd_step(const char* who, const ct_sgd_tensor* items, int n, float momentum, float dampening, int nesterov,
-             float grad_scale, const ct_clip_state* clip, ct_stream_t stream)
+// The three step entry points: Launch / ct_sgd_tensor (ema == nullptr) and SgdEmaLaunch / ct_sgd_ema_tensor; `who`
+// names the entry point in the messages, clip != nullptr takes the CLIP kernel
+template <class LaunchT, class Item>
+int sgd_step(const char* who, const Item* items, int n, float momentum, float dampening, int nesterov, float grad_scale,
+             const ct_clip_state* clip, const ct_ema_state* ema, ct_stream_t stream)
 {
-    using namespace ctdet;
-    CT_REQUIRE(n >= 0, "%s: n = %d is negative", who, n);
-    CT_REQUIRE(n == 0 || items != nullptr, "%s: items is NULL with n = %d", who, n);
+    constexpr bool EMA = std::is_same<LaunchT, SgdEmaLaunch>::value;
+    if (const int rc = check_table(who, items, n)) return rc;
     CT_REQUIRE(!nesterov || (momentum != 0.f && dampening == 0.f),
                "%s: nesterov needs a momentum and zero dampening (momentum %g, dampening %g)", who, (double)momentum,
                (double)dampening);
-    for (int i = 0; i < n; ++i) {
-        const ct_sgd_tensor& it = items[i];
-        CT_REQUIRE(it.numel >= 0 && it.numel <= MAX_NUMEL, "%s: tensor %d has numel %lld (0 .. 2^31-1)", who, i,
-                   (long long)it.numel);
-        if (it.numel == 0) continue;        // a no-op whatever its pointers are (an empty tensor may have none)
-        CT_REQUIRE(it.param && it.grad, "%s: tensor %d has a NULL %s", who, i, it.param ? "grad" : "param");
-        CT_REQUIRE(momentum == 0.f || it.momentum_buf, "%s: tensor %d has no momentum_buf but momentum = %g", who, i,
-                   (double)momentum);
-        CT_REQUIRE(((reinterpret_cast<uintptr_t>(it.param) | reinterpret_cast<uintptr_t>(it.grad) |
-                     reinterpret_cast<uintptr_t>(it.momentum_buf)) & 3) == 0,
-                   "%s: tensor %d has a pointer that is not 4-byte aligned", who, i);
+    LaunchT L = {};
+    if constexpr (EMA) {
+        if (const int rc = check_state(who, ema, "the ema state")) return rc;
+        if (const int rc = check_state(who, clip, "the clip state", true)) return rc;
+        L.ema = ema;
     }
-    hipStream_t st = as_stream(stream);
-    Launch L = {};
+    char no_buf[64];
+    snprintf(no_buf, sizeof(no_buf), "no momentum_buf but momentum = %g", (double)momentum);
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        const Item& it = items[i];
+        const float* e = nullptr;
+        if constexpr (EMA) e = it.ema;
+        const Ptr ptrs[] = {{it.param, "param", false},
+                            {it.grad, "grad", false},
+                            {it.momentum_buf, "momentum_buf", momentum == 0.f, no_buf},
+                            {e, "ema", !EMA}};
+        if (const int rc = check_tensor(who, i, it.numel, ptrs)) return rc;
+        if constexpr (EMA) total += max_chunks(it.numel);
+    }
+    // ct_sgd_step has never limited the chunks of a call (a launch holds 80 * 2^18 at most), and still does not
+    if constexpr (EMA) {
+        if (const int rc = check_chunks(who, total)) return rc;
+    }
     L.momentum = momentum;
     L.one_minus_damp = 1.0f - dampening;
     L.grad_scale = grad_scale;
     L.nesterov = nesterov ? 1 : 0;
     L.clip = clip;
     const bool has_buf = momentum != 0.f;
-    int i = 0;
-    while (i < n) {
-        int k = 0;
-        int64_t blocks = 0;
-        for (; i < n && k < TENSORS_PER_LAUNCH; ++i) {
-            const ct_sgd_tensor& it = items[i];
-            if (it.numel == 0) continue;
-            const int off = line_offset(it.param);
-            const bool vec = off == line_offset(it.grad) && (!has_buf || off == line_offset(it.momentum_buf));
-            Tensor& t = L.t[k];
-            t.p = it.param;
-            t.g = it.grad;
-            t.b = has_buf ? it.momentum_buf : nullptr;
-            t.numel = (int)it.numel;
-            t.lr = it.lr;
-            t.wd = it.weight_decay;
-            t.flags = (it.first_step ? F_FIRST : 0) | (vec ? F_VEC | off * F_SHIFT : 0);
-            L.first_block[k] = (int)blocks;
-            blocks += ceil_div<int64_t>(it.numel + (vec ? off : 0), CHUNK);
-            ++k;
-        }
-        if (k == 0) break;
-        for (int q = k; q <= TENSORS_PER_LAUNCH; ++q) L.first_block[q] = (int)blocks;
-        L.n = k;
-        if (clip) {
-            CT_PROF("sgd_multi_kernel_clipped", st);
-            hipLaunchKernelGGL(sgd_multi_kernel<true>, dim3((unsigned)blocks), dim3(THREADS), 0, st, L);
-            CT_LAUNCH_CHECK("sgd_multi_kernel_clipped");
-        } else {
-            CT_PROF("sgd_multi_kernel", st);
-            hipLaunchKernelGGL(sgd_multi_kernel<false>, dim3((unsigned)blocks), dim3(THREADS), 0, st, L);
-            CT_LAUNCH_CHECK("sgd_multi_kernel");
-        }
-    }
-    return CT_OK;
+    const auto fill = [&](LaunchT& rec, int k, int i) -> int64_t {
+        const Item& it = items[i];
+        if (it.numel == 0) return 0;
+        auto& t = rec.t[k];
+        t.p = it.param;
+        t.g = it.grad;
+        t.b = has_buf ? it.momentum_buf : nullptr;
+        const float* e = nullptr;
+        if constexpr (EMA) e = t.e = it.ema;
+        t.numel = (int)it.numel;
+        t.lr = it.lr;
+        t.wd = it.weight_decay;
+        const void* const ptrs[4] = {t.p, t.g, t.b, e};
+        t.flags = (it.first_step ? F_FIRST : 0) | vec_flags(ptrs);
+        return chunks_of(t.numel, t.flags);
+    };
+    const char* name = EMA ? (clip ? "sgd_multi_kernel_ema_clipped" : "sgd_multi_kernel_ema")
+                           : (clip ? "sgd_multi_kernel_clipped" : "sgd_multi_kernel");
+    const auto kernel = clip ? sgd_multi_kernel<LaunchT, true> : sgd_multi_kernel<LaunchT, false>;
+    hipStream_t st = ctdet::as_stream(stream);
+    return pack(L, n, fill, [&](const LaunchT& rec, unsigned blocks) { return launch(name, kernel, rec, blocks, st); });
 }
 
 }  // namespace
@@ -378,43 +354,30 @@ extern "C" size_t ct_grad_norm_workspace_bytes(const ct_grad_tensor* items, int 
 extern "C" int ct_grad_norm_clip(const ct_grad_tensor* items, int n, float grad_scale, float max_norm, void* workspace,
                                  size_t workspace_bytes, ct_clip_state* state_dev, ct_stream_t stream)
 {
-    using namespace ctdet;
+    const char* who = "ct_grad_norm_clip";
     int64_t slots = 0;
-    const int rc = check_grads("ct_grad_norm_clip", items, n, &slots);
-    if (rc != CT_OK) return rc;
-    CT_REQUIRE(max_norm > 0.f, "ct_grad_norm_clip: max_norm = %g must be positive (+inf: guard only)", (double)max_norm);
-    CT_REQUIRE(state_dev != nullptr, "ct_grad_norm_clip: state_dev is NULL");
-    CT_REQUIRE((reinterpret_cast<uintptr_t>(state_dev) & 3) == 0, "ct_grad_norm_clip: state_dev is not 4-byte aligned");
+    if (const int rc = check_grads(who, items, n, &slots)) return rc;
+    CT_REQUIRE(max_norm > 0.f, "%s: max_norm = %g must be positive (+inf: guard only)", who, (double)max_norm);
+    if (const int rc = check_state(who, state_dev, "state_dev")) return rc;
     const size_t need = sizeof(double) * (size_t)(slots > 0 ? slots : 1);
     CT_REQUIRE(workspace != nullptr && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
-               "ct_grad_norm_clip: workspace is NULL or not 8-byte aligned");
-    CT_REQUIRE(workspace_bytes >= need, "ct_grad_norm_clip: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    hipStream_t st = as_stream(stream);
+               "%s: workspace is NULL or not 8-byte aligned", who);
+    CT_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    hipStream_t st = ctdet::as_stream(stream);
     NormLaunch L = {};
     L.slots = static_cast<double*>(workspace);
     int64_t slot0 = 0;
-    int i = 0;
-    while (i < n) {
-        int k = 0;
-        int64_t blocks = 0;
-        for (; i < n && k < GRADS_PER_LAUNCH; ++i) {
-            const ct_grad_tensor& it = items[i];
-            if (it.numel == 0) continue;
-            L.g[k] = it.grad;
-            L.numel[k] = (int)it.numel;
-            L.first_block[k] = (int)blocks;
-            blocks += grad_chunks(it);
-            ++k;
-        }
-        if (k == 0) break;
-        for (int q = k; q <= GRADS_PER_LAUNCH; ++q) L.first_block[q] = (int)blocks;
-        L.n = k;
-        L.slot0 = (int)slot0;
-        CT_PROF("grad_norm_kernel", st);
-        hipLaunchKernelGGL(grad_norm_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, L);
-        CT_LAUNCH_CHECK("grad_norm_kernel");
+    const auto fill = [&](NormLaunch& rec, int k, int i) {
+        rec.g[k] = items[i].grad;
+        rec.numel[k] = (int)items[i].numel;
+        return grad_chunks(items[i]);
+    };
+    const int rc = pack(L, n, fill, [&](NormLaunch& rec, unsigned blocks) {
+        rec.slot0 = (int)slot0;
         slot0 += blocks;
-    }
+        return launch("grad_norm_kernel", grad_norm_kernel, rec, blocks, st);
+    });
+    if (rc != CT_OK) return rc;
     // slot0 == slots: every slot the finish reads was written by the launches above
     CT_PROF("grad_norm_finish_kernel", st);
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(FINISH_THREADS), 0, st, L.slots, (int)slot0, grad_scale,
@@ -426,15 +389,25 @@ extern "C" int ct_grad_norm_clip(const ct_grad_tensor* items, int n, float grad_
 extern "C" int ct_sgd_step(const ct_sgd_tensor* items, int n, float momentum, float dampening, int nesterov,
                            float grad_scale, ct_stream_t stream)
 {
-    return sgd_step("ct_sgd_step", items, n, momentum, dampening, nesterov, grad_scale, nullptr, stream);
+    return sgd_step<Launch>("ct_sgd_step", items, n, momentum, dampening, nesterov, grad_scale, nullptr, nullptr, stream);
 }
 
 extern "C" int ct_sgd_step_clipped(const ct_sgd_tensor* items, int n, float momentum, float dampening, int nesterov,
                                    float grad_scale, const ct_clip_state* state_dev, ct_stream_t stream)
 {
-    CT_REQUIRE(state_dev != nullptr, "ct_sgd_step_clipped: state_dev is NULL");
-    CT_REQUIRE((reinterpret_cast<uintptr_t>(state_dev) & 3) == 0, "ct_sgd_step_clipped: state_dev is not 4-byte aligned");
-    return sgd_step("ct_sgd_step_clipped", items, n, momentum, dampening, nesterov, grad_scale, state_dev, stream);
+    const char* who = "ct_sgd_step_clipped";
+    if (const int rc = check_state(who, state_dev, "state_dev")) return rc;
+    return sgd_step<Launch>(who, items, n, momentum, dampening, nesterov, grad_scale, state_dev, nullptr, stream);
+}
+
+extern "C" int ct_sgd_step_ema(const ct_sgd_ema_tensor* items, int n, float momentum, float dampening, int nesterov,
+                               float grad_scale, const ct_clip_state* clip, const ct_ema_state* ema_dev,
+                               ct_stream_t stream)
+{
+    return sgd_step<SgdEmaLaunch>("ct_sgd_step_ema", items, n, momentum, dampening, nesterov, grad_scale, clip, ema_dev,
+                                  stream);
 }
 
 extern "C" int ct_sgd_tensors_per_launch(void) { return TENSORS_PER_LAUNCH; }
+
+extern "C" int ct_sgd_ema_tensors_per_launch(void) { return SGD_EMA_PER_LAUNCH; }

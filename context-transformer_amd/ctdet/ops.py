@@ -214,17 +214,20 @@ def multibox_loss_backward(loc, conf, obj, loc_t, conf_t, obj_t, w, g, num_class
 
 
 # ------------------------------------------------------------------ optimizer
-def sgd_table(items):
-    """ctypes table of ct_sgd_tensor for `items` = [(param, grad, momentum_buf or None, lr, weight_decay, first_step)];
-    every tensor contiguous fp32 on the HIP device (views at any element offset are fine)."""
-    table = (_lib.SgdTensor * max(len(items), 1))()
-    for i, (p, g, buf, lr, wd, first) in enumerate(items):
+def sgd_table(items, ema=False):
+    """ctypes table of ct_sgd_tensor for `items` = [(param, grad, momentum_buf or None, lr, weight_decay, first_step)],
+    or of ct_sgd_ema_tensor when `ema`: the same with the tensor's average as a seventh column.  Every tensor
+    contiguous fp32 on the HIP device (views at any element offset are fine)."""
+    struct, who = (_lib.SgdEmaTensor, 'sgd_step_ema') if ema else (_lib.SgdTensor, 'sgd_step')
+    table = (struct * max(len(items), 1))()
+    for i, (p, g, buf, lr, wd, first, *avg) in enumerate(items):
         n = p.numel()
-        if g.numel() != n or (buf is not None and buf.numel() != n):
-            raise _lib.CtdetError('sgd_step: tensor %d has %d elements, its grad %d, its momentum buffer %s'
-                                  % (i, n, g.numel(), None if buf is None else buf.numel()))
-        table[i] = _lib.SgdTensor(_dev(p, 'param').value, _dev(g, 'grad').value, _opt(buf, 'momentum_buf').value, n,
-                                  lr, wd, int(bool(first)))
+        if g.numel() != n or (buf is not None and buf.numel() != n) or any(e.numel() != n for e in avg):
+            raise _lib.CtdetError('%s: tensor %d has %d elements, its grad %d, its momentum buffer %s%s'
+                                  % (who, i, n, g.numel(), None if buf is None else buf.numel(),
+                                     ''.join(', its average %d' % e.numel() for e in avg)))
+        table[i] = struct(_dev(p, 'param').value, _dev(g, 'grad').value, _opt(buf, 'momentum_buf').value, n, lr, wd,
+                          int(bool(first)), *[_dev(e, 'ema').value for e in avg])
     return table
 
 
@@ -312,27 +315,13 @@ def ema_begin(state, decay, warmup=0.0, clip_state=None):
     return state
 
 
-def sgd_ema_table(items):
-    """ctypes table of ct_sgd_ema_tensor for `items` = [(param, grad, momentum_buf or None, lr, weight_decay,
-    first_step, ema)], as sgd_table."""
-    table = (_lib.SgdEmaTensor * max(len(items), 1))()
-    for i, (p, g, buf, lr, wd, first, ema) in enumerate(items):
-        n = p.numel()
-        if g.numel() != n or (buf is not None and buf.numel() != n) or ema.numel() != n:
-            raise _lib.CtdetError('sgd_step_ema: tensor %d has %d elements, its grad %d, its momentum buffer %s, its '
-                                  'average %d' % (i, n, g.numel(), None if buf is None else buf.numel(), ema.numel()))
-        table[i] = _lib.SgdEmaTensor(_dev(p, 'param').value, _dev(g, 'grad').value, _opt(buf, 'momentum_buf').value, n,
-                                     lr, wd, int(bool(first)), _dev(ema, 'ema').value)
-    return table
-
-
 def sgd_step_ema(items, momentum, dampening, nesterov, grad_scale, ema_state, clip_state=None):
-    """sgd_step over `items` (see sgd_ema_table) that also moves each tensor's average towards the new parameter value
+    """sgd_step over `items` (see sgd_table, with the average as the seventh column) that also moves each tensor's average towards the new parameter value
     in the same pass (ct_sgd_step_ema), with the decay ema_begin left in `ema_state`.  A step `clip_state` skips, or
     one ema_begin did not open, leaves the averages alone."""
     if not items:
         return
-    check(lib().ct_sgd_step_ema(sgd_ema_table(items), len(items), float(momentum), float(dampening),
+    check(lib().ct_sgd_step_ema(sgd_table(items, ema=True), len(items), float(momentum), float(dampening),
                                 int(bool(nesterov)), float(grad_scale),
                                 None if clip_state is None else _clip_state(clip_state), _ema_state(ema_state),
                                 _stream()), 'ct_sgd_step_ema')

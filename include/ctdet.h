@@ -329,9 +329,10 @@ int ct_grad_norm_clip(const ct_grad_tensor* items_host, int n, float grad_scale,
 int ct_sgd_step_clipped(const ct_sgd_tensor* items_host, int n, float momentum, float dampening, int nesterov,
                         float grad_scale, const ct_clip_state* state_dev, ct_stream_t stream);
 
-/* Exponential moving average of the weights ("model averaging") riding on the fused step (csrc/ct_ema.hip).  Off unless
- * called.  The update count, the decay of the step and the decision whether the step is averaged at all live in a
- * 16-byte ct_ema_state on the device, next to ct_clip_state: nothing is synchronised to the host.
+/* Exponential moving average of the weights ("model averaging") riding on the fused step (csrc/ct_optim.hip: the
+ * step; csrc/ct_ema.hip: the rest).  Off unless called.  The update count, the decay of the step and the decision
+ * whether the step is averaged at all live in a 16-byte ct_ema_state on the device, next to ct_clip_state: nothing is
+ * synchronised to the host.
  * ct_ema_begin opens one update; one launch of one thread, plain loads and stores of the 16 bytes, no atomics:
  *     n       = state->updates
  *     applied = clip ? clip->finite : 1

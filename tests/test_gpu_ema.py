@@ -603,3 +603,80 @@ def test_pipeline_runs_on_the_averaged_weights_inside_swapped():
     # the test cannot pass on a swap that does nothing
     assert not (torch.equal(got_avg[0], got_live[0]) and torch.equal(got_avg[1], got_live[1]))
     assert not (torch.equal(got_live[0], first[0][0]) and torch.equal(got_live[1], first[0][1]))
+
+
+# 9 -----------------------------------------------------------------------------------------------------------------
+# Around the chunk of 8192 elements a workgroup owns, where "whole chunk" flips to "first / last chunk": with the line
+# offsets 0..3 these give a one-chunk tensor (8188 and 8189 at any offset, 8191 at 0 and 1, 8192 at 0: the chunk is
+# whole), a tensor its shift pushes into a second chunk (8191 at 2 and 3, 8192 at 1..3), a whole middle chunk (16384 at
+# 1..3, 16387: at 3 it is 8189 + 8192 + 6 elements), a whole last chunk (16381 at 3) and a last chunk of one element
+# (8193 at 0, 8192 and 16384 at 1).
+EDGE_SIZES = [8188, 8189, 8191, 8192, 8193, 16381, 16384, 16387]
+EDGE_KERNELS = ['step', 'step_clipped', 'step_skipped', 'step_ema', 'ema_update', 'tensor_swap']
+
+
+@pytest.mark.parametrize('kernel', EDGE_KERNELS)
+def test_chunk_boundaries_of_every_walked_kernel(kernel):
+    """Every size at the four common line offsets and once with four disagreeing ones (the dword path), 40 tensors in
+    ONE call of the kernel: all four whole buffers against the restatement bit for bit, NaN gaps included."""
+    sizes = [n for n in EDGE_SIZES for _ in range(5)]
+    offs = []
+    for k, _ in enumerate(EDGE_SIZES):
+        offs += [(o, o, o, o) for o in range(4)] + [tuple((k + r) % 4 for r in range(4))]
+    a = Arena(sizes, offs, 83)
+    n = len(sizes)
+    lrs = [0.01 * (1 + i % 7) for i in range(n)]
+    wds = [0.0 if i % 3 == 0 else 5e-4 for i in range(n)]
+    triple = (0.9, 0.0, 0)
+    state, ref = new_state(), ema_ref.State()
+    if kernel in ('ema_update', 'tensor_swap'):
+        if kernel == 'ema_update':
+            ops.ema_begin(state, 0.9, 0.0)
+            ema_ref.begin(ref, 0.9, 0.0)
+            ops.ema_update([(a.view(E, i), a.view(P, i)) for i in range(n)], state)
+            for i in range(n):
+                a.view(E, i, False)[:] = ema_ref.update(a.view(E, i, False), a.view(P, i, False), ref)
+        else:
+            ops.tensor_swap([(a.view(P, i), a.view(E, i)) for i in range(n)])
+            for i in range(n):
+                tmp = a.view(P, i, False).copy()
+                a.view(P, i, False)[:] = a.view(E, i, False)
+                a.view(E, i, False)[:] = tmp
+        assert a.same_bits() == [True] * 4, kernel
+        return
+    first = [kernel == 'step_skipped' and i % 2 == 0 for i in range(n)]
+    clip, gs = None, F32(1.0)
+    if kernel == 'step_skipped':
+        for i in range(n):
+            if first[i]:
+                a.view(B, i, False)[:] = np.nan                 # "uninitialised": the skip must leave +0 here
+        a.view(G, n - 1, False)[sizes[-1] - 1] = np.inf
+        for r in (G, B):
+            a.dev[r].copy_(torch.from_numpy(a.host[r]))
+    if kernel in ('step_clipped', 'step_skipped'):
+        gh = [a.view(G, i, False) for i in range(n)]
+        max_norm = 0.5 * clip_ref.norm64(gh) if kernel == 'step_clipped' else 1.0
+        clip = ops.grad_norm_clip([a.view(G, i) for i in range(n)], max_norm)
+        info = ops.clip_info(clip)
+        if kernel == 'step_clipped':
+            assert clip_ref.ulps_apart(F32(info['norm']), clip_ref.norm32(gh)) <= 1     # as tests/test_gpu_grad_clip.py
+            coef, finite = clip_ref.coef(F32(info['norm']), max_norm)
+            assert finite == 1 and info['finite'] and coef < 1 and F32(info['coef']) == coef
+            gs = F32(1.0) * coef
+        else:
+            assert not info['finite'] and info['coef'] == 0.0
+    items = [(a.view(P, i), a.view(G, i), a.view(B, i), lrs[i], wds[i], first[i]) +
+             ((a.view(E, i),) if kernel == 'step_ema' else ()) for i in range(n)]
+    if kernel == 'step_ema':
+        ops.ema_begin(state, 0.9998, 10.0)
+        ema_ref.begin(ref, 0.9998, 10.0)
+        ops.sgd_step_ema(items, *triple, 1.0, state)
+    else:
+        ops.sgd_step(items, *triple, 1.0, clip_state=clip)
+    for i in range(n):
+        if kernel == 'step_skipped':
+            if first[i]:
+                a.view(B, i, False)[:] = 0.0                    # nothing else is written
+        else:
+            a.expect_step(i, lrs[i], wds[i], triple, ref, grad_scale=gs)       # ref not applied: the average stays
+    assert a.same_bits() == [True] * 4, kernel
