@@ -41,6 +41,7 @@ SOURCES = {
     'ct_attn.hip': [],
     'ct_attn_bwd.hip': [],
     'ct_train.hip': [],
+    'ct_wgrad.hip': [],
     'ct_wgrad_h2.hip': [],
     'ct_box.hip': ['-ffp-contract=off'],
     'ct_loss.hip': ['-ffp-contract=off'],

@@ -1,248 +1,17 @@
-// libctdet: training-side kernels of the RFBNet stack (what autograd + cuDNN do for the reference
-// in train.py:222-229): weight gradient of a convolution, batch-statistics BatchNorm forward /
-// backward, bias+ReLU backward, max-pool backward and the head-gradient gather.  The data gradient
-// of a convolution is the `transposed` mode of ct_conv2d_fwd (ct_conv.hip).
+// libctdet: the non-convolution training kernels of the RFBNet stack (part of what autograd + cuDNN do for the reference
+// in train.py:222-229): batch-statistics BatchNorm forward / backward, bias+ReLU backward, max-pool backward and the
+// head-gradient gather.  The weight gradients of a convolution are in ct_wgrad.hip (direct), ct_wino_wgrad.hip,
+// ct_wino4_wgrad.hip and ct_wgrad_h2.hip; its data gradient is the `transposed` mode of ct_conv2d_fwd (ct_conv.hip).
 #include "ct_common.h"
 #include "ct_device.h"
 #include "ct_f16x2.h"
-#include "ct_wgrad_launch.h"
 #include <algorithm>
 #include <cstdint>
 
 namespace {
 
-using ctdet::f32x16;
-using ctdet::kInvalidOff;
-using ctdet::kMaxBufBytes;
-using ctdet::make_rsrc;
-
 // ------------------------------------------------------------------------------------------
-// weight gradient:  dW[co][ci][kh][kw] = sum_{n,oh,ow} dZ[n][co][oh][ow] * X[n][ci][ih][iw]
-// GEMM  M = cout, N = cin*kh*kw, K = batch*oh*ow (pixels), fp32 MFMA 32x32x2, 128x128 (or 64x64) tile,
-// split over pixel ranges across workgroups (fp32 atomicAdd into a zeroed dW; with WgradArgs::slab every split stores its
-// tile into its own [Cout][Ncols] slab instead, and ctdet::wgrad_slab_sum adds the slabs in order: ct_conv2d_wgrad_det).
-// Lanes run along pixels (coalesced rows of dZ and of the shifted X), tiles are staged to LDS
-// transposed ([pixel][row], stride 65) so the MFMA fragments read conflict-free.
-// ------------------------------------------------------------------------------------------
-struct WgradArgs {
-    const float* x;
-    const float* dz;
-    float* dw;
-    float* slab;             // null: atomics into dw.  Else slab blockIdx.y of [splits][Cout][Ncols], every element stored
-    unsigned x_bytes, dz_bytes;
-    int Cin, H, W, x_ctot, x_coff;
-    int Cout, OW, OHW, dz_ctot, dz_coff;
-    int stride, pad_h, pad_w, dil;
-    int Npix, Ncols;
-    int tiles_m, tiles_n, pix_per_split;
-};
-
-// TAPMAJOR (needs cin % (64*TB) == 0): the GEMM columns are ordered tap-major (col = tap*cin + ci), so all rows of
-// a column tile share ONE filter tap: the shifted-pixel offset and its bounds test are computed once per chunk and
-// lane instead of once per gathered row -- the generic path spends ~12 VALU instructions per MFMA on that and starves
-// the matrix pipe (measured 78 TFLOP/s, half of peak, independent of tile shape).
-template <int KH, int KW, int TB, bool TAPMAJOR>
-__global__ __launch_bounds__(256) void conv_wgrad_f32(const WgradArgs a)
-{
-    // workgroup tile (64*TB couts) x (64*TB columns), each wave TB x TB accumulator blocks of 32x32
-    constexpr int KHW = KH * KW;
-    constexpr int BM = 64 * TB, BN = 64 * TB, BKP = 64, LD = BM + 1, ROWS = 16 * TB;
-    extern __shared__ float wg_lds[];
-    float* As = wg_lds;
-    float* Bs = wg_lds + BKP * LD;
-
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hsel = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm0 = (wave & 1) * 32 * TB, wn0 = (wave >> 1) * 32 * TB;
-    const int tile = blockIdx.x;
-    const int m0 = (tile % a.tiles_m) * BM;
-    const int c0 = (tile / a.tiles_m) * BN;
-    const int p_begin = blockIdx.y * a.pix_per_split;
-    const int p_end = min(p_begin + a.pix_per_split, a.Npix);
-    if (p_begin >= p_end) return;
-
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, a.x_bytes);
-    const __amdgpu_buffer_rsrc_t rz = make_rsrc(a.dz, a.dz_bytes);
-    const int HW = a.H * a.W;
-
-    // wave-uniform row descriptors: A rows = cout m0 + wave + 4j, B rows = column c0 + wave + 4j
-    int a_soff[ROWS], b_soff[ROWS], b_dh[ROWS], b_dw[ROWS];
-    const int tm_tap = TAPMAJOR ? c0 / a.Cin : 0, tm_ci0 = TAPMAJOR ? c0 - tm_tap * a.Cin : 0;
-    const int tm_dh = (tm_tap / KW) * a.dil - a.pad_h, tm_dw = (tm_tap % KW) * a.dil - a.pad_w;
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) {
-        const int m = m0 + wave + 4 * j;
-        a_soff[j] = min(m, a.Cout - 1) * a.OHW * 4;      // rows past Cout repeat the last one: their results are never stored
-        if (TAPMAJOR) {
-            b_soff[j] = (tm_ci0 + wave + 4 * j) * HW * 4;
-            b_dh[j] = tm_dh;
-            b_dw[j] = tm_dw;
-        } else {
-            const int col = c0 + wave + 4 * j;
-            const int ci = col / KHW, tap = col - ci * KHW;
-            const int kh = tap / KW, kw = tap - kh * KW;
-            b_soff[j] = min(ci, a.Cin - 1) * HW * 4;    // columns past Ncols: clamped, never stored
-            b_dh[j] = kh * a.dil - a.pad_h;
-            b_dw[j] = kw * a.dil - a.pad_w;
-        }
-    }
-
-    float areg[ROWS], breg[ROWS];
-    auto load_chunk = [&](int p0) {
-        const int P = p0 + lane;
-        const bool pv = P < p_end;
-        const int Pc = pv ? P : 0;
-        const int n = Pc / a.OHW;
-        const int s = Pc - n * a.OHW;
-        const int oh = s / a.OW, ow = s - oh * a.OW;
-        const int zoff = pv ? ((n * a.dz_ctot + a.dz_coff) * a.OHW + s) * 4 : kInvalidOff;
-        const int xbase = (n * a.x_ctot + a.x_coff) * HW;
-        const int ih0 = oh * a.stride, iw0 = ow * a.stride;
-        if (TAPMAJOR) {
-            const int ih = ih0 + tm_dh, iw = iw0 + tm_dw;
-            const bool ok = pv && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
-            const int xoff = ok ? (xbase + ih * a.W + iw) * 4 : kInvalidOff;
-#pragma unroll
-            for (int j = 0; j < ROWS; ++j) {
-                areg[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rz, zoff, a_soff[j], 0));
-                breg[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, xoff, b_soff[j], 0));
-            }
-            return;
-        }
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-            areg[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rz, zoff, a_soff[j], 0));
-            const int ih = ih0 + b_dh[j], iw = iw0 + b_dw[j];
-            const bool ok = pv && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
-            const int xoff = ok ? (xbase + ih * a.W + iw) * 4 : kInvalidOff;
-            breg[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, xoff, b_soff[j], 0));
-        }
-    };
-
-    f32x16 acc[TB][TB], acc2[TB][TB];
-#pragma unroll
-    for (int i = 0; i < TB; ++i)
-#pragma unroll
-        for (int j = 0; j < TB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; acc2[i][j][r] = 0.f; }
-
-    if (TAPMAJOR && TB == 1) {
-        // Pipelined variant (same structure as the forward implicit-GEMM kernel): two LDS buffers, ONE barrier
-        // per chunk; in k-pair slot e the wave stores element e of chunk c+1 (loaded during chunk c-1) into
-        // the other buffer and re-issues the load of element e for chunk c+2, then runs the slot's MFMA.
-        float* As2 = wg_lds + 2 * BKP * LD;
-        float* Bs2 = As2 + BKP * LD;
-        int zoff, xoff;
-        auto setup = [&](int p0) {
-            const int P = p0 + lane;
-            const bool pv = P < p_end;
-            const int Pc = pv ? P : 0;
-            const int n = Pc / a.OHW;
-            const int sp = Pc - n * a.OHW;
-            const int oh = sp / a.OW, ow = sp - oh * a.OW;
-            zoff = pv ? ((n * a.dz_ctot + a.dz_coff) * a.OHW + sp) * 4 : kInvalidOff;
-            const int ih = oh * a.stride + tm_dh, iw = ow * a.stride + tm_dw;
-            const bool ok = pv && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
-            xoff = ok ? ((n * a.x_ctot + a.x_coff) * HW + ih * a.W + iw) * 4 : kInvalidOff;
-        };
-        auto load_e = [&](int e) {
-            if (e < ROWS) areg[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rz, zoff, a_soff[e], 0));
-            else breg[e - ROWS] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, xoff, b_soff[e - ROWS], 0));
-        };
-        auto store_e = [&](int e, float* Ad, float* Bd) {
-            if (e < ROWS) Ad[lane * LD + wave + 4 * e] = areg[e];
-            else Bd[lane * LD + wave + 4 * (e - ROWS)] = breg[e - ROWS];
-        };
-        setup(p_begin);
-#pragma unroll
-        for (int e = 0; e < 2 * ROWS; ++e) load_e(e);
-#pragma unroll
-        for (int e = 0; e < 2 * ROWS; ++e) store_e(e, As, Bs);
-        setup(p_begin + BKP);                    // past the end: every offset invalid -> zeros
-#pragma unroll
-        for (int e = 0; e < 2 * ROWS; ++e) load_e(e);
-        __syncthreads();
-        int cidx = 0;
-        for (int p0 = p_begin; p0 < p_end; p0 += BKP, ++cidx) {
-            const float* Ac = (cidx & 1) ? As2 : As;
-            const float* Bc = (cidx & 1) ? Bs2 : Bs;
-            float* An = (cidx & 1) ? As : As2;
-            float* Bn = (cidx & 1) ? Bs : Bs2;
-            const float* Ab = Ac + hsel * LD + wm0 + l31;
-            const float* Bb = Bc + hsel * LD + wn0 + l31;
-            // registers hold chunk c+1; the loads issued below fetch chunk c+2
-            setup(p0 + 2 * BKP);
-            float af[2], bf[2];
-            af[0] = Ab[0];
-            bf[0] = Bb[0];
-#pragma unroll
-            for (int sidx = 0; sidx < BKP / 2; ++sidx) {
-                const int cur = sidx & 1;
-                if (sidx + 1 < BKP / 2) {
-                    af[cur ^ 1] = Ab[(2 * sidx + 2) * LD];
-                    bf[cur ^ 1] = Bb[(2 * sidx + 2) * LD];
-                }
-                store_e(sidx, An, Bn);
-                load_e(sidx);
-                if (sidx & 1) acc2[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur], bf[cur], acc2[0][0], 0, 0, 0);
-                else acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur], bf[cur], acc[0][0], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __syncthreads();
-        }
-    } else {
-    load_chunk(p_begin);
-        for (int p0 = p_begin; p0 < p_end; p0 += BKP) {
-    #pragma unroll
-            for (int j = 0; j < ROWS; ++j) {
-                As[lane * LD + wave + 4 * j] = areg[j];
-                Bs[lane * LD + wave + 4 * j] = breg[j];
-            }
-            __syncthreads();
-            if (p0 + BKP < p_end) load_chunk(p0 + BKP);
-            const float* Ab = As + hsel * LD + wm0 + l31;
-            const float* Bb = Bs + hsel * LD + wn0 + l31;
-    #pragma unroll 8
-            for (int s = 0; s < BKP / 2; ++s) {
-                float af[TB], bf[TB];
-    #pragma unroll
-                for (int i = 0; i < TB; ++i) {
-                    af[i] = Ab[(2 * s) * LD + 32 * i];
-                    bf[i] = Bb[(2 * s) * LD + 32 * i];
-                }
-    #pragma unroll
-                for (int i = 0; i < TB; ++i)
-    #pragma unroll
-                    for (int j = 0; j < TB; ++j) {
-                        if (s & 1) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc2[i][j], 0, 0, 0);
-                        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
-                    }
-            }
-            __syncthreads();
-        }
-    }
-
-#pragma unroll
-    for (int j = 0; j < TB; ++j) {
-        int col = c0 + wn0 + 32 * j + l31;
-        if (col >= a.Ncols) continue;
-        if (TAPMAJOR) col = (tm_ci0 + wn0 + 32 * j + l31) * KHW + tm_tap;      // back to dW's [ci][tap] order
-#pragma unroll
-        for (int i = 0; i < TB; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm0 + 32 * i + ctdet::acc_row(r, hsel);
-                if (m >= a.Cout) continue;
-                const float v = acc[i][j][r] + acc2[i][j][r];
-                if (a.slab) a.slab[((size_t)blockIdx.y * a.Cout + m) * a.Ncols + col] = v;
-                else unsafeAtomicAdd(a.dw + (size_t)m * a.Ncols + col, v);
-            }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// BatchNorm2d training statistics over (batch, h, w) of a channel slice of an NCHW buffer
+// Per-channel reductions of the BatchNorm passes over (batch, h, w) of a channel slice of an NCHW buffer
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ double block_sum(double v, double* red)
 {
@@ -256,64 +25,43 @@ __device__ __forceinline__ double block_sum(double v, double* red)
     return t;
 }
 
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ z, int batch, int ctot,
-                                                       int coff, int HW, float* __restrict__ mean,
-                                                       float* __restrict__ var, float momentum, float unbias,
-                                                       float* __restrict__ rmean, float* __restrict__ rvar)
-{
-    __shared__ double red[4];
-    const int c = blockIdx.x;
-    double s = 0.0, ss = 0.0;
-    for (int n = 0; n < batch; ++n) {
-        const float* p = z + ((size_t)n * ctot + coff + c) * HW;
-        for (int i = threadIdx.x; i < HW; i += 256) {
-            const double v = p[i];
-            s += v;
-            ss += v * v;
-        }
-    }
-    s = block_sum(s, red);
-    ss = block_sum(ss, red);
-    if (threadIdx.x == 0) {
-        const double cnt = (double)batch * HW;
-        const double m = s / cnt;
-        const float mf = (float)m, vf = (float)fmax(ss / cnt - m * m, 0.0);   // biased variance (normalisation)
-        mean[c] = mf;
-        var[c] = vf;
-        if (rmean) {
-            rmean[c] = (1.f - momentum) * rmean[c] + momentum * mf;
-            rvar[c] = (1.f - momentum) * rvar[c] + momentum * (vf * unbias);
-        }
-    }
-}
+// Both passes sum two double terms per element of a channel (StatsOp: z, z^2; BwdOp: dy, dy * xhat) with 256 threads.  An Op adds
+// the terms of element (n, c, i) and finishes a channel from its two sums; the walk over the elements is one of two:
+//   WHOLE (grid = channels): images outer, i = tid, tid + 256, ... inside each image; the block finishes its channel in place.
+//   SLICE (grid = channels x slices, most of the chip would idle otherwise): e = e0 + tid, e0 + tid + 256, ... over slice blockIdx.y
+//     of the flat batch*HW range.  The block sums meet in `scratch` ([2][C] doubles, zeroed by the host entry) through f64 atomics;
+//     det: slice y STORES them at scratch[y][2][C] instead (nothing zeroed).  The *_final_kernel adds the records in slice order.
+// A thread's partial sums differ between the walks whenever HW % 256 != 0: one walk for both would move result bits.
+enum class Walk { WHOLE, SLICE };
 
-// sliced variants (grid = channels x slices): block sums in double meet in `scratch` ([2][C] doubles, zeroed by the
-// host entry) through f64 atomics; a one-block-per-channel reduction leaves most of the chip idle on the RFB maps.
-// det: slice y STORES its two sums at scratch[y][2][C] instead (nothing zeroed), and the final kernel adds the slices in order.
-__global__ __launch_bounds__(256) void bn_stats_part_kernel(const float* __restrict__ z, int batch, int ctot,
-                                                            int coff, int C, int HW, int per_slice,
-                                                            double* __restrict__ scratch, int det)
+template <Walk WALK, class Op>
+__device__ __forceinline__ void bn_reduce(Op op, int batch, int C, int HW, int per_slice, double* __restrict__ scratch, int det)
 {
     __shared__ double red[4];
     const int c = blockIdx.x;
-    const long e0 = (long)blockIdx.y * per_slice, e1 = min(e0 + per_slice, (long)batch * HW);
-    double s = 0.0, ss = 0.0;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
-        const int n = (int)(e / HW), i = (int)(e - (long)n * HW);
-        const double v = z[((size_t)n * ctot + coff + c) * HW + i];
-        s += v;
-        ss += v * v;
-    }
-    s = block_sum(s, red);
-    ss = block_sum(ss, red);
-    if (threadIdx.x == 0) {
-        if (det) {
-            scratch[(size_t)blockIdx.y * 2 * C + c] = s;
-            scratch[(size_t)blockIdx.y * 2 * C + C + c] = ss;
-        } else {
-            unsafeAtomicAdd(&scratch[c], s);
-            unsafeAtomicAdd(&scratch[C + c], ss);
+    op.channel(c);
+    double s0 = 0.0, s1 = 0.0;
+    if (WALK == Walk::WHOLE) {
+        for (int n = 0; n < batch; ++n)
+            for (int i = threadIdx.x; i < HW; i += 256) op.add(n, c, i, s0, s1);
+    } else {
+        const long e0 = (long)blockIdx.y * per_slice, e1 = min(e0 + per_slice, (long)batch * HW);
+        for (long e = e0 + threadIdx.x; e < e1; e += 256) {
+            const int n = (int)(e / HW);
+            op.add(n, c, (int)(e - (long)n * HW), s0, s1);
         }
+    }
+    s0 = block_sum(s0, red);
+    s1 = block_sum(s1, red);
+    if (threadIdx.x != 0) return;
+    if (WALK == Walk::WHOLE) {
+        op.finish(c, s0, s1);
+    } else if (det) {
+        scratch[(size_t)blockIdx.y * 2 * C + c] = s0;
+        scratch[(size_t)blockIdx.y * 2 * C + C + c] = s1;
+    } else {
+        unsafeAtomicAdd(&scratch[c], s0);
+        unsafeAtomicAdd(&scratch[C + c], s1);
     }
 }
 
@@ -329,23 +77,51 @@ __device__ __forceinline__ void slice_sums(const double* __restrict__ scratch, i
     }
 }
 
-__global__ void bn_stats_final_kernel(const double* __restrict__ scratch, int slices, int C, double cnt,
-                                      float* __restrict__ mean, float* __restrict__ var, float momentum,
-                                      float unbias, float* __restrict__ rmean, float* __restrict__ rvar)
+template <class Op>
+__device__ __forceinline__ void bn_reduce_final(const Op& op, const double* __restrict__ scratch, int slices, int C)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    double s, ss;
-    slice_sums(scratch, C, slices, c, s, ss);
-    const double m = s / cnt;
-    const float mf = (float)m, vf = (float)fmax(ss / cnt - m * m, 0.0);
-    mean[c] = mf;
-    var[c] = vf;
-    if (rmean) {        // running statistics of nn.BatchNorm2d (momentum, unbiased variance), same launch
-        rmean[c] = (1.f - momentum) * rmean[c] + momentum * mf;
-        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (vf * unbias);
-    }
+    double s0, s1;
+    slice_sums(scratch, C, slices, c, s0, s1);
+    op.finish(c, s0, s1);
 }
+
+// BatchNorm2d training statistics of channels [coff, coff + C) of z
+struct StatsOp {
+    const float* z;
+    float *mean, *var;
+    float *rmean, *rvar;     // running statistics of nn.BatchNorm2d (momentum, unbiased variance), same launch; or null
+    double cnt;              // batch * HW
+    int batch, ctot, coff, C, HW;
+    float momentum, unbias;
+
+    __device__ void channel(int) {}
+    __device__ void add(int n, int c, int i, double& s, double& ss) const
+    {
+        const double v = z[((size_t)n * ctot + coff + c) * HW + i];
+        s += v;
+        ss += v * v;
+    }
+    __device__ void finish(int c, double s, double ss) const
+    {
+        const double m = s / cnt;
+        const float mf = (float)m, vf = (float)fmax(ss / cnt - m * m, 0.0);   // biased variance (normalisation)
+        mean[c] = mf;
+        var[c] = vf;
+        if (rmean) {
+            rmean[c] = (1.f - momentum) * rmean[c] + momentum * mf;
+            rvar[c] = (1.f - momentum) * rvar[c] + momentum * (vf * unbias);
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void bn_stats_kernel(const StatsOp op) { bn_reduce<Walk::WHOLE>(op, op.batch, op.C, op.HW, 0, nullptr, 0); }
+__global__ __launch_bounds__(256) void bn_stats_part_kernel(const StatsOp op, int per_slice, double* __restrict__ scratch, int det)
+{
+    bn_reduce<Walk::SLICE>(op, op.batch, op.C, op.HW, per_slice, scratch, det);
+}
+__global__ void bn_stats_final_kernel(const StatsOp op, const double* __restrict__ scratch, int slices) { bn_reduce_final(op, scratch, slices, op.C); }
 
 struct BnApplyArgs {
     const float* z;          // conv output, channel slice [z_coff, z_coff+C) of z_ctot
@@ -404,65 +180,27 @@ __device__ __forceinline__ float masked_dy(const BnBwdArgs& a, int n, int c, int
     return g;
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdArgs a)
-{
-    __shared__ double red[4];
-    const int c = blockIdx.x;
-    const float inv = 1.f / sqrtf(a.var[c] + a.eps), mu = a.mean[c];
-    double sb = 0.0, sg = 0.0;
-    for (int n = 0; n < a.batch; ++n) {
-        const float* zp = a.z + ((size_t)n * a.z_ctot + a.z_coff + c) * a.HW;
-        for (int i = threadIdx.x; i < a.HW; i += 256) {
-            const float g = masked_dy(a, n, c, i) * a.rscale;
-            sb += g;
-            sg += (double)g * ((zp[i] - mu) * inv);
-        }
-    }
-    sb = block_sum(sb, red);
-    sg = block_sum(sg, red);
-    if (threadIdx.x == 0) {
-        a.dbeta[c] = (float)sb;
-        a.dgamma[c] = (float)sg;
-    }
-}
+// dbeta = sum of the masked, scaled dy; dgamma = sum of that times the normalised z
+struct BwdOp {
+    const BnBwdArgs& a;
+    float inv, mu;
 
-__global__ __launch_bounds__(256) void bn_bwd_reduce_part_kernel(const BnBwdArgs a, int per_slice,
-                                                                 double* __restrict__ scratch, int det)
-{
-    __shared__ double red[4];
-    const int c = blockIdx.x;
-    const float inv = 1.f / sqrtf(a.var[c] + a.eps), mu = a.mean[c];
-    const long e0 = (long)blockIdx.y * per_slice, e1 = min(e0 + per_slice, (long)a.batch * a.HW);
-    double sb = 0.0, sg = 0.0;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
-        const int n = (int)(e / a.HW), i = (int)(e - (long)n * a.HW);
+    __device__ void channel(int c) { inv = 1.f / sqrtf(a.var[c] + a.eps); mu = a.mean[c]; }
+    __device__ void add(int n, int c, int i, double& sb, double& sg) const
+    {
         const float g = masked_dy(a, n, c, i) * a.rscale;
         sb += g;
         sg += (double)g * ((a.z[((size_t)n * a.z_ctot + a.z_coff + c) * a.HW + i] - mu) * inv);
     }
-    sb = block_sum(sb, red);
-    sg = block_sum(sg, red);
-    if (threadIdx.x == 0) {
-        if (det) {
-            scratch[(size_t)blockIdx.y * 2 * a.C + c] = sb;
-            scratch[(size_t)blockIdx.y * 2 * a.C + a.C + c] = sg;
-        } else {
-            unsafeAtomicAdd(&scratch[c], sb);
-            unsafeAtomicAdd(&scratch[a.C + c], sg);
-        }
-    }
-}
+    __device__ void finish(int c, double sb, double sg) const { a.dbeta[c] = (float)sb; a.dgamma[c] = (float)sg; }
+};
 
-__global__ void bn_bwd_reduce_final_kernel(const double* __restrict__ scratch, int slices, int C, float* __restrict__ dbeta,
-                                           float* __restrict__ dgamma)
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdArgs a) { bn_reduce<Walk::WHOLE>(BwdOp{a}, a.batch, a.C, a.HW, 0, nullptr, 0); }
+__global__ __launch_bounds__(256) void bn_bwd_reduce_part_kernel(const BnBwdArgs a, int per_slice, double* __restrict__ scratch, int det)
 {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double sb, sg;
-    slice_sums(scratch, C, slices, c, sb, sg);
-    dbeta[c] = (float)sb;
-    dgamma[c] = (float)sg;
+    bn_reduce<Walk::SLICE>(BwdOp{a}, a.batch, a.C, a.HW, per_slice, scratch, det);
 }
+__global__ void bn_bwd_reduce_final_kernel(const BnBwdArgs a, const double* __restrict__ scratch, int slices) { bn_reduce_final(BwdOp{a}, scratch, slices, a.C); }
 
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a)
 {
@@ -484,6 +222,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a)
         const float xh = (a.z[zi] - a.mean[c]) * inv;
         a.dz[zi] = a.frozen ? a.gamma[c] * inv * g
                             : a.gamma[c] * inv * (g - a.dbeta[c] / cnt - xh * a.dgamma[c] / cnt);
+    }
+}
+
+// The tail of the two bias backward kernels: the block's share of dbias[c] is stored at slab[slot][C] (deterministic mode:
+// dbias_slab_sum_kernel adds the slots in order), else it joins dbias[c] through one float atomic.
+__device__ __forceinline__ void dbias_sink(double sb, double* red, int c, int C, int slot, float* __restrict__ dbias,
+                                           double* __restrict__ slab)
+{
+    sb = block_sum(sb, red);
+    if (threadIdx.x == 0 && dbias) {
+        if (slab) slab[(size_t)slot * C + c] = sb;
+        else unsafeAtomicAdd(&dbias[c], (float)sb);
     }
 }
 
@@ -543,11 +293,7 @@ __global__ __launch_bounds__(256) void bias_act_bwd_kernel(const float* __restri
         i0 = 0;
         ++n;
     }
-    sb = block_sum(sb, red);
-    if (threadIdx.x == 0 && dbias) {
-        if (slab) slab[(size_t)blockIdx.y * C + c] = sb;
-        else unsafeAtomicAdd(&dbias[c], (float)sb);
-    }
+    dbias_sink(sb, red, c, C, blockIdx.y, dbias, slab);
 }
 
 // dbias[c] = the `nslabs` partial sums slab[.][C] of channel c added in slab order (bias + activation backward: one per
@@ -725,11 +471,7 @@ __global__ __launch_bounds__(256) void maxpool2x2_bias_relu_bwd_kernel(const flo
         ctdet::h2::track_absmax(run, gm);
     }
     if (amax) ctdet::h2::flush_absmax(amax, n, run);
-    sb = block_sum(sb, red);
-    if (threadIdx.x == 0 && dbias) {
-        if (slab) slab[(size_t)n * C + c] = sb;         // one partial sum per image, added in image order
-        else unsafeAtomicAdd(&dbias[c], (float)sb);
-    }
+    dbias_sink(sb, red, c, C, n, dbias, slab);          // one partial sum per image, added in image order
 }
 
 // gradient of the channels-last head scatter: dz[n][co][pix] = dflat[n*img_stride + base + pix*ps + (co-co0)]
@@ -767,166 +509,6 @@ inline int grid_for(long total) { return (int)std::min<long>((total + 255) / 256
 
 }  // namespace
 
-static bool wgrad_filter_built(const ct_conv_desc* d)
-{
-    return (d->kh == 3 && d->kw == 3) || (d->kh == 1 && d->kw == 1) || (d->kh == 1 && d->kw == 3) || (d->kh == 3 && d->kw == 1) ||
-           (d->kh == 4 && d->kw == 4);
-}
-
-// Tile edge and pixel splits of a launch over nb images: a pure function of the descriptor and the environment (host only).
-struct WgradPlan { int tb, tiles_m, tiles_n, splits, pix_per_split; };
-static WgradPlan wgrad_plan(const ct_conv_desc* d, int nb)
-{
-    WgradPlan p{};
-    const int Npix = nb * d->oh * d->ow, Ncols = d->cin * d->kh * d->kw;
-    // the 128x128 variant (TB = 2) measured slower on the RFBNet shapes (fewer pixel splits in flight, the
-    // 64 gathers per thread arrive in one burst); kept for experiments behind CTDET_WGRAD_TB=2
-    static const int tb_env = getenv("CTDET_WGRAD_TB") ? atoi(getenv("CTDET_WGRAD_TB")) : 1;
-    p.tb = (tb_env == 2 && d->cout >= 96 && Ncols >= 96) ? 2 : 1;
-    const int bt = 64 * p.tb;
-    p.tiles_m = (d->cout + bt - 1) / bt;
-    p.tiles_n = (Ncols + bt - 1) / bt;
-    const int tiles = p.tiles_m * p.tiles_n;
-    // Pixel splits: the chip holds `slots` workgroups at a time (2 per CU with the double-buffered LDS); take the
-    // smallest split count whose last round is at least 92 % full -- one workgroup too many costs a whole round,
-    // and every extra split pays the atomic epilogue again.
-    static const int slots = getenv("CTDET_WGRAD_WGS") ? atoi(getenv("CTDET_WGRAD_WGS")) : 512;
-    const int smax = std::max(1, std::min((Npix + 255) / 256, (4 * slots) / tiles));
-    int splits = 1;
-    double best = 0.0;
-    for (int sp = 1; sp <= smax; ++sp) {
-        const int wg = tiles * sp, rounds = (wg + slots - 1) / slots;
-        const double eff = (double)wg / ((double)rounds * slots);
-        if (eff > best + 1e-9) { best = eff; splits = sp; }
-        if (eff >= 0.92) break;
-    }
-    const ctdet::Split sp = ctdet::even_split((Npix + 63) / 64, splits);       // in blocks of 64 pixels: no split is empty
-    p.pix_per_split = sp.per_split * 64;
-    p.splits = sp.splits;
-    return p;
-}
-
-// the images [b0, b0 + nb) of the batch; the first chunk zeroes dw.  slab != null (ct_conv2d_wgrad_det): the chunk's splits
-// store into slab[0 .. splits) instead and dw is left to the caller's slab sum.
-static int wgrad_chunk(const char* who, const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw,
-                       const ctdet::WgradLimits& lim, int b0, int nb, const WgradPlan& plan, float* slab, ct_stream_t stream)
-{
-    WgradArgs a{};
-    ctdet::wgrad_fill(a, d, dz, dz_ctot, dz_coff, lim, b0, nb);
-    a.dw = dw;
-    a.slab = slab;
-    a.H = d->h; a.W = d->w;
-    a.OW = d->ow; a.OHW = d->oh * d->ow;
-    a.stride = d->stride; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.dil = d->dil;
-    a.Npix = nb * a.OHW;
-    a.Ncols = d->cin * d->kh * d->kw;
-    const int tb = plan.tb, bt = 64 * tb;
-    a.tiles_m = plan.tiles_m;
-    a.tiles_n = plan.tiles_n;
-    const int tiles = a.tiles_m * a.tiles_n;
-    a.pix_per_split = plan.pix_per_split;
-    const int splits = plan.splits;
-    hipStream_t st = ctdet::as_stream(stream);
-    if (!slab && b0 == 0 && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dw, 0, (size_t)d->cout * a.Ncols * 4, st));
-    const bool tapmajor = d->cin % bt == 0 && !(getenv("CTDET_WGRAD_GENERIC"));
-    const bool tapmajor_for_smem = tapmajor;
-    const dim3 grid(tiles, splits), block(256);
-    const bool pipelined = tapmajor_for_smem && tb == 1;
-    const size_t smem = (pipelined ? 4 : 2) * 64 * (size_t)(bt + 1) * 4;
-    hipError_t le = hipSuccess;
-    auto go = [&](auto kernel) {
-        le = ctdet::raise_lds_limit((const void*)kernel, smem);
-        if (le == hipSuccess) hipLaunchKernelGGL(kernel, grid, block, smem, st, a);
-    };
-#define CT_WGRAD_GO(KH, KW)                                                    \
-    do {                                                                       \
-        if (tb == 2 && tapmajor) go(conv_wgrad_f32<KH, KW, 2, true>);          \
-        else if (tb == 2) go(conv_wgrad_f32<KH, KW, 2, false>);                \
-        else if (tapmajor) go(conv_wgrad_f32<KH, KW, 1, true>);                \
-        else go(conv_wgrad_f32<KH, KW, 1, false>);                             \
-    } while (0)
-    if (d->kh == 3 && d->kw == 3) CT_WGRAD_GO(3, 3);
-    else if (d->kh == 1 && d->kw == 1) CT_WGRAD_GO(1, 1);
-    else if (d->kh == 1 && d->kw == 3) CT_WGRAD_GO(1, 3);
-    else if (d->kh == 3 && d->kw == 1) CT_WGRAD_GO(3, 1);
-    else if (d->kh == 4 && d->kw == 4) CT_WGRAD_GO(4, 4);
-    else return ctdet::fail(CT_ERR_UNSUPPORTED, "%s: %dx%d filters not built", who, d->kh, d->kw);
-#undef CT_WGRAD_GO
-    CT_HIP(le);
-    CT_LAUNCH_CHECK("conv_wgrad_f32");
-    return CT_OK;
-}
-
-static bool wgrad_geometry_ok(const ct_conv_desc* d)
-{
-    if (d->stride < 1 || d->dil < 1 || d->kh < 1 || d->kw < 1) return false;
-    const int eoh = (d->h + 2 * d->pad_h - d->dil * (d->kh - 1) - 1) / d->stride + 1;
-    const int eow = (d->w + 2 * d->pad_w - d->dil * (d->kw - 1) - 1) / d->stride + 1;
-    return eoh == d->oh && eow == d->ow;
-}
-
-// slabs of all batch chunks of a launch, in chunk order (the count ct_conv2d_wgrad_det writes and sums)
-static int wgrad_total_splits(const ct_conv_desc* d, const ctdet::WgradLimits& lim)
-{
-    int total = 0;
-    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) total += wgrad_plan(d, std::min(lim.max_chunk, d->batch - b0)).splits;
-    return total;
-}
-
-// ws == null: ct_conv2d_wgrad (atomics); else ct_conv2d_wgrad_det with ws_bytes of slabs
-static int wgrad_impl(const char* who, const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, bool det, void* ws,
-                      size_t ws_bytes, ct_stream_t stream)
-{
-    if (int rc = ctdet::wgrad_check_pointers(d, dz, dw, det ? ws : ctdet::no_workspace(), who)) return rc;
-    if (int rc = ctdet::wgrad_check_slices(d, dz_ctot, dz_coff, who)) return rc;
-    CT_REQUIRE(wgrad_geometry_ok(d), "%s: oh/ow mismatch", who);
-    // buffers above 2 GiB (32-bit buffer offsets): batch chunks accumulate into the same dw (det: append their slabs)
-    ctdet::WgradLimits lim;
-    if (int rc = ctdet::wgrad_limits(d, dz_ctot, who, &lim, kMaxBufBytes - 1)) return rc;
-    const size_t n = (size_t)d->cout * d->cin * d->kh * d->kw;
-    int total = 0;
-    if (det) {
-        if (!wgrad_filter_built(d)) return ctdet::fail(CT_ERR_UNSUPPORTED, "%s: %dx%d filters not built", who, d->kh, d->kw);
-        if (int rc = ctdet::wgrad_check_det_workspace(ws, ws_bytes, (size_t)wgrad_total_splits(d, lim) * n * sizeof(float), who)) return rc;
-    }
-    for (int b0 = 0; b0 < d->batch; b0 += lim.max_chunk) {
-        const int nb = std::min(lim.max_chunk, d->batch - b0);
-        float* slab = det ? static_cast<float*>(ws) + (size_t)total * n : nullptr;
-        const WgradPlan plan = wgrad_plan(d, nb);
-        if (int rc = wgrad_chunk(who, d, dz, dz_ctot, dz_coff, dw, lim, b0, nb, plan, slab, stream)) return rc;
-        total += plan.splits;
-    }
-    if (det) {
-        if (int rc = ctdet::wgrad_slab_sum(static_cast<const float*>(ws), total, n, dw, ctdet::as_stream(stream))) return rc;
-    }
-    return CT_OK;
-}
-
-extern "C" int ct_conv2d_wgrad(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff,
-                               float* dw, ct_stream_t stream)
-{
-    return wgrad_impl("ct_conv2d_wgrad", d, dz, dz_ctot, dz_coff, dw, false, nullptr, 0, stream);
-}
-
-extern "C" size_t ct_conv_wgrad_det_workspace_bytes(const ct_conv_desc* d, int* partials)
-{
-    if (partials) *partials = 0;
-    if (!d || d->batch <= 0 || d->cin <= 0 || d->cout <= 0 || d->oh <= 0 || d->ow <= 0 || !wgrad_geometry_ok(d) ||
-        !wgrad_filter_built(d))
-        return 0;
-    const ctdet::WgradLimits lim = ctdet::wgrad_sizes(d, d->cout, kMaxBufBytes - 1);      // dZ taken as dense
-    if (lim.img_x_bytes >= kMaxBufBytes || lim.img_z_bytes >= kMaxBufBytes) return 0;
-    const int total = wgrad_total_splits(d, lim);
-    if (partials) *partials = total;
-    return (size_t)total * d->cout * d->cin * d->kh * d->kw * sizeof(float);
-}
-
-extern "C" int ct_conv2d_wgrad_det(const ct_conv_desc* d, const float* dz, int dz_ctot, int dz_coff, float* dw, void* workspace,
-                                   size_t workspace_bytes, ct_stream_t stream)
-{
-    return wgrad_impl("ct_conv2d_wgrad_det", d, dz, dz_ctot, dz_coff, dw, true, workspace, workspace_bytes, stream);
-}
-
 // slices of a channel's batch*hw elements in the BatchNorm reductions (both passes)
 static int bn_slices(int batch, int channels, int hw)
 {
@@ -943,36 +525,53 @@ static int det_scratch_check(const char* who, const void* scratch, size_t have, 
     return CT_OK;
 }
 
+// the three kernels of one BatchNorm reduction (each takes the arguments A first) and the names their launch checks report
+template <class A>
+struct BnReduction {
+    void (*whole)(A);
+    void (*part)(A, int per_slice, double* scratch, int det);
+    void (*fin)(A, const double* scratch, int slices);
+    const char *whole_name, *part_name, *fin_name;
+};
+
+// One reduction: sliced (part + final launch) when there is a scratch and more than one slice, else one block per channel.  The
+// atomic path zeroes its [2][C] record unless the caller has (ct_scratch_prezeroed); det stores `slices` records, zeroes nothing.
+template <class A>
+static int bn_reduce_launch(const char* who, const BnReduction<A>& k, const A& a, int batch, int channels, int hw, void* scratch,
+                            bool det, size_t scratch_bytes, hipStream_t st)
+{
+    const long per_channel = (long)batch * hw;
+    const int slices = bn_slices(batch, channels, hw);
+    if (det && slices > 1)
+        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)slices * 2 * channels * sizeof(double))) return rc;
+    if (!scratch || slices == 1) {
+        hipLaunchKernelGGL(k.whole, dim3(channels), dim3(256), 0, st, a);
+        CT_LAUNCH_CHECK(k.whole_name);
+        return CT_OK;
+    }
+    const int per_slice = (int)((per_channel + slices - 1) / slices);
+    if (!det && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(scratch, 0, (size_t)2 * channels * sizeof(double), st));
+    hipLaunchKernelGGL(k.part, dim3(channels, slices), dim3(256), 0, st, a, per_slice, (double*)scratch, (int)det);
+    CT_LAUNCH_CHECK(k.part_name);
+    hipLaunchKernelGGL(k.fin, dim3((channels + 255) / 256), dim3(256), 0, st, a, (const double*)scratch, det ? slices : 1);
+    CT_LAUNCH_CHECK(k.fin_name);
+    return CT_OK;
+}
+
 static int bn_stats_impl(const char* who, const float* z, int batch, int ctot, int coff, int channels, int hw,
                          float* mean, float* var, float momentum, float* running_mean,
                          float* running_var, void* scratch, bool det, size_t scratch_bytes, ct_stream_t stream)
 {
     CT_REQUIRE(z && mean && var && batch > 0 && channels > 0 && hw > 0, "%s: bad arguments", who);
-    hipStream_t st = ctdet::as_stream(stream);
-    const long per_channel = (long)batch * hw;
-    const int slices = bn_slices(batch, channels, hw);
-    if (det && slices > 1)
-        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)slices * 2 * channels * sizeof(double))) return rc;
     const bool run = running_mean && running_var;
-    float* const rm = run ? running_mean : nullptr;
-    float* const rv = run ? running_var : nullptr;
     const float cntf = (float)batch * hw;
-    const float unbias = cntf > 1.f ? cntf / (cntf - 1.f) : 1.f;
-    if (scratch && slices > 1) {
-        const int per_slice = (int)((per_channel + slices - 1) / slices);
-        if (!det && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(scratch, 0, (size_t)2 * channels * sizeof(double), st));
-        hipLaunchKernelGGL(bn_stats_part_kernel, dim3(channels, slices), dim3(256), 0, st, z, batch, ctot, coff,
-                           channels, hw, per_slice, (double*)scratch, (int)det);
-        CT_LAUNCH_CHECK("bn_stats_part_kernel");
-        hipLaunchKernelGGL(bn_stats_final_kernel, dim3((channels + 255) / 256), dim3(256), 0, st,
-                           (const double*)scratch, det ? slices : 1, channels, (double)per_channel, mean, var, momentum, unbias, rm, rv);
-        CT_LAUNCH_CHECK("bn_stats_final_kernel");
-    } else {
-        hipLaunchKernelGGL(bn_stats_kernel, dim3(channels), dim3(256), 0, st, z, batch, ctot, coff, hw, mean, var,
-                           momentum, unbias, rm, rv);
-        CT_LAUNCH_CHECK("bn_stats_kernel");
-    }
-    return CT_OK;
+    StatsOp op{};
+    op.z = z; op.mean = mean; op.var = var; op.rmean = run ? running_mean : nullptr; op.rvar = run ? running_var : nullptr;
+    op.cnt = (double)((long)batch * hw); op.batch = batch; op.ctot = ctot; op.coff = coff; op.C = channels; op.HW = hw;
+    op.momentum = momentum; op.unbias = cntf > 1.f ? cntf / (cntf - 1.f) : 1.f;
+    static const BnReduction<StatsOp> kernels{bn_stats_kernel, bn_stats_part_kernel, bn_stats_final_kernel,
+                                              "bn_stats_kernel", "bn_stats_part_kernel", "bn_stats_final_kernel"};
+    return bn_reduce_launch(who, kernels, op, batch, channels, hw, scratch, det, scratch_bytes, ctdet::as_stream(stream));
 }
 
 extern "C" int ct_bn_train_stats(const float* z, int batch, int ctot, int coff, int channels, int hw,
@@ -1042,23 +641,9 @@ static int bn_backward_impl(const char* who, bool det, size_t scratch_bytes, int
     a.z_ctot = z_ctot; a.z_coff = z_coff;
     a.frozen = frozen;
     hipStream_t st = ctdet::as_stream(stream);
-    const long per_channel = (long)batch * hw;
-    const int slices = bn_slices(batch, channels, hw);
-    if (det && slices > 1)
-        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)slices * 2 * channels * sizeof(double))) return rc;
-    if (scratch && slices > 1) {
-        const int per_slice = (int)((per_channel + slices - 1) / slices);
-        if (!det && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(scratch, 0, (size_t)2 * channels * sizeof(double), st));
-        hipLaunchKernelGGL(bn_bwd_reduce_part_kernel, dim3(channels, slices), dim3(256), 0, st, a, per_slice,
-                           (double*)scratch, (int)det);
-        CT_LAUNCH_CHECK("bn_bwd_reduce_part_kernel");
-        hipLaunchKernelGGL(bn_bwd_reduce_final_kernel, dim3((channels + 255) / 256), dim3(256), 0, st,
-                           (const double*)scratch, det ? slices : 1, channels, dbeta, dgamma);
-        CT_LAUNCH_CHECK("bn_bwd_reduce_final_kernel");
-    } else {
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(channels), dim3(256), 0, st, a);
-        CT_LAUNCH_CHECK("bn_bwd_reduce_kernel");
-    }
+    static const BnReduction<BnBwdArgs> kernels{bn_bwd_reduce_kernel, bn_bwd_reduce_part_kernel, bn_bwd_reduce_final_kernel,
+                                                "bn_bwd_reduce_kernel", "bn_bwd_reduce_part_kernel", "bn_bwd_reduce_final_kernel"};
+    if (int rc = bn_reduce_launch(who, kernels, a, batch, channels, hw, scratch, det, scratch_bytes, st)) return rc;
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for((long)batch * channels * hw)), dim3(256), 0, st, a);
     CT_LAUNCH_CHECK("bn_bwd_apply_kernel");
     return CT_OK;
@@ -1085,7 +670,7 @@ extern "C" int ct_bn_eval_backward(const float* dy, int dy_ctot, int dy_coff, co
                                    int z_ctot, int z_coff, int batch, int channels, int hw,
                                    void* scratch, ct_stream_t stream)
 {
-    return bn_backward_impl("ct_bn_train_backward", false, 0, 1, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, running_mean, running_var, gamma, eps, relu,
+    return bn_backward_impl("ct_bn_eval_backward", false, 0, 1, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, running_mean, running_var, gamma, eps, relu,
                             lo, res_scale, dres, dres_ctot, dres_coff, dres_accumulate, dz, dgamma, dbeta, z_ctot,
                             z_coff, batch, channels, hw, scratch, stream);
 }
@@ -1129,8 +714,21 @@ static BiasSlices bias_slices(int batch, int channels, int hw)
     return {slices, per_slice};
 }
 
-static int dbias_slab_sum(const double* slab, int nslabs, int channels, float* dbias, hipStream_t st)
+// Around the launch of a bias backward kernel: where its per-block dbias sums go.  det: `nslabs` x channels doubles in the checked
+// scratch, added in order after the launch; else float atomics into dbias, zeroed here unless the caller has
+// (ct_scratch_prezeroed).  launch(slab) returns a status.
+template <class Launch>
+static int with_dbias_sink(const char* who, bool det, float* dbias, int nslabs, int channels, void* scratch, size_t scratch_bytes,
+                           hipStream_t st, Launch launch)
 {
+    double* slab = nullptr;
+    if (det && dbias) {
+        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)nslabs * channels * sizeof(double))) return rc;
+        slab = static_cast<double*>(scratch);
+    }
+    if (dbias && !slab && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dbias, 0, (size_t)channels * 4, st));
+    if (int rc = launch(slab)) return rc;
+    if (!slab) return CT_OK;
     hipLaunchKernelGGL(dbias_slab_sum_kernel, dim3((channels + 255) / 256), dim3(256), 0, st, slab, nslabs, channels, dbias);
     CT_LAUNCH_CHECK("dbias_slab_sum_kernel");
     return CT_OK;
@@ -1145,16 +743,12 @@ static int bias_act_backward_impl(const char* who, const float* dy, int dy_ctot,
     CT_REQUIRE(batch > 0 && channels > 0 && hw > 0, "%s: bad shape", who);
     hipStream_t st = ctdet::as_stream(stream);
     const BiasSlices sl = bias_slices(batch, channels, hw);
-    double* slab = nullptr;
-    if (det && dbias) {
-        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)sl.slices * channels * sizeof(double))) return rc;
-        slab = static_cast<double*>(scratch);
-    }
-    if (dbias && !slab && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dbias, 0, (size_t)channels * 4, st));
-    hipLaunchKernelGGL(bias_act_bwd_kernel, dim3(channels, sl.slices), dim3(256), 0, st, dy, dy_ctot, dy_coff, y,
-                       y_ctot, y_coff, relu, batch, channels, hw, dz, dz_ctot, dz_coff, dbias, sl.per_slice, dz_absmax, slab);
-    CT_LAUNCH_CHECK("bias_act_bwd_kernel");
-    return slab ? dbias_slab_sum(slab, sl.slices, channels, dbias, st) : CT_OK;
+    return with_dbias_sink(who, det, dbias, sl.slices, channels, scratch, scratch_bytes, st, [&](double* slab) {
+        hipLaunchKernelGGL(bias_act_bwd_kernel, dim3(channels, sl.slices), dim3(256), 0, st, dy, dy_ctot, dy_coff, y,
+                           y_ctot, y_coff, relu, batch, channels, hw, dz, dz_ctot, dz_coff, dbias, sl.per_slice, dz_absmax, slab);
+        CT_LAUNCH_CHECK("bias_act_bwd_kernel");
+        return (int)CT_OK;
+    });
 }
 
 extern "C" int ct_bias_act_backward_amax(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
@@ -1227,16 +821,12 @@ static int maxpool2x2_bias_relu_bwd_impl(const char* who, const float* y, int y_
     CT_REQUIRE(y_coff >= 0 && y_coff + channels <= y_ctot && dz_coff >= 0 && dz_coff + channels <= dz_ctot, "%s: channel slice", who);
     CT_REQUIRE((long)batch * channels <= 0x7FFFFFFFL, "%s: too many planes", who);
     hipStream_t st = ctdet::as_stream(stream);
-    double* slab = nullptr;
-    if (det && dbias) {
-        if (int rc = det_scratch_check(who, scratch, scratch_bytes, (size_t)batch * channels * sizeof(double))) return rc;
-        slab = static_cast<double*>(scratch);
-    }
-    if (dbias && !slab && !ctdet::scratch_prezeroed()) CT_HIP(hipMemsetAsync(dbias, 0, (size_t)channels * 4, st));
-    hipLaunchKernelGGL(maxpool2x2_bias_relu_bwd_kernel, dim3((unsigned)(batch * channels)), dim3(256), 0, st, y, y_ctot, y_coff, dy,
-                       channels, h, w, oh, ow, dz, dz_ctot, dz_coff, dbias, dz_absmax, slab);
-    CT_LAUNCH_CHECK("maxpool2x2_bias_relu_bwd_kernel");
-    return slab ? dbias_slab_sum(slab, batch, channels, dbias, st) : CT_OK;
+    return with_dbias_sink(who, det, dbias, batch, channels, scratch, scratch_bytes, st, [&](double* slab) {
+        hipLaunchKernelGGL(maxpool2x2_bias_relu_bwd_kernel, dim3((unsigned)(batch * channels)), dim3(256), 0, st, y, y_ctot, y_coff,
+                           dy, channels, h, w, oh, ow, dz, dz_ctot, dz_coff, dbias, dz_absmax, slab);
+        CT_LAUNCH_CHECK("maxpool2x2_bias_relu_bwd_kernel");
+        return (int)CT_OK;
+    });
 }
 
 extern "C" int ct_maxpool2x2_bias_relu_bwd(const float* y, int y_ctot, int y_coff, const float* dy, int batch, int channels, int h,

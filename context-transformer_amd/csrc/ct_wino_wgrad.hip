@@ -9,7 +9,7 @@
 //   dg[k][c] = G^T [ sum_tiles (A e A^T) .* (B^T d B) ] G      e = 2x2 tile of dZ[k], d = 4x4 patch of X[c]
 //
 // i.e. 16 independent [cout] x [cin] x [tiles] GEMMs instead of 9 [cout] x [cin] x [4 x tiles] ones: 2.25x fewer
-// multiplications than the direct weight-gradient GEMM (conv_wgrad_f32 in ct_train.hip).
+// multiplications than the direct weight-gradient GEMM (conv_wgrad_f32 in ct_wgrad.hip).
 //
 // Kernel: workgroup (512 threads, 8 waves) = 64 output channels x 64 input channels x all 16 transform points,
 // walking its share of the tiles in chunks of 8:

@@ -607,9 +607,9 @@ class TrainRuntime:
                 mean_t, var_t = bn.running_mean, bn.running_var
             else:
                 mean_t, var_t = s.mean[i], s.var[i]
-                _lib.check((lib.ct_bn_train_stats_det if self.det else lib.ct_bn_train_stats)(
-                    z.data_ptr(), B, z.shape[1], off, p.cout, hw, mean_t.data_ptr(), var_t.data_ptr(), float(bn.momentum),
-                    bn.running_mean.data_ptr(), bn.running_var.data_ptr(), *self._scratch(s, i), self._s()), st.name + ' bn stats')
+                self._reduce('ct_bn_train_stats', 'ct_bn_train_stats_det',
+                             (z.data_ptr(), B, z.shape[1], off, p.cout, hw, mean_t.data_ptr(), var_t.data_ptr(), float(bn.momentum),
+                              bn.running_mean.data_ptr(), bn.running_var.data_ptr()), s, i, st.name + ' bn stats')
             res = self.bufs[st.res] if st.res is not None else None
             _lib.check(lib.ct_bn_train_apply(
                 z.data_ptr(), mean_t.data_ptr(), var_t.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps),
@@ -625,6 +625,19 @@ class TrainRuntime:
             return (s.scratch[i].data_ptr(),)
         t = s.det_scratch[i]
         return t.data_ptr(), t.numel() * 8
+
+    def _reduce(self, plain, det, args, s, i, what, det_args=()):
+        """Call the reduction entry `plain`, or in deterministic mode its twin `det`, for part i of state s.
+        Both take `args` first and the stream last.  Between them:
+          det entry:               `det_args`, then the slab pointer and its bytes
+          plain BatchNorm entry:   the scratch pointer
+          plain bias entry:        nothing
+        `det_args` is what only the twin takes ahead of the slab (the heads' null dz_absmax)."""
+        if self.det:
+            name, tail = det, det_args + self._scratch(s, i)
+        else:
+            name, tail = plain, self._scratch(s, i) if s.is_bn else ()
+        _lib.check(getattr(self.lib, name)(*args, *tail, self._s()), what)
 
     def policy_record(self):
         """What shaped this runtime's training launches, resolved to what is in force (tools/train_bench.py prints it as `policy`):
@@ -726,10 +739,9 @@ class TrainRuntime:
             pr = self._pool_bwd[st.name]
             sp = self.state[pr.name]
             y = self.bufs[pr.dst]
-            _lib.check((lib.ct_maxpool2x2_bias_relu_bwd_det if self.det else lib.ct_maxpool2x2_bias_relu_bwd)(
-                y.data_ptr(), y.shape[1], pr.dst_coff, self.grads[st.dst].data_ptr(), B, st.ch, st.h, st.w, st.oh, st.ow,
-                sp.dz.data_ptr(), sp.zc, 0, sp.dbias[0].data_ptr(), sp.dz_amax, *(self._scratch(sp, 0) if self.det else ()), self._s()),
-                st.name + ' + ' + pr.name + ' bias bwd')
+            self._reduce('ct_maxpool2x2_bias_relu_bwd', 'ct_maxpool2x2_bias_relu_bwd_det',
+                         (y.data_ptr(), y.shape[1], pr.dst_coff, self.grads[st.dst].data_ptr(), B, st.ch, st.h, st.w, st.oh, st.ow,
+                          sp.dz.data_ptr(), sp.zc, 0, sp.dbias[0].data_ptr(), sp.dz_amax), sp, 0, st.name + ' + ' + pr.name + ' bias bwd')
             sp.dz_from_pool = True
             return
         _lib.check(lib.ct_maxpool2d_bwd(self.bufs[st.src].data_ptr(), self.grads[st.dst].data_ptr(), self.grads[st.src].data_ptr(),
@@ -752,13 +764,10 @@ class TrainRuntime:
                        st.name + ' head gather')
             off = 0
             for i, p in enumerate(st.parts):
-                if self.det:
-                    _lib.check(lib.ct_bias_act_backward_det(s.dz.data_ptr(), ctot, off, None, 0, 0, 0, B, p.cout, hw, s.dz.data_ptr(), ctot,
-                                                            off, s.dbias[i].data_ptr(), None, *self._scratch(s, i), self._s()),
-                               st.name + ' bias bwd')
-                else:
-                    _lib.check(lib.ct_bias_act_backward(s.dz.data_ptr(), ctot, off, None, 0, 0, 0, B, p.cout, hw, s.dz.data_ptr(), ctot,
-                                                        off, s.dbias[i].data_ptr(), self._s()), st.name + ' bias bwd')
+                # no maxima wanted: the plain entry is the one without dz_absmax, the twin takes a null one
+                self._reduce('ct_bias_act_backward', 'ct_bias_act_backward_det',
+                             (s.dz.data_ptr(), ctot, off, None, 0, 0, 0, B, p.cout, hw, s.dz.data_ptr(), ctot, off, s.dbias[i].data_ptr()),
+                             s, i, st.name + ' bias bwd', det_args=(None,))
                 put(p.bias, s.dbias[i])
                 off += p.cout
             return
@@ -776,21 +785,21 @@ class TrainRuntime:
                 frozen = s.frozen[i]
                 mean_t, var_t = (p.bn.running_mean, p.bn.running_var) if frozen else (s.mean[i], s.var[i])
                 fn = 'ct_bn_eval_backward' if frozen else 'ct_bn_train_backward'
-                _lib.check(getattr(lib, fn + '_det' if self.det else fn)(
-                    gy.data_ptr(), gy.shape[1], st.dst_coff + off, y.data_ptr(), y.shape[1], st.dst_coff + off, z.data_ptr(),
-                    mean_t.data_ptr(), var_t.data_ptr(), p.bn.weight.data_ptr(), float(p.bn.eps), int(p.relu), None,
-                    float(st.res_scale), dres, dres_ctot, st.res_coff, dres_acc, s.dz.data_ptr(), s.dgamma[i].data_ptr(),
-                    s.dbeta[i].data_ptr(), ctot, off, B, p.cout, hw, *self._scratch(s, i), self._s()), st.name + ' bn bwd')
+                self._reduce(fn, fn + '_det',
+                             (gy.data_ptr(), gy.shape[1], st.dst_coff + off, y.data_ptr(), y.shape[1], st.dst_coff + off, z.data_ptr(),
+                              mean_t.data_ptr(), var_t.data_ptr(), p.bn.weight.data_ptr(), float(p.bn.eps), int(p.relu), None,
+                              float(st.res_scale), dres, dres_ctot, st.res_coff, dres_acc, s.dz.data_ptr(), s.dgamma[i].data_ptr(),
+                              s.dbeta[i].data_ptr(), ctot, off, B, p.cout, hw), s, i, st.name + ' bn bwd')
                 put(p.bn.weight, s.dgamma[i])
                 put(p.bn.bias, s.dbeta[i])
             else:
                 if s.dz_from_pool:
                     s.dz_from_pool = False          # dZ and dbias came from the pool's fused backward (_pool_backward)
                 else:
-                    _lib.check((lib.ct_bias_act_backward_det if self.det else lib.ct_bias_act_backward_amax)(
-                        gy.data_ptr(), gy.shape[1], st.dst_coff + off, y.data_ptr(), y.shape[1], st.dst_coff + off, int(p.relu), B,
-                        p.cout, hw, s.dz.data_ptr(), ctot, off, s.dbias[i].data_ptr() if p.bias is not None else None, s.dz_amax,
-                        *(self._scratch(s, i) if self.det else ()), self._s()), st.name + ' bias bwd')
+                    self._reduce('ct_bias_act_backward_amax', 'ct_bias_act_backward_det',
+                                 (gy.data_ptr(), gy.shape[1], st.dst_coff + off, y.data_ptr(), y.shape[1], st.dst_coff + off, int(p.relu), B,
+                                  p.cout, hw, s.dz.data_ptr(), ctot, off, s.dbias[i].data_ptr() if p.bias is not None else None, s.dz_amax),
+                                 s, i, st.name + ' bias bwd')
                 if p.bias is not None:
                     put(p.bias, s.dbias[i])
             off += p.cout

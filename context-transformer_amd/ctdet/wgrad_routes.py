@@ -1,7 +1,7 @@
 """The weight-gradient routes of the training engine: one record per entry point, the rule that picks one for a layer, and the
 launch (the forward and data-gradient launches have ctdet/wino_forms.py).
 
-  direct   ct_conv2d_wgrad: the fp32 MFMA GEMM with atomics, every filter size (csrc/ct_train.hip)
+  direct   ct_conv2d_wgrad: the fp32 MFMA GEMM with atomics, every filter size (csrc/ct_wgrad.hip)
   wino2    Winograd F(3x3, 2x2) fused on the fp32 MFMA (csrc/ct_wino_wgrad.hip)
   wino4    Winograd F(3x3, 4x4) fused on the fp32 MFMA (csrc/ct_wino4_wgrad.hip)
   wino4s   F(3x3, 4x4) as transform kernels + the bf16x3 GEMM, also the dilated 3x3 layers (csrc/ct_wino4s.hip)

@@ -91,7 +91,7 @@ class Case:
 
     @property
     def tapmajor(self):
-        """wgrad_impl's choice at the default 64x64 tile (csrc/ct_train.hip)."""
+        """wgrad_impl's choice at the default 64x64 tile (csrc/ct_wgrad.hip)."""
         return self.cin % 64 == 0
 
     @property

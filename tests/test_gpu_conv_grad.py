@@ -1,6 +1,6 @@
 """The two direct gradient kernels of training, path by path, against float64 autograd (tests/conv_grad_cases.py):
 
-  * ct_conv2d_wgrad (csrc/ct_train.hip, conv_wgrad_f32): every row once on the tap-major, software-pipelined kernel
+  * ct_conv2d_wgrad (csrc/ct_wgrad.hip, conv_wgrad_f32): every row once on the tap-major, software-pipelined kernel
     (cin % 64 == 0) and once on the generic one, dw NaN on entry, rel_err (max|a-b| / max|b|) below WGRAD_TOL = 1e-5 -- the bound
     test_gpu_train.py::test_direct_wgrad_above_2gib already holds this kernel to; the tap-major rows again with
     CTDET_WGRAD_GENERIC=1 (read per call), which must agree with the tap-major result to the same bound; the accumulate contract

@@ -294,6 +294,30 @@ def test_reduction_entries_refuse_a_short_or_missing_scratch():
     assert pool(oh=40) == CT_ERR_INVALID and lib.ct_last_error_string().decode().startswith('ct_maxpool2x2_bias_relu_bwd_det:')
 
 
+def test_plain_reduction_entries_report_under_their_own_name():
+    """One refused call per plain entry (a null required pointer, refused before any device work): the message names the entry
+    that was called.  The one exception: ct_bias_act_backward_amax reports as ct_bias_act_backward, the entry it extends."""
+    lib = _lib.lib()
+    B, Cc, HW, p = 8, 64, 5625, 0x10000
+
+    def bwd(fn):
+        return fn(None, Cc, 0, p, Cc, 0, p, p, p, p, 1e-5, 1, None, 1.0, None, 0, 0, 0, p, p, p, Cc, 0, B, Cc, HW, p, None)
+
+    calls = (('ct_bn_train_stats', 'ct_bn_train_stats', lambda: lib.ct_bn_train_stats(None, B, Cc, 0, Cc, HW, p, p, 0.01, None, None, p, None)),
+             ('ct_bn_train_backward', 'ct_bn_train_backward', lambda: bwd(lib.ct_bn_train_backward)),
+             ('ct_bn_eval_backward', 'ct_bn_eval_backward', lambda: bwd(lib.ct_bn_eval_backward)),
+             ('ct_bias_act_backward', 'ct_bias_act_backward',
+              lambda: lib.ct_bias_act_backward(None, Cc, 0, p, Cc, 0, 1, B, Cc, HW, p, Cc, 0, p, None)),
+             ('ct_bias_act_backward_amax', 'ct_bias_act_backward',
+              lambda: lib.ct_bias_act_backward_amax(None, Cc, 0, p, Cc, 0, 1, B, Cc, HW, p, Cc, 0, p, None, None)),
+             ('ct_maxpool2x2_bias_relu_bwd', 'ct_maxpool2x2_bias_relu_bwd',
+              lambda: lib.ct_maxpool2x2_bias_relu_bwd(None, Cc, 0, p, B, Cc, 64, 64, 32, 32, p, Cc, 0, p, None, None)))
+    for entry, name, call in calls:
+        assert call() == CT_ERR_INVALID, entry
+        msg = lib.ct_last_error_string().decode()
+        assert msg.split(':')[0] == name, (entry, msg)
+
+
 # ------------------------------------------------------------------ dispatch: the routes
 TWIN = {WD.DIRECT: 'ct_conv2d_wgrad_det', WD.WINO2: 'ct_conv2d_wgrad_wino_det', WD.WINO4: 'ct_conv2d_wgrad_wino4_det'}
 
