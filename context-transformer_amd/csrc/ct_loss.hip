@@ -6,6 +6,9 @@
 // its batch mates.  Compiled with -ffp-contract=off.
 // The localisation term is smooth-L1 on the encoded offsets or, in the IOU instantiations of the two per-prior kernels
 // (ct_multibox_loss_fwd_loc / _bwd_loc), one of the IoU-family terms of ct_iou_loss.h on the decoded boxes.
+// The classification terms are those cross-entropies over the mined sample or, with CT_CONF_FOCAL (ct_multibox_loss_fwd_terms
+// / _bwd_terms), focal terms over every prior that is not ignored: focal_prior_kernel, loss_image_sum_kernel (no keys, no radix
+// passes) and focal_bwd_kernel, which never read the conf row of a background prior.
 #include "ct_common.h"
 #include "ct_iou_loss.h"
 
@@ -75,6 +78,142 @@ struct LocArgs {
     float var0, var1;
 };
 
+// The row pieces of loss_prior_kernel / loss_bwd_kernel below as functions, for the focal kernels.  The two cross-entropy
+// kernels keep their own text: a call in place of it moved their instruction schedule, and their code is held to the bits
+// and the time they had before the focal form came.
+// The localisation term of one row: the smooth-L1 sum of every row or, with IOU, the IoU-family term of a positive row of
+// non-zero weight and 0 of any other row, whose loc, loc_t and prior are then not read (la.kind is uniform over the launch).
+template <bool IOU>
+__device__ inline float loc_row_forward(const float4* __restrict__ loc, const float4* __restrict__ loc_t, long long r,
+                                        float2 ct, const LocArgs& la)
+{
+    float l1 = 0.f;
+    if (!IOU) {
+        const float4 a = loc[r], b = loc_t[r];
+        l1 = (smooth_l1(a.x - b.x) + smooth_l1(a.y - b.y)) + (smooth_l1(a.z - b.z) + smooth_l1(a.w - b.w));
+    } else if (ct.x > 0.f && ct.y != 0.f) {
+        l1 = ctdet::iou_row_forward(loc[r], loc_t[r], la.priors[r % la.num_priors], la.var0, la.var1, la.kind).loss;
+    }
+    return l1;
+}
+
+// ... and its gradient times g0 * weight: zeros for a row that is not positive or has weight 0, which is not read
+template <bool IOU>
+__device__ inline float4 loc_row_backward(const float4* __restrict__ loc, const float4* __restrict__ loc_t, long long row,
+                                          float2 ct, float g0, const LocArgs& la)
+{
+    float4 dl = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ct.x > 0.f && ct.y != 0.f) {
+        const float4 a = loc[row], b = loc_t[row];
+        const float gl = g0 * ct.y;
+        if (!IOU) {
+            dl.x = gl * fminf(fmaxf(a.x - b.x, -1.f), 1.f);
+            dl.y = gl * fminf(fmaxf(a.y - b.y, -1.f), 1.f);
+            dl.z = gl * fminf(fmaxf(a.z - b.z, -1.f), 1.f);
+            dl.w = gl * fminf(fmaxf(a.w - b.w, -1.f), 1.f);
+        } else {
+            const float4 p = la.priors[row % la.num_priors];
+            const ctdet::IouRow ir = ctdet::iou_row_forward(a, b, p, la.var0, la.var1, la.kind);
+            ctdet::iou_row_backward(ir, p, la.var0, la.var1, la.kind, gl, dl.x, dl.y, dl.z, dl.w);
+        }
+    }
+    return dl;
+}
+
+// drow = gw * (softmax(crow) - onehot(col)) from the row's max m and exp-sum s, each lane its own items; or zeros
+template <int G, bool VEC>
+__device__ inline void write_dconf_row(const float* crow, float* drow, int sub, int items, float4 v0, float m, float s,
+                                       int col, float gw)
+{
+    for (int i = sub; i < items; i += G) {
+        const float4 v = i == sub ? v0 : load_item<VEC>(crow, i, items);
+        const int c0 = VEC ? 4 * i : i;
+        const float dx = gw * (expf(v.x - m) / s - (c0 == col ? 1.f : 0.f));
+        if (VEC) {
+            const float dy = gw * (expf(v.y - m) / s - (c0 + 1 == col ? 1.f : 0.f));
+            const float dz = gw * (expf(v.z - m) / s - (c0 + 2 == col ? 1.f : 0.f));
+            const float dw = gw * (expf(v.w - m) / s - (c0 + 3 == col ? 1.f : 0.f));
+            reinterpret_cast<float4*>(drow)[i] = make_float4(dx, dy, dz, dw);
+        } else {
+            drow[i] = dx;
+        }
+    }
+}
+
+template <int G, bool VEC>
+__device__ inline void zero_dconf_row(float* drow, int sub, int items)
+{
+    for (int i = sub; i < items; i += G) {
+        if (VEC) reinterpret_cast<float4*>(drow)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        else drow[i] = 0.f;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- focal terms
+// CT_CONF_FOCAL (include/ctdet.h, ct_multibox_loss_fwd_terms).  For a target of probability p, with m the SUM OF THE OTHER
+// probabilities and ce = -log p taken from the logits: FL = a m^gamma ce, dFL/dz_j = c (p_j - [j = t]) with
+// c = a m^gamma (1 - gamma p r), r = log p / m (-1 at m = 0).
+struct FocalArgs {
+    float gamma;
+    float a_fg, a_bg;       // alpha and 1 - alpha; both 1 when alpha < 0
+};
+
+// m^gamma with 0^0 = 1; gamma is uniform over the launch, and the usual 2 needs no powf
+__device__ inline float focal_weight(float m, float gamma)
+{
+    return gamma == 0.f ? 1.f : gamma == 2.f ? m * m : powf(m, gamma);
+}
+
+__device__ inline float focal_grad_factor(float a, float gamma, float p, float m, float ce)
+{
+    const float r = m == 0.f ? -1.f : -ce / m;
+    return a * focal_weight(m, gamma) * (1.f - gamma * p * r);
+}
+
+// softmax and both cross-entropies of one objectness row, in the arithmetic of loss_prior_kernel / loss_bwd_kernel
+struct ObjRow { float s0, s1, ce0, ce1; };
+__device__ inline ObjRow obj_row(float2 o)
+{
+    const float om = fmaxf(o.x, o.y);
+    const float e0 = expf(o.x - om), e1 = expf(o.y - om);
+    const float olse = logf(e0 + e1);
+    return {e0 / (e0 + e1), e1 / (e0 + e1), olse - (o.x - om), olse - (o.y - om)};
+}
+
+__device__ inline float sumexp4_except(float4 v, float m, int c0, int col)
+{
+    return ((c0 == col ? 0.f : expf(v.x - m)) + (c0 + 1 == col ? 0.f : expf(v.y - m))) +
+           ((c0 + 2 == col ? 0.f : expf(v.z - m)) + (c0 + 3 == col ? 0.f : expf(v.w - m)));
+}
+
+// sum(exp(x - m)) over one conf row WITHOUT column col, spread over the group like row_max_sumexp
+template <int G, bool VEC>
+__device__ inline float row_sumexp_except(const float* row, int sub, int items, float4 v0, float m, int col)
+{
+    float s = 0.f;
+    for (int i = sub; i < items; i += G)
+        s += sumexp4_except(i == sub ? v0 : load_item<VEC>(row, i, items), m, VEC ? 4 * i : i, col);
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    return s;
+}
+
+// What a foreground row (target column col of conf) hands to the class term: ce = -log p_t on the fused logits,
+// p = s_1 q_t and m = s_0 + s_1 * (sum of the other q), every lane of the group with the same values.
+struct FgRow { float mx, s, ce, p, m; };
+template <int G, bool VEC>
+__device__ inline FgRow fg_row(const float* crow, int sub, int items, float4 v0, int col, const ObjRow& o)
+{
+    FgRow f;
+    row_max_sumexp<G, VEC>(crow, sub, items, v0, f.mx, f.s);
+    const float others = row_sumexp_except<G, VEC>(crow, sub, items, v0, f.mx, col);
+    const float zt = crow[col];
+    f.ce = ((f.mx + logf(f.s)) - zt) + o.ce1;
+    f.p = o.s1 * (expf(zt - f.mx) / f.s);
+    f.m = o.s0 + o.s1 * (others / f.s);
+    return f;
+}
+
 // ---------------------------------------------------------------------------------------------------- per prior
 // ws[row] = (localisation term, objectness CE, mining key, class CE).  The localisation term is the smooth-L1 sum of
 // every row or, with IOU, the IoU-family term of a positive row of non-zero weight and 0 of any other row, whose loc,
@@ -117,6 +256,41 @@ __global__ __launch_bounds__(ROW_THREADS) void loss_prior_kernel(
     float ce_cls = ce0;
     if (t > 0) ce_cls = ((m + logf(s)) - crow[t - 1]) + ce1;
     ws[r] = make_float4(l1, ce_obj, key, ce_cls);
+}
+
+// The focal form: ws[row] = (localisation term, objectness FL, 0, class FL).  The row weight is known before any logit
+// is loaded (w = weight for label >= 0, 0 for an ignored row; nothing is mined), so a row of weight 0 reads neither obj
+// nor conf, and conf is read by the groups of foreground rows alone: a background target has p = s_0, m = s_1.
+template <int G, bool VEC, bool IOU>
+__global__ __launch_bounds__(ROW_THREADS) void focal_prior_kernel(
+    const float4* __restrict__ loc, const float* __restrict__ conf, const float2* __restrict__ obj,
+    const float4* __restrict__ loc_t, const float2* __restrict__ conf_t, const uint8_t* __restrict__ obj_t,
+    long long rows, int nfg, float4* __restrict__ ws, LocArgs la, FocalArgs fa)
+{
+    const int sub = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
+    if (row >= rows) return;                            // whole groups leave together; shuffles stay inside a group
+    const float2 ct = conf_t[row];
+    const float wr = ct.x >= 0.f ? ct.y : 0.f;
+    const int t = class_target(ct.x, nfg);
+    ObjRow o = {0.f, 0.f, 0.f, 0.f};
+    FgRow f = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (wr != 0.f) o = obj_row(obj[row]);
+    if (wr != 0.f && t > 0) {
+        const float* crow = conf + row * nfg;
+        const int items = VEC ? nfg / 4 : nfg;
+        f = fg_row<G, VEC>(crow, sub, items, load_item<VEC>(crow, sub, items), t - 1, o);
+    }
+    if (sub != 0) return;
+
+    const float l1 = loc_row_forward<IOU>(loc, loc_t, row, ct, la);
+    float fl_obj = 0.f, fl_cls = 0.f;
+    if (wr != 0.f) {
+        fl_obj = fl_cls = fa.a_bg * focal_weight(o.s1, fa.gamma) * o.ce0;         // target 0 of either term: nearly every row
+        if (obj_t[row] != 0) fl_obj = fa.a_fg * focal_weight(o.s0, fa.gamma) * o.ce1;
+        if (t > 0) fl_cls = fa.a_fg * focal_weight(f.m, fa.gamma) * f.ce;
+    }
+    ws[row] = make_float4(l1, fl_obj, 0.f, fl_cls);
 }
 
 // ---------------------------------------------------------------------------------------------------- selection
@@ -266,6 +440,42 @@ __global__ __launch_bounds__(SEL_THREADS) void loss_select_kernel(
     }
 }
 
+// The per-image pass of the focal form: nothing is selected, so there are no keys in LDS and no radix passes.  num_pos, the
+// three sums and their block_sum order are loss_select_kernel's; w = weight for label >= 0 and 0 for an ignored row.
+__global__ __launch_bounds__(SEL_THREADS) void loss_image_sum_kernel(
+    const float4* __restrict__ ws, const float2* __restrict__ conf_t, int P, float* __restrict__ w_out,
+    long long* __restrict__ num_pos_out, double* __restrict__ partial)
+{
+    __shared__ double red[SEL_WAVES];
+    const int tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * P;
+    ws += base; conf_t += base; w_out += base;
+
+    double acc = 0.0, sl = 0.0, sc = 0.0, so = 0.0;
+    for (int i = tid; i < P; i += SEL_THREADS) {
+        const float2 ct = conf_t[i];
+        const bool pos = ct.x > 0.f;
+        const float w = ct.x >= 0.f ? ct.y : 0.f;
+        if (pos) acc += (double)ct.y;
+        w_out[i] = w;
+        if (pos || w != 0.f) {
+            const float4 v = ws[i];
+            if (pos) sl += (double)(v.x * ct.y);
+            if (w != 0.f) { so += (double)(v.y * w); sc += (double)(v.w * w); }
+        }
+    }
+    const float possum = (float)block_sum(acc, red);    // long(sum of weight * pos), as loss_select_kernel rounds it
+    sl = block_sum(sl, red);
+    sc = block_sum(sc, red);
+    so = block_sum(so, red);
+    if (tid == 0) {
+        partial[blockIdx.x * 3 + 0] = sl;
+        partial[blockIdx.x * 3 + 1] = sc;
+        partial[blockIdx.x * 3 + 2] = so;
+        num_pos_out[blockIdx.x] = (long long)possum;
+    }
+}
+
 // sums = (sum loc, sum cls, sum obj) over the images in index order, n = sum of num_pos
 __global__ void loss_finish_kernel(const double* __restrict__ partial, const long long* __restrict__ num_pos, int batch,
                                    float* __restrict__ sums, long long* __restrict__ n)
@@ -360,6 +570,57 @@ __global__ __launch_bounds__(ROW_THREADS) void loss_bwd_kernel(
     dobj[row] = dob;
 }
 
+// The focal form: the same shape, each term times its factor c.  The class factor scales dconf, so every lane of a row
+// of non-zero weight evaluates the objectness row; a background row (t = 0) writes zeros to dconf and does not read conf.
+template <int G, bool VEC, bool IOU>
+__global__ __launch_bounds__(ROW_THREADS) void focal_bwd_kernel(
+    const float4* __restrict__ loc, const float* __restrict__ conf, const float2* __restrict__ obj,
+    const float4* __restrict__ loc_t, const float2* __restrict__ conf_t, const uint8_t* __restrict__ obj_t,
+    const float* __restrict__ w, const float* __restrict__ g, long long rows, int nfg,
+    float4* __restrict__ dloc, float* __restrict__ dconf, float2* __restrict__ dobj, LocArgs la, FocalArgs fa)
+{
+    const int sub = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
+    if (row >= rows) return;                            // whole groups leave together; shuffles stay inside a group
+    const float wr = w[row];
+    const float2 ct = conf_t[row];
+    const int t = class_target(ct.x, nfg);
+    const float g0 = g[0], g1 = g[1], g2 = g[2];
+    const float* crow = conf + row * nfg;
+    float* drow = dconf + row * nfg;
+    const int items = VEC ? nfg / 4 : nfg;
+
+    ObjRow o = {0.f, 0.f, 0.f, 0.f};
+    float c_bg = 0.f;                                   // the factor of a background target, of either term: nearly every row
+    if (wr != 0.f) {
+        o = obj_row(obj[row]);
+        c_bg = focal_grad_factor(fa.a_bg, fa.gamma, o.s0, o.s1, o.ce0);
+    }
+    float c_cls = c_bg;
+    if (wr != 0.f && t > 0) {
+        const float4 v0 = load_item<VEC>(crow, sub, items);
+        const FgRow f = fg_row<G, VEC>(crow, sub, items, v0, t - 1, o);
+        c_cls = focal_grad_factor(fa.a_fg, fa.gamma, f.p, f.m, f.ce);
+        write_dconf_row<G, VEC>(crow, drow, sub, items, v0, f.mx, f.s, t - 1, (g1 * wr) * c_cls);
+    } else {
+        zero_dconf_row<G, VEC>(drow, sub, items);
+    }
+    if (sub != 0) return;
+
+    dloc[row] = loc_row_backward<IOU>(loc, loc_t, row, ct, g0, la);
+
+    float2 dob = make_float2(0.f, 0.f);
+    if (wr != 0.f) {
+        const bool ot = obj_t[row] != 0;
+        float c_obj = c_bg;
+        if (ot) c_obj = focal_grad_factor(fa.a_fg, fa.gamma, o.s1, o.s0, o.ce1);
+        const float go = (g2 * wr) * c_obj, gc = (g1 * wr) * c_cls;
+        dob.x = go * (o.s0 - (ot ? 0.f : 1.f)) + gc * (o.s0 - (t == 0 ? 1.f : 0.f));
+        dob.y = go * (o.s1 - (ot ? 1.f : 0.f)) + gc * (o.s1 - (t == 0 ? 0.f : 1.f));
+    }
+    dobj[row] = dob;
+}
+
 size_t ws_rows_bytes(int batch, int num_priors) { return ctdet::align_up((size_t)batch * num_priors * sizeof(float4), 256); }
 
 // lanes per conf row: the smallest supported group that holds the row in one item per lane (64 = a whole wave, looping)
@@ -411,11 +672,35 @@ int check_loc_args(const char* fn, const float* priors, int loc_loss, float var0
     return CT_OK;
 }
 
-// the shared launcher of ct_multibox_loss_fwd and _fwd_loc: the same three launches whatever la.kind
+// the classification terms of a call: CT_CONF_CE, or CT_CONF_FOCAL with its constants
+struct ConfArgs {
+    int kind;
+    FocalArgs focal;
+};
+
+// the checks of the _terms entries, before any HIP call -> la, ca
+int check_terms(const char* fn, const ct_loss_terms* terms, LocArgs& la, ConfArgs& ca)
+{
+    CT_REQUIRE(terms != nullptr, "%s: terms is a null pointer", fn);
+    if (const int rc = check_loc_args(fn, terms->priors, terms->loc_loss, terms->var0, terms->var1)) return rc;
+    CT_REQUIRE(terms->conf_loss == CT_CONF_CE || terms->conf_loss == CT_CONF_FOCAL, "%s: conf_loss=%d (0 ce, 1 focal)", fn,
+               terms->conf_loss);
+    const float gamma = terms->focal_gamma, alpha = terms->focal_alpha;
+    if (terms->conf_loss == CT_CONF_FOCAL) {
+        CT_REQUIRE(std::isfinite(gamma) && gamma >= 0.f, "%s: focal_gamma=%g must be finite and >= 0", fn, (double)gamma);
+        CT_REQUIRE(alpha <= 1.f, "%s: focal_alpha=%g must be in [0, 1], or negative for none", fn, (double)alpha);   // no NaN
+    }
+    la = {terms->loc_loss == CT_LOC_SMOOTH_L1 ? nullptr : (const float4*)terms->priors, 0, terms->loc_loss, terms->var0,
+          terms->var1};
+    ca = {terms->conf_loss, {gamma, alpha < 0.f ? 1.f : alpha, alpha < 0.f ? 1.f : 1.f - alpha}};
+    return CT_OK;
+}
+
+// the shared launcher of the forward entries: three launches whatever la.kind and ca.kind
 int loss_fwd(const char* fn, const float* loc, const float* conf, const float* obj, const float* loc_t,
              const float* conf_t, const uint8_t* obj_t, int batch, int num_priors, int num_classes, int negpos_ratio,
              float* sums, long long* num_pos, long long* n, float* w, void* ws, size_t ws_bytes, ct_stream_t stream,
-             LocArgs la)
+             LocArgs la, const ConfArgs& ca)
 {
     CT_REQUIRE(loc && conf && obj && loc_t && conf_t && obj_t && sums && num_pos && n && w && ws, "%s: null pointer", fn);
     CT_REQUIRE(batch > 0 && num_priors > 0, "%s: batch=%d num_priors=%d", fn, batch, num_priors);
@@ -431,29 +716,41 @@ int loss_fwd(const char* fn, const float* loc, const float* conf, const float* o
     la.num_priors = num_priors;
 
     const bool vec = nfg % 4 == 0 && (reinterpret_cast<uintptr_t>(conf) & 15) == 0;
-    if (la.kind == CT_LOC_SMOOTH_L1)
-        CT_LOSS_DISPATCH(loss_prior_kernel, false, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
-                         (const float2*)conf_t, obj_t, rows, nfg, rows_ws, la);
-    else
-        CT_LOSS_DISPATCH(loss_prior_kernel, true, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
-                         (const float2*)conf_t, obj_t, rows, nfg, rows_ws, la);
-
-    if (num_priors <= LDS_MAX_KEYS) {
-        const size_t lds = (size_t)num_priors * sizeof(unsigned);
-        static std::once_flag once;
-        static hipError_t attr = hipSuccess;
-        std::call_once(once, [] {
-            attr = hipFuncSetAttribute((const void*)loss_select_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       LDS_MAX_KEYS * (int)sizeof(unsigned));
-        });
-        CT_HIP(attr);
-        hipLaunchKernelGGL(loss_select_kernel<true>, dim3(batch), dim3(SEL_THREADS), lds, st, (const float4*)rows_ws,
-                           (const float2*)conf_t, num_priors, negpos_ratio, w, num_pos, partial);
+    if (ca.kind == CT_CONF_FOCAL) {
+        if (la.kind == CT_LOC_SMOOTH_L1)
+            CT_LOSS_DISPATCH(focal_prior_kernel, false, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                             (const float2*)conf_t, obj_t, rows, nfg, rows_ws, la, ca.focal);
+        else
+            CT_LOSS_DISPATCH(focal_prior_kernel, true, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                             (const float2*)conf_t, obj_t, rows, nfg, rows_ws, la, ca.focal);
+        hipLaunchKernelGGL(loss_image_sum_kernel, dim3(batch), dim3(SEL_THREADS), 0, st, (const float4*)rows_ws,
+                           (const float2*)conf_t, num_priors, w, num_pos, partial);
+        CT_LAUNCH_CHECK("loss_image_sum_kernel");
     } else {
-        hipLaunchKernelGGL(loss_select_kernel<false>, dim3(batch), dim3(SEL_THREADS), 0, st, (const float4*)rows_ws,
-                           (const float2*)conf_t, num_priors, negpos_ratio, w, num_pos, partial);
+        if (la.kind == CT_LOC_SMOOTH_L1)
+            CT_LOSS_DISPATCH(loss_prior_kernel, false, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                             (const float2*)conf_t, obj_t, rows, nfg, rows_ws, la);
+        else
+            CT_LOSS_DISPATCH(loss_prior_kernel, true, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                             (const float2*)conf_t, obj_t, rows, nfg, rows_ws, la);
+
+        if (num_priors <= LDS_MAX_KEYS) {
+            const size_t lds = (size_t)num_priors * sizeof(unsigned);
+            static std::once_flag once;
+            static hipError_t attr = hipSuccess;
+            std::call_once(once, [] {
+                attr = hipFuncSetAttribute((const void*)loss_select_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           LDS_MAX_KEYS * (int)sizeof(unsigned));
+            });
+            CT_HIP(attr);
+            hipLaunchKernelGGL(loss_select_kernel<true>, dim3(batch), dim3(SEL_THREADS), lds, st, (const float4*)rows_ws,
+                               (const float2*)conf_t, num_priors, negpos_ratio, w, num_pos, partial);
+        } else {
+            hipLaunchKernelGGL(loss_select_kernel<false>, dim3(batch), dim3(SEL_THREADS), 0, st, (const float4*)rows_ws,
+                               (const float2*)conf_t, num_priors, negpos_ratio, w, num_pos, partial);
+        }
+        CT_LAUNCH_CHECK("loss_select_kernel");
     }
-    CT_LAUNCH_CHECK("loss_select_kernel");
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(64), 0, st, (const double*)partial, (const long long*)num_pos,
                        batch, sums, n);
     CT_LAUNCH_CHECK("loss_finish_kernel");
@@ -462,7 +759,7 @@ int loss_fwd(const char* fn, const float* loc, const float* conf, const float* o
 
 int loss_bwd(const char* fn, const float* loc, const float* conf, const float* obj, const float* loc_t,
              const float* conf_t, const uint8_t* obj_t, const float* w, const float* g, int batch, int num_priors,
-             int num_classes, float* dloc, float* dconf, float* dobj, ct_stream_t stream, LocArgs la)
+             int num_classes, float* dloc, float* dconf, float* dobj, ct_stream_t stream, LocArgs la, const ConfArgs& ca)
 {
     CT_REQUIRE(loc && conf && obj && loc_t && conf_t && obj_t && w && g && dloc && dconf && dobj, "%s: null pointer", fn);
     CT_REQUIRE(batch > 0 && num_priors > 0, "%s: batch=%d num_priors=%d", fn, batch, num_priors);
@@ -472,16 +769,25 @@ int loss_bwd(const char* fn, const float* loc, const float* conf, const float* o
     const int nfg = num_classes - 1;
     la.num_priors = num_priors;
     const bool vec = nfg % 4 == 0 && ((reinterpret_cast<uintptr_t>(conf) | reinterpret_cast<uintptr_t>(dconf)) & 15) == 0;
-    if (la.kind == CT_LOC_SMOOTH_L1)
+    if (ca.kind == CT_CONF_FOCAL) {
+        if (la.kind == CT_LOC_SMOOTH_L1)
+            CT_LOSS_DISPATCH(focal_bwd_kernel, false, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                             (const float2*)conf_t, obj_t, w, g, rows, nfg, (float4*)dloc, dconf, (float2*)dobj, la, ca.focal);
+        else
+            CT_LOSS_DISPATCH(focal_bwd_kernel, true, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
+                             (const float2*)conf_t, obj_t, w, g, rows, nfg, (float4*)dloc, dconf, (float2*)dobj, la, ca.focal);
+    } else if (la.kind == CT_LOC_SMOOTH_L1) {
         CT_LOSS_DISPATCH(loss_bwd_kernel, false, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
                          (const float2*)conf_t, obj_t, w, g, rows, nfg, (float4*)dloc, dconf, (float2*)dobj, la);
-    else
+    } else {
         CT_LOSS_DISPATCH(loss_bwd_kernel, true, (const float4*)loc, conf, (const float2*)obj, (const float4*)loc_t,
                          (const float2*)conf_t, obj_t, w, g, rows, nfg, (float4*)dloc, dconf, (float2*)dobj, la);
+    }
     return CT_OK;
 }
 
 const LocArgs SMOOTH_L1_ARGS = {nullptr, 0, CT_LOC_SMOOTH_L1, 0.f, 0.f};
+const ConfArgs CE_ARGS = {CT_CONF_CE, {0.f, 1.f, 1.f}};
 
 }  // namespace
 
@@ -491,7 +797,7 @@ extern "C" int ct_multibox_loss_fwd(const float* loc, const float* conf, const f
                                     float* w, void* ws, size_t ws_bytes, ct_stream_t stream)
 {
     return loss_fwd("ct_multibox_loss_fwd", loc, conf, obj, loc_t, conf_t, obj_t, batch, num_priors, num_classes,
-                    negpos_ratio, sums, num_pos, n, w, ws, ws_bytes, stream, SMOOTH_L1_ARGS);
+                    negpos_ratio, sums, num_pos, n, w, ws, ws_bytes, stream, SMOOTH_L1_ARGS, CE_ARGS);
 }
 
 extern "C" int ct_multibox_loss_bwd(const float* loc, const float* conf, const float* obj, const float* loc_t,
@@ -500,7 +806,7 @@ extern "C" int ct_multibox_loss_bwd(const float* loc, const float* conf, const f
                                     float* dobj, ct_stream_t stream)
 {
     return loss_bwd("ct_multibox_loss_bwd", loc, conf, obj, loc_t, conf_t, obj_t, w, g, batch, num_priors, num_classes,
-                    dloc, dconf, dobj, stream, SMOOTH_L1_ARGS);
+                    dloc, dconf, dobj, stream, SMOOTH_L1_ARGS, CE_ARGS);
 }
 
 extern "C" int ct_multibox_loss_fwd_loc(const float* loc, const float* conf, const float* obj, const float* loc_t,
@@ -512,7 +818,7 @@ extern "C" int ct_multibox_loss_fwd_loc(const float* loc, const float* conf, con
     if (const int rc = check_loc_args("ct_multibox_loss_fwd_loc", priors, loc_loss, var0, var1)) return rc;
     const LocArgs la = {loc_loss == CT_LOC_SMOOTH_L1 ? nullptr : (const float4*)priors, 0, loc_loss, var0, var1};
     return loss_fwd("ct_multibox_loss_fwd_loc", loc, conf, obj, loc_t, conf_t, obj_t, batch, num_priors, num_classes,
-                    negpos_ratio, sums, num_pos, n, w, ws, ws_bytes, stream, la);
+                    negpos_ratio, sums, num_pos, n, w, ws, ws_bytes, stream, la, CE_ARGS);
 }
 
 extern "C" int ct_multibox_loss_bwd_loc(const float* loc, const float* conf, const float* obj, const float* loc_t,
@@ -524,6 +830,30 @@ extern "C" int ct_multibox_loss_bwd_loc(const float* loc, const float* conf, con
     if (const int rc = check_loc_args("ct_multibox_loss_bwd_loc", priors, loc_loss, var0, var1)) return rc;
     const LocArgs la = {loc_loss == CT_LOC_SMOOTH_L1 ? nullptr : (const float4*)priors, 0, loc_loss, var0, var1};
     return loss_bwd("ct_multibox_loss_bwd_loc", loc, conf, obj, loc_t, conf_t, obj_t, w, g, batch, num_priors,
-                    num_classes, dloc, dconf, dobj, stream, la);
+                    num_classes, dloc, dconf, dobj, stream, la, CE_ARGS);
 }
 
+extern "C" int ct_multibox_loss_fwd_terms(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                                          const float* conf_t, const uint8_t* obj_t, int batch, int num_priors,
+                                          int num_classes, int negpos_ratio, float* sums, long long* num_pos, long long* n,
+                                          float* w, void* ws, size_t ws_bytes, ct_stream_t stream,
+                                          const ct_loss_terms* terms)
+{
+    LocArgs la;
+    ConfArgs ca;
+    if (const int rc = check_terms("ct_multibox_loss_fwd_terms", terms, la, ca)) return rc;
+    return loss_fwd("ct_multibox_loss_fwd_terms", loc, conf, obj, loc_t, conf_t, obj_t, batch, num_priors, num_classes,
+                    negpos_ratio, sums, num_pos, n, w, ws, ws_bytes, stream, la, ca);
+}
+
+extern "C" int ct_multibox_loss_bwd_terms(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                                          const float* conf_t, const uint8_t* obj_t, const float* w, const float* g,
+                                          int batch, int num_priors, int num_classes, float* dloc, float* dconf,
+                                          float* dobj, ct_stream_t stream, const ct_loss_terms* terms)
+{
+    LocArgs la;
+    ConfArgs ca;
+    if (const int rc = check_terms("ct_multibox_loss_bwd_terms", terms, la, ca)) return rc;
+    return loss_bwd("ct_multibox_loss_bwd_terms", loc, conf, obj, loc_t, conf_t, obj_t, w, g, batch, num_priors,
+                    num_classes, dloc, dconf, dobj, stream, la, ca);
+}

@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get('CTDET_LIB') or os.path.join(os.path.dirname(_HERE), '
 CT_OK = 0
 # CT_LOC_*: the localisation term of ct_multibox_loss_fwd_loc / _bwd_loc, by position
 LOC_LOSSES = ('smooth_l1', 'iou', 'giou', 'diou', 'ciou')
+# CT_CONF_*: the classification terms of ct_multibox_loss_fwd_terms / _bwd_terms, by position
+CONF_LOSSES = ('ce', 'focal')
 
 
 class CtdetError(RuntimeError):
@@ -94,6 +96,12 @@ class SwapTensor(C.Structure):
     _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('numel', C.c_int64)]
 
 
+class LossTerms(C.Structure):
+    """ct_loss_terms: the options of ct_multibox_loss_fwd_terms / _bwd_terms."""
+    _fields_ = [('priors', C.c_void_p), ('loc_loss', C.c_int), ('var0', C.c_float), ('var1', C.c_float),
+                ('conf_loss', C.c_int), ('focal_gamma', C.c_float), ('focal_alpha', C.c_float)]
+
+
 class ResizeTap(C.Structure):
     """ct_resize_tap: first source index (unclamped) and the 11-bit coefficients of one output coordinate."""
     _fields_ = [('first', C.c_int), ('c', C.c_short * 8)]
@@ -139,6 +147,9 @@ SIGNATURES = {
     'ct_multibox_loss_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     'ct_multibox_loss_fwd_loc': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _F, _F]),
     'ct_multibox_loss_bwd_loc': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, _F]),
+    'ct_multibox_loss_fwd_terms': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P,
+                                        C.POINTER(LossTerms)]),
+    'ct_multibox_loss_bwd_terms': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, C.POINTER(LossTerms)]),
     'ct_sgd_tensors_per_launch': (_I, []),
     'ct_sgd_step': (_I, [C.POINTER(SgdTensor), _I, _F, _F, _I, _F, _P]),
     'ct_grad_norm_tensors_per_launch': (_I, []),

@@ -7,6 +7,7 @@ there is deliberately NO CPU / PyTorch fallback for these ops.
 import collections
 import ctypes as C
 import functools
+import math
 
 import numpy as np
 import torch
@@ -163,12 +164,37 @@ def _loc_args(priors, loc_loss, variances, num_priors):
     return (_dev(priors, 'priors'), _lib.LOC_LOSSES.index(loc_loss), float(variances[0]), float(variances[1]))
 
 
+def check_focal(conf_loss, focal_gamma, focal_alpha):
+    """The rules of include/ctdet.h (ct_multibox_loss_fwd_terms) on the host -> (conf_loss, gamma, alpha); ValueError."""
+    if conf_loss not in _lib.CONF_LOSSES:
+        raise ValueError('conf_loss must be one of %s, got %r' % (', '.join(_lib.CONF_LOSSES), conf_loss))
+    gamma, alpha = float(focal_gamma), float(focal_alpha)
+    if not (math.isfinite(gamma) and gamma >= 0):
+        raise ValueError('focal_gamma must be finite and >= 0, got %r' % (focal_gamma,))
+    if not alpha <= 1:
+        raise ValueError('focal_alpha must be in [0, 1], or negative for no class balancing, got %r' % (focal_alpha,))
+    return conf_loss, gamma, alpha
+
+
+def _loss_terms(priors, loc_loss, variances, num_priors, conf_loss, focal_gamma, focal_alpha):
+    """-> (ct_loss_terms or None, the trailing arguments of the _loc entries or None).  The struct is built for
+    conf_loss='focal' alone: with 'ce' the calls are the ones made before the focal form existed."""
+    conf_loss, gamma, alpha = check_focal(conf_loss, focal_gamma, focal_alpha)
+    extra = _loc_args(priors, loc_loss, variances, num_priors)
+    if conf_loss == 'ce':
+        return None, extra
+    ptr, kind, var0, var1 = extra if extra is not None else (None, 0, float(variances[0]), float(variances[1]))
+    return _lib.LossTerms(ptr, kind, var0, var1, _lib.CONF_LOSSES.index(conf_loss), gamma, alpha), None
+
+
 def multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio, priors=None, loc_loss='smooth_l1',
-                  variances=(0.1, 0.2)):
+                  variances=(0.1, 0.2), conf_loss='ce', focal_gamma=2.0, focal_alpha=0.25):
     """layers/modules/multibox_loss_combined.py:76-122 fused (ct_multibox_loss_fwd) -> sums [3] = un-normalised
     (loc, cls, obj) losses, n int64 [1], num_pos int64 [B], w [B,P] = weight * (pos | hard negative).
     loc_loss: 'smooth_l1' or one of 'iou', 'giou', 'diou', 'ciou' on the boxes decoded with `priors` [P,4] (centre form)
-    and `variances` (include/ctdet.h, ct_multibox_loss_fwd_loc, which is called whenever priors are given)."""
+    and `variances` (include/ctdet.h, ct_multibox_loss_fwd_loc, which is called whenever priors are given).
+    conf_loss: 'ce', or 'focal' for the mining-free focal terms with `focal_gamma` and `focal_alpha` (a negative alpha: no
+    class balancing) through ct_multibox_loss_fwd_terms; w is then weight * (label >= 0) and negpos_ratio is not read."""
     _dev(loc, 'loc')
     dev = loc.device
     B, P = loc.shape[0], loc.shape[1]
@@ -178,7 +204,7 @@ def multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_rati
             raise _lib.CtdetError('%s must be [%d,%d,%d], got %s' % (name, B, P, last, tuple(t.shape)))
     if tuple(obj_t.shape) != (B, P):
         raise _lib.CtdetError('obj_t must be [%d,%d], got %s' % (B, P, tuple(obj_t.shape)))
-    extra = _loc_args(priors, loc_loss, variances, P)
+    terms, extra = _loss_terms(priors, loc_loss, variances, P, conf_loss, focal_gamma, focal_alpha)
     sums = torch.empty(3, device=dev)
     n = torch.empty(1, device=dev, dtype=torch.int64)
     num_pos = torch.empty(B, device=dev, dtype=torch.int64)
@@ -189,7 +215,9 @@ def multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_rati
             _u8(obj_t, 'obj_t'), B, P, int(num_classes), int(negpos_ratio), _dev(sums, 'sums'),
             _dev(num_pos, 'num_pos', torch.int64), _dev(n, 'n', torch.int64), _dev(w, 'w'), _dev(ws, 'ws', torch.uint8),
             ws_bytes, _stream())
-    if extra is None:
+    if terms is not None:
+        check(lib().ct_multibox_loss_fwd_terms(*args, C.byref(terms)), 'ct_multibox_loss_fwd_terms')
+    elif extra is None:
         check(lib().ct_multibox_loss_fwd(*args), 'ct_multibox_loss_fwd')
     else:
         check(lib().ct_multibox_loss_fwd_loc(*args, *extra), 'ct_multibox_loss_fwd_loc')
@@ -197,16 +225,19 @@ def multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_rati
 
 
 def multibox_loss_backward(loc, conf, obj, loc_t, conf_t, obj_t, w, g, num_classes, priors=None, loc_loss='smooth_l1',
-                           variances=(0.1, 0.2)):
+                           variances=(0.1, 0.2), conf_loss='ce', focal_gamma=2.0, focal_alpha=0.25):
     """Gradients of (g * sums).sum() w.r.t. (loc, conf, obj); g is a DEVICE [3] tensor (ct_multibox_loss_bwd, or
-    ct_multibox_loss_bwd_loc when priors are given -- the same priors, loc_loss and variances as in the forward)."""
+    ct_multibox_loss_bwd_loc when priors are given -- the same priors, loc_loss and variances as in the forward; or
+    ct_multibox_loss_bwd_terms with conf_loss='focal' and the forward's focal_gamma / focal_alpha)."""
     B, P = loc.shape[0], loc.shape[1]
-    extra = _loc_args(priors, loc_loss, variances, P)
+    terms, extra = _loss_terms(priors, loc_loss, variances, P, conf_loss, focal_gamma, focal_alpha)
     dloc, dconf, dobj = torch.empty_like(loc), torch.empty_like(conf), torch.empty_like(obj)
     args = (_dev(loc, 'loc'), _dev(conf, 'conf'), _dev(obj, 'obj'), _dev(loc_t, 'loc_t'), _dev(conf_t, 'conf_t'),
             _u8(obj_t, 'obj_t'), _dev(w, 'w'), _dev(g, 'g'), B, P, int(num_classes), _dev(dloc, 'dloc'),
             _dev(dconf, 'dconf'), _dev(dobj, 'dobj'), _stream())
-    if extra is None:
+    if terms is not None:
+        check(lib().ct_multibox_loss_bwd_terms(*args, C.byref(terms)), 'ct_multibox_loss_bwd_terms')
+    elif extra is None:
         check(lib().ct_multibox_loss_bwd(*args), 'ct_multibox_loss_bwd')
     else:
         check(lib().ct_multibox_loss_bwd_loc(*args, *extra), 'ct_multibox_loss_bwd_loc')

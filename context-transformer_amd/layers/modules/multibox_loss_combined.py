@@ -8,6 +8,9 @@ ct_multibox_loss_fwd / _bwd (three launches forward, one backward, no sort) behi
 The localisation term is the reference's smooth-L1 on the encoded offsets (the default) or -- `loc_loss=` /
 CTDET_LOC_LOSS -- 1 - IoU, GIoU, DIoU or CIoU between the decoded prediction and the decoded target of every positive
 prior (defined in include/ctdet.h at ct_multibox_loss_fwd_loc), in both forms; `loc_weight` multiplies loss_box_reg.
+The classification terms are the reference's two cross-entropies over the 3:1 mined sample (the default) or -- `conf_loss=
+'focal'` / CTDET_CONF_LOSS -- focal terms over every prior that is not ignored, with no mining (defined in include/ctdet.h
+at ct_multibox_loss_fwd_terms), in both forms; focal_prior_init() below sets the objectness biases such a run starts from.
 targets: list of [G,6] tensors = [x1,y1,x2,y2,label,mixup_weight], or an ops.PackedTargets holding the same rows on
 the device (what preproc(decisions='device').batch_device returns).
 """
@@ -33,26 +36,25 @@ class FusedMultiBoxLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio, priors=None, loc_loss='smooth_l1',
-                variances=(0.1, 0.2)):
-        sums, n, num_pos, w = ops.multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio,
-                                                priors=priors, loc_loss=loc_loss, variances=variances)
+                variances=(0.1, 0.2), conf_loss='ce', focal_gamma=2.0, focal_alpha=0.25):
+        ctx.terms = dict(priors=priors, loc_loss=loc_loss, variances=tuple(variances), conf_loss=conf_loss,
+                         focal_gamma=focal_gamma, focal_alpha=focal_alpha)
+        sums, n, num_pos, w = ops.multibox_loss(loc, conf, obj, loc_t, conf_t, obj_t, num_classes, negpos_ratio, **ctx.terms)
         ctx.save_for_backward(loc, conf, obj, loc_t, conf_t, obj_t, w)
         ctx.num_classes = num_classes
-        ctx.loc = (priors, loc_loss, tuple(variances))
         ctx.mark_non_differentiable(n, num_pos, w)
         return sums, n, num_pos, w
 
     @staticmethod
     def backward(ctx, g, *unused):
         loc, conf, obj, loc_t, conf_t, obj_t, w = ctx.saved_tensors
-        priors, loc_loss, variances = ctx.loc
         dloc, dconf, dobj = ops.multibox_loss_backward(loc, conf, obj, loc_t, conf_t, obj_t, w,
-                                                       g.to(torch.float32).contiguous(), ctx.num_classes,
-                                                       priors=priors, loc_loss=loc_loss, variances=variances)
-        return dloc, dconf, dobj, None, None, None, None, None, None, None, None
+                                                       g.to(torch.float32).contiguous(), ctx.num_classes, **ctx.terms)
+        return (dloc, dconf, dobj) + (None,) * 11
 
 
 LOC_LOSSES = _lib.LOC_LOSSES        # 'smooth_l1' and the four IoU kinds
+CONF_LOSSES = _lib.CONF_LOSSES      # 'ce' and 'focal'
 
 
 class _ScaleGrad(torch.autograd.Function):
@@ -114,9 +116,44 @@ def iou_loss_rows(kind, loc, loc_t, priors, variance):
     return loss + alpha * v
 
 
+def focal_rows(ce, p, m, a, gamma):
+    """FL = a m^gamma ce per row, with the gradient of include/ctdet.h attached: c * d ce, c = a m^gamma (1 - gamma p r),
+    r = log p / m (-1 where m = 0) -- finite for every gamma >= 0, where autograd through m^gamma is not (gamma < 1, m = 0).
+    ce = -log p carries the graph; p and m (the sum of the other probabilities) are constants here."""
+    with torch.no_grad():
+        pw = torch.ones_like(m) if gamma == 0 else m.pow(gamma)             # 0^0 = 1
+        r = torch.where(m > 0, -ce / torch.where(m > 0, m, torch.ones_like(m)), -torch.ones_like(m))
+        c = a * pw * (1 - gamma * p * r)
+        value = a * pw * ce
+    return value + c * (ce - ce.detach())
+
+
+def focal_prior_init(net, pi=0.01):
+    """The prior-probability initialisation focal training starts from: every objectness conv of `net.obj` (channel order
+    (anchor, 2)) gets bias 0 in column 0 and -log((1 - pi) / pi) in column 1, so that every prior starts at
+    softmax(obj)[1] = pi instead of 0.5; the weights are left alone."""
+    if not 0.0 < pi < 1.0:
+        raise ValueError('pi must be in (0, 1), got %r' % (pi,))
+    with torch.no_grad():
+        for conv in net.obj:
+            bias = conv.bias.view(-1, 2)
+            bias[:, 0] = 0.0
+            bias[:, 1] = -math.log((1.0 - pi) / pi)
+    return net
+
+
+def _env_float(name, default):
+    text = os.environ.get(name, '')
+    try:
+        return float(text) if text else default
+    except ValueError:
+        raise ValueError('%s must be a number, got %r' % (name, text))
+
+
 class MultiBoxLoss_combined(nn.Module):
     def __init__(self, num_classes, overlap_thresh, prior_for_matching, bkg_label, neg_mining, neg_pos,
-                 neg_overlap, encode_target, fused=None, loc_loss=None, loc_weight=1.0):
+                 neg_overlap, encode_target, fused=None, loc_loss=None, loc_weight=1.0, conf_loss=None, focal_gamma=None,
+                 focal_alpha=None):
         super().__init__()
         # fused: the HIP loss kernels instead of the torch ops below; None reads CTDET_LOSS_FUSED (default off)
         self.fused = os.environ.get('CTDET_LOSS_FUSED', '0') == '1' if fused is None else bool(fused)
@@ -136,6 +173,13 @@ class MultiBoxLoss_combined(nn.Module):
             raise ValueError('loc_loss must be one of %s, got %r' % (', '.join(LOC_LOSSES), loc_loss))
         self.loc_loss = loc_loss
         self.loc_weight = float(loc_weight)   # multiplies loss_box_reg (published GIoU-style recipes use 2-5)
+        # conf_loss: the classification terms, one of CONF_LOSSES; None reads CTDET_CONF_LOSS (unset or empty: ce).  The focal
+        # constants: None reads CTDET_FOCAL_GAMMA / CTDET_FOCAL_ALPHA (unset or empty: 2.0 / 0.25; a negative alpha: no balancing)
+        if conf_loss is None:
+            conf_loss = os.environ.get('CTDET_CONF_LOSS', '') or 'ce'
+        self.conf_loss, self.focal_gamma, self.focal_alpha = ops.check_focal(
+            conf_loss, _env_float('CTDET_FOCAL_GAMMA', 2.0) if focal_gamma is None else focal_gamma,
+            _env_float('CTDET_FOCAL_ALPHA', 0.25) if focal_alpha is None else focal_alpha)
         self.sync_normalizer = False      # set True under multi-process data parallelism
 
     @torch.no_grad()
@@ -193,9 +237,14 @@ class MultiBoxLoss_combined(nn.Module):
                                  priors.to(dev), self.variance)
             loss_l = (rows * (weights * pos.float())).sum()
 
-        # hard negatives ranked by objectness loss, 3:1 (:88-96)
         obj_flat = obj_data.reshape(-1, 2)
         obj_lab = obj_t.long().view(-1)
+        if self.conf_loss == 'focal':
+            loss_c, loss_obj = self._focal_sums(obj_flat, conf_data.reshape(-1, self.num_classes - 1), obj_lab,
+                                                labels.reshape(-1), weights.reshape(-1))
+            return self._normalized(loss_l, loss_c, loss_obj, num_pos, dev)
+
+        # hard negatives ranked by objectness loss, 3:1 (:88-96)
         with torch.no_grad():
             ce = F.cross_entropy(obj_flat, obj_lab, reduction='none')
             ce = ce.masked_fill(obj_t.view(-1), 0.0)
@@ -217,7 +266,41 @@ class MultiBoxLoss_combined(nn.Module):
         # here their row is evaluated against class 0 and multiplied by w = 0: a valid target index, the same sum
         cls_t = labels.long().clamp_min(0).view(-1)
         loss_c = (F.cross_entropy(logit, cls_t, reduction='none') * w).sum()
+        return self._normalized(loss_l, loss_c, loss_obj, num_pos, dev)
 
+    def _focal_sums(self, obj_flat, flat_conf, obj_lab, labels, weights):
+        """The two focal sums over all priors (include/ctdet.h, ct_multibox_loss_fwd_terms): nothing is mined, w = weight of
+        every row that is not ignored.  A row of w = 0 is evaluated on zero logits and a background row on a zero conf row
+        (finite values, times w = 0 or not used), so that whatever they hold reaches neither a value nor a gradient."""
+        gamma, alpha = self.focal_gamma, self.focal_alpha
+        w = weights * (labels >= 0).float()
+        live = (w != 0).unsqueeze(1)
+        cls_t = labels.long().clamp(0, self.num_classes - 1)
+        fg = cls_t > 0
+        zero = torch.zeros((), dtype=obj_flat.dtype, device=obj_flat.device)
+        lo = F.log_softmax(torch.where(live, obj_flat, zero), 1)
+        lq = F.log_softmax(torch.where(live & fg.unsqueeze(1), flat_conf, zero), 1)
+        col = (cls_t - 1).clamp_min(0).unsqueeze(1)
+        with torch.no_grad():
+            s, q = lo.exp(), lq.exp()
+            q_t = q.gather(1, col).squeeze(1)
+            q_others = q.scatter(1, col, 0.0).sum(1)
+
+        def balance(is_fg):             # a = alpha for a foreground target, 1 - alpha for background, 1 when alpha < 0
+            return torch.where(is_fg, alpha, 1.0 - alpha).to(w.dtype) if alpha >= 0 else torch.ones_like(w)
+
+        # objectness: target obj_t, p = s_t, m = the other column
+        is_obj = obj_lab == 1
+        ce_obj = -lo.gather(1, obj_lab.unsqueeze(1)).squeeze(1)
+        fl_obj = focal_rows(ce_obj, torch.where(is_obj, s[:, 1], s[:, 0]), torch.where(is_obj, s[:, 0], s[:, 1]),
+                            balance(is_obj), gamma)
+        # class, on p_0 = s_0, p_k = s_1 q_k: log p_t from the logits, m = the sum of the other probabilities
+        ce_cls = torch.where(fg, -(lo[:, 1] + lq.gather(1, col).squeeze(1)), -lo[:, 0])
+        fl_cls = focal_rows(ce_cls, torch.where(fg, s[:, 1] * q_t, s[:, 0]),
+                            torch.where(fg, s[:, 0] + s[:, 1] * q_others, s[:, 1]), balance(fg), gamma)
+        return (fl_cls * w).sum(), (fl_obj * w).sum()
+
+    def _normalized(self, loss_l, loss_c, loss_obj, num_pos, dev):
         n = num_pos.sum()
         if self.sync_normalizer:          # data-parallel: N over the global batch (see ctdet.dist)
             from ctdet.dist import global_normalizer
@@ -234,8 +317,14 @@ class MultiBoxLoss_combined(nn.Module):
                                       'there is no CPU form of the fused loss -- use fused=False' % t.device)
         args = (loc_data.contiguous(), conf_data.contiguous(), obj_data.contiguous(), loc_t.contiguous(),
                 conf_t.contiguous(), obj_t.contiguous(), self.num_classes, int(self.negpos_ratio))
+        # the trailing arguments are given only where they differ from the defaults: the default criterion calls what it always did
+        loc_args = (None, 'smooth_l1', tuple(self.variance))
         if self.loc_loss != 'smooth_l1':
-            args += (priors.to(loc_data.device, torch.float32).contiguous(), self.loc_loss, tuple(self.variance))
+            loc_args = (priors.to(loc_data.device, torch.float32).contiguous(), self.loc_loss, tuple(self.variance))
+        if self.conf_loss != 'ce':
+            args += loc_args + (self.conf_loss, self.focal_gamma, self.focal_alpha)
+        elif self.loc_loss != 'smooth_l1':
+            args += loc_args
         sums, n, _, _ = FusedMultiBoxLoss.apply(*args)
         n = n[0]
         if self.sync_normalizer:

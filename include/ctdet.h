@@ -243,6 +243,51 @@ int ct_multibox_loss_bwd_loc(const float* loc, const float* conf, const float* o
                              int batch, int num_priors, int num_classes, float* dloc, float* dconf, float* dobj,
                              ct_stream_t stream, const float* priors, int loc_loss, float var0, float var1);
 
+/* The same loss with a choice of classification terms as well, the options in one struct (so this is the last suffix of
+ * the argument list).  conf_loss = CT_CONF_CE is the _loc entries launch for launch and bit for bit (focal_gamma and
+ * focal_alpha are then not read); CT_CONF_FOCAL replaces the two cross-entropies over the mined sample by focal terms
+ * over EVERY prior that is not ignored (no counterpart in the reference).  Same workspace query; forward three launches
+ * (the per-image pass holds no keys and runs no radix passes), backward one; no allocation, no host synchronisation,
+ * capturable.
+ * Definition of CT_CONF_FOCAL.  The matcher's outputs as they are: conf_t = (label, weight), obj_t = label != 0, background
+ * rows carry weight 1, ignored rows label -1.  Row weight w = weight when label >= 0, w = 0 for an ignored row; nothing is
+ * mined, negpos_ratio is accepted and not read; num_pos, n and the localisation term (any loc_loss) are what they are with
+ * CT_CONF_CE.  s = softmax(obj) over the 2 columns, q = softmax(conf) over the C-1 columns; the fused class probabilities
+ * are p_0 = s_0, p_k = s_1 q_k.  For a target t with probability p, and m = THE SUM OF THE OTHER PROBABILITIES (never 1 - p):
+ *   FL = -a m^gamma log p,   0^0 = 1,   log p taken from the logits (the cross-entropy of CT_CONF_CE, negated)
+ *   objectness term: t = obj_t;  a = alpha for t = 1, 1 - alpha for t = 0, and a = 1 when alpha < 0
+ *   class term:      t = clamp(label, 0, C-1), p = p_t;  a = alpha for a foreground target, 1 - alpha for background
+ *                    (1 when alpha < 0)
+ *   sums[1] = sum of w FL_cls, sums[2] = sum of w FL_obj, in the fixed-order fp64 accumulation of the other entries.
+ * Gradient: with r = log p / m (r = -1 where m = 0) and c = a m^gamma (1 - gamma p r), dFL/dz_j = c (p_j - [j = t]), finite
+ * for every gamma >= 0.  Through the fused logits: d/dconf_k = c ([t >= 1] q_k - [k = t]), d/dobj = c (s - onehot(t >= 1)),
+ * and the objectness term adds c_obj (s - onehot(obj_t)).
+ * A row with w = 0 gets exact zeros whatever its logits hold, and its logits are not read.  The conf row of a background
+ * prior (label 0) is read neither in the forward nor in the backward, and its dconf is exact zeros.  w (output) = the row
+ * weight above.
+ * CT_ERR_INVALID before any HIP call: NULL terms, what the _loc entries refuse, an unknown conf_loss, and with
+ * CT_CONF_FOCAL a focal_gamma that is not finite and >= 0 or a focal_alpha that is neither in [0, 1] nor negative. */
+enum {
+    CT_CONF_CE = 0,
+    CT_CONF_FOCAL = 1
+};
+typedef struct ct_loss_terms {
+    const float* priors;            /* as in the _loc entries; may be NULL with CT_LOC_SMOOTH_L1 */
+    int loc_loss;                   /* CT_LOC_* */
+    float var0, var1;
+    int conf_loss;                  /* CT_CONF_* */
+    float focal_gamma, focal_alpha; /* read with CT_CONF_FOCAL only */
+} ct_loss_terms;
+int ct_multibox_loss_fwd_terms(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                               const float* conf_t, const uint8_t* obj_t, int batch, int num_priors, int num_classes,
+                               int negpos_ratio, float* sums, long long* num_pos, long long* n, float* w,
+                               void* workspace, size_t workspace_bytes, ct_stream_t stream,
+                               const ct_loss_terms* terms);
+int ct_multibox_loss_bwd_terms(const float* loc, const float* conf, const float* obj, const float* loc_t,
+                               const float* conf_t, const uint8_t* obj_t, const float* w, const float* g,
+                               int batch, int num_priors, int num_classes, float* dloc, float* dconf, float* dobj,
+                               ct_stream_t stream, const ct_loss_terms* terms);
+
 /* train.py `optimizer.step()` over the parameter groups of utils/solver.py:6-33 (torch.optim.SGD, one group per
  * tensor, maximize=False): weight decay, momentum, dampening, Nesterov and the update fused into one pass over
  * (param, grad, momentum_buf) for ALL tensors of a call (csrc/ct_optim.hip).  lr and weight_decay are per tensor (the
