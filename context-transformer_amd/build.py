@@ -44,6 +44,7 @@ SOURCES = {
     'ct_wgrad.hip': [],
     'ct_wgrad_h2.hip': [],
     'ct_box.hip': ['-ffp-contract=off'],
+    'ct_atss.hip': ['-ffp-contract=off'],
     'ct_loss.hip': ['-ffp-contract=off'],
     'ct_optim.hip': ['-ffp-contract=off'],
     'ct_ema.hip': ['-ffp-contract=off'],

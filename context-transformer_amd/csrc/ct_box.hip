@@ -5,6 +5,7 @@
 // reference's rounding sequence (no FMA contraction), so integer results derived from these
 // values (arg-max indices, match labels) are reproducible against the CPU path.
 #include "ct_common.h"
+#include "ct_box_math.h"
 #include <cstdint>
 #include <mutex>
 #include <algorithm>
@@ -12,6 +13,10 @@
 #pragma clang fp contract(off)
 
 namespace {
+
+using ctdet::encode_box;
+using ctdet::iou_plain;
+using ctdet::point_form;
 
 inline int grid_for(long total, int block = 256)
 {
@@ -59,13 +64,7 @@ __global__ __launch_bounds__(256) void encode_kernel(const float4* __restrict__ 
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
-    const float4 m = matched[i], p = priors[i];
-    float4 o;
-    o.x = ((m.x + m.z) / 2.f - p.x) / (v0 * p.z);
-    o.y = ((m.y + m.w) / 2.f - p.y) / (v0 * p.w);
-    o.z = logf((m.z - m.x) / p.z) / v1;
-    o.w = logf((m.w - m.y) / p.w) / v1;
-    out[i] = o;
+    out[i] = encode_box(matched[i], priors[i], v0, v1);
 }
 
 // layers/functions/detection.py:44-53 (+ models/RFB_Net_vgg.py:282-284 when SOFTMAX)
@@ -242,23 +241,6 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     }
 }
 
-// utils/box_utils.py:29-68: inter / (area_a + area_b - inter), no +1
-__device__ __forceinline__ float iou_plain(const float4 a, const float4 b)
-{
-    const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
-    const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
-    const float inter = w * h;
-    const float area_a = (a.z - a.x) * (a.w - a.y);
-    const float area_b = (b.z - b.x) * (b.w - b.y);
-    return inter / (area_a + area_b - inter);
-}
-
-// utils/box_utils.py:5-14
-__device__ __forceinline__ float4 point_form(const float4 p)
-{
-    return make_float4(p.x - p.z / 2.f, p.y - p.w / 2.f, p.x + p.z / 2.f, p.y + p.w / 2.f);
-}
-
 __global__ __launch_bounds__(256) void jaccard_kernel(const float4* __restrict__ a, int na,
                                                       const float4* __restrict__ b, int nb,
                                                       int b_center, float* __restrict__ out)
@@ -357,11 +339,7 @@ __global__ __launch_bounds__(256) void match_pass2(const float* __restrict__ tru
         label = t[4];
         weight = t[5];
         if (ov < threshold) { label = 0.f; weight = 1.f; }
-        const float4 pr = priors[p];
-        out.x = ((t[0] + t[2]) / 2.f - pr.x) / (v0 * pr.z);
-        out.y = ((t[1] + t[3]) / 2.f - pr.y) / (v0 * pr.w);
-        out.z = logf((t[2] - t[0]) / pr.z) / v1;
-        out.w = logf((t[3] - t[1]) / pr.w) / v1;
+        out = encode_box(make_float4(t[0], t[1], t[2], t[3]), priors[p], v0, v1);
     }
     loc_t[o] = out;
     conf_t[o] = make_float2(label, weight);

@@ -14,6 +14,8 @@ CT_OK = 0
 LOC_LOSSES = ('smooth_l1', 'iou', 'giou', 'diou', 'ciou')
 # CT_CONF_*: the classification terms of ct_multibox_loss_fwd_terms / _bwd_terms, by position
 CONF_LOSSES = ('ce', 'focal')
+# the target assignment of MultiBoxLoss: ct_match_batched (the reference's fixed IoU rule) or ct_atss_match_batched
+MATCHERS = ('ssd', 'atss')
 
 
 class CtdetError(RuntimeError):
@@ -142,6 +144,8 @@ SIGNATURES = {
     'ct_jaccard': (_I, [_P, _I, _P, _I, _I, _P, _P]),
     'ct_match_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_match_batched': (_I, [_P, _P, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, _P, _Z, _P]),
+    'ct_atss_workspace_bytes': (_Z, [_I, _I, _I]),
+    'ct_atss_match_batched': (_I, [_P, _P, _I, _I, _P, _I, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_multibox_loss_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_multibox_loss_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_multibox_loss_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),

@@ -142,6 +142,69 @@ def match_packed(truths, gt_off, batch, max_gt, priors, threshold, variances, wa
     return (loc_t, conf_t, obj_t.bool(), overlap) if want_overlap else (loc_t, conf_t, obj_t.bool())
 
 
+def check_atss(level_offsets, topk, num_priors):
+    """The rules of include/ctdet.h (ct_atss_match_batched) on the host -> (offsets as a list of ints, topk); ValueError."""
+    if level_offsets is None:
+        raise ValueError("matcher='atss' needs level_offsets (PriorBox.level_offsets())")
+    off = [int(o) for o in level_offsets]
+    if len(off) < 2 or off[-1] != int(num_priors):
+        raise ValueError('level_offsets must end at the number of priors %d, got %r' % (num_priors, off))
+    if int(topk) != topk or not 1 <= int(topk) <= 16:
+        raise ValueError('atss_topk must be an integer in 1..16, got %r' % (topk,))
+    return off, int(topk)
+
+
+def _atss_call(truths, gt_off, B, max_gt, priors, level_offsets, topk, variances, want_overlap, want_stats):
+    dev = priors.device
+    P = priors.shape[0]
+    off, topk = check_atss(level_offsets, topk, P)
+    levels = (C.c_int * len(off))(*off)             # a host array: it travels in the kernel arguments
+    loc_t = torch.empty(B, P, 4, device=dev)
+    conf_t = torch.empty(B, P, 2, device=dev)
+    obj_t = torch.empty(B, P, device=dev, dtype=torch.uint8)
+    overlap = torch.empty(B, P, device=dev) if want_overlap else None
+    stats = torch.empty(B, max_gt, 4, device=dev) if want_stats else None
+    ws_bytes = lib().ct_atss_workspace_bytes(B, P, max_gt)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    check(lib().ct_atss_match_batched(_dev(truths, 'truths'), _dev(gt_off, 'gt_off', torch.int32), B, max_gt,
+                                      _dev(priors, 'priors'), P, levels, len(off) - 1, topk, float(variances[0]),
+                                      float(variances[1]), _dev(loc_t, 'loc_t'), _dev(conf_t, 'conf_t'),
+                                      _dev(obj_t, 'obj_t', torch.uint8), _opt(overlap, 'overlap'), _opt(stats, 'gt_stats'),
+                                      _dev(ws, 'ws', torch.uint8), ws_bytes, _stream()), 'ct_atss_match_batched')
+    out = (loc_t, conf_t, obj_t.bool())
+    if want_overlap:
+        out += (overlap,)
+    if want_stats:
+        out += (stats,)
+    return out
+
+
+def atss_match_batched(targets, priors, level_offsets, topk, variances, want_overlap=False, want_stats=False):
+    """match_batched with the ATSS rule (include/ctdet.h, ct_atss_match_batched) in place of the IoU threshold.  targets:
+    list of [G,6] tensors; level_offsets: the L+1 prior offsets of the pyramid levels (PriorBox.level_offsets()); topk:
+    candidates per level -> loc_t, conf_t, obj_t[, overlap][, gt_stats [B,max_gt,4]]."""
+    dev = priors.device
+    B = len(targets)
+    counts = [int(t.shape[0]) for t in targets]
+    max_gt = max(max(counts), 1)
+    off = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32).to(dev)
+    if sum(counts) > 0:
+        truths = torch.cat([t.reshape(-1, 6) for t in targets], 0).to(dev, torch.float32).contiguous()
+    else:
+        truths = torch.zeros(1, 6, device=dev)
+    return _atss_call(truths, off, B, max_gt, priors, level_offsets, topk, variances, want_overlap, want_stats)
+
+
+def atss_match_packed(truths, gt_off, batch, max_gt, priors, level_offsets, topk, variances, want_overlap=False,
+                      want_stats=False):
+    """atss_match_batched on device-resident inputs, as match_packed is to match_batched: no host-built offset table and
+    no copy.  An image with more than max_gt rows is matched against its first max_gt rows."""
+    B, max_gt = int(batch), max(int(max_gt), 1)
+    if gt_off.numel() < B + 1:
+        raise ValueError('atss_match_packed: gt_off has %d entries, batch %d needs %d' % (gt_off.numel(), B, B + 1))
+    return _atss_call(truths, gt_off, B, max_gt, priors, level_offsets, topk, variances, want_overlap, want_stats)
+
+
 # ------------------------------------------------------------------ loss
 def _u8(t, name):
     """The matcher's ignore mask: uint8 as ct_match_batched writes it, or the bool view match_batched returns."""

@@ -23,6 +23,14 @@ class PriorBox(object):
         if any(v <= 0 for v in self.variance):
             raise ValueError('Variances must be greater than 0')
 
+    def level_offsets(self):
+        """The L+1 ascending offsets of the pyramid levels in forward()'s rows: level l owns rows [off[l], off[l+1]),
+        fmap^2 cells of 2 + 2 * len(aspect_ratios[l]) priors each (what the ATSS matcher takes as `level_offsets`)."""
+        off = [0]
+        for level, fmap in enumerate(self.feature_maps):
+            off.append(off[-1] + fmap * fmap * (2 + 2 * len(self.aspect_ratios[level])))
+        return off
+
     def forward(self):
         rows = []
         for level, fmap in enumerate(self.feature_maps):

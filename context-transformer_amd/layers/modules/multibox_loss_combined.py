@@ -11,6 +11,8 @@ prior (defined in include/ctdet.h at ct_multibox_loss_fwd_loc), in both forms; `
 The classification terms are the reference's two cross-entropies over the 3:1 mined sample (the default) or -- `conf_loss=
 'focal'` / CTDET_CONF_LOSS -- focal terms over every prior that is not ignored, with no mining (defined in include/ctdet.h
 at ct_multibox_loss_fwd_terms), in both forms; focal_prior_init() below sets the objectness biases such a run starts from.
+The assignment itself is the reference's fixed IoU rule (the default) or -- `matcher='atss'` / CTDET_MATCHER -- adaptive
+training sample selection (defined in include/ctdet.h at ct_atss_match_batched), one library call either way.
 targets: list of [G,6] tensors = [x1,y1,x2,y2,label,mixup_weight], or an ops.PackedTargets holding the same rows on
 the device (what preproc(decisions='device').batch_device returns).
 """
@@ -55,6 +57,7 @@ class FusedMultiBoxLoss(torch.autograd.Function):
 
 LOC_LOSSES = _lib.LOC_LOSSES        # 'smooth_l1' and the four IoU kinds
 CONF_LOSSES = _lib.CONF_LOSSES      # 'ce' and 'focal'
+MATCHERS = _lib.MATCHERS            # 'ssd' and 'atss'
 
 
 class _ScaleGrad(torch.autograd.Function):
@@ -153,7 +156,7 @@ def _env_float(name, default):
 class MultiBoxLoss_combined(nn.Module):
     def __init__(self, num_classes, overlap_thresh, prior_for_matching, bkg_label, neg_mining, neg_pos,
                  neg_overlap, encode_target, fused=None, loc_loss=None, loc_weight=1.0, conf_loss=None, focal_gamma=None,
-                 focal_alpha=None):
+                 focal_alpha=None, matcher=None, atss_topk=None, level_offsets=None):
         super().__init__()
         # fused: the HIP loss kernels instead of the torch ops below; None reads CTDET_LOSS_FUSED (default off)
         self.fused = os.environ.get('CTDET_LOSS_FUSED', '0') == '1' if fused is None else bool(fused)
@@ -180,6 +183,25 @@ class MultiBoxLoss_combined(nn.Module):
         self.conf_loss, self.focal_gamma, self.focal_alpha = ops.check_focal(
             conf_loss, _env_float('CTDET_FOCAL_GAMMA', 2.0) if focal_gamma is None else focal_gamma,
             _env_float('CTDET_FOCAL_ALPHA', 0.25) if focal_alpha is None else focal_alpha)
+        # matcher: the target assignment, one of MATCHERS; None reads CTDET_MATCHER (unset or empty: ssd, the reference's IoU >=
+        # overlap_thresh rule).  'atss' (include/ctdet.h, ct_atss_match_batched) does not read overlap_thresh; it takes atss_topk
+        # candidates per pyramid level (None reads CTDET_ATSS_TOPK; unset or empty: 9) and needs level_offsets, the L+1 prior
+        # offsets of the levels (PriorBox.level_offsets()), which match() checks against the priors it is given
+        if matcher is None:
+            matcher = os.environ.get('CTDET_MATCHER', '') or 'ssd'
+        if matcher not in MATCHERS:
+            raise ValueError('matcher must be one of %s, got %r' % (', '.join(MATCHERS), matcher))
+        self.matcher = matcher
+        if atss_topk is None:
+            text = os.environ.get('CTDET_ATSS_TOPK', '')
+            try:
+                atss_topk = int(text) if text else 9
+            except ValueError:
+                raise ValueError('CTDET_ATSS_TOPK must be an integer, got %r' % text)
+        if isinstance(atss_topk, bool) or int(atss_topk) != atss_topk or not 1 <= int(atss_topk) <= 16:
+            raise ValueError('atss_topk must be an integer in 1..16, got %r' % (atss_topk,))
+        self.atss_topk = int(atss_topk)
+        self.level_offsets = None if level_offsets is None else [int(o) for o in level_offsets]
         self.sync_normalizer = False      # set True under multi-process data parallelism
 
     @torch.no_grad()
@@ -189,7 +211,9 @@ class MultiBoxLoss_combined(nn.Module):
         in place -- a training step captured as a hipGraph (bench.py --train) reads the same three tensors at every
         replay, the matching itself (a host-built offset table, an H2D copy) stays outside the graph."""
         dev = torch.device(device) if device is not None else priors.device
-        if isinstance(targets, ops.PackedTargets):      # device-resident truths / gt_off (ops.AugPlanner): no host table
+        if self.matcher == 'atss':
+            loc_t, conf_t, obj_t = self._match_atss(priors, targets, dev)
+        elif isinstance(targets, ops.PackedTargets):      # device-resident truths / gt_off (ops.AugPlanner): no host table
             loc_t, conf_t, obj_t = ops.match_packed(targets.truths, targets.gt_off, targets.gt_off.numel() - 1,
                                                     targets.max_gt, priors.to(dev).float().contiguous(),
                                                     self.threshold, self.variance)
@@ -200,6 +224,14 @@ class MultiBoxLoss_combined(nn.Module):
             return MatchedTargets(loc_t, conf_t, obj_t)
         out.loc_t.copy_(loc_t); out.conf_t.copy_(conf_t); out.obj_t.copy_(obj_t)
         return out
+
+    def _match_atss(self, priors, targets, dev):
+        off, topk = ops.check_atss(self.level_offsets, self.atss_topk, priors.shape[0])
+        pri = priors.to(dev).float().contiguous()
+        if isinstance(targets, ops.PackedTargets):
+            return ops.atss_match_packed(targets.truths, targets.gt_off, targets.gt_off.numel() - 1, targets.max_gt, pri, off,
+                                         topk, self.variance)
+        return ops.atss_match_batched([t.to(dev) for t in targets], pri, off, topk, self.variance)
 
     def forward(self, predictions, priors, targets):
         loc_data, conf_data, obj_data = predictions

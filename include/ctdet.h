@@ -178,6 +178,61 @@ int ct_match_batched(const float* truths, const int* gt_off, int batch, int max_
                      float* loc_t, float* conf_t, uint8_t* obj_t, float* overlap,
                      void* workspace, size_t workspace_bytes, ct_stream_t stream);
 
+/* ADAPTIVE TRAINING SAMPLE SELECTION (ATSS, Zhang et al., CVPR 2020): the second matcher.  It replaces the hand-set IoU
+ * threshold of ct_match_batched by one computed per box from the box's own candidates; the outputs have the same layout, so
+ * the loss entries below read either matcher's result.
+ *
+ * Inputs are those of ct_match_batched, plus two new ones:
+ *   truths dev [sum G,6], gt_off dev [B+1], priors dev [P,4] in centre form.
+ *   level_off: a HOST array of L+1 ascending prior offsets, with level_off[0] = 0 and level_off[L] = P.  It gives the pyramid
+ *     level of every prior.
+ *   topk.
+ * All fp32 arithmetic is rounded operation by operation (no FMA contraction).
+ *
+ * For every image b, every box g < min(G_b, max_gt) is handled independently of the others.  The max_gt truncation contract of
+ * ct_match_batched is kept.
+ *  1. DEGENERATE BOXES.  A box with !(x2 > x1 && y2 > y1) is skipped: it has no candidates and no positives.
+ *     (ct_match_batched does not skip such boxes and can write logf(0) for them.  Here the result stays finite.)
+ *  2. CANDIDATES.  The box centre is gx = (x1+x2)/2, gy = (y1+y2)/2.  The distance to prior p is d = dx*dx + dy*dy, with
+ *     dx = pcx - gx and dy = pcy - gy.  In each level l the candidates are the min(topk, n_l) priors with the smallest d.  Ties
+ *     go to the lower prior index.  Candidate order is level-major, then ascending (d, index).  The priors of one cell share a
+ *     centre: with topk = 9 and 6 priors per cell this takes the nearest cell's six priors and three of the next cell, which
+ *     is the behaviour of the published implementations.
+ *  3. IOU.  The IoU of each candidate is the expression of ct_jaccard with b_center_form != 0: inter / (area_a + area_b -
+ *     inter) of the box and the prior in point form.
+ *  4. THRESHOLD.  Let n be the number of candidates.  mean is the sum of the IoUs, accumulated in float64 in candidate order,
+ *     divided by n.  var is the float64 sum of (iou - mean)^2, in the same order, divided by n - 1.  It is 0 when n < 2.
+ *     t = (float)(mean + sqrt(var)).
+ *  5. POSITIVE CANDIDATES.  A candidate is positive if iou >= t and x1 < pcx < x2 and y1 < pcy < y2.  The inequalities are
+ *     strict and are taken on the fp32 values as they are.
+ *  6. FORCED POSITIVE.  If no candidate of a non-degenerate box is positive, the candidate with the largest IoU becomes its one
+ *     forced positive.  The first in candidate order wins a tie.  The centre test is waived for it.  This keeps the reference
+ *     matcher's property that every box trains at least one prior, which a few-shot detector cannot give up; it is the one
+ *     deliberate departure from the published rule.  A BOX CAN STILL END WITH NO PRIOR if all of its positives are lost under
+ *     rule 7.
+ *  7. CONFLICTS.  A prior claimed by several boxes goes to the claim that wins this order: a forced claim over an ordinary
+ *     one, then the larger IoU, then the lower box index.
+ *  8. OUTPUTS.  The layout is ct_match_batched's.  An assigned prior gets loc_t = the encode expression of ct_encode /
+ *     ct_match_batched, conf_t = (label, weight) of its box, label -1 and mixup weights included, and obj_t = label != 0.
+ *     Every other prior gets loc_t = 0, conf_t = (0, 1) and obj_t = 0, exactly.  overlap may be NULL: it holds the IoU with
+ *     the assigned box, else 0.  gt_stats may be NULL: it is [B, max_gt, 4] floats = (t, number of candidates, number of
+ *     positive candidates before conflicts with the forced one counted, forced ? 1 : 0); rows of skipped or absent boxes are
+ *     zeros.
+ * An image's result never depends on its batch mates, and the same inputs give the same bits on every run (conflicts are
+ * resolved by an order-independent packed atomicMax).  The entry makes no allocation, does no host synchronisation and makes
+ * no H2D copy: level_off travels in the kernel arguments.  One memset and two launches on `stream`.
+ * workspace: ct_atss_workspace_bytes(batch, num_priors, max_gt) bytes, 8-byte aligned.
+ * CT_ERR_INVALID before any HIP call: NULL tensors (overlap and gt_stats excepted) or a NULL level_off; batch, num_priors or
+ * max_gt < 1; num_priors above 2^30 or batch above 65535; num_levels outside 1..8; topk outside 1..16; a level_off that is
+ * not 0 = off[0] < ... < off[L] = P; a variance that is not positive and finite; a workspace that is too small or not
+ * 8-byte aligned. */
+size_t ct_atss_workspace_bytes(int batch, int num_priors, int max_gt);
+int ct_atss_match_batched(const float* truths, const int* gt_off, int batch, int max_gt,
+                          const float* priors, int num_priors, const int* level_off_host, int num_levels,
+                          int topk, float var0, float var1, float* loc_t, float* conf_t, uint8_t* obj_t,
+                          float* overlap, float* gt_stats, void* workspace, size_t workspace_bytes,
+                          ct_stream_t stream);
+
 /* layers/modules/multibox_loss_combined.py:76-122 (`MultiBoxLoss_combined.forward` after the matching): the loss
  * arithmetic, fused.  Forward = three launches, backward = one; no allocation, no host synchronisation, capturable.
  *   loc dev [B,P,4], conf dev [B,P,C-1], obj dev [B,P,2]      the network's raw outputs (C = num_classes >= 2)

@@ -2,7 +2,7 @@
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
    python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
                                [--clip-norm X] [--ema DECAY] [--deterministic] [--loc-loss NAME] [--loc-weight X]
-                               [--conf-loss focal [--focal-gamma X --focal-alpha X]] [--json]
+                               [--conf-loss focal [--focal-gamma X --focal-alpha X]] [--matcher ssd|atss [--atss-topk K]] [--json]
    --classes: classes of the conf head; default 20, with --phase 2 the width of the Context-Transformer block (60 for 'transfer',
    15 for 'incre': the head feeds the block);
    --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
@@ -21,6 +21,8 @@
    --conf-loss NAME [--focal-gamma X --focal-alpha X]: the criterion's classification terms (ce, focal; default: what CTDET_CONF_LOSS
    says, else ce) and the focal constants (default: CTDET_FOCAL_GAMMA / CTDET_FOCAL_ALPHA, else 2.0 / 0.25); a focal run starts from
    focal_prior_init(net) (objectness prior 0.01); all three are reported on the JSON line, which is then always printed;
+   --matcher NAME [--atss-topk K]: the criterion's target assignment (ssd, atss; default: what CTDET_MATCHER says, else ssd) and the
+   ATSS candidates per level (default: CTDET_ATSS_TOPK, else 9); both are reported on the JSON line, which is then always printed;
    --json: one more line, JSON, with the step time, the optimizer's device time and the training runtime's `policy` record
    (always with --clip-norm and --deterministic; with --clip-norm it
    also carries the last norm, coef and the number of skipped steps);
@@ -41,6 +43,7 @@ ap.add_argument('--ema', type=float, default=None)
 ap.add_argument('--loc-loss', default=None); ap.add_argument('--loc-weight', type=float, default=1.0)
 ap.add_argument('--conf-loss', default=None); ap.add_argument('--focal-gamma', type=float, default=None)
 ap.add_argument('--focal-alpha', type=float, default=None)
+ap.add_argument('--matcher', default=None); ap.add_argument('--atss-topk', type=int, default=None)
 a = ap.parse_args()
 if a.clip_norm is not None or a.ema is not None:
     a.fused_sgd = True
@@ -62,10 +65,12 @@ if a.classes is None:
 net = build_net(types.SimpleNamespace(method='ours', phase=a.phase, setting=a.setting), a.size, a.classes)
 net.load_state_dict(synth.fill_state_dict(net.state_dict()))
 net = net.cuda().train(); net.device = 'cuda'
-priors = PriorBox(getattr(cfgs, 'VOC_%d' % a.size)).forward().cuda()
+prior_box = PriorBox(getattr(cfgs, 'VOC_%d' % a.size))
+priors = prior_box.forward().cuda()
 nout = a.classes if a.phase == 1 else net.OBJ_Target.weight.shape[0] + (a.classes if a.setting == 'incre' else 0)
 crit = MultiBoxLoss_combined(nout + 1, 0.5, True, 0, True, 3, 0.5, False, loc_loss=a.loc_loss, loc_weight=a.loc_weight,
-                             conf_loss=a.conf_loss, focal_gamma=a.focal_gamma, focal_alpha=a.focal_alpha)
+                             conf_loss=a.conf_loss, focal_gamma=a.focal_gamma, focal_alpha=a.focal_alpha, matcher=a.matcher,
+                             atss_topk=a.atss_topk, level_offsets=prior_box.level_offsets())
 if crit.conf_loss == 'focal':
     focal_prior_init(net)       # every prior starts at objectness 0.01 instead of 0.5 (the biases; set before the runtime is built)
 crit.sync_normalizer = world > 1
@@ -117,13 +122,13 @@ if rank == 0:
           % (a.size, a.phase, a.batch, world, ' [%s, %d groups]' % (type(opt).__name__, len(opt.param_groups))
              if a.fused_sgd or a.per_tensor_groups else '', dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
     if a.json or a.clip_norm is not None or a.ema is not None or a.deterministic or a.loc_loss is not None or a.loc_weight != 1.0 \
-            or a.conf_loss is not None:
+            or a.conf_loss is not None or a.matcher is not None:
         row = {'train_bench': 'RFBNet-%d phase %d' % (a.size, a.phase), 'batch': a.batch, 'gpus': world, 'steps': n,
                'optimizer': type(opt).__name__, 'groups': len(opt.param_groups), 'ms_per_step': round(dt * 1e3, 3),
                'fwd_ms': round(tf / n, 3), 'loss_ms': round(tl / n, 3), 'bwd_ms': round(tb / n, 3), 'opt_ms': round(to / n, 3),
                'clip_norm': a.clip_norm, 'loss': float(loss), 'loc_loss': crit.loc_loss, 'loc_weight': crit.loc_weight,
                'loss_fused': crit.fused, 'conf_loss': crit.conf_loss, 'focal_gamma': crit.focal_gamma,
-               'focal_alpha': crit.focal_alpha}
+               'focal_alpha': crit.focal_alpha, 'matcher': crit.matcher, 'atss_topk': crit.atss_topk}
         if a.clip_norm is not None:
             row.update(opt.clip_info())                 # norm, coef, finite, nonfinite of the last step
         if a.ema is not None:
