@@ -48,6 +48,8 @@ SOURCES = {
     'ct_loss.hip': ['-ffp-contract=off'],
     'ct_optim.hip': ['-ffp-contract=off'],
     'ct_ema.hip': ['-ffp-contract=off'],
+    # AdamW's sqrt and divisions are part of the bit-exact contract: ask for the correctly rounded ones by name
+    'ct_adamw.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
     'ct_nms.hip': ['-ffp-contract=off'],
     'ct_soft_nms.hip': ['-ffp-contract=off'],
     'ct_post.hip': ['-ffp-contract=off'],

@@ -1,5 +1,5 @@
 // What the multi-tensor element-wise kernels share (ct_optim.hip: the SGD step, with and without a weight average, and
-// the gradient norm; ct_ema.hip: the average alone and the exchange).
+// the gradient norm; ct_ema.hip: the average alone and the exchange; ct_adamw.hip: the AdamW step).
 //
 // Device side.  The tensor table and the first workgroup of every tensor travel in the kernel arguments (no device
 // table, no staging copy, nothing read from the caller's array after the call returns); a workgroup finds its tensor

@@ -98,6 +98,18 @@ class SwapTensor(C.Structure):
     _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('numel', C.c_int64)]
 
 
+class AdamState(C.Structure):
+    """ct_adam_state: the 32-byte per-tensor record ct_adamw_begin advances and ct_adamw_step reads."""
+    _fields_ = [('beta1_pow', C.c_double), ('beta2_pow', C.c_double), ('step', C.c_int), ('applied', C.c_int),
+                ('bc1', C.c_float), ('rs2', C.c_float)]
+
+
+class AdamwTensor(C.Structure):
+    _fields_ = [('param', C.c_void_p), ('grad', C.c_void_p), ('exp_avg', C.c_void_p), ('exp_avg_sq', C.c_void_p),
+                ('ema', C.c_void_p), ('state', C.c_void_p), ('numel', C.c_int64), ('lr', C.c_float),
+                ('weight_decay', C.c_float)]
+
+
 class LossTerms(C.Structure):
     """ct_loss_terms: the options of ct_multibox_loss_fwd_terms / _bwd_terms."""
     _fields_ = [('priors', C.c_void_p), ('loc_loss', C.c_int), ('var0', C.c_float), ('var1', C.c_float),
@@ -165,6 +177,10 @@ SIGNATURES = {
     'ct_sgd_step_ema': (_I, [C.POINTER(SgdEmaTensor), _I, _F, _F, _I, _F, _P, _P, _P]),
     'ct_ema_update': (_I, [C.POINTER(EmaTensor), _I, _P, _P]),
     'ct_tensor_swap': (_I, [C.POINTER(SwapTensor), _I, _P]),
+    'ct_adamw_begin_indices_per_launch': (_I, []),
+    'ct_adamw_begin': (_I, [_P, C.POINTER(_I), _I, _D, _D, _P, _P]),
+    'ct_adamw_tensors_per_launch': (_I, []),
+    'ct_adamw_step': (_I, [C.POINTER(AdamwTensor), _I, _F, _F, _F, _F, _P, _P, _P]),
     'ct_postprocess_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_postprocess_soft_workspace_bytes': (_Z, [_I, _I, _I]),

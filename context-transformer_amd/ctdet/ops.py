@@ -455,6 +455,88 @@ def ema_info(state):
     return {'updates': int(s.updates), 'decay': float(s.decay), 'applied': bool(s.applied)}
 
 
+# ------------------------------------------------------------------ AdamW
+ADAM_STATE_BYTES = C.sizeof(_lib.AdamState)
+ADAM_STATE_DTYPE = np.dtype([('beta1_pow', '<f8'), ('beta2_pow', '<f8'), ('step', '<i4'), ('applied', '<i4'),
+                             ('bc1', '<f4'), ('rs2', '<f4')])        # ct_adam_state
+
+
+def _adam_states(t):
+    if not isinstance(t, torch.Tensor) or t.numel() % ADAM_STATE_BYTES:
+        raise _lib.CtdetError('adam states must be a uint8 tensor of a multiple of %d bytes, got %s'
+                              % (ADAM_STATE_BYTES, t.numel() if isinstance(t, torch.Tensor) else type(t)))
+    return _dev(t, 'adam_states', torch.uint8)
+
+
+def adamw_begin(states, indices, beta1, beta2, clip_state=None):
+    """ct_adamw_begin on the records `indices` (distinct ints) of `states`, a uint8 device tensor of ADAM_STATE_BYTES
+    per record that the caller zeroed once: each record's beta powers, step count and bias corrections advance by one
+    step, or -- when `clip_state` (what grad_norm_clip returned) says the step is skipped -- the record is marked as
+    not applied and keeps everything else.  No synchronisation."""
+    n = len(indices)
+    ptr = _adam_states(states)
+    slots = states.numel() // ADAM_STATE_BYTES
+    if any(i >= slots for i in indices):        # the library cannot know how many records the tensor holds
+        raise _lib.CtdetError('adamw_begin: record %d of %d' % (max(indices), slots))
+    table = (C.c_int * max(n, 1))(*indices)
+    check(lib().ct_adamw_begin(ptr, table, n, float(beta1), float(beta2),
+                               None if clip_state is None else _clip_state(clip_state), _stream()), 'ct_adamw_begin')
+    return states
+
+
+def adamw_table(items, states, ema=False):
+    """ctypes table of ct_adamw_tensor for `items` = [(param, grad, exp_avg, exp_avg_sq, record, lr, weight_decay)]
+    -- `record` is the tensor's position in `states` -- with the tensor's average as an eighth column when `ema`.
+    Every tensor contiguous fp32 on the HIP device (views at any element offset are fine)."""
+    base = _adam_states(states).value
+    slots = states.numel() // ADAM_STATE_BYTES
+    table = (_lib.AdamwTensor * max(len(items), 1))()
+    for i, (p, g, m, v, slot, lr, wd, *avg) in enumerate(items):
+        n = p.numel()
+        if len(avg) != int(bool(ema)):
+            raise _lib.CtdetError('adamw_step: tensor %d comes %s an average' % (i, 'with' if avg else 'without'))
+        if any(t.numel() != n for t in (g, m, v, *avg)):
+            raise _lib.CtdetError('adamw_step: tensor %d has %d elements, its grad %d, its moments %d and %d%s'
+                                  % (i, n, g.numel(), m.numel(), v.numel(),
+                                     ''.join(', its average %d' % e.numel() for e in avg)))
+        if not 0 <= slot < slots:
+            raise _lib.CtdetError('adamw_step: tensor %d names record %d of %d' % (i, slot, slots))
+        table[i] = _lib.AdamwTensor(_dev(p, 'param').value, _dev(g, 'grad').value, _dev(m, 'exp_avg').value,
+                                    _dev(v, 'exp_avg_sq').value, _dev(avg[0], 'ema').value if avg else None,
+                                    base + slot * ADAM_STATE_BYTES, n, lr, wd)
+    return table
+
+
+def adamw_step(items, beta1, beta2, eps, grad_scale, states, ema_state=None, clip_state=None):
+    """torch.optim.AdamW's update (amsgrad=False, maximize=False) of every tensor of `items` (see adamw_table) in
+    ceil(len / ct_adamw_tensors_per_launch) launches (ct_adamw_step), with the bias corrections adamw_begin has just
+    left in the tensors' records of `states`; params and both moments are updated in place.  With `ema_state` every
+    item carries its average, moved towards the new parameter value in the same pass; with `clip_state` the state's
+    coef is multiplied into grad_scale on the device and a non-finite norm skips the update."""
+    if not items:
+        return
+    check(lib().ct_adamw_step(adamw_table(items, states, ema=ema_state is not None), len(items), float(beta1),
+                              float(beta2), float(eps), float(grad_scale),
+                              None if clip_state is None else _clip_state(clip_state),
+                              None if ema_state is None else _ema_state(ema_state), _stream()), 'ct_adamw_step')
+
+
+def adam_states_read(states):
+    """Synchronising read of all records -> a NumPy structured array (ADAM_STATE_DTYPE), one device-to-host copy."""
+    _adam_states(states)
+    return np.frombuffer(states.cpu().numpy().tobytes(), dtype=ADAM_STATE_DTYPE).copy()
+
+
+def adam_states_write(states, records):
+    """Writes a structured array of one entry per record (ADAM_STATE_DTYPE) over `states`, one host-to-device copy."""
+    _adam_states(states)
+    records = np.ascontiguousarray(records, dtype=ADAM_STATE_DTYPE)
+    if records.size * ADAM_STATE_BYTES != states.numel():
+        raise _lib.CtdetError('adam_states_write: %d records for %d' % (records.size, states.numel() // ADAM_STATE_BYTES))
+    states.copy_(torch.frombuffer(bytearray(records.tobytes()), dtype=torch.uint8))
+    return states
+
+
 # ------------------------------------------------------------------ NMS
 def nms_sorted_host(dets_sorted, thresh, ge=False, device_id=0, plain_iou=False):
     """The `_nms` contract (utils/nms/nms_kernel.cu:91-144): host numpy [n,dim>=4] sorted by

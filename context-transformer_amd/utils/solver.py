@@ -11,6 +11,9 @@ args.max_grad_norm (optional; a positive float, or math.inf for the non-finite g
 gradient-norm clipping and the skip of non-finite steps on the device.  Only the fused optimizer has it.
 args.ema_decay (optional, with args.ema_warmup) attaches a ctdet.optim.WeightEMA of the model as `optimizer.ema`: the
 weights are averaged inside the fused update; evaluate under `with optimizer.ema.swapped():`.  Fused only as well.
+args.optimizer (optional; 'sgd' when absent) = 'adamw' builds AdamW over the same per-tensor groups, with args.betas and
+args.eps when given: ctdet.optim.FusedAdamW when fused, torch.optim.AdamW otherwise; max_grad_norm and ema_decay need
+the fused class here too.  Any other name is an error.
 """
 import os
 from bisect import bisect_right
@@ -34,6 +37,11 @@ def build_optimizer(args, model, fused=None):
         fused = os.environ.get('CTDET_SGD_FUSED', '0') == '1'
     max_grad_norm = getattr(args, 'max_grad_norm', None)
     ema_decay = getattr(args, 'ema_decay', None)
+    name = getattr(args, 'optimizer', 'sgd')
+    if name == 'adamw':
+        return _build_adamw(args, model, groups, fused, max_grad_norm, ema_decay)
+    if name != 'sgd':
+        raise ValueError("args.optimizer = %r: 'sgd' or 'adamw'" % (name,))
     if ema_decay is not None:
         if not fused:
             raise ValueError('args.ema_decay = %r needs the fused optimizer (fused=True or CTDET_SGD_FUSED=1): with '
@@ -51,6 +59,28 @@ def build_optimizer(args, model, fused=None):
         raise ValueError('args.max_grad_norm = %r needs the fused optimizer (fused=True or CTDET_SGD_FUSED=1): there is '
                          'no torch path for it' % (max_grad_norm,))
     return torch.optim.SGD(groups, args.lr, momentum=args.momentum)
+
+
+def _build_adamw(args, model, groups, fused, max_grad_norm, ema_decay):
+    """args.optimizer == 'adamw': ctdet.optim.FusedAdamW when fused, else torch.optim.AdamW, over the same groups."""
+    kw = {}
+    if getattr(args, 'betas', None) is not None:
+        kw['betas'] = tuple(args.betas)
+    if getattr(args, 'eps', None) is not None:
+        kw['eps'] = args.eps
+    if not fused:
+        for name, v in (('max_grad_norm', max_grad_norm), ('ema_decay', ema_decay)):
+            if v is not None:
+                raise ValueError('args.%s = %r needs the fused optimizer (fused=True or CTDET_SGD_FUSED=1): there is no '
+                                 'torch path for it' % (name, v))
+        return torch.optim.AdamW(groups, args.lr, **kw)
+    from ctdet.optim import FusedAdamW, WeightEMA
+    if max_grad_norm is not None:
+        kw['max_grad_norm'] = max_grad_norm
+    if ema_decay is not None:
+        warmup = getattr(args, 'ema_warmup', None)
+        kw['ema'] = WeightEMA(model, ema_decay) if warmup is None else WeightEMA(model, ema_decay, warmup)
+    return FusedAdamW(groups, args.lr, **kw)
 
 
 def _get_warmup_factor_at_iter(method, iter, warmup_iters, warmup_factor):

@@ -505,6 +505,73 @@ int ct_sgd_step_ema(const ct_sgd_ema_tensor* items_host, int n, float momentum, 
 int ct_ema_update(const ct_ema_tensor* items_host, int n, const ct_ema_state* ema_dev, ct_stream_t stream);
 int ct_tensor_swap(const ct_swap_tensor* items_host, int n, ct_stream_t stream);
 
+/* AdamW (decoupled weight decay; torch.optim.AdamW with amsgrad=False, maximize=False) as a second update rule on the
+ * multi-tensor walk of ct_sgd_step (csrc/ct_adamw.hip).  Off unless called.  Two entries per optimizer step:
+ * ct_adamw_begin advances the per-tensor step records on the device, ct_adamw_step moves the seven arrays.
+ *
+ * ct_adam_state is one 32-byte device record per tensor, zeroed once by the caller.  ct_adamw_begin runs one thread per
+ * listed record (index_host[i] is the record's position in states_dev; the indices travel in the kernel arguments,
+ * ct_adamw_begin_indices_per_launch() (1000) per launch, ceil(n / 1000) launches), plain loads and stores, no atomics.
+ * With ok = clip ? clip->finite : 1:
+ *     if ok:  b1p = (step == 0 ? 1.0 : beta1_pow) * beta1            binary64, one rounding
+ *             b2p = (step == 0 ? 1.0 : beta2_pow) * beta2
+ *             bc1 = (float)(1.0 - b1p);  bc2 = (float)(1.0 - b2p);  rs2 = sqrtf(bc2)     each rounded once
+ *             record = { b1p, b2p, step == INT_MAX ? step : step + 1, 1, bc1, rs2 }
+ *     else:   record.applied = 0                                      nothing else is written
+ * The powers are running binary64 products: NumPy reproduces them bit for bit, and against beta ** step they are off
+ * by about step * 1e-16, far below fp32 (an fp32 product would put about 1e-5 of relative error into 1 - 0.999^1).
+ * ct_adamw_step takes its betas as float; a caller that wants the bias corrections to belong to exactly those values
+ * passes (double)(float)beta here (ctdet.optim.FusedAdamW does): 1 - 0.999 and 1 - (float)0.999 differ by 1.3e-5.
+ * CT_ERR_INVALID (nothing launched): n < 0; a NULL or misaligned (8 bytes) states_dev or a NULL index_host with n > 0;
+ * a negative or repeated index; beta1 or beta2 outside [0, 1) or NaN; a misaligned clip state.
+ *
+ * ct_adamw_step.  Once per call on the host: om1 = (float)(1.0 - (double)beta1), om2 = (float)(1.0 - (double)beta2).
+ * Per tensor: lw = lr * weight_decay (host, one fp32 rounding), a = lr / state->bc1 (device, one correctly rounded fp32
+ * division, the same value in every workgroup of the tensor).  With a clip state gs = grad_scale * clip->coef, once, as
+ * in ct_sgd_step_clipped; else gs = grad_scale.  Per element, one fp32 rounding per line, no FMA, sqrt and both
+ * divisions correctly rounded:
+ *     g   = grad * gs
+ *     p   = p - lw * p                       (only when weight_decay != 0)
+ *     m   = beta1 * m + om1 * g
+ *     v   = beta2 * v + (om2 * g) * g
+ *     den = sqrtf(v) / rs2 + eps             rs2 = state->rs2
+ *     p   = p - a * (m / den)
+ *     ema = d * ema + om * p                 (only with ema_dev, iff ema_dev->applied; the line of ct_sgd_step_ema)
+ * A NumPy float32 restatement of these lines reproduces the result bit for bit as long as no intermediate is subnormal.
+ * exp_avg and exp_avg_sq start as zeros the caller allocates: there is no first-step flag.  A skipped step
+ * (clip->finite == 0) writes nothing at all: param, exp_avg, exp_avg_sq, ema and (ct_adamw_begin) the record keep their
+ * bits.  Without a clip state non-finite gradients propagate as the lines say.
+ * Transport as ct_sgd_step: the table travels in the kernel arguments, ct_adamw_tensors_per_launch() (59) tensors per
+ * launch, ceil(tensors with numel > 0 / 59) launches; 16-byte accesses when all non-NULL pointers of a tensor share their
+ * offset inside the 16-byte line, else one dword per lane; no byte outside [ptr, ptr + numel) is touched; plain vector
+ * stores; the whole table is validated before any device work; no allocation, no host synchronisation; capturable.
+ * CT_ERR_INVALID (nothing launched): the list of ct_sgd_step, plus, for a non-empty tensor, a NULL exp_avg, exp_avg_sq
+ * or state, or a state that is not 8-byte aligned; eps < 0 or NaN; beta1 or beta2 outside [0, 1) or NaN; an ema pointer
+ * without ema_dev, or ema_dev with a non-empty tensor whose ema is NULL; a misaligned clip or ema state. */
+typedef struct ct_adam_state {
+    double beta1_pow, beta2_pow;  /* beta^step as running binary64 products; not read while step == 0 */
+    int    step;                  /* applied steps of this tensor, saturates at INT_MAX */
+    int    applied;               /* 1: the last ct_adamw_begin advanced this record, 0: skipped step */
+    float  bc1;                   /* (float)(1.0 - beta1_pow) */
+    float  rs2;                   /* sqrtf((float)(1.0 - beta2_pow)) */
+} ct_adam_state;
+typedef struct ct_adamw_tensor {
+    float* param;                 /* dev, updated in place */
+    const float* grad;            /* dev, read only, must not alias the others */
+    float* exp_avg;               /* dev, updated in place; zeros before the first step */
+    float* exp_avg_sq;            /* dev, updated in place; zeros before the first step */
+    float* ema;                   /* NULL unless ema_dev is given; then non-NULL for every non-empty tensor */
+    const ct_adam_state* state;   /* the record ct_adamw_begin has just advanced */
+    int64_t numel;                /* 0 .. 2^31-1 */
+    float lr, weight_decay;
+} ct_adamw_tensor;
+int ct_adamw_begin_indices_per_launch(void);
+int ct_adamw_begin(ct_adam_state* states_dev, const int* index_host, int n, double beta1, double beta2,
+                   const ct_clip_state* clip_dev_or_null, ct_stream_t stream);
+int ct_adamw_tensors_per_launch(void);
+int ct_adamw_step(const ct_adamw_tensor* items_host, int n, float beta1, float beta2, float eps, float grad_scale,
+                  const ct_clip_state* clip_dev_or_null, const ct_ema_state* ema_dev_or_null, ct_stream_t stream);
+
 /* ---------------------------------------- batched test.py post-processing ---- */
 
 /* test.py:136-161 for a batch: per (image, class>=1) select score > conf_thresh, order by

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
    python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
-                               [--clip-norm X] [--ema DECAY] [--deterministic] [--loc-loss NAME] [--loc-weight X]
+                               [--optimizer sgd|adamw] [--clip-norm X] [--ema DECAY] [--deterministic] [--loc-loss NAME] [--loc-weight X]
                                [--conf-loss focal [--focal-gamma X --focal-alpha X]] [--matcher ssd|atss [--atss-topk K]] [--json]
    --classes: classes of the conf head; default 20, with --phase 2 the width of the Context-Transformer block (60 for 'transfer',
    15 for 'incre': the head feeds the block);
    --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
+   --optimizer adamw: ctdet.optim.FusedAdamW (lr 1e-4, betas 0.9 / 0.999, eps 1e-8, weight decay 5e-4; the fused multi-tensor HIP AdamW
+   update) in place of SGD; --clip-norm and --ema then go to it; the JSON line is always printed;
    --wgrad-h2: CTDET_WGRAD_H2=1 for this run (the 1x1 weight gradients on ct_conv2d_wgrad_h2);
    --clip-norm X: FusedSGD(max_grad_norm=X) (implies --fused-sgd; `inf` is the non-finite guard alone): the norm and the
    clipping coefficient are computed on the device in front of the update, a non-finite step is skipped;
@@ -39,7 +41,7 @@ ap.add_argument('--phase', type=int, default=1); ap.add_argument('--setting', de
 ap.add_argument('--fused-sgd', action='store_true'); ap.add_argument('--per-tensor-groups', action='store_true')
 ap.add_argument('--wgrad-h2', action='store_true'); ap.add_argument('--deterministic', action='store_true')
 ap.add_argument('--clip-norm', type=float, default=None); ap.add_argument('--json', action='store_true')
-ap.add_argument('--ema', type=float, default=None)
+ap.add_argument('--ema', type=float, default=None); ap.add_argument('--optimizer', choices=('sgd', 'adamw'), default='sgd')
 ap.add_argument('--loc-loss', default=None); ap.add_argument('--loc-weight', type=float, default=1.0)
 ap.add_argument('--conf-loss', default=None); ap.add_argument('--focal-gamma', type=float, default=None)
 ap.add_argument('--focal-alpha', type=float, default=None)
@@ -78,7 +80,12 @@ def make_opt():
     if a.per_tensor_groups:
         from utils import solver
         return solver.build_optimizer(types.SimpleNamespace(method='ours', phase=a.phase, lr=1e-4, momentum=0.9, weight_decay=5e-4,
-                                                            max_grad_norm=a.clip_norm, ema_decay=a.ema), net, fused=a.fused_sgd)
+                                                            max_grad_norm=a.clip_norm, ema_decay=a.ema, optimizer=a.optimizer),
+                                      net, fused=a.fused_sgd or a.optimizer == 'adamw')
+    if a.optimizer == 'adamw':
+        from ctdet.optim import FusedAdamW, WeightEMA
+        return FusedAdamW(net.parameters(), lr=1e-4, weight_decay=5e-4, max_grad_norm=a.clip_norm,
+                          ema=None if a.ema is None else WeightEMA(net, a.ema))
     if a.fused_sgd:
         from ctdet.optim import FusedSGD, WeightEMA
         return FusedSGD(net.parameters(), lr=1e-4, momentum=0.9, weight_decay=5e-4, max_grad_norm=a.clip_norm,
@@ -120,9 +127,9 @@ if rank == 0:
     n = a.steps
     print('RFBNet-%d phase %d bs=%d x %d GPU(s)%s: %.1f ms/step = %.1f img/s | fwd %.1f  loss %.1f  bwd %.1f ms | loss %.4f'
           % (a.size, a.phase, a.batch, world, ' [%s, %d groups]' % (type(opt).__name__, len(opt.param_groups))
-             if a.fused_sgd or a.per_tensor_groups else '', dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
+             if a.fused_sgd or a.per_tensor_groups or a.optimizer != 'sgd' else '', dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
     if a.json or a.clip_norm is not None or a.ema is not None or a.deterministic or a.loc_loss is not None or a.loc_weight != 1.0 \
-            or a.conf_loss is not None or a.matcher is not None:
+            or a.conf_loss is not None or a.matcher is not None or a.optimizer != 'sgd':
         row = {'train_bench': 'RFBNet-%d phase %d' % (a.size, a.phase), 'batch': a.batch, 'gpus': world, 'steps': n,
                'optimizer': type(opt).__name__, 'groups': len(opt.param_groups), 'ms_per_step': round(dt * 1e3, 3),
                'fwd_ms': round(tf / n, 3), 'loss_ms': round(tl / n, 3), 'bwd_ms': round(tb / n, 3), 'opt_ms': round(to / n, 3),
