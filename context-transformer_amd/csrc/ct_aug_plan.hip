@@ -7,6 +7,8 @@
 //             sample's workspace slot.
 //   launch 2  aug_pack_kernel: one workgroup scans the per-sample counts into gt_off_out, refuses samples whose image
 //             index decreases, copies the rows and writes the status words.
+// ct_aug_plan_mosaic runs the same two launches over 4 samples per image with aug_mosaic_kernel between them: the four
+// samples' rows are mapped into the tiles of one composed image (include/ctdet.h MOSAIC).
 // All decision arithmetic is fp64 with +, -, *, /, sqrt, comparisons and truncation only (compiled with contraction
 // off), the sequence ctdet/aug_plan_ref.py evaluates in numpy: both give the same bytes.
 #include "ct_common.h"
@@ -337,7 +339,100 @@ __global__ __launch_bounds__(PACK_THREADS) void aug_pack_kernel(const ct_aug_sam
     }
 }
 
+// Mosaic, between the two launches above: one wave per image composes its four samples (include/ctdet.h MOSAIC).
+// It draws the meeting point, writes the four tiles, refuses a sample whose image field is not its group, maps each
+// sample's rows from its own canvas into its tile (fp64, operation by operation), filters them in units of the output
+// image and compacts them in place in the sample's workspace slot, and rewrites the per-sample counts.  `fixed` gets
+// the sample table with image = s / 4, which is what aug_pack_kernel then scans: a foreign image field cannot make
+// it refuse a neighbour.
+constexpr int SLOT_MOSAIC = 0x300;
+
+__device__ __forceinline__ bool mosaic_row(const float* q, const ct_mosaic_tile& t, int S, double (&o)[4])
+{
+    o[0] = (t.x0 + (double)q[0] * t.w) / S; o[1] = (t.y0 + (double)q[1] * t.h) / S;
+    o[2] = (t.x0 + (double)q[2] * t.w) / S; o[3] = (t.y0 + (double)q[3] * t.h) / S;
+    return fmin(o[2] - o[0], o[3] - o[1]) > 0.01;
+}
+
+__global__ __launch_bounds__(64) void aug_mosaic_kernel(const ct_aug_sample* __restrict__ samples, int num_images,
+                                                        int max_gt, unsigned long long seed, int S, int margin,
+                                                        AugPlan* __restrict__ plans, ct_mosaic_tile* __restrict__ tiles,
+                                                        ct_aug_sample* __restrict__ fixed, int* __restrict__ counts,
+                                                        float* rows)
+{
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= num_images) return;
+    const Words d = philox(seed, samples[4 * i].sample_id, SLOT_MOSAIC, 0);
+    const int span = S - 2 * margin + 1;
+    const int cx = margin + randrange(span, d.w[0]), cy = margin + randrange(span, d.w[1]);
+    int cnt = 0;
+    if (lane < 4) {
+        const int s = 4 * i + lane;
+        ct_aug_sample sm = samples[s];
+        cnt = counts[s];
+        if (sm.image != i) {                        // refused here; H < 1, W < 1 were refused by the plan launch
+            AugPlan p = plans[s];
+            identity_plan(p, p.H, p.W);
+            plans[s] = p;
+            cnt = -1;
+        }
+        sm.image = i;
+        fixed[s] = sm;
+        ct_mosaic_tile t;
+        t.x0 = (lane & 1) ? cx : 0; t.y0 = (lane & 2) ? cy : 0;
+        t.w = (lane & 1) ? S - cx : cx; t.h = (lane & 2) ? S - cy : cy;
+        tiles[s] = t;
+    }
+    ct_mosaic_tile tile[4];
+    int n[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        tile[k].x0 = (k & 1) ? cx : 0; tile[k].y0 = (k & 2) ? cy : 0;
+        tile[k].w = (k & 1) ? S - cx : cx; tile[k].h = (k & 2) ? S - cy : cy;
+        n[k] = min(max(__shfl(cnt, k), 0), max_gt);
+    }
+    // pass 1: does any mapped row of the image pass the filter
+    bool any_kept = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float* src = rows + (size_t)(4 * i + k) * max_gt * 6;
+        for (int base = 0; base < n[k]; base += 64) {
+            const int j = base + lane;
+            double o[4];
+            any_kept |= __ballot(j < n[k] && mosaic_row(src + (size_t)j * 6, tile[k], S, o)) != 0;
+        }
+    }
+    // pass 2: map, filter and compact in place.  A row moves to an index no larger than its own, and every lane of a
+    // stride has read its row before any lane writes (the stores depend on the wave's loads), so no row is lost.
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float* slot = rows + (size_t)(4 * i + k) * max_gt * 6;
+        int at = 0;
+        for (int base = 0; base < n[k]; base += 64) {
+            const int j = base + lane;
+            double o[4];
+            float label = 0.f, weight = 0.f;
+            bool keep = false;
+            if (j < n[k]) {
+                const float* q = slot + (size_t)j * 6;
+                keep = mosaic_row(q, tile[k], S, o) || !any_kept;
+                label = q[4]; weight = q[5];
+            }
+            const unsigned long long mask = __ballot(keep);
+            if (keep) {
+                float* q = slot + (size_t)(at + __popcll(mask & ((1ull << lane) - 1ull))) * 6;
+                q[0] = (float)o[0]; q[1] = (float)o[1]; q[2] = (float)o[2]; q[3] = (float)o[3];
+                q[4] = label; q[5] = weight;
+            }
+            at += __popcll(mask);
+        }
+        if (lane == k) cnt = cnt < 0 ? -1 : at;
+    }
+    if (lane < 4) counts[4 * i + lane] = cnt;
+}
+
 size_t counts_bytes(int num_samples) { return ctdet::align_up((size_t)num_samples * sizeof(int), 256); }
+size_t fixed_bytes(int num_samples) { return ctdet::align_up((size_t)num_samples * sizeof(ct_aug_sample), 256); }
 
 }  // namespace
 
@@ -381,6 +476,63 @@ extern "C" int ct_aug_plan(const ct_aug_sample* samples, int num_samples, const 
         hipLaunchKernelGGL(aug_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, st, samples, num_samples, num_images, max_gt,
                            (AugPlan*)plans_out, (const int*)counts, (const float*)rows, truths_out, truths_cap, gt_off_out,
                            status);
+        CT_LAUNCH_CHECK("aug_pack_kernel");
+    }
+    return CT_OK;
+}
+
+extern "C" size_t ct_aug_plan_mosaic_workspace_bytes(int num_images, int max_gt)
+{
+    if (num_images < 1 || max_gt < 1 || num_images > (1 << 26)) return 0;
+    const int num_samples = 4 * num_images;
+    return counts_bytes(num_samples) + fixed_bytes(num_samples) + (size_t)num_samples * max_gt * 6 * sizeof(float);
+}
+
+extern "C" int ct_aug_plan_mosaic(const ct_aug_sample* samples, int num_images, const float* boxes, int total_boxes,
+                                  int max_gt, unsigned long long seed, float p_expand, const int* interp_of_draw5,
+                                  const float* fill3, int size, int margin, void* plans_out, ct_mosaic_tile* tiles_out,
+                                  float* truths_out, int truths_cap, int* gt_off_out, int* status, void* workspace,
+                                  size_t workspace_bytes, ct_stream_t stream)
+{
+    CT_REQUIRE(samples && interp_of_draw5 && fill3 && plans_out && tiles_out && truths_out && gt_off_out && status &&
+               workspace, "ct_aug_plan_mosaic: null pointer");
+    CT_REQUIRE(boxes || total_boxes == 0, "ct_aug_plan_mosaic: boxes is null with total_boxes=%d", total_boxes);
+    CT_REQUIRE(num_images >= 1 && num_images <= (1 << 26) && total_boxes >= 0 && max_gt >= 1 && truths_cap >= 0,
+               "ct_aug_plan_mosaic: num_images=%d total_boxes=%d max_gt=%d truths_cap=%d", num_images, total_boxes, max_gt,
+               truths_cap);
+    CT_REQUIRE(size >= 2 && size <= 4096, "ct_aug_plan_mosaic: size=%d", size);
+    CT_REQUIRE(margin >= 1 && margin <= size / 2, "ct_aug_plan_mosaic: margin=%d outside 1..%d", margin, size / 2);
+    const int num_samples = 4 * num_images;
+    CT_REQUIRE((size_t)num_samples * max_gt <= (size_t)1 << 28,
+               "ct_aug_plan_mosaic: 4 * num_images * max_gt = %zu is too large", (size_t)num_samples * max_gt);
+    const size_t need = ct_aug_plan_mosaic_workspace_bytes(num_images, max_gt);
+    CT_REQUIRE(workspace_bytes >= need, "ct_aug_plan_mosaic: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    CT_REQUIRE(((size_t)workspace & 15) == 0, "ct_aug_plan_mosaic: workspace is not 16-byte aligned");
+    Interp5 ip;
+    for (int i = 0; i < 5; ++i) ip.v[i] = interp_of_draw5[i];
+    Fill3 fl;
+    for (int i = 0; i < 3; ++i) fl.v[i] = fill3[i];
+    int* counts = (int*)workspace;
+    ct_aug_sample* fixed = (ct_aug_sample*)((char*)workspace + counts_bytes(num_samples));
+    float* rows = (float*)((char*)fixed + fixed_bytes(num_samples));
+    hipStream_t st = ctdet::as_stream(stream);
+    {
+        CT_PROF("aug_plan_kernel", st);
+        hipLaunchKernelGGL(aug_plan_kernel, dim3(num_samples), dim3(64), 0, st, samples, num_samples, boxes, total_boxes,
+                           num_images, max_gt, seed, (double)p_expand, ip, fl, (AugPlan*)plans_out, counts, rows);
+        CT_LAUNCH_CHECK("aug_plan_kernel");
+    }
+    {
+        CT_PROF("aug_mosaic_kernel", st);
+        hipLaunchKernelGGL(aug_mosaic_kernel, dim3(num_images), dim3(64), 0, st, samples, num_images, max_gt, seed, size,
+                           margin, (AugPlan*)plans_out, tiles_out, fixed, counts, rows);
+        CT_LAUNCH_CHECK("aug_mosaic_kernel");
+    }
+    {
+        CT_PROF("aug_pack_kernel", st);
+        hipLaunchKernelGGL(aug_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, st, (const ct_aug_sample*)fixed, num_samples,
+                           num_images, max_gt, (AugPlan*)plans_out, (const int*)counts, (const float*)rows, truths_out,
+                           truths_cap, gt_off_out, status);
         CT_LAUNCH_CHECK("aug_pack_kernel");
     }
     return CT_OK;

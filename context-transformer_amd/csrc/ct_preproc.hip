@@ -175,11 +175,12 @@ __device__ inline void final_px(const unsigned char* __restrict__ img, const Aug
 }
 
 // output pixel (dx, dy) of the float filters (interp 0 linear, 1 nearest, 2 area; anything else runs as linear), before
-// rounding.  The one definition both augmentation kernels call.
-__device__ inline void float_filter_px(const unsigned char* __restrict__ img, const AugPlan& p, int S, int dx, int dy,
-                                       float (&acc)[3])
+// rounding, of a resize to tw x th (the whole square, or a mosaic tile).  The one definition every augmentation kernel
+// calls.
+__device__ inline void float_filter_px(const unsigned char* __restrict__ img, const AugPlan& p, int tw, int th, int dx,
+                                       int dy, float (&acc)[3])
 {
-    const float sx = (float)p.exp_w / S, sy = (float)p.exp_h / S;
+    const float sx = (float)p.exp_w / tw, sy = (float)p.exp_h / th;
     acc[0] = acc[1] = acc[2] = 0.f;
     if (p.interp == 1) {                        // INTER_NEAREST: floor(d * scale)
         final_px(img, p, min((int)floorf(dx * sx), p.exp_w - 1), min((int)floorf(dy * sy), p.exp_h - 1), acc);
@@ -233,8 +234,41 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
     if (pix >= S * S) return;
     const int dy = pix / S, dx = pix - dy * S;
     float acc[3];
-    float_filter_px(img, p, S, dx, dy, acc);
+    float_filter_px(img, p, S, S, dx, dy, acc);
     store_float_px(acc, out + (long)n * 3 * S * S + pix, S, m0, m1, m2);
+}
+
+// Mosaic (include/ctdet.h MOSAIC): image n is composed of the plans 4n..4n+3, each resized into its tile instead of
+// the whole square.  A thread finds its pixel's tile with four comparisons (the lowest slot that holds it; the
+// differences are formed unsigned, so no tile content overflows) and runs the filter of augment_kernel with the tile's
+// size as the resize target.  Lanes diverge only where a wave crosses a seam.  A pixel no tile holds gets slot 0's
+// canvas fill: that, and skipping empty tiles, is what makes foreign tile tables memory-safe.
+__global__ __launch_bounds__(256) void augment_mosaic_kernel(const unsigned char* __restrict__ src, const AugPlan* __restrict__ plans,
+                                                             const ct_mosaic_tile* __restrict__ tiles, float* __restrict__ out,
+                                                             int S, float m0, float m1, float m2)
+{
+    const int n = blockIdx.y;
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= S * S) return;
+    const int dy = pix / S, dx = pix - dy * S;
+    int k = -1, tx = 0, ty = 0, tw = 0, th = 0;
+#pragma unroll
+    for (int kk = 3; kk >= 0; --kk) {
+        const ct_mosaic_tile t = tiles[4 * n + kk];
+        const unsigned ux = (unsigned)dx - (unsigned)t.x0, uy = (unsigned)dy - (unsigned)t.y0;
+        if (t.w >= 1 && t.h >= 1 && ux < (unsigned)t.w && uy < (unsigned)t.h) { k = kk; tx = (int)ux; ty = (int)uy; tw = t.w; th = t.h; }
+    }
+    float* o = out + (long)n * 3 * S * S + pix;
+    float acc[3];
+    if (k < 0) {
+        const AugPlan& p0 = plans[4 * n];
+        acc[0] = (float)(int)p0.fill[0]; acc[1] = (float)(int)p0.fill[1]; acc[2] = (float)(int)p0.fill[2];
+        o[0] = acc[0] - m0; o[(long)S * S] = acc[1] - m1; o[2L * S * S] = acc[2] - m2;
+        return;
+    }
+    const AugPlan p = plans[4 * n + k];
+    float_filter_px(src + p.src_off, p, tw, th, tx, ty, acc);
+    store_float_px(acc, o, S, m0, m1, m2);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -281,7 +315,7 @@ __global__ __launch_bounds__(256) void augment_taps_kernel(const unsigned char* 
     if (p.interp != 3 && p.interp != 4) {
         if (!live) return;
         float acc[3];
-        float_filter_px(img, p, S, dx, dy, acc);
+        float_filter_px(img, p, S, S, dx, dy, acc);
         store_float_px(acc, o, S, m0, m1, m2);
         return;
     }
@@ -375,6 +409,20 @@ extern "C" int ct_preproc_augment(const unsigned char* src, const void* plans, i
     hipLaunchKernelGGL(augment_kernel, grid, dim3(256), 0, ctdet::as_stream(stream), src, (const AugPlan*)plans, out, size,
                        means3[0], means3[1], means3[2]);
     CT_LAUNCH_CHECK("augment_kernel");
+    return CT_OK;
+}
+
+extern "C" int ct_preproc_augment_mosaic(const unsigned char* src, const void* plans, const ct_mosaic_tile* tiles,
+                                         int num_images, int size, const float* means3, float* out, ct_stream_t stream)
+{
+    CT_REQUIRE(src && plans && tiles && out && means3, "ct_preproc_augment_mosaic: null pointer");
+    CT_REQUIRE(num_images > 0 && num_images <= 65535 && size >= 2 && size <= 4096,
+               "ct_preproc_augment_mosaic: num_images=%d size=%d", num_images, size);
+    static_assert(sizeof(ct_mosaic_tile) == 16, "ct_mosaic_tile layout is mirrored in ctdet/aug_plan_ref.py");
+    dim3 grid((size * size + 255) / 256, num_images);
+    hipLaunchKernelGGL(augment_mosaic_kernel, grid, dim3(256), 0, ctdet::as_stream(stream), src, (const AugPlan*)plans,
+                       tiles, out, size, means3[0], means3[1], means3[2]);
+    CT_LAUNCH_CHECK("augment_mosaic_kernel");
     return CT_OK;
 }
 

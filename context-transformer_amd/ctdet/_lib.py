@@ -325,6 +325,10 @@ SIGNATURES = {
     'ct_aug_plan_workspace_bytes': (_Z, [_I, _I]),
     'ct_aug_plan': (_I, [_P, _I, _P, _I, _I, _I, C.c_ulonglong, _F, C.POINTER(_I), C.POINTER(_F), _P, _P, _I, _P, _P, _P,
                          _Z, _P]),
+    'ct_aug_plan_mosaic_workspace_bytes': (_Z, [_I, _I]),
+    'ct_aug_plan_mosaic': (_I, [_P, _I, _P, _I, _I, C.c_ulonglong, _F, C.POINTER(_I), C.POINTER(_F), _I, _I, _P, _P, _P,
+                                _I, _P, _P, _P, _Z, _P]),
+    'ct_preproc_augment_mosaic': (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     'ct_ctx_pool_fwd': (_I, [_P, _LL, _P, _LL, _I, _I, _I, _I, _I, _P]),
     'ct_ctx_attention_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     'ct_ctx_attention_piece_products': (_I, []),

@@ -15,6 +15,7 @@ coin = w >> 31.
     0x100 + r      63       crop mode rr(7)
     0x100 + r      0..49    scale U(.3,1)      ratio u           left rr(W - w)      top rr(H - h)
     0x200 + r      0..63    scale U(1,4)       ratio u           left rr(w - cw + 1) top rr(h - ch + 1)
+    0x300 (mosaic) 0        cx margin+rr(S-2m+1) cy likewise     (of a group's first sample; `mosaic_batch` below)
 
 Crop rounds r = 0..255, expand rounds r = 0..63; the lowest passing lane of the first round with one wins.
 """
@@ -280,3 +281,77 @@ def make_samples(shapes, targets, images=None, sample_ids=None, cls=-1, weights=
     s['weight'] = 1.0 if weights is None else weights
     boxes = np.concatenate(parts, 0) if parts else np.zeros((0, 5), dtype=np.float32)
     return s, np.ascontiguousarray(boxes, dtype=np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------- mosaic
+SLOT_MOSAIC = 0x300
+TILE_DTYPE = np.dtype([('x0', '<i4'), ('y0', '<i4'), ('w', '<i4'), ('h', '<i4')])
+assert TILE_DTYPE.itemsize == 16                # ct_mosaic_tile
+
+MosaicResult = collections.namedtuple('MosaicResult', 'plans tiles truths gt_off status sample_rows fallback info')
+
+
+def mosaic_tiles(seed, sample_id, size, margin):
+    """The four tiles of the image whose first sample draws with `sample_id` -> TILE_DTYPE [4] (include/ctdet.h MOSAIC)."""
+    w = draws(seed, sample_id, SLOT_MOSAIC, 0)
+    span = size - 2 * margin + 1
+    cx, cy = margin + int(randrange(span, w[0])), margin + int(randrange(span, w[1]))
+    t = np.zeros(4, dtype=TILE_DTYPE)
+    t['x0'], t['y0'] = (0, cx, 0, cx), (0, 0, cy, cy)
+    t['w'], t['h'] = (cx, size - cx, cx, size - cx), (cy, cy, size - cy, size - cy)
+    return t
+
+
+def mosaic_rows(rows, tile, size):
+    """float32 rows [k,6] of one sample, normalised to its canvas -> (float32 rows in the output image, keep [k])."""
+    r = np.asarray(rows, dtype=np.float32).reshape(-1, 6)
+    x0, y0, w, h = [float(tile[k]) for k in ('x0', 'y0', 'w', 'h')]
+    S = float(size)
+    X1, Y1 = (x0 + r[:, 0].astype(np.float64) * w) / S, (y0 + r[:, 1].astype(np.float64) * h) / S
+    X2, Y2 = (x0 + r[:, 2].astype(np.float64) * w) / S, (y0 + r[:, 3].astype(np.float64) * h) / S
+    out = r.copy()
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3] = X1, Y1, X2, Y2
+    return out, np.minimum(X2 - X1, Y2 - Y1) > 0.01
+
+
+def mosaic_batch(samples, boxes, num_images, max_gt, seed, p_expand, interp_of_draw, fill, size, margin, truths_cap=None):
+    """What `ct_aug_plan_mosaic` computes, safety rule included.  samples: SAMPLE_DTYPE array [4*num_images],
+    group-major.  -> MosaicResult: plans (PLAN_DTYPE [4n]), tiles (TILE_DTYPE [4n]), truths float32 [rows, 6] in the
+    output image's units, gt_off int32 [n+1], status int32 [4], each sample's kept rows, whether an image's fallback
+    fired [n], and plan_sample's dicts (None for a refused sample)."""
+    samples = np.asarray(samples, dtype=SAMPLE_DTYPE)
+    num_images, size, margin = int(num_images), int(size), int(margin)
+    if len(samples) != 4 * num_images or num_images < 1:
+        raise ValueError('mosaic_batch: %d samples for %d images' % (len(samples), num_images))
+    if size < 2 or not 1 <= margin <= size // 2:
+        raise ValueError('mosaic_batch: size %d, margin %d' % (size, margin))
+    group = np.arange(len(samples)) // 4
+    fixed = samples.copy()
+    fixed['image'] = group
+    res = plan_batch(fixed, boxes, num_images, max_gt, seed, p_expand, interp_of_draw, fill)
+    plans, rows_of, info = res.plans.copy(), list(res.sample_rows), list(res.info)
+    bad = int(res.status[1])
+    for s in np.flatnonzero(samples['image'] != group):
+        if info[s] is not None:                     # planned, but its image field is foreign: refused here
+            _identity(plans[s], int(samples[s]['H']), int(samples[s]['W']))
+            rows_of[s], info[s] = np.zeros((0, 6), dtype=np.float32), None
+            bad += 1
+    tiles = np.zeros(len(samples), dtype=TILE_DTYPE)
+    fallback = np.zeros(num_images, dtype=bool)
+    counts = np.zeros(num_images, dtype=np.int64)
+    for i in range(num_images):
+        tiles[4 * i:4 * i + 4] = mosaic_tiles(seed, samples[4 * i]['sample_id'], size, margin)
+        mapped = [mosaic_rows(rows_of[4 * i + k], tiles[4 * i + k], size) for k in range(4)]
+        n_rows, n_kept = sum(len(m[0]) for m in mapped), sum(int(m[1].sum()) for m in mapped)
+        fallback[i] = n_rows > 0 and n_kept == 0
+        for k, (r, keep) in enumerate(mapped):
+            rows_of[4 * i + k] = r if fallback[i] else r[keep]
+            counts[i] += len(rows_of[4 * i + k])
+    all_rows = np.concatenate(rows_of, 0)
+    n_rows = len(all_rows)
+    cap = n_rows if truths_cap is None else int(truths_cap)
+    gt_off = np.minimum(np.concatenate([[0], np.cumsum(counts)]), cap).astype(np.int32)
+    dropped = max(n_rows - cap, 0)
+    status = np.array([(STATUS_BAD_SAMPLE if bad else 0) | (STATUS_ROWS_DROPPED if dropped else 0), bad, dropped, n_rows],
+                      dtype=np.int32)
+    return MosaicResult(plans, tiles, all_rows[:cap], gt_off, status, rows_of, fallback, info)

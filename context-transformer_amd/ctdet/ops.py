@@ -1069,6 +1069,20 @@ class Augmenter:
               'ct_preproc_augment')
         return out
 
+    def render_mosaic(self, plans_d, tiles_d, n, out=None):
+        """ct_preproc_augment_mosaic: n images, each composed of four device-resident plan records (uint8
+        [>= 4n*96]) resized into their tiles (uint8 [>= 4n*16], ct_mosaic_tile); what AugPlanner.mosaic returns."""
+        if n == 0 or plans_d.numel() < 4 * n * 96 or tiles_d.numel() < 4 * n * 16:
+            raise ValueError('Augmenter.render_mosaic: %d images, %d plan bytes, %d tile bytes'
+                             % (n, plans_d.numel(), tiles_d.numel()))
+        if out is None:
+            out = torch.empty(n, 3, self.size, self.size, device=self.device, dtype=torch.float32)
+        check(lib().ct_preproc_augment_mosaic(_dev(self.dev, 'src', torch.uint8), _dev(plans_d, 'plans', torch.uint8),
+                                              _dev(tiles_d, 'tiles', torch.uint8), n, self.size,
+                                              C.cast(self.means, C.c_void_p), _dev(out, 'out'), _stream()),
+              'ct_preproc_augment_mosaic')
+        return out
+
 
 AUG_SAMPLE_DTYPE = np.dtype([('src_off', '<i8'), ('sample_id', '<u8'), ('H', '<i4'), ('W', '<i4'), ('box_begin', '<i4'),
                              ('box_end', '<i4'), ('image', '<i4'), ('cls', '<i4'), ('weight', '<f4'), ('flags', '<i4')])
@@ -1101,15 +1115,9 @@ class AugPlanner:
             self.stage = torch.empty(need, dtype=torch.uint8).pin_memory()
             self.dev = torch.empty(need, dtype=torch.uint8, device=self.device)
 
-    def __call__(self, samples, boxes, num_images, max_gt, truths_cap=None):
-        """samples: AUG_SAMPLE_DTYPE array [n]; boxes float32 [total,5]; max_gt: boxes per sample the kernel looks at.
-        -> (plans uint8 [n*96] on the device, PackedTargets).  truths_cap defaults to the input box count, which the
-        rows cannot exceed."""
-        samples = np.ascontiguousarray(samples, dtype=AUG_SAMPLE_DTYPE)
-        boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 5)
-        n, total, num_images, max_gt = len(samples), len(boxes), int(num_images), int(max_gt)
-        if n == 0 or num_images < 1 or max_gt < 1:
-            raise ValueError('AugPlanner: %d samples, %d images, max_gt %d' % (n, num_images, max_gt))
+    def _upload(self, samples, boxes):
+        """Stage the sample records and the boxes and enqueue their one H2D copy -> byte offset of the boxes."""
+        n, total = len(samples), len(boxes)
         if self.copied is not None:
             self.copied.synchronize()
         self._reserve(n, total)
@@ -1121,6 +1129,18 @@ class AugPlanner:
         self.copied = torch.cuda.Event()
         self.copied.record()
         self.upload_bytes = nb
+        return nb_s
+
+    def __call__(self, samples, boxes, num_images, max_gt, truths_cap=None):
+        """samples: AUG_SAMPLE_DTYPE array [n]; boxes float32 [total,5]; max_gt: boxes per sample the kernel looks at.
+        -> (plans uint8 [n*96] on the device, PackedTargets).  truths_cap defaults to the input box count, which the
+        rows cannot exceed."""
+        samples = np.ascontiguousarray(samples, dtype=AUG_SAMPLE_DTYPE)
+        boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 5)
+        n, total, num_images, max_gt = len(samples), len(boxes), int(num_images), int(max_gt)
+        if n == 0 or num_images < 1 or max_gt < 1:
+            raise ValueError('AugPlanner: %d samples, %d images, max_gt %d' % (n, num_images, max_gt))
+        nb_s = self._upload(samples, boxes)
         cap = max(total, 1) if truths_cap is None else int(truths_cap)
         dev = self.device
         plans = torch.empty(n * 96, dtype=torch.uint8, device=dev)
@@ -1141,6 +1161,36 @@ class AugPlanner:
         ok = (img >= 0) & (img < num_images)
         per_image = np.bincount(img[ok], weights=np.maximum(cnt[ok], 0), minlength=1) if ok.any() else np.zeros(1)
         return plans, PackedTargets(truths, gt_off, max(int(per_image.max()), 1))
+
+    def mosaic(self, samples, boxes, num_images, max_gt, size, margin, truths_cap=None):
+        """ct_aug_plan_mosaic (three launches): samples AUG_SAMPLE_DTYPE [4*num_images], group-major (sample s is slot
+        s % 4 of image s // 4); boxes float32 [total,5].  -> (plans uint8 [4n*96], tiles uint8 [4n*16], PackedTargets
+        in the output image's units), all on the device.  Staged and uploaded like `__call__`."""
+        samples = np.ascontiguousarray(samples, dtype=AUG_SAMPLE_DTYPE)
+        boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 5)
+        n, total, num_images, max_gt = len(samples), len(boxes), int(num_images), int(max_gt)
+        if num_images < 1 or n != 4 * num_images or max_gt < 1:
+            raise ValueError('AugPlanner.mosaic: %d samples, %d images, max_gt %d' % (n, num_images, max_gt))
+        nb_s = self._upload(samples, boxes)
+        cap = max(total, 1) if truths_cap is None else int(truths_cap)
+        dev = self.device
+        plans = torch.empty(n * 96, dtype=torch.uint8, device=dev)
+        tiles = torch.empty(n * 16, dtype=torch.uint8, device=dev)
+        truths = torch.empty(max(cap, 1), 6, dtype=torch.float32, device=dev)
+        gt_off = torch.empty(num_images + 1, dtype=torch.int32, device=dev)
+        self.status = torch.empty(4, dtype=torch.int32, device=dev)
+        ws_bytes = lib().ct_aug_plan_mosaic_workspace_bytes(num_images, max_gt)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(lib().ct_aug_plan_mosaic(_dev(self.dev, 'samples', torch.uint8), num_images,
+                                       C.c_void_p(self.dev.data_ptr() + nb_s), total, max_gt, self.seed, self.p_expand,
+                                       self.interp, self.fill, int(size), int(margin), _dev(plans, 'plans', torch.uint8),
+                                       _dev(tiles, 'tiles', torch.uint8), _dev(truths, 'truths'), cap,
+                                       _dev(gt_off, 'gt_off', torch.int32), _dev(self.status, 'status', torch.int32),
+                                       _dev(ws, 'workspace', torch.uint8), ws_bytes, _stream()), 'ct_aug_plan_mosaic')
+        # host-known bound of an image's rows: the boxes its four samples hand in (each capped at max_gt)
+        cnt = np.minimum(np.clip(samples['box_end'], 0, total) - np.clip(samples['box_begin'], 0, total), max_gt)
+        per_image = np.maximum(cnt, 0).reshape(num_images, 4).sum(1)
+        return plans, tiles, PackedTargets(truths, gt_off, max(int(per_image.max()), 1))
 
     def check(self):
         """Read the status words of the last call (a host synchronisation) and raise when a sample was refused or a

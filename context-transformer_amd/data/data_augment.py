@@ -11,6 +11,8 @@ batch are then produced by one gather kernel (`ct_preproc_augment`) that never m
 expanded intermediates.  `filters='cv2'` (or CTDET_AUG_FILTERS=cv2) adds the bicubic and Lanczos4 resize filters the
 reference also draws (`ct_preproc_augment_taps`); the default maps those two draws onto linear.
 `preproc.batch(images, targets)` is the batched entry that keeps 8 GPUs fed; `mixup_targets` / `mixup_images` are the mixup of data/voc0712.py:240-275.
+With `decisions='device'`, `preproc.batch_device` draws the decisions on the device too and `preproc.mosaic_device`
+composes four samples into each output image (`ct_aug_plan_mosaic`, `ct_preproc_augment_mosaic`).
 """
 import math
 import os
@@ -201,6 +203,14 @@ class preproc(object):
         return imgs[0], touts[0]
 
     # ------------------------------------------------------------------ decisions on the device
+    def _device_staging(self, per_image):
+        """The staging Augmenter and AugPlanner of the device path, sized for `per_image` samples per batch image
+        (2 for mixup, 4 for mosaic); created by the first call that needs them, replaced by larger ones on demand."""
+        if self._planner is None or self._aug_dev.max_batch < per_image * self.max_batch:
+            self._aug_dev = ops.Augmenter(self.resize, self.means, self.device, per_image * self.max_batch)
+            self._planner = ops.AugPlanner(self.device, self.seed, self.p, self.interp_of_draw, self.means,
+                                           per_image * self.max_batch)
+
     def batch_device(self, images, targets, sample_ids, cls=None, mix=None):
         """decisions='device': lists of uint8 HxWx3 images and [G,5] pixel targets, one 64-bit sample id per image ->
         (float32 [n,3,S,S], ops.PackedTargets(truths, gt_off, max_gt)), all on the device; no per-sample host work
@@ -213,10 +223,7 @@ class preproc(object):
         if n == 0 or n > self.max_batch or len(targets) != n or len(sample_ids) != n:
             raise ValueError('preproc.batch_device: %d images, %d targets, %d sample ids (max %d)'
                              % (n, len(targets), len(sample_ids), self.max_batch))
-        if self._planner is None:
-            self._aug_dev = ops.Augmenter(self.resize, self.means, self.device, 2 * self.max_batch)
-            self._planner = ops.AugPlanner(self.device, self.seed, self.p, self.interp_of_draw, self.means,
-                                           2 * self.max_batch)
+        self._device_staging(2)
         lam = [1.0] * n if mix is None else [float(v) for v in mix[2]]
         imgs, tgs, rec = [], [], []           # samples in image order: first, then second where there is one
         first, second = [], []
@@ -248,6 +255,39 @@ class preproc(object):
         order = torch.tensor(first + second, dtype=torch.int64).to(self.device, non_blocking=True)
         x = self._aug_dev.render(plans.view(m, 96).index_select(0, order).reshape(-1), 2 * n)
         return ops.mixup_blend(x[:n], x[n:], torch.tensor(lam, dtype=torch.float32).clamp(max=1.0).to(self.device)), packed
+
+    def mosaic_device(self, images, targets, sample_ids, cls=None, margin=None):
+        """decisions='device': four-image mosaic.  4n uint8 HxWx3 images and [G,5] pixel targets, group-major (sample
+        4i+k is slot k of image i: top-left, top-right, bottom-left, bottom-right), and n 64-bit sample ids ->
+        (float32 [n,3,S,S], ops.PackedTargets), all on the device.  Sample k of image i draws with id
+        (sample_ids[i] + k * 2**61) mod 2**64 (distinct from mixup's + 2**63); the tiles meet at a point drawn per
+        image at least `margin` (default S // 4) pixels from every edge (include/ctdet.h MOSAIC).  Every sample is
+        cropped / distorted / expanded / mirrored as in `batch_device`, then resized into its tile; the rows are in
+        units of the composed image."""
+        if self.decisions != 'device':
+            raise ValueError("preproc.mosaic_device needs preproc(..., decisions='device')")
+        n = len(sample_ids)
+        if n == 0 or n > self.max_batch or len(images) != 4 * n or len(targets) != 4 * n:
+            raise ValueError('preproc.mosaic_device: %d images, %d targets, %d sample ids (4 images per id, max %d ids)'
+                             % (len(images), len(targets), n, self.max_batch))
+        S = int(self.resize)
+        margin = S // 4 if margin is None else int(margin)
+        if not 1 <= margin <= S // 2:
+            raise ValueError('preproc.mosaic_device: margin %d outside 1..%d' % (margin, S // 2))
+        self._device_staging(4)
+        offs = self._aug_dev.upload(images)
+        samples = np.zeros(4 * n, dtype=ops.AUG_SAMPLE_DTYPE)
+        parts, pos = [], 0
+        for s, (img, tg) in enumerate(zip(images, targets)):
+            tg = np.asarray(tg, dtype=np.float32).reshape(-1, 5)
+            samples[s] = (offs[s], (int(sample_ids[s // 4]) + (s % 4) * 2 ** 61) % 2 ** 64, img.shape[0], img.shape[1],
+                          pos, pos + len(tg), s // 4, -1 if cls is None else cls, 1.0, 0)
+            pos += len(tg)
+            parts.append(tg)
+        boxes = np.concatenate(parts, 0) if pos else np.zeros((0, 5), dtype=np.float32)
+        max_gt = max(max(len(p) for p in parts), 1)
+        plans, tiles, packed = self._planner.mosaic(samples, boxes, n, max_gt, S, margin)
+        return self._aug_dev.render_mosaic(plans, tiles, n), packed
 
 
 def mixup_targets(target1, target2, lambd, ignore_minus1=False):

@@ -1446,6 +1446,51 @@ int ct_aug_plan(const ct_aug_sample* samples,   /* device array [num_samples] */
                 size_t workspace_bytes,
                 ct_stream_t stream);
 
+/* MOSAIC: four samples composed into one size x size image (csrc/ct_aug_plan.hip, csrc/ct_preproc.hip; host twin
+ * ctdet/aug_plan_ref.py mosaic_batch).  Opt-in; ct_aug_plan and ct_preproc_augment are untouched by it.
+ *
+ * SAMPLES  a batch of B images has 4B samples, group-major: sample s belongs to image s / 4 and sits in slot
+ *   k = s % 4: 0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right.
+ * PER-SAMPLE DECISIONS  every sample gets the plan and the rows ct_aug_plan gives it: the draws, the crop / expand /
+ *   mirror geometry, the cls constraint, the identity fallback and the flags / weight handling are unchanged and
+ *   keyed by (seed, sample_id) and nothing else.
+ * MEETING POINT  one Philox evaluation per image: key = seed, counter = (sample_id lo, sample_id hi, slot 0x300,
+ *   lane 0) with the sample_id of the group's FIRST sample (slot 0x300 is outside the draw table above).
+ *   cx = margin + randrange(S - 2*margin + 1) on w0, cy the same on w1; S = size, 1 <= margin <= S/2.
+ * TILES (x0, y0, w, h; output pixels)  k0 (0, 0, cx, cy)  k1 (cx, 0, S-cx, cy)  k2 (0, cy, cx, S-cy)
+ *   k3 (cx, cy, S-cx, S-cy).  They partition the square; every side is at least `margin`.
+ * PIXELS (ct_preproc_augment_mosaic)  output pixel (x, y) of image i belongs to the lowest slot k whose tile has
+ *   (unsigned)(x-x0) < (unsigned)w && (unsigned)(y-y0) < (unsigned)h.  Its value is what ct_preproc_augment computes
+ *   for the plan of sample 4i+k at output coordinate (x-x0, y-y0) when the resize target is w x h instead of S x S:
+ *   sx = (float)exp_w / w, sy = (float)exp_h / h; linear, nearest, area, area-when-enlarging taken as linear, unknown
+ *   interp values as linear; then round, clamp, minus mean, CHW.  No tap filters (interp 3 / 4 run as linear).
+ *   A tile with w < 1 or h < 1 is skipped; a pixel in no tile gets slot 0's canvas fill, (float)(int)fill[c] -
+ *   means3[c].  These two rules only make foreign tile tables memory-safe: the planner produces neither case.
+ * ROWS  a sample's rows are the float32 rows of its plan, normalised to its own canvas.  Each is mapped in fp64,
+ *   rounded operation by operation: X1 = (x0 + (double)x1 * w) / S, X2 likewise, Y1 = (y0 + (double)y1 * h) / S, Y2
+ *   likewise.  A row is kept when fmin(X2 - X1, Y2 - Y1) > 0.01 (the reference's rule, in units of the output image);
+ *   label and weight pass through; kept rows are float32 [X1, Y1, X2, Y2, label, weight].  FALLBACK: an image with
+ *   mapped rows of which none passes keeps all its mapped rows, unfiltered, so an image loses its targets only when
+ *   all four samples were refused or had none.  An image's rows are those of its samples in slot order, in the
+ *   planner's order within a sample.  gt_off_out, truths_cap and status keep their ct_aug_plan meaning.
+ * SAFETY RULE (this entry cannot inspect device tables)  a sample whose `image` field is not s / 4, or whose H or W
+ *   is below 1, is refused as in ct_aug_plan: identity plan, no rows, status bit 1; its tile is still rendered from
+ *   that identity plan.  box_begin / box_end are clamped; nothing is written outside the given sizes.
+ * INDEPENDENCE  an image's plans, tiles, rows and pixels depend on its own four samples and the seed only.
+ * Three launches (plan, mosaic, pack) and one (render); no allocation, no host synchronisation, no H2D copy,
+ * capturable.  CT_ERR_INVALID before any device work: null pointers, num_images < 1, max_gt < 1, size < 2, margin
+ * outside 1..size/2, a workspace that is too small or not 16-byte aligned. */
+typedef struct { int x0, y0, w, h; } ct_mosaic_tile;            /* 16 bytes */
+size_t ct_aug_plan_mosaic_workspace_bytes(int num_images, int max_gt);
+int ct_aug_plan_mosaic(const ct_aug_sample* samples /* dev [4*num_images] */, int num_images,
+                       const float* boxes, int total_boxes, int max_gt, unsigned long long seed, float p_expand,
+                       const int* interp_of_draw5, const float* fill3, int size, int margin,
+                       void* plans_out /* dev, 4*num_images x 96 B */, ct_mosaic_tile* tiles_out /* dev [4*num_images] */,
+                       float* truths_out, int truths_cap, int* gt_off_out, int* status,
+                       void* workspace, size_t workspace_bytes, ct_stream_t stream);
+int ct_preproc_augment_mosaic(const unsigned char* src, const void* plans, const ct_mosaic_tile* tiles,
+                              int num_images, int size, const float* means3, float* out, ct_stream_t stream);
+
 /* torch.nn.MaxPool2d of models/RFB_Net_vgg.py:328-330,338 (2x2 s2 [ceil], 3x3 s1 p1) on an NCHW
  * buffer: planes = batch*channels; windows are clipped to the input (ceil_mode semantics are
  * encoded in oh/ow by the caller). */
