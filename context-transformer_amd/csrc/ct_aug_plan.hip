@@ -1,5 +1,5 @@
 // libctdet: the augmentation DECISIONS and the box targets of data/data_augment.py `preproc.decide` on the device.
-// ct_preproc.hip produces the pixels from a 96-byte plan per image; until here the plan came from the host's scalar
+// ct_preproc.hip produces the pixels from a ct_aug_plan_record per image; until here the plan came from the host's scalar
 // rejection sampler.  ct_aug_plan draws the same decisions from a counter-based generator (Philox4x32-10, the draw
 // table of include/ctdet.h), transforms the boxes and packs them as ct_match_batched reads them.
 //   launch 1  aug_plan_kernel: one wave per sample, lanes = trials of a crop / expand round; the lowest passing lane
@@ -16,19 +16,7 @@
 
 namespace {
 
-struct AugPlan {            // csrc/ct_preproc.hip AugPlan, ctdet/ops.py AugPlan
-    long long src_off;
-    int H, W;
-    int crop_l, crop_t, crop_w, crop_h;
-    int exp_w, exp_h, exp_left, exp_top;
-    int mirror, interp;
-    int flags, hue_delta;
-    float beta, alpha, sat_alpha;
-    float fill[3];
-    float pad0, pad1;
-};
-static_assert(sizeof(AugPlan) == 96, "AugPlan is 96 bytes");
-static_assert(sizeof(ct_aug_sample) == 48, "ct_aug_sample is 48 bytes");
+using AugPlan = ct_aug_plan_record;         // one image's decisions (include/ctdet.h)
 
 struct Interp5 { int v[5]; };
 struct Fill3 { float v[3]; };
@@ -434,6 +422,68 @@ __global__ __launch_bounds__(64) void aug_mosaic_kernel(const ct_aug_sample* __r
 size_t counts_bytes(int num_samples) { return ctdet::align_up((size_t)num_samples * sizeof(int), 256); }
 size_t fixed_bytes(int num_samples) { return ctdet::align_up((size_t)num_samples * sizeof(ct_aug_sample), 256); }
 
+// What ct_aug_plan and ct_aug_plan_mosaic (num_samples = 4 * num_images) are handed alike, and what they do alike with it.
+struct PlanCall {
+    const char* who;                // the entry's name, as its messages spell it
+    const ct_aug_sample* samples;
+    int num_samples;
+    const float* boxes;
+    int total_boxes, num_images, max_gt;
+    unsigned long long seed;
+    float p_expand;
+    const int* interp_of_draw5;
+    const float* fill3;
+    AugPlan* plans;
+    float* truths;
+    int truths_cap;
+    int* gt_off;
+    int* status;
+    int* counts;                    // the two parts of the workspace both entries have
+    float* rows;
+    hipStream_t st;
+};
+
+// `tiles`: ct_aug_plan_mosaic's extra output; any non-null pointer for ct_aug_plan
+int check_pointers(const PlanCall& c, const void* tiles, const void* workspace)
+{
+    CT_REQUIRE(c.samples && c.interp_of_draw5 && c.fill3 && c.plans && tiles && c.truths && c.gt_off && c.status && workspace,
+               "%s: null pointer", c.who);
+    CT_REQUIRE(c.boxes || c.total_boxes == 0, "%s: boxes is null with total_boxes=%d", c.who, c.total_boxes);
+    return CT_OK;
+}
+
+// `product`: how the entry's message names num_samples * max_gt
+int check_sizes(const PlanCall& c, const char* product, size_t need, size_t workspace_bytes)
+{
+    CT_REQUIRE((size_t)c.num_samples * c.max_gt <= (size_t)1 << 28, "%s: %s = %zu is too large", c.who, product,
+               (size_t)c.num_samples * c.max_gt);
+    CT_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", c.who, workspace_bytes, need);
+    return CT_OK;
+}
+
+int launch_plan(const PlanCall& c)
+{
+    Interp5 ip;
+    for (int i = 0; i < 5; ++i) ip.v[i] = c.interp_of_draw5[i];
+    Fill3 fl;
+    for (int i = 0; i < 3; ++i) fl.v[i] = c.fill3[i];
+    CT_PROF("aug_plan_kernel", c.st);
+    hipLaunchKernelGGL(aug_plan_kernel, dim3(c.num_samples), dim3(64), 0, c.st, c.samples, c.num_samples, c.boxes,
+                       c.total_boxes, c.num_images, c.max_gt, c.seed, (double)c.p_expand, ip, fl, c.plans, c.counts, c.rows);
+    CT_LAUNCH_CHECK("aug_plan_kernel");
+    return CT_OK;
+}
+
+// `samples`: the table whose image fields the scan trusts (the caller's, or the mosaic kernel's corrected copy)
+int launch_pack(const PlanCall& c, const ct_aug_sample* samples)
+{
+    CT_PROF("aug_pack_kernel", c.st);
+    hipLaunchKernelGGL(aug_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, c.st, samples, c.num_samples, c.num_images, c.max_gt,
+                       c.plans, (const int*)c.counts, (const float*)c.rows, c.truths, c.truths_cap, c.gt_off, c.status);
+    CT_LAUNCH_CHECK("aug_pack_kernel");
+    return CT_OK;
+}
+
 }  // namespace
 
 extern "C" size_t ct_aug_plan_workspace_bytes(int num_samples, int max_gt)
@@ -448,37 +498,18 @@ extern "C" int ct_aug_plan(const ct_aug_sample* samples, int num_samples, const 
                            int truths_cap, int* gt_off_out, int* status, void* workspace, size_t workspace_bytes,
                            ct_stream_t stream)
 {
-    CT_REQUIRE(samples && interp_of_draw5 && fill3 && plans_out && truths_out && gt_off_out && status && workspace,
-               "ct_aug_plan: null pointer");
-    CT_REQUIRE(boxes || total_boxes == 0, "ct_aug_plan: boxes is null with total_boxes=%d", total_boxes);
+    PlanCall c{"ct_aug_plan", samples, num_samples, boxes, total_boxes, num_images, max_gt, seed, p_expand, interp_of_draw5,
+               fill3, (AugPlan*)plans_out, truths_out, truths_cap, gt_off_out, status, (int*)workspace, nullptr,
+               ctdet::as_stream(stream)};
+    if (int e = check_pointers(c, workspace, workspace)) return e;
     CT_REQUIRE(num_samples >= 1 && total_boxes >= 0 && num_images >= 1 && max_gt >= 1 && truths_cap >= 0,
                "ct_aug_plan: num_samples=%d total_boxes=%d num_images=%d max_gt=%d truths_cap=%d", num_samples,
                total_boxes, num_images, max_gt, truths_cap);
-    CT_REQUIRE((size_t)num_samples * max_gt <= (size_t)1 << 28, "ct_aug_plan: num_samples * max_gt = %zu is too large",
-               (size_t)num_samples * max_gt);
-    const size_t need = ct_aug_plan_workspace_bytes(num_samples, max_gt);
-    CT_REQUIRE(workspace_bytes >= need, "ct_aug_plan: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    Interp5 ip;
-    for (int i = 0; i < 5; ++i) ip.v[i] = interp_of_draw5[i];
-    Fill3 fl;
-    for (int i = 0; i < 3; ++i) fl.v[i] = fill3[i];
-    int* counts = (int*)workspace;
-    float* rows = (float*)((char*)workspace + counts_bytes(num_samples));
-    hipStream_t st = ctdet::as_stream(stream);
-    {
-        CT_PROF("aug_plan_kernel", st);
-        hipLaunchKernelGGL(aug_plan_kernel, dim3(num_samples), dim3(64), 0, st, samples, num_samples, boxes, total_boxes,
-                           num_images, max_gt, seed, (double)p_expand, ip, fl, (AugPlan*)plans_out, counts, rows);
-        CT_LAUNCH_CHECK("aug_plan_kernel");
-    }
-    {
-        CT_PROF("aug_pack_kernel", st);
-        hipLaunchKernelGGL(aug_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, st, samples, num_samples, num_images, max_gt,
-                           (AugPlan*)plans_out, (const int*)counts, (const float*)rows, truths_out, truths_cap, gt_off_out,
-                           status);
-        CT_LAUNCH_CHECK("aug_pack_kernel");
-    }
-    return CT_OK;
+    if (int e = check_sizes(c, "num_samples * max_gt", ct_aug_plan_workspace_bytes(num_samples, max_gt), workspace_bytes))
+        return e;
+    c.rows = (float*)((char*)workspace + counts_bytes(num_samples));
+    if (int e = launch_plan(c)) return e;
+    return launch_pack(c, samples);
 }
 
 extern "C" size_t ct_aug_plan_mosaic_workspace_bytes(int num_images, int max_gt)
@@ -494,46 +525,28 @@ extern "C" int ct_aug_plan_mosaic(const ct_aug_sample* samples, int num_images, 
                                   float* truths_out, int truths_cap, int* gt_off_out, int* status, void* workspace,
                                   size_t workspace_bytes, ct_stream_t stream)
 {
-    CT_REQUIRE(samples && interp_of_draw5 && fill3 && plans_out && tiles_out && truths_out && gt_off_out && status &&
-               workspace, "ct_aug_plan_mosaic: null pointer");
-    CT_REQUIRE(boxes || total_boxes == 0, "ct_aug_plan_mosaic: boxes is null with total_boxes=%d", total_boxes);
+    PlanCall c{"ct_aug_plan_mosaic", samples, 0, boxes, total_boxes, num_images, max_gt, seed, p_expand, interp_of_draw5,
+               fill3, (AugPlan*)plans_out, truths_out, truths_cap, gt_off_out, status, (int*)workspace, nullptr,
+               ctdet::as_stream(stream)};
+    if (int e = check_pointers(c, tiles_out, workspace)) return e;
     CT_REQUIRE(num_images >= 1 && num_images <= (1 << 26) && total_boxes >= 0 && max_gt >= 1 && truths_cap >= 0,
                "ct_aug_plan_mosaic: num_images=%d total_boxes=%d max_gt=%d truths_cap=%d", num_images, total_boxes, max_gt,
                truths_cap);
     CT_REQUIRE(size >= 2 && size <= 4096, "ct_aug_plan_mosaic: size=%d", size);
     CT_REQUIRE(margin >= 1 && margin <= size / 2, "ct_aug_plan_mosaic: margin=%d outside 1..%d", margin, size / 2);
-    const int num_samples = 4 * num_images;
-    CT_REQUIRE((size_t)num_samples * max_gt <= (size_t)1 << 28,
-               "ct_aug_plan_mosaic: 4 * num_images * max_gt = %zu is too large", (size_t)num_samples * max_gt);
-    const size_t need = ct_aug_plan_mosaic_workspace_bytes(num_images, max_gt);
-    CT_REQUIRE(workspace_bytes >= need, "ct_aug_plan_mosaic: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    c.num_samples = 4 * num_images;
+    if (int e = check_sizes(c, "4 * num_images * max_gt", ct_aug_plan_mosaic_workspace_bytes(num_images, max_gt),
+                            workspace_bytes))
+        return e;
     CT_REQUIRE(((size_t)workspace & 15) == 0, "ct_aug_plan_mosaic: workspace is not 16-byte aligned");
-    Interp5 ip;
-    for (int i = 0; i < 5; ++i) ip.v[i] = interp_of_draw5[i];
-    Fill3 fl;
-    for (int i = 0; i < 3; ++i) fl.v[i] = fill3[i];
-    int* counts = (int*)workspace;
-    ct_aug_sample* fixed = (ct_aug_sample*)((char*)workspace + counts_bytes(num_samples));
-    float* rows = (float*)((char*)fixed + fixed_bytes(num_samples));
-    hipStream_t st = ctdet::as_stream(stream);
+    ct_aug_sample* fixed = (ct_aug_sample*)((char*)workspace + counts_bytes(c.num_samples));
+    c.rows = (float*)((char*)fixed + fixed_bytes(c.num_samples));
+    if (int e = launch_plan(c)) return e;
     {
-        CT_PROF("aug_plan_kernel", st);
-        hipLaunchKernelGGL(aug_plan_kernel, dim3(num_samples), dim3(64), 0, st, samples, num_samples, boxes, total_boxes,
-                           num_images, max_gt, seed, (double)p_expand, ip, fl, (AugPlan*)plans_out, counts, rows);
-        CT_LAUNCH_CHECK("aug_plan_kernel");
-    }
-    {
-        CT_PROF("aug_mosaic_kernel", st);
-        hipLaunchKernelGGL(aug_mosaic_kernel, dim3(num_images), dim3(64), 0, st, samples, num_images, max_gt, seed, size,
-                           margin, (AugPlan*)plans_out, tiles_out, fixed, counts, rows);
+        CT_PROF("aug_mosaic_kernel", c.st);
+        hipLaunchKernelGGL(aug_mosaic_kernel, dim3(num_images), dim3(64), 0, c.st, samples, num_images, max_gt, seed, size,
+                           margin, c.plans, tiles_out, fixed, c.counts, c.rows);
         CT_LAUNCH_CHECK("aug_mosaic_kernel");
     }
-    {
-        CT_PROF("aug_pack_kernel", st);
-        hipLaunchKernelGGL(aug_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, st, (const ct_aug_sample*)fixed, num_samples,
-                           num_images, max_gt, (AugPlan*)plans_out, (const int*)counts, (const float*)rows, truths_out,
-                           truths_cap, gt_off_out, status);
-        CT_LAUNCH_CHECK("aug_pack_kernel");
-    }
-    return CT_OK;
+    return launch_pack(c, fixed);
 }

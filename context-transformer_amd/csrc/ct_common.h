@@ -7,6 +7,11 @@
 #include <unordered_set>
 #include "ctdet.h"
 
+// The input pipeline's records, as csrc/ct_preproc.hip and csrc/ct_aug_plan.hip read and write them and
+// ctdet/aug_records.py lays them out for the host (tests/test_aug_records_cpu.py compares every offset).
+static_assert(sizeof(ct_aug_plan_record) == 96 && sizeof(ct_aug_sample) == 48 && sizeof(ct_mosaic_tile) == 16 &&
+              sizeof(ct_resize_tap) == 20, "an input-pipeline record of ctdet.h changed size");
+
 namespace ctdet {
 
 // Thread-local text of the last error (returned by ct_last_error_string()).

@@ -94,17 +94,7 @@ extern "C" int ct_preproc_resize(const unsigned char* src, const long long* offs
 // nearest) -- tolerance-based parity, pinned by oracle/augment_ref.py.
 namespace {
 
-struct AugPlan {            // one image; mirrors the python struct in ctdet/ops.py (16 ints + 8 floats)
-    long long src_off;      // byte offset of the HxWx3 uint8 source image
-    int H, W;
-    int crop_l, crop_t, crop_w, crop_h;
-    int exp_w, exp_h, exp_left, exp_top;      // canvas size (= crop size when not expanded) and placement
-    int mirror, interp;                       // interp: 0 linear, 1 nearest, 2 area; 3 bicubic, 4 Lanczos4 (taps entry only)
-    int flags, hue_delta;                     // flags: 1 brightness, 2 contrast, 4 hue, 8 saturation
-    float beta, alpha, sat_alpha;
-    float fill[3];
-    float pad0, pad1;
-};
+using AugPlan = ct_aug_plan_record;         // one image's decisions (include/ctdet.h)
 
 __device__ __forceinline__ int clip255_trunc(double v)      // numpy: float64 tmp clipped to [0,255], stored into uint8 (truncation)
 {
@@ -404,7 +394,6 @@ extern "C" int ct_preproc_augment(const unsigned char* src, const void* plans, i
 {
     CT_REQUIRE(src && plans && out && means3, "ct_preproc_augment: null pointer");
     CT_REQUIRE(batch > 0 && batch <= 65535 && size > 0 && size <= 4096, "ct_preproc_augment: batch=%d size=%d", batch, size);
-    static_assert(sizeof(AugPlan) == 96, "AugPlan layout is mirrored in ctdet/ops.py");
     dim3 grid((size * size + 255) / 256, batch);
     hipLaunchKernelGGL(augment_kernel, grid, dim3(256), 0, ctdet::as_stream(stream), src, (const AugPlan*)plans, out, size,
                        means3[0], means3[1], means3[2]);
@@ -418,7 +407,6 @@ extern "C" int ct_preproc_augment_mosaic(const unsigned char* src, const void* p
     CT_REQUIRE(src && plans && tiles && out && means3, "ct_preproc_augment_mosaic: null pointer");
     CT_REQUIRE(num_images > 0 && num_images <= 65535 && size >= 2 && size <= 4096,
                "ct_preproc_augment_mosaic: num_images=%d size=%d", num_images, size);
-    static_assert(sizeof(ct_mosaic_tile) == 16, "ct_mosaic_tile layout is mirrored in ctdet/aug_plan_ref.py");
     dim3 grid((size * size + 255) / 256, num_images);
     hipLaunchKernelGGL(augment_mosaic_kernel, grid, dim3(256), 0, ctdet::as_stream(stream), src, (const AugPlan*)plans,
                        tiles, out, size, means3[0], means3[1], means3[2]);
@@ -431,7 +419,6 @@ extern "C" int ct_preproc_augment_taps(const unsigned char* src, const void* pla
 {
     CT_REQUIRE(src && plans && taps && out && means3, "ct_preproc_augment_taps: null pointer");
     CT_REQUIRE(batch > 0 && batch <= 65535 && size > 0 && size <= 4096, "ct_preproc_augment_taps: batch=%d size=%d", batch, size);
-    static_assert(sizeof(ct_resize_tap) == 20, "ct_resize_tap layout is mirrored in ctdet/_lib.py");
     static const int tiled = [] {                   // CTDET_AUG_TILED=0: gather form everywhere (read once)
         const char* e = getenv("CTDET_AUG_TILED");
         return !(e && e[0] == '0' && e[1] == 0);

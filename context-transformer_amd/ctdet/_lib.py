@@ -6,6 +6,8 @@ FAILS LOUDLY -- there is no PyTorch / CPU fallback for the device path.
 import ctypes as C
 import os
 
+from .aug_records import ResizeTap     # noqa: F401  (ct_resize_tap, with the other input-pipeline records)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CTDET_LIB') or os.path.join(os.path.dirname(_HERE), 'lib', 'libctdet.so')
 
@@ -114,11 +116,6 @@ class LossTerms(C.Structure):
     """ct_loss_terms: the options of ct_multibox_loss_fwd_terms / _bwd_terms."""
     _fields_ = [('priors', C.c_void_p), ('loc_loss', C.c_int), ('var0', C.c_float), ('var1', C.c_float),
                 ('conf_loss', C.c_int), ('focal_gamma', C.c_float), ('focal_alpha', C.c_float)]
-
-
-class ResizeTap(C.Structure):
-    """ct_resize_tap: first source index (unclamped) and the 11-bit coefficients of one output coordinate."""
-    _fields_ = [('first', C.c_int), ('c', C.c_short * 8)]
 
 
 _P = C.c_void_p

@@ -23,6 +23,8 @@ import collections
 
 import numpy as np
 
+from .aug_records import PLAN_DTYPE, SAMPLE_DTYPE, TILE_DTYPE, plan_dict, plan_records     # noqa: F401
+
 PHILOX_M = (0xD2511F53, 0xCD9E8D57)
 PHILOX_W = (0x9E3779B9, 0xBB67AE85)
 _MASK = np.uint64(0xFFFFFFFF)
@@ -32,13 +34,6 @@ LANE_COINS, LANE_PARAMS, LANE_MISC, LANE_MODE = 0, 1, 2, 63
 CROP_TRIALS, CROP_ROUNDS, EXPAND_TRIALS, EXPAND_ROUNDS = 50, 256, 64, 64
 CROP_MIN_IOU = (None, 0.1, 0.3, 0.5, 0.7, 0.9, -np.inf)     # data_augment.py CROP_MODES; every upper bound is None
 STATUS_BAD_SAMPLE, STATUS_ROWS_DROPPED = 1, 2
-
-SAMPLE_DTYPE = np.dtype([('src_off', '<i8'), ('sample_id', '<u8'), ('H', '<i4'), ('W', '<i4'), ('box_begin', '<i4'),
-                         ('box_end', '<i4'), ('image', '<i4'), ('cls', '<i4'), ('weight', '<f4'), ('flags', '<i4')])
-PLAN_DTYPE = np.dtype([('src_off', '<i8'), ('H', '<i4'), ('W', '<i4'), ('crop', '<i4', (4,)), ('exp', '<i4', (4,)),
-                       ('mirror', '<i4'), ('interp', '<i4'), ('flags', '<i4'), ('hue', '<i4'), ('beta', '<f4'),
-                       ('alpha', '<f4'), ('sat', '<f4'), ('fill', '<f4', (3,)), ('pad', '<f4', (2,))])
-assert SAMPLE_DTYPE.itemsize == 48 and PLAN_DTYPE.itemsize == 96
 
 AugPlanResult = collections.namedtuple(
     'AugPlanResult', 'plans truths gt_off status crop_rounds expand_rounds sample_rows info')
@@ -227,10 +222,7 @@ def plan_batch(samples, boxes, num_images, max_gt, seed, p_expand, interp_of_dra
         b0, b1 = min(max(int(s['box_begin']), 0), total), min(max(int(s['box_end']), 0), total)
         cnt = min(max(b1 - b0, 0), int(max_gt))
         r = plan_sample(seed, s['sample_id'], H, W, boxes[b0:b0 + cnt], s['cls'], p, interp_of_draw)
-        pl = plans[i]
-        pl['H'], pl['W'], pl['crop'], pl['exp'] = H, W, r['crop'], r['exp']
-        pl['mirror'], pl['interp'], pl['flags'], pl['hue'] = r['mirror'], r['interp'], r['flags'], r['hue']
-        pl['beta'], pl['alpha'], pl['sat'] = r['beta'], r['alpha'], r['sat']
+        plan_records(plans[i:i + 1], [r])
         crop_rounds[i], expand_rounds[i] = r['crop_rounds'], r['expand_rounds']
         rows = np.zeros((len(r['rows']), 6), dtype=np.float64)
         rows[:, :5] = r['rows']
@@ -257,14 +249,6 @@ def plan_batch(samples, boxes, num_images, max_gt, seed, p_expand, interp_of_dra
     return AugPlanResult(plans, all_rows[:cap], gt_off, status, crop_rounds, expand_rounds, rows_of, info)
 
 
-def plan_dict(plan):
-    """A PLAN_DTYPE record as the dict `ops.Augmenter` takes (data_augment.py `_plan`)."""
-    return dict(H=int(plan['H']), W=int(plan['W']), crop=tuple(int(v) for v in plan['crop']),
-                exp=tuple(int(v) for v in plan['exp']), mirror=int(plan['mirror']), interp=int(plan['interp']),
-                flags=int(plan['flags']), hue=int(plan['hue']), beta=float(plan['beta']), alpha=float(plan['alpha']),
-                sat=float(plan['sat']))
-
-
 def make_samples(shapes, targets, images=None, sample_ids=None, cls=-1, weights=None, flags=0):
     """Pack per-sample (H, W) shapes and [G,5] target arrays into (SAMPLE_DTYPE array, float32 [total,5] boxes)."""
     n = len(shapes)
@@ -285,8 +269,6 @@ def make_samples(shapes, targets, images=None, sample_ids=None, cls=-1, weights=
 
 # ---------------------------------------------------------------------------------------------------------- mosaic
 SLOT_MOSAIC = 0x300
-TILE_DTYPE = np.dtype([('x0', '<i4'), ('y0', '<i4'), ('w', '<i4'), ('h', '<i4')])
-assert TILE_DTYPE.itemsize == 16                # ct_mosaic_tile
 
 MosaicResult = collections.namedtuple('MosaicResult', 'plans tiles truths gt_off status sample_rows fallback info')
 

@@ -14,6 +14,8 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
+from .aug_records import (PLAN_BYTES, PLAN_DTYPE, SAMPLE_BYTES, SAMPLE_DTYPE as AUG_SAMPLE_DTYPE, TAP_BYTES, TAP_DTYPE,
+                          TILE_BYTES, AugPlan, plan_records)   # noqa: F401  (AugPlan: callers of the C ABI fill it by name)
 
 
 def _stream():
@@ -839,6 +841,53 @@ def coco_accumulate(keys, matched, ignored, order, cat_off, npig, max_dets, n_io
 
 
 # ------------------------------------------------------------------ input transform
+class _Staging:
+    """A pinned host buffer, its device twin `dev` and the event of the last copy between them; `put` is its one
+    operation.  grow: None refuses items that do not fit, a factor replaces both buffers by ones of that many times
+    the need.  pad_end: the copy also moves the padding after the last item, as the image copies always have."""
+
+    def __init__(self, device, nbytes, who, grow=None, pad_end=False):
+        self.device, self.who, self.grow, self.pad_end = device, who, grow, pad_end
+        self.copied = torch.cuda.Event()        # recorded after every copy: the pinned buffer is free for reuse
+        self.nbytes = 0                         # of the last copy
+        self._alloc(nbytes)
+
+    def _alloc(self, nbytes):
+        self.cap = nbytes
+        self.host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def put(self, items):
+        """Contiguous numpy arrays -> the list of their byte offsets in `dev` (multiples of 16): wait for the previous
+        copy, fill the pinned buffer, enqueue ONE non-blocking H2D copy of the bytes in use, record the event."""
+        self.copied.synchronize()
+        offs, end = [], 0
+        for a in items:
+            offs.append((end + 15) // 16 * 16)
+            end = offs[-1] + a.nbytes
+        nb = (end + 15) // 16 * 16 if self.pad_end else end
+        if self.grow is None:
+            if end > self.cap:
+                raise _lib.CtdetError('%s: staging capacity %d bytes exceeded' % (self.who, self.cap))
+        elif nb > self.cap:
+            self._alloc(int(nb * self.grow))
+        for a, o in zip(items, offs):
+            self.host[o:o + a.nbytes] = torch.from_numpy(a.reshape(-1).view(np.uint8))
+        self.nbytes = min(nb, self.cap)
+        self.dev[:self.nbytes].copy_(self.host[:self.nbytes], non_blocking=True)
+        self.copied.record()
+        return offs
+
+
+def _images(images, who):
+    """The uint8 HxWx3 images of a batch as contiguous arrays."""
+    arrays = [np.ascontiguousarray(img) for img in images]
+    for i, a in enumerate(arrays):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError('%s: image %d is %s %s, expected uint8 HxWx3' % (who, i, a.dtype, a.shape))
+    return arrays
+
+
 class Preprocessor:
     """Batched BaseTransform (data/data_augment.py:224-266) on the device: uint8 HxWx3 images of
     any size -> float32 [B,3,S,S] (bilinear resize, minus means, CHW) in one launch.
@@ -847,41 +896,23 @@ class Preprocessor:
     def __init__(self, size, means, device, max_batch=32, max_pixels=512 * 512):
         self.size, self.device, self.max_batch = size, torch.device(device), max_batch
         self.means = (C.c_float * 3)(*[float(m) for m in means])
-        self.cap = max_batch * max_pixels * 3
-        self.stage = torch.empty(self.cap, dtype=torch.uint8).pin_memory()
-        self.dev = torch.empty(self.cap, dtype=torch.uint8, device=self.device)
-        self.meta_h = torch.empty(max_batch * 4, dtype=torch.int32).pin_memory()    # offsets (i64) | hw (i32)
-        self.meta_d = torch.empty(max_batch * 4, dtype=torch.int32, device=self.device)
-        self.copied = None                      # event: staging buffers free for reuse
+        self.src = _Staging(self.device, max_batch * max_pixels * 3, 'Preprocessor', pad_end=True)
+        self.meta = _Staging(self.device, max_batch * (8 + 2 * 4), 'Preprocessor')     # offsets (i64) | hw (2 x i32)
 
     def __call__(self, images, out=None):
-        n = len(images)
-        if n == 0 or n > self.max_batch:
-            raise ValueError('Preprocessor: batch of %d images (max %d)' % (n, self.max_batch))
-        if self.copied is not None:
-            self.copied.synchronize()
-        offs = self.meta_h[:2 * self.max_batch].view(torch.int64)
-        hw = self.meta_h[2 * self.max_batch:]
-        pos = 0
-        for i, img in enumerate(images):
-            a = np.ascontiguousarray(img)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise ValueError('Preprocessor: image %d is %s %s, expected uint8 HxWx3' % (i, a.dtype, a.shape))
-            if pos + a.size > self.cap:
-                raise _lib.CtdetError('Preprocessor: staging capacity %d bytes exceeded' % self.cap)
-            self.stage[pos:pos + a.size] = torch.from_numpy(a.reshape(-1))
-            offs[i], hw[2 * i], hw[2 * i + 1] = pos, a.shape[0], a.shape[1]
-            pos += (a.size + 15) // 16 * 16
-        self.dev[:pos].copy_(self.stage[:pos], non_blocking=True)
-        self.meta_d.copy_(self.meta_h, non_blocking=True)
-        self.copied = torch.cuda.Event()
-        self.copied.record()
+        n, mb = len(images), self.max_batch
+        if n == 0 or n > mb:
+            raise ValueError('Preprocessor: batch of %d images (max %d)' % (n, mb))
+        arrays = _images(images, 'Preprocessor')
+        meta = np.zeros(4 * mb, dtype=np.int32)
+        meta[:2 * mb].view(np.int64)[:n] = self.src.put(arrays)
+        meta[2 * mb:2 * mb + 2 * n] = [v for a in arrays for v in a.shape[:2]]
+        self.meta.put([meta])
         if out is None:
             out = torch.empty(n, 3, self.size, self.size, device=self.device, dtype=torch.float32)
-        offs_d = self.meta_d[:2 * self.max_batch]
-        hw_d = self.meta_d[2 * self.max_batch:]
-        check(lib().ct_preproc_resize(_dev(self.dev, 'src', torch.uint8), _dev(offs_d, 'offsets', torch.int32),
-                                      _dev(hw_d, 'hw', torch.int32), n,
+        offs_d, hw_d = self.meta.dev[:8 * mb], self.meta.dev[8 * mb:]
+        check(lib().ct_preproc_resize(_dev(self.src.dev, 'src', torch.uint8), _dev(offs_d, 'offsets', torch.uint8),
+                                      _dev(hw_d, 'hw', torch.uint8), n,
                                       self.size, C.cast(self.means, C.c_void_p), _dev(out, 'out'), _stream()),
               'ct_preproc_resize')
         return out
@@ -890,8 +921,6 @@ class Preprocessor:
 # ------------------------------------------------------------------ resize taps (host decisions of the augmentation)
 RESIZE_TAPS = {'cubic': 4, 'lanczos4': 8}           # kind -> taps per axis; AugPlan.interp 3 and 4
 INTERP_KIND = {3: 'cubic', 4: 'lanczos4'}
-TAP_DTYPE = np.dtype([('first', '<i4'), ('c', '<i2', (8,))])        # ct_resize_tap
-assert TAP_DTYPE.itemsize == C.sizeof(_lib.ResizeTap) == 20
 
 
 def resize_coeffs(x, kind):
@@ -953,35 +982,24 @@ def tap_records(n_src, S, kind):
     return rec
 
 
-class AugPlan(C.Structure):
-    """One image's augmentation decisions (csrc/ct_preproc.hip AugPlan, 96 bytes)."""
-    _fields_ = [('src_off', C.c_longlong), ('H', C.c_int), ('W', C.c_int),
-                ('crop_l', C.c_int), ('crop_t', C.c_int), ('crop_w', C.c_int), ('crop_h', C.c_int),
-                ('exp_w', C.c_int), ('exp_h', C.c_int), ('exp_left', C.c_int), ('exp_top', C.c_int),
-                ('mirror', C.c_int), ('interp', C.c_int), ('flags', C.c_int), ('hue_delta', C.c_int),
-                ('beta', C.c_float), ('alpha', C.c_float), ('sat_alpha', C.c_float), ('fill', C.c_float * 3),
-                ('pad0', C.c_float), ('pad1', C.c_float)]
-
-
-assert C.sizeof(AugPlan) == 96
-
-
 class Augmenter:
     """Batched training-time augmentation (data/data_augment.py:164-221) on the device: the host hands over the
-    uint8 images and one AugPlan per image (the random decisions); ONE launch writes float32 [B,3,S,S].  A batch
+    uint8 images and one plan per image (the random decisions); ONE launch writes float32 [B,3,S,S].  A batch
     with a bicubic or Lanczos4 image (interp 3 / 4) also carries their taps and goes to ct_preproc_augment_taps."""
 
     def __init__(self, size, means, device, max_batch=32, max_pixels=512 * 512):
         self.size, self.device, self.max_batch = size, torch.device(device), max_batch
         self.means_f = [float(m) for m in means]
         self.means = (C.c_float * 3)(*self.means_f)
-        self.cap = max_batch * max_pixels * 3
-        self.stage = torch.empty(self.cap, dtype=torch.uint8).pin_memory()
-        self.dev = torch.empty(self.cap, dtype=torch.uint8, device=self.device)
-        self.plan_h = torch.empty(max_batch * 96, dtype=torch.uint8).pin_memory()
-        self.plan_d = torch.empty(max_batch * 96, dtype=torch.uint8, device=self.device)
-        self.tap_h = self.tap_d = None      # ct_resize_tap staging, allocated by the first batch that needs it
-        self.copied = None
+        # any image size, like the reference (COCO is 640x480): the source staging grows, never refuses
+        self.src = _Staging(self.device, max_batch * max_pixels * 3, 'Augmenter', grow=1.25, pad_end=True)
+        self.plans = _Staging(self.device, max_batch * PLAN_BYTES, 'Augmenter')
+        self.taps = None                    # ct_resize_tap staging, allocated by the first batch that needs it
+
+    @property
+    def dev(self):
+        """The device source buffer `upload` filled last (src_off counts from its start)."""
+        return self.src.dev
 
     def __call__(self, images, plans, out=None):
         n = len(images)
@@ -990,103 +1008,60 @@ class Augmenter:
         for i, (img, p) in enumerate(zip(images, plans)):
             if tuple(np.shape(img)[:2]) != (p['H'], p['W']):
                 raise ValueError('Augmenter: image %d is %s, plan says %dx%d' % (i, np.shape(img), p['H'], p['W']))
-        offs = self.upload(images)
-        recs = (AugPlan * n)()
-        for i, p in enumerate(plans):
-            r = recs[i]
-            r.src_off, r.H, r.W = int(offs[i]), p['H'], p['W']
-            r.crop_l, r.crop_t, r.crop_w, r.crop_h = p['crop']
-            r.exp_w, r.exp_h, r.exp_left, r.exp_top = p['exp']
-            r.mirror, r.interp, r.flags, r.hue_delta = p['mirror'], p['interp'], p['flags'], p['hue']
-            r.beta, r.alpha, r.sat_alpha = p['beta'], p['alpha'], p['sat']
-            for c in range(3):
-                r.fill[c] = self.means_f[c]
-        self.plan_h[:n * 96] = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8)
-        self.plan_d[:n * 96].copy_(self.plan_h[:n * 96], non_blocking=True)
-        self.copied.record()                # the plan staging is free again after this copy too
-        if out is None:
-            out = torch.empty(n, 3, self.size, self.size, device=self.device, dtype=torch.float32)
+        recs = np.zeros(n, dtype=PLAN_DTYPE)
+        recs['src_off'], recs['fill'] = self.upload(images), self.means_f
+        plan_records(recs, plans)
+        self.plans.put([recs])
         if not any(p['interp'] in INTERP_KIND for p in plans):
-            check(lib().ct_preproc_augment(_dev(self.dev, 'src', torch.uint8), _dev(self.plan_d, 'plans', torch.uint8), n,
-                                           self.size, C.cast(self.means, C.c_void_p), _dev(out, 'out'), _stream()),
-                  'ct_preproc_augment')
-            return out
+            return self._render('ct_preproc_augment', self.plans.dev, n, out)
         # bicubic / Lanczos4 images: their taps are host decisions too (resize_taps), uploaded like the plans
         S = self.size
-        if self.tap_h is None:
-            self.tap_h = torch.zeros(self.max_batch * 2 * S * 20, dtype=torch.uint8).pin_memory()
-            self.tap_d = torch.zeros(self.max_batch * 2 * S * 20, dtype=torch.uint8, device=self.device)
+        if self.taps is None:
+            self.taps = _Staging(self.device, self.max_batch * 2 * S * TAP_BYTES, 'Augmenter')
         recs_t = np.zeros((n, 2, S), dtype=TAP_DTYPE)               # images with interp 0..2 ignore theirs
         for i, p in enumerate(plans):
             kind = INTERP_KIND.get(p['interp'])
             if kind:
                 recs_t[i, 0], recs_t[i, 1] = tap_records(p['exp'][0], S, kind), tap_records(p['exp'][1], S, kind)
-        nb = n * 2 * S * 20
-        self.tap_h[:nb] = torch.from_numpy(recs_t.reshape(-1).view(np.uint8))
-        self.tap_d[:nb].copy_(self.tap_h[:nb], non_blocking=True)
-        self.copied.record()
-        check(lib().ct_preproc_augment_taps(_dev(self.dev, 'src', torch.uint8), _dev(self.plan_d, 'plans', torch.uint8),
-                                            _dev(self.tap_d, 'taps', torch.uint8), n, S, C.cast(self.means, C.c_void_p),
-                                            _dev(out, 'out'), _stream()), 'ct_preproc_augment_taps')
-        return out
+        self.taps.put([recs_t])
+        return self._render('ct_preproc_augment_taps', self.plans.dev, n, out, ('taps', self.taps.dev))
 
     def upload(self, images):
-        """Stage and upload the images: -> int64 [n] byte offsets of the images in the source buffer (AugPlan.src_off,
-        ct_aug_sample.src_off).  On its own for plans the device draws itself (AugPlanner, then `render`)."""
+        """Stage and upload the images: -> int64 [n] byte offsets of the images in the source buffer (the plan's and
+        ct_aug_sample's src_off).  On its own for plans the device draws itself (AugPlanner, then `render`)."""
         n = len(images)
         if n == 0 or n > self.max_batch:
             raise ValueError('Augmenter: batch of %d images (max %d)' % (n, self.max_batch))
-        if self.copied is not None:
-            self.copied.synchronize()
-        need = sum((int(np.asarray(img).size) + 15) // 16 * 16 for img in images)
-        if need > self.cap:                 # any image size, like the reference (COCO is 640x480): grow, never refuse
-            self.cap = int(need * 1.25)
-            self.stage = torch.empty(self.cap, dtype=torch.uint8).pin_memory()
-            self.dev = torch.empty(self.cap, dtype=torch.uint8, device=self.device)
-        offs = np.zeros(n, dtype=np.int64)
-        pos = 0
-        for i, img in enumerate(images):
-            a = np.ascontiguousarray(img)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise ValueError('Augmenter: image %d is %s %s, expected uint8 HxWx3' % (i, a.dtype, a.shape))
-            self.stage[pos:pos + a.size] = torch.from_numpy(a.reshape(-1))
-            offs[i] = pos
-            pos += (a.size + 15) // 16 * 16
-        self.dev[:pos].copy_(self.stage[:pos], non_blocking=True)
-        self.copied = torch.cuda.Event()
-        self.copied.record()
-        return offs
+        return np.array(self.src.put(_images(images, 'Augmenter')), dtype=np.int64)
 
-    def render(self, plans_d, n, out=None):
-        """ct_preproc_augment over n device-resident plan records (uint8 [>= n*96]) whose src_off point into the
-        buffer `upload` filled.  The float filters only: tap tables are host decisions."""
-        if n == 0 or plans_d.numel() < n * 96:
-            raise ValueError('Augmenter.render: %d plans in a buffer of %d bytes' % (n, plans_d.numel()))
+    def _render(self, entry, plans_d, n, out, *extra):
+        """The one body of the ct_preproc_augment* calls over the buffer `upload` filled: n output images from the
+        plan records plans_d and the (name, uint8 tensor) tables `extra` the entry takes after them."""
         if out is None:
             out = torch.empty(n, 3, self.size, self.size, device=self.device, dtype=torch.float32)
-        check(lib().ct_preproc_augment(_dev(self.dev, 'src', torch.uint8), _dev(plans_d, 'plans', torch.uint8), n,
-                                       self.size, C.cast(self.means, C.c_void_p), _dev(out, 'out'), _stream()),
-              'ct_preproc_augment')
+        u8 = torch.uint8
+        check(getattr(lib(), entry)(_dev(self.dev, 'src', u8), _dev(plans_d, 'plans', u8),
+                                    *[_dev(t, name, u8) for name, t in extra], n, self.size,
+                                    C.cast(self.means, C.c_void_p), _dev(out, 'out'), _stream()), entry)
         return out
+
+    def render(self, plans_d, n, out=None):
+        """ct_preproc_augment over n device-resident plan records (uint8 [>= n*PLAN_BYTES]) whose src_off point into
+        the buffer `upload` filled.  The float filters only: tap tables are host decisions."""
+        if n == 0 or plans_d.numel() < n * PLAN_BYTES:
+            raise ValueError('Augmenter.render: %d plans in a buffer of %d bytes' % (n, plans_d.numel()))
+        return self._render('ct_preproc_augment', plans_d, n, out)
 
     def render_mosaic(self, plans_d, tiles_d, n, out=None):
         """ct_preproc_augment_mosaic: n images, each composed of four device-resident plan records (uint8
-        [>= 4n*96]) resized into their tiles (uint8 [>= 4n*16], ct_mosaic_tile); what AugPlanner.mosaic returns."""
-        if n == 0 or plans_d.numel() < 4 * n * 96 or tiles_d.numel() < 4 * n * 16:
+        [>= 4n*PLAN_BYTES]) resized into their tiles (uint8 [>= 4n*TILE_BYTES], ct_mosaic_tile); what
+        AugPlanner.mosaic returns."""
+        if n == 0 or plans_d.numel() < 4 * n * PLAN_BYTES or tiles_d.numel() < 4 * n * TILE_BYTES:
             raise ValueError('Augmenter.render_mosaic: %d images, %d plan bytes, %d tile bytes'
                              % (n, plans_d.numel(), tiles_d.numel()))
-        if out is None:
-            out = torch.empty(n, 3, self.size, self.size, device=self.device, dtype=torch.float32)
-        check(lib().ct_preproc_augment_mosaic(_dev(self.dev, 'src', torch.uint8), _dev(plans_d, 'plans', torch.uint8),
-                                              _dev(tiles_d, 'tiles', torch.uint8), n, self.size,
-                                              C.cast(self.means, C.c_void_p), _dev(out, 'out'), _stream()),
-              'ct_preproc_augment_mosaic')
-        return out
+        return self._render('ct_preproc_augment_mosaic', plans_d, n, out, ('tiles', tiles_d))
 
 
-AUG_SAMPLE_DTYPE = np.dtype([('src_off', '<i8'), ('sample_id', '<u8'), ('H', '<i4'), ('W', '<i4'), ('box_begin', '<i4'),
-                             ('box_end', '<i4'), ('image', '<i4'), ('cls', '<i4'), ('weight', '<f4'), ('flags', '<i4')])
-assert AUG_SAMPLE_DTYPE.itemsize == 48          # ct_aug_sample
 AUG_STATUS_BAD_SAMPLE, AUG_STATUS_ROWS_DROPPED = 1, 2
 
 
@@ -1102,95 +1077,60 @@ class AugPlanner:
             raise ValueError('AugPlanner: interp_of_draw has 5 entries and fill 3')
         self.interp = (C.c_int * 5)(*[int(v) for v in interp_of_draw])
         self.fill = (C.c_float * 3)(*[float(v) for v in fill])
-        self.cap_bytes = 0
-        self._reserve(max_samples, max_boxes)
-        self.copied = None
+        # the sample records, then the float32 [x1,y1,x2,y2,label] boxes; grows to exactly what a batch needs
+        self.stage = _Staging(self.device, max_samples * SAMPLE_BYTES + max_boxes * 5 * 4, 'AugPlanner', grow=1.0)
         self.status = None                  # int32 [4] on the device, of the last call
         self.upload_bytes = 0               # of the last call
 
-    def _reserve(self, n, total):
-        need = n * 48 + total * 20
-        if need > self.cap_bytes:
-            self.cap_bytes = need
-            self.stage = torch.empty(need, dtype=torch.uint8).pin_memory()
-            self.dev = torch.empty(need, dtype=torch.uint8, device=self.device)
-
-    def _upload(self, samples, boxes):
-        """Stage the sample records and the boxes and enqueue their one H2D copy -> byte offset of the boxes."""
-        n, total = len(samples), len(boxes)
-        if self.copied is not None:
-            self.copied.synchronize()
-        self._reserve(n, total)
-        nb_s, nb = n * 48, n * 48 + total * 20
-        self.stage[:nb_s] = torch.from_numpy(samples.view(np.uint8).reshape(-1))
-        if total:
-            self.stage[nb_s:nb] = torch.from_numpy(boxes.view(np.uint8).reshape(-1))
-        self.dev[:nb].copy_(self.stage[:nb], non_blocking=True)
-        self.copied = torch.cuda.Event()
-        self.copied.record()
-        self.upload_bytes = nb
-        return nb_s
-
-    def __call__(self, samples, boxes, num_images, max_gt, truths_cap=None):
-        """samples: AUG_SAMPLE_DTYPE array [n]; boxes float32 [total,5]; max_gt: boxes per sample the kernel looks at.
-        -> (plans uint8 [n*96] on the device, PackedTargets).  truths_cap defaults to the input box count, which the
-        rows cannot exceed."""
+    def _plan(self, entry, samples, boxes, num_images, max_gt, truths_cap, tiles=None, *geometry):
+        """The one body of `__call__` and `mosaic` (which adds its `tiles` output and the (size, margin) geometry):
+        normalise the inputs, upload them, allocate the outputs, call `entry` -> (plans, PackedTargets)."""
+        mosaic = tiles is not None
         samples = np.ascontiguousarray(samples, dtype=AUG_SAMPLE_DTYPE)
         boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 5)
         n, total, num_images, max_gt = len(samples), len(boxes), int(num_images), int(max_gt)
-        if n == 0 or num_images < 1 or max_gt < 1:
-            raise ValueError('AugPlanner: %d samples, %d images, max_gt %d' % (n, num_images, max_gt))
-        nb_s = self._upload(samples, boxes)
+        if num_images < 1 or max_gt < 1 or (n != 4 * num_images if mosaic else n == 0):
+            raise ValueError('%s: %d samples, %d images, max_gt %d'
+                             % ('AugPlanner.mosaic' if mosaic else 'AugPlanner', n, num_images, max_gt))
+        box_off = self.stage.put([samples, boxes])[1]
+        self.upload_bytes = self.stage.nbytes
         cap = max(total, 1) if truths_cap is None else int(truths_cap)
-        dev = self.device
-        plans = torch.empty(n * 96, dtype=torch.uint8, device=dev)
+        dev, u8, i32 = self.device, torch.uint8, torch.int32
+        plans = torch.empty(n * PLAN_BYTES, dtype=u8, device=dev)
         truths = torch.empty(max(cap, 1), 6, dtype=torch.float32, device=dev)
-        gt_off = torch.empty(num_images + 1, dtype=torch.int32, device=dev)
-        self.status = torch.empty(4, dtype=torch.int32, device=dev)
-        ws_bytes = lib().ct_aug_plan_workspace_bytes(n, max_gt)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        check(lib().ct_aug_plan(_dev(self.dev, 'samples', torch.uint8), n,
-                                C.c_void_p(self.dev.data_ptr() + nb_s), total, num_images, max_gt, self.seed,
-                                self.p_expand, self.interp, self.fill, _dev(plans, 'plans', torch.uint8),
-                                _dev(truths, 'truths'), cap, _dev(gt_off, 'gt_off', torch.int32),
-                                _dev(self.status, 'status', torch.int32), _dev(ws, 'workspace', torch.uint8),
-                                ws_bytes, _stream()), 'ct_aug_plan')
+        gt_off = torch.empty(num_images + 1, dtype=i32, device=dev)
+        self.status = torch.empty(4, dtype=i32, device=dev)
+        ws_bytes = getattr(lib(), entry + '_workspace_bytes')(num_images if mosaic else n, max_gt)
+        ws = torch.empty(ws_bytes, dtype=u8, device=dev)
+        smp, bxp = _dev(self.stage.dev, 'samples', u8), C.c_void_p(self.stage.dev.data_ptr() + box_off)
+        draw = (max_gt, self.seed, self.p_expand, self.interp, self.fill)
+        if mosaic:
+            args = (smp, num_images, bxp, total) + draw + geometry + (_dev(plans, 'plans', u8), _dev(tiles, 'tiles', u8))
+        else:
+            args = (smp, n, bxp, total, num_images) + draw + (_dev(plans, 'plans', u8),)
+        check(getattr(lib(), entry)(*args, _dev(truths, 'truths'), cap, _dev(gt_off, 'gt_off', i32),
+                                    _dev(self.status, 'status', i32), _dev(ws, 'workspace', u8), ws_bytes, _stream()), entry)
         # host-known bound of an image's rows: the boxes its samples hand in (each capped at max_gt)
         cnt = np.minimum(np.clip(samples['box_end'], 0, total) - np.clip(samples['box_begin'], 0, total), max_gt)
-        img = samples['image']
+        img = np.arange(n) // 4 if mosaic else samples['image']
         ok = (img >= 0) & (img < num_images)
         per_image = np.bincount(img[ok], weights=np.maximum(cnt[ok], 0), minlength=1) if ok.any() else np.zeros(1)
         return plans, PackedTargets(truths, gt_off, max(int(per_image.max()), 1))
 
+    def __call__(self, samples, boxes, num_images, max_gt, truths_cap=None):
+        """samples: AUG_SAMPLE_DTYPE array [n]; boxes float32 [total,5]; max_gt: boxes per sample the kernel looks at.
+        -> (plans uint8 [n*PLAN_BYTES] on the device, PackedTargets).  truths_cap defaults to the input box count,
+        which the rows cannot exceed."""
+        return self._plan('ct_aug_plan', samples, boxes, num_images, max_gt, truths_cap)
+
     def mosaic(self, samples, boxes, num_images, max_gt, size, margin, truths_cap=None):
         """ct_aug_plan_mosaic (three launches): samples AUG_SAMPLE_DTYPE [4*num_images], group-major (sample s is slot
-        s % 4 of image s // 4); boxes float32 [total,5].  -> (plans uint8 [4n*96], tiles uint8 [4n*16], PackedTargets
-        in the output image's units), all on the device.  Staged and uploaded like `__call__`."""
-        samples = np.ascontiguousarray(samples, dtype=AUG_SAMPLE_DTYPE)
-        boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 5)
-        n, total, num_images, max_gt = len(samples), len(boxes), int(num_images), int(max_gt)
-        if num_images < 1 or n != 4 * num_images or max_gt < 1:
-            raise ValueError('AugPlanner.mosaic: %d samples, %d images, max_gt %d' % (n, num_images, max_gt))
-        nb_s = self._upload(samples, boxes)
-        cap = max(total, 1) if truths_cap is None else int(truths_cap)
-        dev = self.device
-        plans = torch.empty(n * 96, dtype=torch.uint8, device=dev)
-        tiles = torch.empty(n * 16, dtype=torch.uint8, device=dev)
-        truths = torch.empty(max(cap, 1), 6, dtype=torch.float32, device=dev)
-        gt_off = torch.empty(num_images + 1, dtype=torch.int32, device=dev)
-        self.status = torch.empty(4, dtype=torch.int32, device=dev)
-        ws_bytes = lib().ct_aug_plan_mosaic_workspace_bytes(num_images, max_gt)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        check(lib().ct_aug_plan_mosaic(_dev(self.dev, 'samples', torch.uint8), num_images,
-                                       C.c_void_p(self.dev.data_ptr() + nb_s), total, max_gt, self.seed, self.p_expand,
-                                       self.interp, self.fill, int(size), int(margin), _dev(plans, 'plans', torch.uint8),
-                                       _dev(tiles, 'tiles', torch.uint8), _dev(truths, 'truths'), cap,
-                                       _dev(gt_off, 'gt_off', torch.int32), _dev(self.status, 'status', torch.int32),
-                                       _dev(ws, 'workspace', torch.uint8), ws_bytes, _stream()), 'ct_aug_plan_mosaic')
-        # host-known bound of an image's rows: the boxes its four samples hand in (each capped at max_gt)
-        cnt = np.minimum(np.clip(samples['box_end'], 0, total) - np.clip(samples['box_begin'], 0, total), max_gt)
-        per_image = np.maximum(cnt, 0).reshape(num_images, 4).sum(1)
-        return plans, tiles, PackedTargets(truths, gt_off, max(int(per_image.max()), 1))
+        s % 4 of image s // 4); boxes float32 [total,5].  -> (plans uint8 [4n*PLAN_BYTES], tiles uint8 [4n*TILE_BYTES],
+        PackedTargets in the output image's units), all on the device.  Staged and uploaded like `__call__`."""
+        tiles = torch.empty(len(samples) * TILE_BYTES, dtype=torch.uint8, device=self.device)
+        plans, packed = self._plan('ct_aug_plan_mosaic', samples, boxes, num_images, max_gt, truths_cap, tiles,
+                                   int(size), int(margin))
+        return plans, tiles, packed
 
     def check(self):
         """Read the status words of the last call (a host synchronisation) and raise when a sample was refused or a

@@ -6,7 +6,7 @@ mean-subtracted image; the resize runs on the device (`ct_preproc_resize`, one l
 `preproc(resize, rgb_means, p)(image, targets[, cls])` (:164-221, training time): random crop -> photometric
 distortion -> expand -> mirror -> resize -> minus means, returning (CHW tensor, normalised targets).  Split the
 MI355X way: the random DECISIONS are the reference's scalar host logic -- drawn here with the same `random` calls in
-the same order, so a seeded run makes the same choices -- and produce a 96-byte plan per image; the PIXELS of a whole
+the same order, so a seeded run makes the same choices -- and produce one plan record per image; the PIXELS of a whole
 batch are then produced by one gather kernel (`ct_preproc_augment`) that never materialises the cropped / distorted /
 expanded intermediates.  `filters='cv2'` (or CTDET_AUG_FILTERS=cv2) adds the bicubic and Lanczos4 resize filters the
 reference also draws (`ct_preproc_augment_taps`); the default maps those two draws onto linear.
@@ -59,6 +59,21 @@ def _plan(h, w):
     """Identity plan for an h x w image: no crop, no distortion, no canvas, no mirror, linear resize."""
     return dict(H=h, W=w, crop=(0, 0, w, h), exp=(w, h, 0, 0), mirror=0, interp=0, flags=0, hue=0,
                 beta=0.0, alpha=1.0, sat=1.0)
+
+
+def _pack_samples(images, targets, offs, sample_ids, image_of, weights, cls):
+    """The ct_aug_sample rows of a device batch and its concatenated pixel boxes: per sample its image, [G,5] targets,
+    source offset, 64-bit id, batch image and row weight -> (samples, boxes float32 [total,5], max_gt)."""
+    samples = np.zeros(len(images), dtype=ops.AUG_SAMPLE_DTYPE)
+    parts, pos = [], 0
+    for k, (img, tg) in enumerate(zip(images, targets)):
+        tg = np.asarray(tg, dtype=np.float32).reshape(-1, 5)
+        samples[k] = (offs[k], sample_ids[k], img.shape[0], img.shape[1], pos, pos + len(tg), image_of[k],
+                      -1 if cls is None else cls, weights[k], 0)
+        pos += len(tg)
+        parts.append(tg)
+    boxes = np.concatenate(parts, 0) if pos else np.zeros((0, 5), dtype=np.float32)
+    return samples, boxes, max(max(len(p) for p in parts), 1)
 
 
 class preproc(object):
@@ -236,24 +251,15 @@ class preproc(object):
             if two:
                 imgs.append(mix[0][i]); tgs.append(mix[1][i])
                 rec.append((i, int(sample_ids[i]) + 2 ** 63, np.float32(1. - lam[i])))
-        offs = self._aug_dev.upload(imgs)
         m = len(imgs)
-        samples = np.zeros(m, dtype=ops.AUG_SAMPLE_DTYPE)
-        parts, pos = [], 0
-        for k, (img, tg) in enumerate(zip(imgs, tgs)):
-            tg = np.asarray(tg, dtype=np.float32).reshape(-1, 5)
-            samples[k] = (offs[k], rec[k][1] % 2 ** 64, img.shape[0], img.shape[1], pos, pos + len(tg), rec[k][0],
-                          -1 if cls is None else cls, rec[k][2], 0)
-            pos += len(tg)
-            parts.append(tg)
-        boxes = np.concatenate(parts, 0) if pos else np.zeros((0, 5), dtype=np.float32)
-        max_gt = max(max(len(p) for p in parts), 1)
+        samples, boxes, max_gt = _pack_samples(imgs, tgs, self._aug_dev.upload(imgs), [r[1] % 2 ** 64 for r in rec],
+                                               [r[0] for r in rec], [r[2] for r in rec], cls)
         plans, packed = self._planner(samples, boxes, n, max_gt)
         if mix is None:
             return self._aug_dev.render(plans, n), packed
         # the plans of the first samples, then of the second ones (a lambda >= 1 blends an image with itself)
         order = torch.tensor(first + second, dtype=torch.int64).to(self.device, non_blocking=True)
-        x = self._aug_dev.render(plans.view(m, 96).index_select(0, order).reshape(-1), 2 * n)
+        x = self._aug_dev.render(plans.view(m, ops.PLAN_BYTES).index_select(0, order).reshape(-1), 2 * n)
         return ops.mixup_blend(x[:n], x[n:], torch.tensor(lam, dtype=torch.float32).clamp(max=1.0).to(self.device)), packed
 
     def mosaic_device(self, images, targets, sample_ids, cls=None, margin=None):
@@ -275,17 +281,9 @@ class preproc(object):
         if not 1 <= margin <= S // 2:
             raise ValueError('preproc.mosaic_device: margin %d outside 1..%d' % (margin, S // 2))
         self._device_staging(4)
-        offs = self._aug_dev.upload(images)
-        samples = np.zeros(4 * n, dtype=ops.AUG_SAMPLE_DTYPE)
-        parts, pos = [], 0
-        for s, (img, tg) in enumerate(zip(images, targets)):
-            tg = np.asarray(tg, dtype=np.float32).reshape(-1, 5)
-            samples[s] = (offs[s], (int(sample_ids[s // 4]) + (s % 4) * 2 ** 61) % 2 ** 64, img.shape[0], img.shape[1],
-                          pos, pos + len(tg), s // 4, -1 if cls is None else cls, 1.0, 0)
-            pos += len(tg)
-            parts.append(tg)
-        boxes = np.concatenate(parts, 0) if pos else np.zeros((0, 5), dtype=np.float32)
-        max_gt = max(max(len(p) for p in parts), 1)
+        ids = [(int(sample_ids[s // 4]) + (s % 4) * 2 ** 61) % 2 ** 64 for s in range(4 * n)]
+        samples, boxes, max_gt = _pack_samples(images, targets, self._aug_dev.upload(images), ids,
+                                               [s // 4 for s in range(4 * n)], [1.0] * (4 * n), cls)
         plans, tiles, packed = self._planner.mosaic(samples, boxes, n, max_gt, S, margin)
         return self._aug_dev.render_mosaic(plans, tiles, n), packed
 

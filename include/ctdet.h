@@ -1335,7 +1335,7 @@ int ct_preproc_resize(const unsigned char* src, const long long* offsets, const 
 
 /* Training-time augmentation, data/data_augment.py:164-221 (`preproc.__call__`): crop -> photometric distortion
  * (8-bit HSV space) -> expand on a mean-filled canvas -> mirror -> resize -> minus means -> CHW, one gather launch
- * per batch.  `plans` = device array of `batch` 96-byte records (ctdet/ops.py AugPlan: source offset / size, crop
+ * per batch.  `plans` = device array of `batch` records, typedef ct_aug_plan_record below (source offset / size, crop
  * rectangle, canvas size and placement, mirror flag, interpolation 0 linear / 1 nearest / 2 area, distortion flags
  * 1 brightness 2 contrast 4 hue 8 saturation with their parameters, canvas fill) holding the random DECISIONS the
  * host logic drew like the reference does.  Pixel arithmetic restates OpenCV's published 8-bit formulas (cv2 is
@@ -1426,6 +1426,20 @@ typedef struct {
                                      2: labels of the kept rows after the first become -1 (voc0712.py:237-238) */
 } ct_aug_sample;                  /* 48 bytes */
 
+/* One image's augmentation decisions: what ct_aug_plan writes per sample and every ct_preproc_augment* entry reads
+ * (their `plans` arguments are arrays of these; the Python twins are in ctdet/aug_records.py). */
+typedef struct {
+    long long src_off;                        /* byte offset of the HxWx3 uint8 source image */
+    int H, W;
+    int crop_l, crop_t, crop_w, crop_h;
+    int exp_w, exp_h, exp_left, exp_top;      /* canvas size (= crop size when not expanded) and placement */
+    int mirror, interp;                       /* interp: 0 linear, 1 nearest, 2 area; 3 bicubic, 4 Lanczos4 (taps entry only) */
+    int flags, hue_delta;                     /* flags: 1 brightness, 2 contrast, 4 hue, 8 saturation */
+    float beta, alpha, sat_alpha;
+    float fill[3];
+    float pad0, pad1;
+} ct_aug_plan_record;             /* 96 bytes */
+
 size_t ct_aug_plan_workspace_bytes(int num_samples, int max_gt);
 int ct_aug_plan(const ct_aug_sample* samples,   /* device array [num_samples] */
                 int num_samples,
@@ -1437,7 +1451,7 @@ int ct_aug_plan(const ct_aug_sample* samples,   /* device array [num_samples] */
                 float p_expand,
                 const int* interp_of_draw5,     /* host array */
                 const float* fill3,             /* host array */
-                void* plans_out,                /* device, num_samples x 96 bytes: the AugPlan layout of csrc/ct_preproc.hip / ctdet/ops.py */
+                void* plans_out,                /* device, ct_aug_plan_record [num_samples] */
                 float* truths_out,              /* device, [truths_cap,6] */
                 int truths_cap,
                 int* gt_off_out,                /* device, [num_images+1] */

@@ -75,6 +75,34 @@ def test_identity_plan_equals_plain_resize():
     assert float((a - b).abs().max()) <= 1.0
 
 
+def test_staging_grows_and_is_reused():
+    """One Augmenter, sized for 16x16 images, through three batches: one inside its capacity, one with a 40x33 image
+    (the source staging must grow) and a bicubic plan (the tap staging is created late), then the first again.  Every
+    result is bit for bit what a fresh, amply sized Augmenter gives for the same images and plans."""
+    from data.data_augment import _plan
+    from ctdet import ops
+    S, rng = 24, np.random.RandomState(7)
+
+    def plan(im, mirror, interp=0):
+        p = _plan(im.shape[0], im.shape[1])
+        p['mirror'], p['interp'] = mirror, interp
+        return p
+    small = [_image(rng, 12, 16), _image(rng, 16, 12)]
+    big = [_image(rng, 40, 33), small[1], _image(rng, 9, 20)]
+    first = (small, [plan(small[0], 1), plan(small[1], 0)])
+    second = (big, [plan(big[0], 1, interp=3), plan(big[1], 1), plan(big[2], 0)])
+    aug = ops.Augmenter(S, MEANS, 'cuda', max_batch=3, max_pixels=16 * 16)
+    cap = aug.dev.numel()
+    assert cap == 3 * 16 * 16 * 3 and sum(im.size for im in small) <= cap < sum(im.size for im in big)
+    got = []
+    for images, plans in (first, second, first):
+        got.append(aug(images, plans))
+        fresh = ops.Augmenter(S, MEANS, 'cuda', max_batch=4, max_pixels=64 * 64)
+        assert torch.equal(got[-1], fresh(images, plans)), len(got)
+        assert (aug.dev.numel() > cap) == (len(got) >= 2)
+    assert torch.equal(got[2], got[0]) and not torch.equal(got[1][1], got[0][1])
+
+
 def test_mixup_blend():
     g = torch.Generator().manual_seed(0)
     a, b = torch.randn(4, 3, 64, 64, generator=g).cuda(), torch.randn(4, 3, 64, 64, generator=g).cuda()

@@ -104,7 +104,7 @@ def probe(batch, g, mixup, rounds):
     return dict(boxes=g, mixup=mixup, samples=m, host_decide_ms=round(statistics.median(t_host), 3),
                 dev_ms=round(statistics.median(t_dev), 4), planner_host_ms=round(statistics.median(t_call), 3),
                 kernels_ms=round(kernels_ms, 4), launches=names,
-                upload_before=m * 96 + rows * 24 + (batch + 1) * 4, upload_after=planner.upload_bytes)
+                upload_before=m * ops.PLAN_BYTES + rows * 24 + (batch + 1) * 4, upload_after=planner.upload_bytes)
 
 
 def main():
