@@ -6,6 +6,7 @@
 #include "ct_device.h"
 #include "ct_f16x2.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 
 namespace {
@@ -123,6 +124,46 @@ __global__ __launch_bounds__(256) void bn_stats_part_kernel(const StatsOp op, in
 }
 __global__ void bn_stats_final_kernel(const StatsOp op, const double* __restrict__ scratch, int slices) { bn_reduce_final(op, scratch, slices, op.C); }
 
+// The synchronized (cross-rank) forms split a pass into local sums, a collective the caller runs on them, and a finish.  SumsOp
+// gives a reduction the terms of Inner, but a channel ends as its two double sums at sums[2][C]; KEEP also runs Inner's finish
+// on those local sums (the backward's parameter gradients, which the gradient all-reduce averages).
+template <class Inner, bool KEEP>
+struct SumsOp {
+    Inner in;
+    double* sums;
+    int C;
+
+    __device__ void channel(int c) { in.channel(c); }
+    __device__ void add(int n, int c, int i, double& s0, double& s1) const { in.add(n, c, i, s0, s1); }
+    __device__ void finish(int c, double s0, double s1) const
+    {
+        sums[c] = s0;
+        sums[C + c] = s1;
+        if (KEEP) in.finish(c, s0, s1);
+    }
+};
+
+struct BnSyncStatsArgs {
+    StatsOp op;              // z and its slicing; nothing of `finish` is used
+    double* sums;
+};
+using SyncStatsOp = SumsOp<StatsOp, false>;
+
+__global__ __launch_bounds__(256) void bn_sync_stats_kernel(const BnSyncStatsArgs s)
+{
+    bn_reduce<Walk::WHOLE>(SyncStatsOp{s.op, s.sums, s.op.C}, s.op.batch, s.op.C, s.op.HW, 0, nullptr, 0);
+}
+__global__ __launch_bounds__(256) void bn_sync_stats_part_kernel(const BnSyncStatsArgs s, int per_slice, double* __restrict__ scratch, int det)
+{
+    bn_reduce<Walk::SLICE>(SyncStatsOp{s.op, s.sums, s.op.C}, s.op.batch, s.op.C, s.op.HW, per_slice, scratch, det);
+}
+__global__ void bn_sync_stats_final_kernel(const BnSyncStatsArgs s, const double* __restrict__ scratch, int slices)
+{
+    bn_reduce_final(SyncStatsOp{s.op, s.sums, s.op.C}, scratch, slices, s.op.C);
+}
+// mean, variance and running statistics from the reduced sums: StatsOp::finish with the global count, on ONE record
+__global__ void bn_sync_finish_kernel(const StatsOp op, const double* __restrict__ sums) { bn_reduce_final(op, sums, 1, op.C); }
+
 struct BnApplyArgs {
     const float* z;          // conv output, channel slice [z_coff, z_coff+C) of z_ctot
     const float* mean;
@@ -202,11 +243,15 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_part_kernel(const BnBwdArgs
 }
 __global__ void bn_bwd_reduce_final_kernel(const BnBwdArgs a, const double* __restrict__ scratch, int slices) { bn_reduce_final(BwdOp{a}, scratch, slices, a.C); }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a)
+// dz (and the residual branch's gradient) of every element.  G gives the two sums of the statistics terms and their divisor: the
+// layer's own dbeta / dgamma and element count, or the cross-rank sums and the global count of the synchronized form.  The kernel
+// passes its grid-stride loop's first index and stride.
+template <class G>
+__device__ __forceinline__ void bn_bwd_apply(const BnBwdArgs& a, const G grads, unsigned first, unsigned stride)
 {
     const long total = (long)a.batch * a.C * a.HW;
-    const float cnt = (float)a.batch * a.HW;
-    for (unsigned idx = blockIdx.x * blockDim.x + threadIdx.x; idx < (unsigned)total; idx += gridDim.x * blockDim.x) {
+    const float cnt = grads.count();
+    for (unsigned idx = first; idx < (unsigned)total; idx += stride) {
         const int i = (int)(idx % a.HW);
         const unsigned t = idx / a.HW;
         const int c = (int)(t % a.C);
@@ -221,8 +266,51 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a)
         const size_t zi = ((size_t)n * a.z_ctot + a.z_coff + c) * a.HW + i;
         const float xh = (a.z[zi] - a.mean[c]) * inv;
         a.dz[zi] = a.frozen ? a.gamma[c] * inv * g
-                            : a.gamma[c] * inv * (g - a.dbeta[c] / cnt - xh * a.dgamma[c] / cnt);
+                            : a.gamma[c] * inv * (g - grads.dbeta(c) / cnt - xh * grads.dgamma(c) / cnt);
     }
+}
+
+struct OwnGrads {
+    const BnBwdArgs& a;
+    __device__ float count() const { return (float)a.batch * a.HW; }
+    __device__ float dbeta(int c) const { return a.dbeta[c]; }
+    __device__ float dgamma(int c) const { return a.dgamma[c]; }
+};
+struct ReducedGrads {
+    const double* sums;      // [2][C]: sum g, sum g * xhat over every rank's shard
+    double cnt;
+    int C;
+    __device__ float count() const { return (float)cnt; }
+    __device__ float dbeta(int c) const { return (float)sums[c]; }
+    __device__ float dgamma(int c) const { return (float)sums[C + c]; }
+};
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a)
+{
+    bn_bwd_apply(a, OwnGrads{a}, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+struct BnSyncBwdArgs {
+    BnBwdArgs a;
+    double* sums;
+};
+using SyncBwdOp = SumsOp<BwdOp, true>;
+
+__global__ __launch_bounds__(256) void bn_sync_bwd_kernel(const BnSyncBwdArgs s)
+{
+    bn_reduce<Walk::WHOLE>(SyncBwdOp{BwdOp{s.a}, s.sums, s.a.C}, s.a.batch, s.a.C, s.a.HW, 0, nullptr, 0);
+}
+__global__ __launch_bounds__(256) void bn_sync_bwd_part_kernel(const BnSyncBwdArgs s, int per_slice, double* __restrict__ scratch, int det)
+{
+    bn_reduce<Walk::SLICE>(SyncBwdOp{BwdOp{s.a}, s.sums, s.a.C}, s.a.batch, s.a.C, s.a.HW, per_slice, scratch, det);
+}
+__global__ void bn_sync_bwd_final_kernel(const BnSyncBwdArgs s, const double* __restrict__ scratch, int slices)
+{
+    bn_reduce_final(SyncBwdOp{BwdOp{s.a}, s.sums, s.a.C}, scratch, slices, s.a.C);
+}
+__global__ __launch_bounds__(256) void bn_sync_bwd_apply_kernel(const BnBwdArgs a, const double* __restrict__ sums, double count)
+{
+    bn_bwd_apply(a, ReducedGrads{sums, count, a.C}, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // The tail of the two bias backward kernels: the block's share of dbias[c] is stored at slab[slot][C] (deterministic mode:
@@ -621,6 +709,27 @@ extern "C" int ct_bn_train_apply(const float* z, const float* mean, const float*
     return CT_OK;
 }
 
+// the checks and the argument record all BatchNorm backward entries share (dgamma / dbeta: null where the entry writes none)
+static int bn_bwd_args(const char* who, BnBwdArgs& a, int frozen, const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
+                       int y_coff, const float* z, const float* mean, const float* var,
+                       const float* gamma, float eps, int relu, const float* lo,
+                       float res_scale, float* dres, int dres_ctot, int dres_coff,
+                       int dres_accumulate, float* dz, float* dgamma, float* dbeta,
+                       int z_ctot, int z_coff, int batch, int channels, int hw)
+{
+    CT_REQUIRE(!(relu || lo) || y, "%s: ReLU mask needs the forward output", who);
+    CT_REQUIRE((long)batch * channels * hw <= kMaxLoopElems, "%s: too many elements (2^32 less one grid stride at most)", who);
+    a = BnBwdArgs{};
+    a.dy = dy; a.y = y; a.z = z; a.mean = mean; a.var = var; a.gamma = gamma; a.lo = lo;
+    a.dz = dz; a.dgamma = dgamma; a.dbeta = dbeta; a.dres = dres;
+    a.batch = batch; a.C = channels; a.HW = hw; a.dy_ctot = dy_ctot; a.dy_coff = dy_coff;
+    a.y_ctot = y_ctot; a.y_coff = y_coff; a.dres_ctot = dres_ctot; a.dres_coff = dres_coff;
+    a.dres_accumulate = dres_accumulate; a.eps = eps; a.rscale = res_scale; a.relu = relu;
+    a.z_ctot = z_ctot; a.z_coff = z_coff;
+    a.frozen = frozen;
+    return CT_OK;
+}
+
 static int bn_backward_impl(const char* who, bool det, size_t scratch_bytes, int frozen, const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot,
                             int y_coff, const float* z, const float* mean, const float* var,
                             const float* gamma, float eps, int relu, const float* lo,
@@ -630,16 +739,9 @@ static int bn_backward_impl(const char* who, bool det, size_t scratch_bytes, int
                             void* scratch, ct_stream_t stream)
 {
     CT_REQUIRE(dy && z && mean && var && gamma && dz && dgamma && dbeta, "%s: null pointer", who);
-    CT_REQUIRE(!(relu || lo) || y, "%s: ReLU mask needs the forward output", who);
-    CT_REQUIRE((long)batch * channels * hw <= kMaxLoopElems, "%s: too many elements (2^32 less one grid stride at most)", who);
-    BnBwdArgs a{};
-    a.dy = dy; a.y = y; a.z = z; a.mean = mean; a.var = var; a.gamma = gamma; a.lo = lo;
-    a.dz = dz; a.dgamma = dgamma; a.dbeta = dbeta; a.dres = dres;
-    a.batch = batch; a.C = channels; a.HW = hw; a.dy_ctot = dy_ctot; a.dy_coff = dy_coff;
-    a.y_ctot = y_ctot; a.y_coff = y_coff; a.dres_ctot = dres_ctot; a.dres_coff = dres_coff;
-    a.dres_accumulate = dres_accumulate; a.eps = eps; a.rscale = res_scale; a.relu = relu;
-    a.z_ctot = z_ctot; a.z_coff = z_coff;
-    a.frozen = frozen;
+    BnBwdArgs a;
+    if (int rc = bn_bwd_args(who, a, frozen, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, mean, var, gamma, eps, relu, lo, res_scale, dres,
+                             dres_ctot, dres_coff, dres_accumulate, dz, dgamma, dbeta, z_ctot, z_coff, batch, channels, hw)) return rc;
     hipStream_t st = ctdet::as_stream(stream);
     static const BnReduction<BnBwdArgs> kernels{bn_bwd_reduce_kernel, bn_bwd_reduce_part_kernel, bn_bwd_reduce_final_kernel,
                                                 "bn_bwd_reduce_kernel", "bn_bwd_reduce_part_kernel", "bn_bwd_reduce_final_kernel"};
@@ -699,6 +801,96 @@ extern "C" int ct_bn_eval_backward_det(const float* dy, int dy_ctot, int dy_coff
     return bn_backward_impl("ct_bn_eval_backward_det", true, scratch_bytes, 1, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, running_mean,
                             running_var, gamma, eps, relu, lo, res_scale, dres, dres_ctot, dres_coff, dres_accumulate, dz, dgamma,
                             dbeta, z_ctot, z_coff, batch, channels, hw, scratch, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// Synchronized BatchNorm: a pass is local sums -> the caller's SUM collective over the ranks -> finish / apply
+// ------------------------------------------------------------------------------------------
+// what the four entries refuse before any HIP call, beyond their null pointers
+static int bn_sync_sizes(const char* who, int batch, int channels, int hw)
+{
+    CT_REQUIRE(batch > 0 && channels > 0 && hw > 0, "%s: batch, channels and hw must be positive", who);
+    return CT_OK;
+}
+static int bn_sync_count(const char* who, double count)
+{
+    CT_REQUIRE(std::isfinite(count) && count >= 1.0, "%s: count must be finite and at least 1 (the global batch * hw)", who);
+    return CT_OK;
+}
+static int bn_sync_scratch(const char* who, const void* scratch)
+{
+    CT_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "%s: scratch must be 8-byte aligned", who);
+    return CT_OK;
+}
+
+extern "C" int ct_bn_sync_stats_local(const float* z, int batch, int ctot, int coff, int channels, int hw, double* sums,
+                                      void* scratch, size_t scratch_bytes, ct_stream_t stream)
+{
+    const char* who = "ct_bn_sync_stats_local";
+    CT_REQUIRE(z && sums, "%s: null pointer", who);
+    if (int rc = bn_sync_sizes(who, batch, channels, hw)) return rc;
+    if (int rc = bn_sync_scratch(who, scratch)) return rc;
+    BnSyncStatsArgs s{};
+    s.op.z = z; s.op.batch = batch; s.op.ctot = ctot; s.op.coff = coff; s.op.C = channels; s.op.HW = hw;
+    s.sums = sums;
+    static const BnReduction<BnSyncStatsArgs> kernels{bn_sync_stats_kernel, bn_sync_stats_part_kernel, bn_sync_stats_final_kernel,
+                                                      "bn_sync_stats_kernel", "bn_sync_stats_part_kernel", "bn_sync_stats_final_kernel"};
+    return bn_reduce_launch(who, kernels, s, batch, channels, hw, scratch, true, scratch_bytes, ctdet::as_stream(stream));
+}
+
+extern "C" int ct_bn_sync_stats_finish(const double* sums, double count, int channels, float* mean, float* var, float momentum,
+                                       float* running_mean, float* running_var, ct_stream_t stream)
+{
+    const char* who = "ct_bn_sync_stats_finish";
+    CT_REQUIRE(sums && mean && var, "%s: null pointer", who);
+    CT_REQUIRE(channels > 0, "%s: channels must be positive", who);
+    if (int rc = bn_sync_count(who, count)) return rc;
+    const bool run = running_mean && running_var;
+    const float cntf = (float)count;
+    StatsOp op{};
+    op.mean = mean; op.var = var; op.rmean = run ? running_mean : nullptr; op.rvar = run ? running_var : nullptr;
+    op.cnt = count; op.C = channels; op.momentum = momentum; op.unbias = cntf > 1.f ? cntf / (cntf - 1.f) : 1.f;
+    hipLaunchKernelGGL(bn_sync_finish_kernel, dim3((channels + 255) / 256), dim3(256), 0, ctdet::as_stream(stream), op, sums);
+    CT_LAUNCH_CHECK("bn_sync_finish_kernel");
+    return CT_OK;
+}
+
+extern "C" int ct_bn_sync_backward_local(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot, int y_coff,
+                                         const float* z, const float* mean, const float* var, float eps, int relu, const float* lo,
+                                         float res_scale, int z_ctot, int z_coff, int batch, int channels, int hw,
+                                         double* sums, float* dgamma, float* dbeta, void* scratch, size_t scratch_bytes,
+                                         ct_stream_t stream)
+{
+    const char* who = "ct_bn_sync_backward_local";
+    CT_REQUIRE(dy && z && mean && var && sums && dgamma && dbeta, "%s: null pointer", who);
+    if (int rc = bn_sync_sizes(who, batch, channels, hw)) return rc;
+    if (int rc = bn_sync_scratch(who, scratch)) return rc;
+    BnSyncBwdArgs s{};
+    if (int rc = bn_bwd_args(who, s.a, 0, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, mean, var, nullptr, eps, relu, lo, res_scale, nullptr,
+                             0, 0, 0, nullptr, dgamma, dbeta, z_ctot, z_coff, batch, channels, hw)) return rc;
+    s.sums = sums;
+    static const BnReduction<BnSyncBwdArgs> kernels{bn_sync_bwd_kernel, bn_sync_bwd_part_kernel, bn_sync_bwd_final_kernel,
+                                                    "bn_sync_bwd_kernel", "bn_sync_bwd_part_kernel", "bn_sync_bwd_final_kernel"};
+    return bn_reduce_launch(who, kernels, s, batch, channels, hw, scratch, true, scratch_bytes, ctdet::as_stream(stream));
+}
+
+extern "C" int ct_bn_sync_backward_apply(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot, int y_coff,
+                                         const float* z, const float* mean, const float* var, const float* gamma, float eps,
+                                         int relu, const float* lo, float res_scale, float* dres, int dres_ctot, int dres_coff,
+                                         int dres_accumulate, float* dz, int z_ctot, int z_coff, int batch, int channels, int hw,
+                                         const double* sums, double count, ct_stream_t stream)
+{
+    const char* who = "ct_bn_sync_backward_apply";
+    CT_REQUIRE(dy && z && mean && var && gamma && dz && sums, "%s: null pointer", who);
+    if (int rc = bn_sync_sizes(who, batch, channels, hw)) return rc;
+    if (int rc = bn_sync_count(who, count)) return rc;
+    BnBwdArgs a;
+    if (int rc = bn_bwd_args(who, a, 0, dy, dy_ctot, dy_coff, y, y_ctot, y_coff, z, mean, var, gamma, eps, relu, lo, res_scale, dres,
+                             dres_ctot, dres_coff, dres_accumulate, dz, nullptr, nullptr, z_ctot, z_coff, batch, channels, hw)) return rc;
+    hipLaunchKernelGGL(bn_sync_bwd_apply_kernel, dim3(grid_for((long)batch * channels * hw)), dim3(256), 0, ctdet::as_stream(stream),
+                       a, sums, count);
+    CT_LAUNCH_CHECK("bn_sync_bwd_apply_kernel");
+    return CT_OK;
 }
 
 // slices of a channel's batch*hw elements in the bias + activation backward, and the elements of one

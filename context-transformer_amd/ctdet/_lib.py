@@ -249,6 +249,12 @@ SIGNATURES = {
                                   _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     'ct_bn_eval_backward': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _I, _P, _F, _P, _I, _I, _I,
                                  _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    'ct_bn_sync_stats_local': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    'ct_bn_sync_stats_finish': (_I, [_P, _D, _I, _P, _P, _F, _P, _P, _P]),
+    'ct_bn_sync_backward_local': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _F, _I, _P, _F, _I, _I, _I, _I, _I,
+                                       _P, _P, _P, _P, _Z, _P]),
+    'ct_bn_sync_backward_apply': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _I, _P, _F, _P, _I, _I, _I,
+                                       _P, _I, _I, _I, _I, _I, _P, _D, _P]),
     'ct_bias_act_backward': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     'ct_maxpool2x2_bias_relu_bwd': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
     'ct_bias_act_backward_amax': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P]),

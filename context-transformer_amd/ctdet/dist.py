@@ -5,9 +5,12 @@ no collective on the data path -- the process group is only used for the timing 
 max-over-ranks step time and (optionally) gathering the per-image detection lists on rank 0.
 """
 import os
+import zlib
 
 import torch
 import torch.distributed as dist
+
+from ._lib import CtdetError
 
 
 def env_world():
@@ -127,6 +130,69 @@ class GradBucketer:
         self.handles = []
         if self.world > 1:
             self.flat.div_(self.world)
+
+
+class BnStatSyncer:
+    """The collectives of synchronized BatchNorm (TrainRuntime.enable_bn_sync; any device, gloo in the CPU tests).
+
+    `stages`: [(name, [channels of every unfrozen BatchNorm part])] in forward order.  ONE float64 arena holds, per stage, a
+    forward view (per part: sum z, then sum z^2, [2][channels]) and a backward view (sum g, then sum g*xhat); the local kernels
+    write a part's pair at part(view, k), reduce_forward / reduce_backward add the stage's view over the ranks with one
+    all_reduce(SUM) on the current stream.  Construction makes one reduction of the per-rank batch sizes (uneven shards are
+    fine: `global_batch`) and compares a checksum of the stage layout across the ranks: on a mismatch EVERY rank raises."""
+
+    def __init__(self, stages, local_batch, device, group=None):
+        self.group = group
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.stages = [(str(n), [int(c) for c in cs]) for n, cs in stages]
+        self.part_off, self.span = {}, {}
+        o = 0
+        for name, cs in self.stages:
+            offs = [0]
+            for c in cs:
+                offs.append(offs[-1] + 2 * c)
+            self.part_off[name] = offs
+            self.span[name] = (o, o + offs[-1], o + 2 * offs[-1])       # forward view, then backward view
+            o += 2 * offs[-1]
+        self.arena = torch.zeros(max(o, 1), dtype=torch.float64, device=device)
+        self.collectives = 0                    # all_reduce calls on the arena so far (two per stage and step)
+        self.global_batch = int(local_batch)
+        if self.world > 1:
+            crc = float(zlib.crc32(repr(self.stages).encode()))
+            t = torch.tensor([crc, -crc], dtype=torch.float64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+            hi, lo = float(t[0]), -float(t[1])
+            b = torch.tensor([float(local_batch)], dtype=torch.float64, device=device)
+            dist.all_reduce(b, op=dist.ReduceOp.SUM, group=group)
+            if hi != lo:
+                raise CtdetError('synchronized BatchNorm: the ranks disagree about the BatchNorm stages (layout checksums '
+                                 '%d .. %d over the group, %d here: %d stages): every rank must build the same network with '
+                                 'the same layers in train mode' % (int(lo), int(hi), int(crc), len(self.stages)))
+            self.global_batch = int(round(float(b[0])))
+
+    def forward_view(self, name):
+        a, b, _ = self.span[name]
+        return self.arena[a:b]
+
+    def backward_view(self, name):
+        _, a, b = self.span[name]
+        return self.arena[a:b]
+
+    def part(self, view, name, k):
+        """The [2][channels] pair of part k inside a stage's view."""
+        offs = self.part_off[name]
+        return view[offs[k]:offs[k + 1]]
+
+    def _reduce(self, view):
+        if self.world > 1 and view.numel():
+            dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group)
+            self.collectives += 1
+
+    def reduce_forward(self, name):
+        self._reduce(self.forward_view(name))
+
+    def reduce_backward(self, name):
+        self._reduce(self.backward_view(name))
 
 
 def global_normalizer(n_local, device):

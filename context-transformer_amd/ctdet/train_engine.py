@@ -23,6 +23,11 @@ per split, added in order, in place of floating-point atomics: include/ctdet.h),
 the Context-Transformer block is refused under it.  CTDET_TRAIN_DETERMINISTIC=2: all of that, and the block's backward runs
 ct_ctx_attention_bwd_det (ops.CtxTrainer(deterministic=True)), so forward(use_ctx=True) is accepted and a whole phase-2 step
 repeats bit for bit.
+
+enable_bn_sync() (opt-in; CTDET_SYNC_BN=1 has enable_grad_sync() call it): data-parallel ranks normalise with the statistics of the
+GLOBAL batch.  Per BatchNorm stage the forward runs ct_bn_sync_stats_local for every unfrozen part, ONE all-reduce of the stage's
+float64 sums (ctdet.dist.BnStatSyncer), ct_bn_sync_stats_finish, then the unchanged ct_bn_train_apply; the backward runs
+ct_bn_sync_backward_local, one all-reduce, ct_bn_sync_backward_apply.  The local reductions are the ordered form in either mode.
 """
 import ctypes as C
 import os
@@ -46,6 +51,10 @@ class LayerState:
     var: list = field(default_factory=list)
     scratch: list = field(default_factory=list)
     frozen: list = field(default_factory=list)
+    # synchronized BatchNorm: the parts enable_bn_sync() found in train mode, and per part the slice sums of the sync entries'
+    # ordered reductions (a view of TrainRuntime.bn_sync_scratch; in deterministic mode the part's det_scratch slice itself)
+    sync_parts: list = field(default_factory=list)
+    sync_scratch: list = field(default_factory=list)
     # epilogue gradients: dZ of zc channels (cout; the heads' padded with zero channels, whose weights are zero_w), per-part
     # parameter gradients (views of the gradient arena); dz_from_pool: the fused pool backward wrote dZ in this pass
     zc: int = 0
@@ -91,13 +100,15 @@ class TrainSwitches:
     ksplit: int             # CTDET_KSPLIT=0: no split-K slabs for the data gradients
     deterministic: bool = False     # CTDET_TRAIN_DETERMINISTIC=1 or 2: ordered slab sums in place of the floating-point atomics
     deterministic_ctx: bool = False     # CTDET_TRAIN_DETERMINISTIC=2: the Context-Transformer block's backward too
+    sync_bn: bool = False           # CTDET_SYNC_BN=1: enable_grad_sync() also synchronizes the BatchNorm statistics (enable_bn_sync)
 
     @classmethod
     def of(cls, env):
         det = env.get('CTDET_TRAIN_DETERMINISTIC', '0')
         return cls(env.get('CTDET_PACK_BATCH', '1') != '0', env.get('CTDET_PREZERO', '1') != '0',
                    env.get('CTDET_TRAIN_FUSE_POOL_BWD', '1') != '0', int(env.get('CTDET_TRAIN_STREAMS', '2')),
-                   int(env.get('CTDET_KSPLIT', '1')), det not in ('', '0'), det == '2')
+                   int(env.get('CTDET_KSPLIT', '1')), det not in ('', '0'), det == '2',
+                   env.get('CTDET_SYNC_BN', '0') not in ('', '0'))
 
 
 class PackList:
@@ -135,6 +146,8 @@ class TrainRuntime:
         self._pack_table, self._pack_ptrs, self._pack_counts, self._recording = None, None, (0, 0), False
         self._x3_list, self._h2_list = PackList(self.lib, 'ct_conv_x3_pack'), PackList(self.lib, 'ct_conv_wino_h2_pack')
         self.bucketer, self.generation, self.used_ctx, self.amax_slots, self._wired_epoch = None, 0, False, {}, None
+        self.bn_sync_scratch = None
+        self.bn_sync = None                     # ctdet.dist.BnStatSyncer once enable_bn_sync() found more than one rank
         self.wgrad_wsh2 = self.wgrad_ws_all = self.bn_scratch = self.wgrad_wsdet = self.det_scratch = None
         self.det, self.det_ctx = self.switches.deterministic, self.switches.deterministic_ctx
         self.params, self._pindex, self.ctx = [], {}, None      # params: ordered parameters that receive gradients
@@ -441,7 +454,49 @@ class TrainRuntime:
         large buckets, overlapped with the rest of the backward pass (ctdet.dist.GradBucketer)."""
         from .dist import GradBucketer
         self.bucketer = GradBucketer([p.numel() for p in self.production_order()], self.be.device, bucket_bytes, group, flat=self.arena)
+        if self.switches.sync_bn:
+            self.enable_bn_sync(group)
         return self.bucketer
+
+    def enable_bn_sync(self, group=None):
+        """Data-parallel training: every BatchNorm layer in train mode normalises with the statistics of the GLOBAL batch, and its
+        backward uses the global sums (ctdet.dist.BnStatSyncer; the ct_bn_sync_* entries).  Per stage and pass: the local sums of
+        every unfrozen part, ONE all-reduce, finish / apply.  Independent of enable_grad_sync(); a no-op for a world of one
+        without a group.  Call it again after moving BatchNorm layers between train() and eval()."""
+        import torch.distributed as dist
+        from .dist import BnStatSyncer
+        if group is None and (not dist.is_initialized() or dist.get_world_size() == 1):
+            self.bn_sync = None
+            return None
+        stages = []
+        for st, s in self._convs():
+            if s.is_bn:
+                s.sync_parts = [i for i, p in enumerate(st.parts) if p.bn.training]
+                if s.sync_parts:
+                    stages.append((st.name, [st.parts[i].cout for i in s.sync_parts]))
+        if self.det:
+            for _, s in self._convs():
+                if s.is_bn:
+                    s.sync_scratch = list(s.det_scratch)
+        elif self.bn_sync_scratch is None:
+            self._alloc_bn_sync_scratch()
+        self.bn_sync = BnStatSyncer(stages, self.batch, self.be.device, group)
+        return self.bn_sync
+
+    def _alloc_bn_sync_scratch(self):
+        """The ordered reductions of the sync entries store their slice sums like the `_det` twins: outside deterministic mode
+        (which has these slices already) every BatchNorm part gets its own slice of one float64 arena."""
+        sizes = []
+        for st, s in self._convs():
+            if s.is_bn:
+                for p in st.parts:
+                    n = self.lib.ct_bn_det_scratch_bytes(self.batch, p.cout, st.oh * st.ow, None)
+                    sizes.append((s, (int(n) + 15) // 16 * 2))
+        self.bn_sync_scratch = self.be.alloc((max(sum(n for _, n in sizes), 1),), torch.float64)
+        o = 0
+        for s, n in sizes:
+            s.sync_scratch.append(self.bn_sync_scratch[o:o + n])
+            o += n
 
     def _s(self):
         return C.c_void_p(torch.cuda.current_stream(self.be.device).cuda_stream)
@@ -600,6 +655,9 @@ class TrainRuntime:
         z, dst, hw = self.bufs[s.fwd.dst], self.bufs[st.dst], st.oh * st.ow
         off = 0
         s.frozen = [not p.bn.training for p in st.parts]
+        sync = self.bn_sync is not None
+        if sync:
+            self._bn_sync_stats(st, s, z, hw)
         for i, p in enumerate(st.parts):
             bn = p.bn
             if s.frozen[i]:
@@ -607,9 +665,10 @@ class TrainRuntime:
                 mean_t, var_t = bn.running_mean, bn.running_var
             else:
                 mean_t, var_t = s.mean[i], s.var[i]
-                self._reduce('ct_bn_train_stats', 'ct_bn_train_stats_det',
-                             (z.data_ptr(), B, z.shape[1], off, p.cout, hw, mean_t.data_ptr(), var_t.data_ptr(), float(bn.momentum),
-                              bn.running_mean.data_ptr(), bn.running_var.data_ptr()), s, i, st.name + ' bn stats')
+                if not sync:
+                    self._reduce('ct_bn_train_stats', 'ct_bn_train_stats_det',
+                                 (z.data_ptr(), B, z.shape[1], off, p.cout, hw, mean_t.data_ptr(), var_t.data_ptr(), float(bn.momentum),
+                                  bn.running_mean.data_ptr(), bn.running_var.data_ptr()), s, i, st.name + ' bn stats')
             res = self.bufs[st.res] if st.res is not None else None
             _lib.check(lib.ct_bn_train_apply(
                 z.data_ptr(), mean_t.data_ptr(), var_t.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps),
@@ -617,6 +676,35 @@ class TrainRuntime:
                 st.res_coff, float(st.res_scale), dst.data_ptr(), dst.shape[1], st.dst_coff + off, z.shape[1], off, B, p.cout, hw,
                 self._s()), st.name + ' bn apply')
             off += p.cout
+
+    def _sync_parts(self, st, s):
+        """(k, part index, part, channel offset) of the unfrozen parts of a synchronized stage, k counting them."""
+        live = [i for i, f in enumerate(s.frozen) if not f]
+        if live != s.sync_parts:
+            raise _lib.CtdetError('%s: BatchNorm layers moved between train() and eval() since enable_bn_sync(); call it again '
+                                  '(on every rank)' % st.name)
+        offs = [sum(p.cout for p in st.parts[:i]) for i in live]
+        return [(k, i, st.parts[i], offs[k]) for k, i in enumerate(live)]
+
+    def _bn_sync_stats(self, st, s, z, hw):
+        """Forward statistics of a synchronized stage: local sums of every unfrozen part, one all-reduce, finish with the global
+        count (mean / var / running statistics as ct_bn_train_stats writes them)."""
+        lib, B, sy = self.lib, self.batch, self.bn_sync
+        parts = self._sync_parts(st, s)
+        if not parts:
+            return
+        view = sy.forward_view(st.name)
+        for k, i, p, off in parts:
+            t = s.sync_scratch[i]
+            _lib.check(lib.ct_bn_sync_stats_local(z.data_ptr(), B, z.shape[1], off, p.cout, hw, sy.part(view, st.name, k).data_ptr(),
+                                                  t.data_ptr(), t.numel() * 8, self._s()), st.name + ' bn sync stats')
+        sy.reduce_forward(st.name)
+        count = float(sy.global_batch * hw)
+        for k, i, p, off in parts:
+            bn = p.bn
+            _lib.check(lib.ct_bn_sync_stats_finish(sy.part(view, st.name, k).data_ptr(), count, p.cout, s.mean[i].data_ptr(),
+                                                   s.var[i].data_ptr(), float(bn.momentum), bn.running_mean.data_ptr(),
+                                                   bn.running_var.data_ptr(), self._s()), st.name + ' bn sync finish')
 
     def _scratch(self, s, i):
         """The scratch arguments of part i's reduction: the BatchNorm scratch, or in deterministic mode the part's slab slice and
@@ -773,6 +861,9 @@ class TrainRuntime:
             return
         gy, y = self.grads[st.dst], self.bufs[st.dst]
         off = 0
+        sync = s.is_bn and self.bn_sync is not None
+        if sync:
+            self._bn_sync_backward_sums(st, s, gy, y, hw, ctot)
         for i, p in enumerate(st.parts):
             if s.is_bn:
                 z = self.bufs[s.fwd.dst]
@@ -785,11 +876,17 @@ class TrainRuntime:
                 frozen = s.frozen[i]
                 mean_t, var_t = (p.bn.running_mean, p.bn.running_var) if frozen else (s.mean[i], s.var[i])
                 fn = 'ct_bn_eval_backward' if frozen else 'ct_bn_train_backward'
-                self._reduce(fn, fn + '_det',
-                             (gy.data_ptr(), gy.shape[1], st.dst_coff + off, y.data_ptr(), y.shape[1], st.dst_coff + off, z.data_ptr(),
-                              mean_t.data_ptr(), var_t.data_ptr(), p.bn.weight.data_ptr(), float(p.bn.eps), int(p.relu), None,
-                              float(st.res_scale), dres, dres_ctot, st.res_coff, dres_acc, s.dz.data_ptr(), s.dgamma[i].data_ptr(),
-                              s.dbeta[i].data_ptr(), ctot, off, B, p.cout, hw), s, i, st.name + ' bn bwd')
+                args = (gy.data_ptr(), gy.shape[1], st.dst_coff + off, y.data_ptr(), y.shape[1], st.dst_coff + off, z.data_ptr(),
+                        mean_t.data_ptr(), var_t.data_ptr(), p.bn.weight.data_ptr(), float(p.bn.eps), int(p.relu), None,
+                        float(st.res_scale), dres, dres_ctot, st.res_coff, dres_acc, s.dz.data_ptr())
+                if sync and not frozen:             # dgamma / dbeta: the local sums (_bn_sync_backward_sums); dz from the global ones
+                    sy = self.bn_sync
+                    sums = sy.part(sy.backward_view(st.name), st.name, s.sync_parts.index(i))
+                    _lib.check(lib.ct_bn_sync_backward_apply(*args, ctot, off, B, p.cout, hw, sums.data_ptr(),
+                                                             float(sy.global_batch * hw), self._s()), st.name + ' bn sync bwd')
+                else:
+                    self._reduce(fn, fn + '_det', args + (s.dgamma[i].data_ptr(), s.dbeta[i].data_ptr(), ctot, off, B, p.cout, hw),
+                                 s, i, st.name + ' bn bwd')
                 put(p.bn.weight, s.dgamma[i])
                 put(p.bn.bias, s.dbeta[i])
             else:
@@ -803,6 +900,23 @@ class TrainRuntime:
                 if p.bias is not None:
                     put(p.bias, s.dbias[i])
             off += p.cout
+
+    def _bn_sync_backward_sums(self, st, s, gy, y, hw, ctot):
+        """Backward sums of a synchronized stage: per unfrozen part the local sum g / sum g*xhat (with the global mean / var) and
+        the local dgamma / dbeta, then one all-reduce of the stage's view."""
+        lib, B, sy = self.lib, self.batch, self.bn_sync
+        parts = self._sync_parts(st, s)
+        if not parts:
+            return
+        z, view = self.bufs[s.fwd.dst], sy.backward_view(st.name)
+        for k, i, p, off in parts:
+            t = s.sync_scratch[i]
+            _lib.check(lib.ct_bn_sync_backward_local(
+                gy.data_ptr(), gy.shape[1], st.dst_coff + off, y.data_ptr(), y.shape[1], st.dst_coff + off, z.data_ptr(),
+                s.mean[i].data_ptr(), s.var[i].data_ptr(), float(p.bn.eps), int(p.relu), None, float(st.res_scale), ctot, off, B,
+                p.cout, hw, sy.part(view, st.name, k).data_ptr(), s.dgamma[i].data_ptr(), s.dbeta[i].data_ptr(), t.data_ptr(),
+                t.numel() * 8, self._s()), st.name + ' bn sync bwd sums')
+        sy.reduce_backward(st.name)
 
     def _launch_wgrad(self, st, s, put, main, side):
         """Weight gradient of the fused conv, split back to its parts.  Nothing downstream in this backward pass reads it, so it

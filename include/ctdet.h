@@ -1301,6 +1301,36 @@ int ct_bn_eval_backward(const float* dy, int dy_ctot, int dy_coff, const float* 
                         float* dres, int dres_ctot, int dres_coff, int dres_accumulate,
                         float* dz, float* dgamma, float* dbeta, int z_ctot, int z_coff,
                         int batch, int channels, int hw, void* scratch, ct_stream_t stream);
+/* Synchronized BatchNorm (data-parallel training: statistics over the GLOBAL batch).  Each pass of a layer is split in three:
+ * a local entry leaves the shard's two per-channel sums as doubles at sums[2][channels], the caller adds `sums` over the ranks
+ * (one SUM all-reduce), and a second entry finishes from the reduced sums and count = global batch * hw.
+ *   stats_local     sums = sum z, then sum z*z, over the shard's batch*hw elements of each channel
+ *   stats_finish    m = S0/count, mean = (float)m, var = (float)max(S1/count - m*m, 0), running statistics with the float
+ *                   unbias = count/(count-1) (1 for count <= 1): the expressions of ct_bn_train_stats
+ *   backward_local  sums = sum g, then sum g*xhat, with g = masked dy * res_scale and xhat = (z - mean) / sqrt(var + eps) from
+ *                   the GLOBAL mean / var; dbeta = (float)sum g and dgamma = (float)sum g*xhat of the shard (the gradient
+ *                   all-reduce averages them like every other parameter gradient)
+ *   backward_apply  dz and dres of ct_bn_train_backward, with (float)sums[c], (float)sums[channels + c] and (float)count in
+ *                   place of dbeta[c], dgamma[c] and batch*hw
+ * The local entries are ordered reductions: walk, slice rule, slice order and scratch (ct_bn_det_scratch_bytes) of the `_det`
+ * twins, no floating-point atomics, no memset; one shard with count = batch*hw reproduces the twins bit for bit.  Refused with
+ * CT_ERR_INVALID before any HIP call: a null pointer (dres, lo, y without a mask, the running statistics and a scratch that
+ * one slice does not need may be null), a non-positive size, a count that is not finite and >= 1, a misaligned scratch, a null
+ * scratch where slices > 1; CT_ERR_WORKSPACE: a scratch smaller than slices * 2 * channels doubles. */
+int ct_bn_sync_stats_local(const float* z, int batch, int ctot, int coff, int channels, int hw, double* sums,
+                           void* scratch, size_t scratch_bytes, ct_stream_t stream);
+int ct_bn_sync_stats_finish(const double* sums, double count, int channels, float* mean, float* var, float momentum,
+                            float* running_mean, float* running_var, ct_stream_t stream);
+int ct_bn_sync_backward_local(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot, int y_coff,
+                              const float* z, const float* mean, const float* var, float eps, int relu, const float* lo,
+                              float res_scale, int z_ctot, int z_coff, int batch, int channels, int hw,
+                              double* sums, float* dgamma, float* dbeta, void* scratch, size_t scratch_bytes,
+                              ct_stream_t stream);
+int ct_bn_sync_backward_apply(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot, int y_coff,
+                              const float* z, const float* mean, const float* var, const float* gamma, float eps,
+                              int relu, const float* lo, float res_scale, float* dres, int dres_ctot, int dres_coff,
+                              int dres_accumulate, float* dz, int z_ctot, int z_coff, int batch, int channels, int hw,
+                              const double* sums, double count, ct_stream_t stream);
 /* y = act(conv + bias): dz = dy * (y > 0 if relu) into a channel slice, dbias[c] = sum dz (may be NULL). */
 int ct_bias_act_backward(const float* dy, int dy_ctot, int dy_coff, const float* y, int y_ctot, int y_coff,
                          int relu, int batch, int channels, int hw, float* dz, int dz_ctot, int dz_coff,

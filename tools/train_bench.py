@@ -3,6 +3,7 @@
    python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
                                [--optimizer sgd|adamw] [--clip-norm X] [--ema DECAY] [--deterministic] [--loc-loss NAME] [--loc-weight X]
                                [--conf-loss focal [--focal-gamma X --focal-alpha X]] [--matcher ssd|atss [--atss-topk K]] [--json]
+                               [--sync-bn]
    --classes: classes of the conf head; default 20, with --phase 2 the width of the Context-Transformer block (60 for 'transfer',
    15 for 'incre': the head feeds the block);
    --fused-sgd: ctdet.optim.FusedSGD (one multi-tensor HIP update) instead of torch.optim.SGD;
@@ -25,6 +26,9 @@
    focal_prior_init(net) (objectness prior 0.01); all three are reported on the JSON line, which is then always printed;
    --matcher NAME [--atss-topk K]: the criterion's target assignment (ssd, atss; default: what CTDET_MATCHER says, else ssd) and the
    ATSS candidates per level (default: CTDET_ATSS_TOPK, else 9); both are reported on the JSON line, which is then always printed;
+   --sync-bn: under torchrun, TrainRuntime.enable_bn_sync(): BatchNorm statistics over the global batch (two small all-reduces per
+   BatchNorm stage and step); the JSON line (then always printed) carries `sync_bn`: the global batch, the
+   stages and the collectives per step;
    --json: one more line, JSON, with the step time, the optimizer's device time and the training runtime's `policy` record
    (always with --clip-norm and --deterministic; with --clip-norm it
    also carries the last norm, coef and the number of skipped steps);
@@ -46,6 +50,7 @@ ap.add_argument('--loc-loss', default=None); ap.add_argument('--loc-weight', typ
 ap.add_argument('--conf-loss', default=None); ap.add_argument('--focal-gamma', type=float, default=None)
 ap.add_argument('--focal-alpha', type=float, default=None)
 ap.add_argument('--matcher', default=None); ap.add_argument('--atss-topk', type=int, default=None)
+ap.add_argument('--sync-bn', action='store_true')
 a = ap.parse_args()
 if a.clip_norm is not None or a.ema is not None:
     a.fused_sgd = True
@@ -97,6 +102,8 @@ tg = [t.cuda() for t in synth.targets(a.batch, nout + 1, 99 + rank)]
 trt = net.train_runtime(a.batch)
 if a.sync or world > 1:
     trt.enable_grad_sync()
+if a.sync_bn:
+    trt.enable_bn_sync()                        # a no-op for one rank; CTDET_SYNC_BN=1 has enable_grad_sync() do the same
 def step():
     opt.zero_grad(set_to_none=True)
     out = net(x)
@@ -129,7 +136,7 @@ if rank == 0:
           % (a.size, a.phase, a.batch, world, ' [%s, %d groups]' % (type(opt).__name__, len(opt.param_groups))
              if a.fused_sgd or a.per_tensor_groups or a.optimizer != 'sgd' else '', dt * 1e3, a.batch * world / dt, tf / n, tl / n, tb / n, float(loss)))
     if a.json or a.clip_norm is not None or a.ema is not None or a.deterministic or a.loc_loss is not None or a.loc_weight != 1.0 \
-            or a.conf_loss is not None or a.matcher is not None or a.optimizer != 'sgd':
+            or a.conf_loss is not None or a.matcher is not None or a.optimizer != 'sgd' or a.sync_bn:
         row = {'train_bench': 'RFBNet-%d phase %d' % (a.size, a.phase), 'batch': a.batch, 'gpus': world, 'steps': n,
                'optimizer': type(opt).__name__, 'groups': len(opt.param_groups), 'ms_per_step': round(dt * 1e3, 3),
                'fwd_ms': round(tf / n, 3), 'loss_ms': round(tl / n, 3), 'bwd_ms': round(tb / n, 3), 'opt_ms': round(to / n, 3),
@@ -140,6 +147,10 @@ if rank == 0:
             row.update(opt.clip_info())                 # norm, coef, finite, nonfinite of the last step
         if a.ema is not None:
             row.update(ema_decay=a.ema, ema_info=opt.ema.info())
+        if trt.bn_sync is not None:
+            sy = trt.bn_sync
+            row['sync_bn'] = {'global_batch': sy.global_batch, 'stages': len(sy.stages),
+                              'collectives_per_step': sy.collectives / float(n + 2)}
         row['policy'] = trt.policy_record()             # deterministic: true / false, the weight-gradient routes
         print(json.dumps(row))
 if a.deterministic:
