@@ -52,6 +52,7 @@ SOURCES = {
     'ct_adamw.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
     'ct_nms.hip': ['-ffp-contract=off'],
     'ct_soft_nms.hip': ['-ffp-contract=off'],
+    'ct_matrix_nms.hip': ['-ffp-contract=off'],
     'ct_post.hip': ['-ffp-contract=off'],
     'ct_tta.hip': ['-ffp-contract=off'],
     'ct_eval.hip': ['-ffp-contract=off'],

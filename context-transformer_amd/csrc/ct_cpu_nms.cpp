@@ -135,3 +135,63 @@ extern "C" int ct_cpu_box_vote(const float* cand_boxes, const float* weights, in
     }
     return CT_OK;
 }
+
+// The host twin of matrix_nms_segments_kernel (ct_matrix_nms.hip) on one (image, class) segment in the pipeline's order:
+// the rule of include/ctdet.h as plain loops.  The fp32 IoU expression of ct_cpu_soft_nms; every term of the Gaussian
+// method takes its own double exp.
+extern "C" int ct_cpu_matrix_nms(const float* rows_sorted, int n, int method, float sigma, float score_threshold, int pre_top,
+                                 int max_emit, float* out_rows, int* out_pos, int* n_out)
+{
+    CT_REQUIRE(n_out && n >= 0 && (n == 0 || (rows_sorted && out_rows && out_pos)), "ct_cpu_matrix_nms: bad arguments");
+    CT_REQUIRE(method == 1 || method == 2, "ct_cpu_matrix_nms: method %d is not 1 (linear) or 2 (Gaussian)", method);
+    CT_REQUIRE(method != 2 || sigma > 0.f, "ct_cpu_matrix_nms: sigma must be > 0 for the Gaussian method");
+    CT_REQUIRE(pre_top > 0 && max_emit >= 0, "ct_cpu_matrix_nms: bad sizes (pre_top=%d max_emit=%d)", pre_top, max_emit);
+    *n_out = 0;
+    const int m = std::min(n, pre_top);
+    if (m == 0) return CT_OK;
+    auto R = [&](int r, int c) { return rows_sorted[(size_t)r * 5 + c]; };
+    auto ov = [&](int i, int j) {
+        const float iw = std::min(R(i, 2), R(j, 2)) - std::max(R(i, 0), R(j, 0)) + 1.0f;
+        if (iw > 0) {
+            const float ih = std::min(R(i, 3), R(j, 3)) - std::max(R(i, 1), R(j, 1)) + 1.0f;
+            if (ih > 0) {
+                const float area = (R(j, 2) - R(j, 0) + 1.0f) * (R(j, 3) - R(j, 1) + 1.0f);
+                const float ua = (R(i, 2) - R(i, 0) + 1.0f) * (R(i, 3) - R(i, 1) + 1.0f) + area - iw * ih;
+                return iw * ih / ua;
+            }
+        }
+        return 0.0f;
+    };
+    std::vector<float> cmax(m, 0.0f), score(m);
+    for (int j = 1; j < m; ++j)
+        for (int k = 0; k < j; ++k) cmax[j] = std::max(cmax[j], ov(k, j));
+    for (int j = 0; j < m; ++j) {
+        float decay = 1.0f;
+        for (int i = 0; i < j; ++i) {
+            const float o = ov(i, j);
+            float t;
+            if (method == 1) {
+                const float den = 1.0f - cmax[i];
+                if (den == 0.0f) continue;
+                t = (1.0f - o) / den;
+            } else {
+                t = (float)std::exp(((double)cmax[i] * (double)cmax[i] - (double)o * (double)o) / (double)sigma);
+            }
+            decay = std::min(decay, t);
+        }
+        score[j] = R(j, 4) * decay;
+    }
+    std::vector<int> order;
+    for (int j = 0; j < m; ++j)
+        if (!(score[j] < score_threshold)) order.push_back(j);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return score[a] > score[b]; });
+    int k = 0;
+    for (int j : order) {
+        if (max_emit > 0 && k >= max_emit && score[j] != out_rows[(size_t)(k - 1) * 5 + 4]) break;
+        for (int c = 0; c < 4; ++c) out_rows[(size_t)k * 5 + c] = R(j, c);
+        out_rows[(size_t)k * 5 + 4] = score[j];
+        out_pos[k++] = j;
+    }
+    *n_out = k;
+    return CT_OK;
+}

@@ -27,6 +27,10 @@ int nms_launch_strided(const float* dets, const int* seg_len, int seg_stride, in
 int soft_nms_launch_strided(float* dets, const int* seg_len, int seg_stride, int nseg, int method, float sigma, float Nt,
                             float score_threshold, int max_emit, float* cur_ws, int* keep, int* keep_count, hipStream_t st);
 int soft_nms_check_params(const char* who, int method, float sigma);
+// ct_matrix_nms.hip
+int matrix_nms_launch_strided(float* dets, const int* seg_len, int seg_stride, int nseg, int method, float sigma,
+                              float score_threshold, int pre_top, int max_emit, int* keep, int* keep_count, hipStream_t st);
+int matrix_nms_check_params(const char* who, int method, float sigma, float score_threshold, int pre_top);
 }
 
 namespace {
@@ -713,6 +717,67 @@ extern "C" int ct_postprocess_batched_soft(const float* boxes, const float* scor
     CT_LAUNCH_CHECK("select_sort_kernel");
     rc = ctdet::soft_nms_launch_strided(w.dets_sorted, w.seg_count, num_priors, S, method, sigma, Nt, score_threshold,
                                         max_per_image, reinterpret_cast<float*>(w.keys), w.keep, w.keep_count, st);
+    if (rc != CT_OK) return rc;
+    { CT_PROF("topk_kernel", st); hipLaunchKernelGGL(topk_kernel, dim3(batch), dim3(256), 0, st, w.dets_sorted, w.keep, w.keep_count,
+                       num_priors, num_fg, max_per_image, out_cap, out_count, overflow); }
+    CT_LAUNCH_CHECK("topk_kernel");
+    { CT_PROF("gather_kernel", st); hipLaunchKernelGGL(gather_kernel, dim3(S), dim3(256), 0, st, w.dets_sorted, w.sorted_idx, w.keep,
+                       out_count, num_priors, out_cap, out_dets, out_index); }
+    CT_LAUNCH_CHECK("gather_kernel");
+    return CT_OK;
+}
+
+// ---- the same pipeline with Matrix NMS (ct_matrix_nms.hip) ----
+// Select and full sort as in the soft entry (the rows behind pre_top are sorted too: the cut by the partial sort is left
+// out), then the matrix kernel on the first pre_top rows of every segment: decayed scores into dets_sorted's score column,
+// emitted positions (non-increasing decayed score, at most max_per_image plus ties) into keep[], the layout topk_kernel /
+// gather_kernel read.
+extern "C" size_t ct_postprocess_matrix_workspace_bytes(int batch, int num_priors, int num_fg)
+{
+    return carve(nullptr, batch, num_priors, num_fg).total;
+}
+
+extern "C" int ct_postprocess_batched_matrix(const float* boxes, const float* scores, int batch, int num_priors, int num_fg,
+                                             float conf_thresh, int method, float sigma, float score_threshold, int pre_top,
+                                             int max_per_image, int out_cap, float* out_dets, int* out_count, int* out_index,
+                                             int* overflow, void* workspace, size_t workspace_bytes, ct_stream_t stream)
+{
+    CT_REQUIRE(boxes && scores && out_dets && out_count && overflow, "ct_postprocess_batched_matrix: null pointer");
+    CT_REQUIRE(batch > 0 && num_priors > 0 && num_fg > 0 && out_cap > 0 && max_per_image >= 0,
+               "ct_postprocess_batched_matrix: bad sizes");
+    CT_REQUIRE(conf_thresh >= 0.f, "ct_postprocess_batched_matrix: conf_thresh must be >= 0 (scores are compared as unsigned bit patterns)");
+    int rc = ctdet::matrix_nms_check_params("ct_postprocess_batched_matrix", method, sigma, score_threshold, pre_top);
+    if (rc != CT_OK) return rc;
+    if (!workspace) return ctdet::fail(CT_ERR_WORKSPACE, "ct_postprocess_batched_matrix: workspace is NULL");
+    const size_t need = ct_postprocess_matrix_workspace_bytes(batch, num_priors, num_fg);
+    if (workspace_bytes < need)
+        return ctdet::fail(CT_ERR_WORKSPACE, "ct_postprocess_batched_matrix: workspace %zu < %zu", workspace_bytes, need);
+    PostWs w = carve((char*)workspace, batch, num_priors, num_fg);
+    const int S = batch * num_fg;
+    const int np2 = std::max(next_pow2(num_priors), 2);
+    hipStream_t st = ctdet::as_stream(stream);
+    CT_HIP(hipMemsetAsync(overflow, 0, sizeof(int), st));
+    constexpr size_t kLds4k = 4096 * 8 + 64, kLds8k = 8192 * 8 + 64;
+    const dim3 sort_grid(8 * ((batch + 7) / 8) * num_fg);
+    {
+        CT_PROF("select_sort_kernel", st);
+        if (num_priors > 16384) {
+            static hipError_t attr8k = hipFuncSetAttribute((const void*)select_sort_kernel<8192, false>,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLds8k);
+            CT_HIP(attr8k);
+            hipLaunchKernelGGL((select_sort_kernel<8192, false>), sort_grid, dim3(kSortThreads), kLds8k, st, boxes, scores, batch, num_priors,
+                               num_fg, conf_thresh, np2, w.keys, w.dets_sorted, w.sorted_idx, w.seg_count, w.seg_sorted, (const int*)nullptr);
+        } else {
+            static hipError_t attr4k = hipFuncSetAttribute((const void*)select_sort_kernel<4096, false>,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLds4k);
+            CT_HIP(attr4k);
+            hipLaunchKernelGGL((select_sort_kernel<4096, false>), sort_grid, dim3(kSortThreads), kLds4k, st, boxes, scores, batch, num_priors,
+                               num_fg, conf_thresh, np2, w.keys, w.dets_sorted, w.sorted_idx, w.seg_count, w.seg_sorted, (const int*)nullptr);
+        }
+    }
+    CT_LAUNCH_CHECK("select_sort_kernel");
+    rc = ctdet::matrix_nms_launch_strided(w.dets_sorted, w.seg_count, num_priors, S, method, sigma, score_threshold, pre_top,
+                                          max_per_image, w.keep, w.keep_count, st);
     if (rc != CT_OK) return rc;
     { CT_PROF("topk_kernel", st); hipLaunchKernelGGL(topk_kernel, dim3(batch), dim3(256), 0, st, w.dets_sorted, w.keep, w.keep_count,
                        num_priors, num_fg, max_per_image, out_cap, out_count, overflow); }

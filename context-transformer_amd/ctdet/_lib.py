@@ -146,6 +146,10 @@ SIGNATURES = {
     'ct_soft_nms_lds_rows': (_I, []),
     'ct_soft_nms_batched_workspace_bytes': (_Z, [_I, _I]),
     'ct_soft_nms_batched_dev': (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P, _Z, _P]),
+    'ct_cpu_matrix_nms': (_I, [_P, _I, _I, _F, _F, _I, _I, _P, _P, _P]),
+    'ct_matrix_nms_max_rows': (_I, []),
+    'ct_matrix_nms_batched_workspace_bytes': (_Z, [_I, _I]),
+    'ct_matrix_nms_batched_dev': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'ct_decode': (_I, [_P, _P, _I, _I, _F, _F, _P, _I, _P, _P]),
     'ct_encode': (_I, [_P, _P, _I, _F, _F, _P, _P]),
     'ct_detect_fused': (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _I, _P, _P, _P]),
@@ -182,6 +186,8 @@ SIGNATURES = {
     'ct_postprocess_batched': (_I, [_P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_postprocess_soft_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_postprocess_batched_soft': (_I, [_P, _P, _I, _I, _I, _F, _I, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    'ct_postprocess_matrix_workspace_bytes': (_Z, [_I, _I, _I]),
+    'ct_postprocess_batched_matrix': (_I, [_P, _P, _I, _I, _I, _F, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_hflip_f32': (_I, [_P, _P, _L, _I, _I, _P]),
     'ct_tta_merge': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     'ct_box_vote_lds_rows': (_I, []),

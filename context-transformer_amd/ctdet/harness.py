@@ -15,14 +15,15 @@ from .pipeline import DetectionPipeline
 
 def detect_dataset(net, priors, dataset, transform, num_fg, batch=32, max_per_image=200, thresh=0.01,
                    force_cpu_rule=False, progress=None, evaluator=None, keep_boxes=True, nms_method='hard',
-                   soft_sigma=0.5, soft_score_threshold=0.001, tta=None, box_vote=None):
+                   soft_sigma=0.5, soft_score_threshold=0.001, tta=None, box_vote=None, matrix_pre_top=1024):
     """-> all_boxes[cls][img] (cls 0 = background, empty lists as in test.py:107-108).
 
     evaluator: an evaluate.DeviceVOCEvaluator or evaluate.DeviceCOCOEvaluator over this data set (image i of the data
     set = its image_ids[i]) -- anything with add(out_dets, out_count, image_index) and finish(); every batch's device output is handed to evaluator.add, the padding images of the ragged last batch as -1.
     keep_boxes=False: no host copy of the detections at all -- no per-batch synchronisation -- and None is returned;
     the post-processing's overflow flag is collected on the device and looked at once, after the last batch.
-    nms_method / soft_sigma / soft_score_threshold: DetectionPipeline's ('linear' / 'gaussian' = soft-NMS on the device).
+    nms_method / soft_sigma / soft_score_threshold / matrix_pre_top: DetectionPipeline's ('linear' / 'gaussian' = soft-NMS
+    on the device, 'matrix_linear' / 'matrix_gaussian' = Matrix NMS on the best matrix_pre_top candidates of a class).
     tta / box_vote: DetectionPipeline's ('hflip' = a second pass on the mirrored batch; box voting at that IoU threshold)."""
     n = len(dataset)
     all_boxes = [[[] for _ in range(n)] for _ in range(num_fg + 1)] if keep_boxes else None
@@ -30,7 +31,8 @@ def detect_dataset(net, priors, dataset, transform, num_fg, batch=32, max_per_im
         return all_boxes
     pipe = DetectionPipeline(net, priors, batch, num_fg, conf_thresh=thresh, max_per_image=max_per_image,
                              force_cpu_rule=force_cpu_rule, nms_method=nms_method, soft_sigma=soft_sigma,
-                             soft_score_threshold=soft_score_threshold, tta=tta, box_vote=box_vote)
+                             soft_score_threshold=soft_score_threshold, tta=tta, box_vote=box_vote,
+                             matrix_pre_top=matrix_pre_top)
     dev = pipe.device
     overflowed = None if keep_boxes else torch.zeros_like(pipe.post.overflow)
     x = torch.zeros(batch, 3, net.size, net.size, device=dev)
@@ -66,7 +68,7 @@ def detect_dataset(net, priors, dataset, transform, num_fg, batch=32, max_per_im
 
 def do_test(net, priors, dataset, transform, num_fg, save_folder, batch=32, max_per_image=200, thresh=0.01,
             force_cpu_rule=False, retest=False, evaluator=None, keep_boxes=True, nms_method='hard', soft_sigma=0.5,
-            soft_score_threshold=0.001, tta=None, box_vote=None):
+            soft_score_threshold=0.001, tta=None, box_vote=None, matrix_pre_top=1024):
     """test.py:96-175: detect, write `detections.pkl`, hand over to the dataset's evaluator.
 
     With `evaluator` the second result is its finish() -- (aps, mean) of evaluate.DeviceVOCEvaluator, (results, stats)
@@ -77,7 +79,7 @@ def do_test(net, priors, dataset, transform, num_fg, save_folder, batch=32, max_
     if evaluator is None and not keep_boxes:
         raise ValueError('keep_boxes=False needs an evaluator: nothing would be left of the detections')
     soft = dict(nms_method=nms_method, soft_sigma=soft_sigma, soft_score_threshold=soft_score_threshold, tta=tta,
-                box_vote=box_vote)
+                box_vote=box_vote, matrix_pre_top=matrix_pre_top)
     os.makedirs(save_folder, exist_ok=True)
     det_file = os.path.join(save_folder, 'detections.pkl')
     if evaluator is not None:

@@ -606,6 +606,82 @@ def soft_nms_batched(dets, seg_off, method=1, sigma=0.5, Nt=0.3, score_threshold
     return rows, pos, cnt
 
 
+MATRIX_METHODS = {'matrix_linear': 1, 'matrix_gaussian': 2}
+
+
+def matrix_method(method):
+    """'matrix_linear' / 'matrix_gaussian' (or the library's 1 / 2) -> the Matrix NMS method number."""
+    if isinstance(method, str):
+        if method not in MATRIX_METHODS:
+            raise ValueError('Matrix NMS method %r is not one of %s' % (method, sorted(MATRIX_METHODS)))
+        return MATRIX_METHODS[method]
+    m = int(method)
+    if m not in (1, 2):
+        raise ValueError('Matrix NMS method %r is not 1 or 2' % (method,))
+    return m
+
+
+def nms_method_number(nms_method):
+    """A post-processing method name -> (is it a Matrix NMS method, the library's method number); ValueError otherwise."""
+    if isinstance(nms_method, str) and nms_method in MATRIX_METHODS:
+        return True, MATRIX_METHODS[nms_method]
+    try:
+        return False, soft_method(nms_method)
+    except ValueError:
+        if isinstance(nms_method, str):
+            raise ValueError('nms_method %r is not one of %s' % (nms_method, sorted(SOFT_METHODS) + sorted(MATRIX_METHODS)))
+        raise
+
+
+def matrix_pre_top(pre_top):
+    """The number of rows per segment Matrix NMS works on: an int in 1 .. ct_matrix_nms_max_rows()."""
+    top = lib().ct_matrix_nms_max_rows()
+    if isinstance(pre_top, bool) or int(pre_top) != pre_top or not 0 < int(pre_top) <= top:
+        raise ValueError('matrix_pre_top %r is not an integer in 1 .. %d' % (pre_top, top))
+    return int(pre_top)
+
+
+def matrix_nms_batched(dets, seg_off, method=1, sigma=0.5, score_threshold=0.001, pre_top=1024, max_emit=0,
+                       max_seg_len=None, out=None, workspace=None):
+    """Matrix NMS of every segment (include/ctdet.h; the device form of cpu_matrix_nms): dets dev [total,5] (segments in
+    descending score order), seg_off dev int32 [S+1] -> (out_rows [total,5], out_pos [total], out_count [S]); segment s
+    emitted out_rows[seg_off[s] : seg_off[s] + out_count[s]] in that order, out_pos are their positions inside the
+    segment.  out: the three tensors to write into; workspace: uint8 tensor of ct_matrix_nms_batched_workspace_bytes
+    (0 bytes today: None is fine)."""
+    S = seg_off.numel() - 1
+    total = dets.shape[0]
+    if out is None:
+        out = (torch.empty(max(total, 1), 5, device=dets.device), torch.empty(max(total, 1), device=dets.device,
+                                                                              dtype=torch.int32),
+               torch.empty(S, device=dets.device, dtype=torch.int32))
+    rows, pos, cnt = out
+    need = lib().ct_matrix_nms_batched_workspace_bytes(total, S)
+    if workspace is None and need:
+        workspace = torch.empty(need, device=dets.device, dtype=torch.uint8)
+    check(lib().ct_matrix_nms_batched_dev(_dev(dets, 'dets'), _dev(seg_off, 'seg_off', torch.int32), S,
+                                          int(total if max_seg_len is None else max_seg_len), matrix_method(method),
+                                          float(sigma), float(score_threshold), int(pre_top), int(max_emit),
+                                          _dev(rows, 'out_rows'), _dev(pos, 'out_pos', torch.int32),
+                                          _dev(cnt, 'out_count', torch.int32), _opt(workspace, 'workspace', torch.uint8),
+                                          0 if workspace is None else workspace.numel(), _stream()),
+          'ct_matrix_nms_batched_dev')
+    return rows, pos, cnt
+
+
+def cpu_matrix_nms(rows_sorted, method=1, sigma=0.5, score_threshold=0.001, pre_top=1024, max_emit=0):
+    """The host twin on one segment: float32 [n,5] rows in the pipeline's order -> (rows [k,5] with decayed scores in
+    emission order, their sorted positions [k])."""
+    d = np.ascontiguousarray(rows_sorted, dtype=np.float32).reshape(-1, 5)
+    n = d.shape[0]
+    rows = np.empty((max(n, 1), 5), dtype=np.float32)
+    pos = np.empty(max(n, 1), dtype=np.int32)
+    n_out = C.c_int(0)
+    check(lib().ct_cpu_matrix_nms(d.ctypes.data_as(C.c_void_p), n, matrix_method(method), float(sigma),
+                                  float(score_threshold), int(pre_top), int(max_emit), rows.ctypes.data_as(C.c_void_p),
+                                  pos.ctypes.data_as(C.c_void_p), C.cast(C.byref(n_out), C.c_void_p)), 'ct_cpu_matrix_nms')
+    return rows[:n_out.value].copy(), pos[:n_out.value].copy()
+
+
 def cpu_nms(dets, thresh, ge=True):
     """utils/nms/cpu_nms.pyx:17-68 on a host numpy array (the reference's --cpu path)."""
     d = np.ascontiguousarray(dets, dtype=np.float32)
@@ -731,15 +807,30 @@ class PostProcessor:
         self.overflow = torch.zeros(1, device=device, dtype=torch.int32)
         self.soft_ws = None             # the soft-NMS entry's workspace, allocated by the first run that needs it
         self.vote_ws = None             # box voting's workspace, likewise
+        self.matrix_ws = None           # the Matrix NMS entry's workspace, likewise
 
     def run(self, boxes, scores, conf_thresh=0.01, nms_thresh=0.45, ge=False, max_per_image=200, nms_method='hard',
-            soft_sigma=0.5, soft_score_threshold=0.001, box_vote=None):
+            soft_sigma=0.5, soft_score_threshold=0.001, box_vote=None, matrix_pre_top=1024):
         """nms_method 'hard': greedy NMS (suppress IoU > nms_thresh, or >= with ge).  'linear' / 'gaussian': soft-NMS
         (cpu_soft_nms methods 1 / 2) with Nt = nms_thresh, sigma = soft_sigma, rows below soft_score_threshold dropped;
-        `ge` does not apply to them.  box_vote (a float in (0, 1]): after the top-k cut every row's box is replaced by the
-        score-weighted mean of the candidates of its class that overlap it by at least that IoU (ops.box_vote)."""
-        method = soft_method(nms_method)
+        `ge` does not apply to them.  'matrix_linear' / 'matrix_gaussian': Matrix NMS (cpu_matrix_nms methods 1 / 2) on
+        the best matrix_pre_top candidates of every class with sigma = soft_sigma, rows below soft_score_threshold dropped;
+        neither nms_thresh nor `ge` applies.  box_vote (a float in (0, 1]): after the top-k cut every row's box is replaced
+        by the score-weighted mean of the candidates of its class that overlap it by at least that IoU (ops.box_vote)."""
+        matrix, method = nms_method_number(nms_method)
         vote = vote_threshold(box_vote)
+        if matrix:
+            if self.matrix_ws is None:
+                nbytes = lib().ct_postprocess_matrix_workspace_bytes(self.B, self.P, self.T)
+                self.matrix_ws = torch.empty(nbytes, device=self.out_dets.device, dtype=torch.uint8)
+            check(lib().ct_postprocess_batched_matrix(
+                _dev(boxes, 'boxes'), _dev(scores, 'scores'), self.B, self.P, self.T, float(conf_thresh), method,
+                float(soft_sigma), float(soft_score_threshold), int(matrix_pre_top), int(max_per_image), self.cap,
+                _dev(self.out_dets, 'out_dets'), _dev(self.out_count, 'out_count', torch.int32),
+                _dev(self.out_index, 'out_index', torch.int32), _dev(self.overflow, 'overflow', torch.int32),
+                _dev(self.matrix_ws, 'matrix_ws', torch.uint8), self.matrix_ws.numel(), _stream()),
+                'ct_postprocess_batched_matrix')
+            return self._vote(boxes, scores, conf_thresh, vote)
         if method != 0:
             if self.soft_ws is None:
                 nbytes = lib().ct_postprocess_soft_workspace_bytes(self.B, self.P, self.T)

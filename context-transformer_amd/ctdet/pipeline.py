@@ -29,9 +29,12 @@ class DetectionPipeline:
 
     def __init__(self, net, priors, batch, num_fg, image_wh=(500, 375), conf_thresh=0.01, nms_thresh=0.45,
                  max_per_image=200, force_cpu_rule=False, variance=(0.1, 0.2), out_cap=None, graph=None,
-                 nms_method='hard', soft_sigma=0.5, soft_score_threshold=0.001, tta=None, box_vote=None):
+                 nms_method='hard', soft_sigma=0.5, soft_score_threshold=0.001, tta=None, box_vote=None,
+                 matrix_pre_top=1024):
         """nms_method 'hard' (default), 'linear' or 'gaussian': the last two run soft-NMS (cpu_soft_nms methods 1 / 2,
         Nt = nms_thresh, sigma = soft_sigma, rows below soft_score_threshold dropped) in place of hard NMS.
+        'matrix_linear' / 'matrix_gaussian': Matrix NMS (cpu_matrix_nms methods 1 / 2) on the best matrix_pre_top candidates
+        of every class, sigma = soft_sigma, rows below soft_score_threshold dropped; nms_thresh does not apply.
         tta 'hflip': two passes, the second on the mirrored batch; self.boxes / self.scores are then the merged [B,2P,...]
         buffers (pass 0's P rows, then pass 1's mirrored back: x1' = W - x2, x2' = W - x1), the post-processor works on 2P
         rows and out_index holds merged indices k*P + p (pass k, prior p).
@@ -45,8 +48,10 @@ class DetectionPipeline:
         self.variance = variance
         self.conf_thresh, self.nms_thresh, self.max_per_image = conf_thresh, nms_thresh, max_per_image
         self.ge = bool(force_cpu_rule)
-        ops.soft_method(nms_method)                 # a misspelt method fails here, not in the first step
+        if ops.nms_method_number(nms_method)[0]:    # a misspelt method fails here, not in the first step
+            ops.matrix_pre_top(matrix_pre_top)
         self.nms_method, self.soft_sigma, self.soft_score_threshold = nms_method, soft_sigma, soft_score_threshold
+        self.matrix_pre_top = matrix_pre_top
         self.tta, self.passes = tta, ops.tta_mode(tta)
         ops.vote_threshold(box_vote)
         self.box_vote = box_vote
@@ -100,11 +105,19 @@ class DetectionPipeline:
     def _post_key(self):
         """The post-processing arguments a captured step froze."""
         key = (self.conf_thresh, self.nms_thresh, self.ge, self.max_per_image)
-        if self.nms_method != 'hard':
+        if self._matrix():
+            key += (self.nms_method, float(self.soft_sigma), float(self.soft_score_threshold), int(self._pre_top()))
+        elif self.nms_method != 'hard':
             key += (ops.soft_method(self.nms_method), float(self.soft_sigma), float(self.soft_score_threshold))
         if self.tta is not None or self.box_vote is not None:
             key += (self.tta, ops.vote_threshold(self.box_vote))
         return key
+
+    def _matrix(self):
+        return ops.nms_method_number(self.nms_method)[0]
+
+    def _pre_top(self):
+        return getattr(self, 'matrix_pre_top', 1024)
 
     def _detect(self, out):
         """The network on rt.bufs['x'] and the fused decode into out = (boxes [B,P,4], scores [B,P,T+1])."""
@@ -124,6 +137,8 @@ class DetectionPipeline:
             self._detect(self.stage)
             ops.tta_merge(self.stage[0], self.stage[1], 1, self.passes, True, self.scale, merged)
         vote = () if self.box_vote is None else (self.box_vote,)
+        if self._matrix():                          # (the other methods keep the call they had)
+            vote = (self.box_vote, self._pre_top())
         self.post.run(self.boxes, self.scores, self.conf_thresh, self.nms_thresh, self.ge, self.max_per_image,
                       self.nms_method, self.soft_sigma, self.soft_score_threshold, *vote)
 

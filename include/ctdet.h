@@ -134,6 +134,42 @@ int ct_soft_nms_batched_dev(const float* dets, const int* seg_off, int num_segme
                             float* out_rows, int* out_pos, int* out_count,
                             void* workspace, size_t workspace_bytes, ct_stream_t stream);
 
+/* Matrix NMS (Wang et al., SOLOv2 section 3.3) on the device, one workgroup per segment: every row's score decay in closed
+ * form from the pairwise IoUs of the sorted rows, corrected by how much each suppressor was itself suppressed.  Segments as
+ * for ct_soft_nms_batched_dev (descending score, lower prior index first on ties).  On one segment:
+ *   1. only the first n = min(len, pre_top) rows take part, rows at sorted positions >= pre_top are dropped (`nms_pre`);
+ *      0 < pre_top <= ct_matrix_nms_max_rows() (at least 1024: what the kernel's LDS layout holds);
+ *   2. ov(i, j), i < j: the +1 pixel fp32 expression of ct_soft_nms_batched_dev and ct_cpu_soft_nms (iw = min(x2) - max(x1)
+ *      + 1, ih likewise, ov = 0 unless iw > 0 && ih > 0, ua = area_i + area_j - iw * ih, ov = iw * ih / ua; IEEE division,
+ *      no contraction);
+ *   3. cmax[i] = max over k < i of ov(k, i), cmax[0] = 0;
+ *   4. decay[j] = min(1, min over i < j of t(i, j)), decay[0] = 1, with
+ *        method 1 (linear)    t = (1 - ov(i,j)) / (1 - cmax[i]) in fp32, IEEE quotient; a term whose denominator is 0 is
+ *                             skipped: a row that exactly duplicates an earlier one is itself decayed to 0 and suppresses
+ *                             nothing;
+ *        method 2 (Gaussian)  t = (float)exp(((double)cmax[i]^2 - (double)ov(i,j)^2) / (double)sigma) -- sigma divides, as in
+ *                             the soft-NMS entries: sigma = 0.5 here is the papers' sigma = 2;
+ *   5. score'[j] = score[j] * decay[j] (one fp32 multiply); a row with score' < score_threshold (>= 0) is removed;
+ *   6. emission in non-increasing score', ties lower sorted position first;
+ *   7. max_emit > 0: a segment stops after max_emit rows, except for further rows that tie with the last one; 0: no limit.
+ * There is no Nt.  out_rows / out_pos / out_count as for ct_soft_nms_batched_dev (out_pos: sorted positions relative to
+ * the segment; out_count is never -1).  dets is not modified, nothing is written past out_count[s] rows of a segment, an
+ * empty segment gives 0.  The workspace query returns 0 and workspace may be NULL: a segment's state lives in LDS.
+ * Minima and maxima do not depend on the order they are taken in: method 1 equals ct_cpu_matrix_nms bit for bit.  Method 2
+ * differs from it only by the two libms' double exp rounded to fp32, at most one fp32 ulp of decay, plus the product's
+ * rounding: every score is within 2^-22 of the host's, relatively, and decisions and order are the same wherever the
+ * host's own margins (between consecutive emitted scores, and to score_threshold) exceed that. */
+int ct_matrix_nms_max_rows(void);
+size_t ct_matrix_nms_batched_workspace_bytes(int total_rows, int num_segments);
+int ct_matrix_nms_batched_dev(const float* dets, const int* seg_off, int num_segments, int max_seg_len,
+                              int method, float sigma, float score_threshold, int pre_top, int max_emit,
+                              float* out_rows, int* out_pos, int* out_count,
+                              void* workspace, size_t workspace_bytes, ct_stream_t stream);
+/* Host twin on one segment: rows_sorted host [n,5] in the pipeline's order -> out_rows host [n,5], out_pos host [n] (what
+ * the device entry emits for that segment), *n_out rows.  The rule above as plain loops; any pre_top > 0. */
+int ct_cpu_matrix_nms(const float* rows_sorted, int n, int method, float sigma, float score_threshold, int pre_top,
+                      int max_emit, float* out_rows, int* out_pos, int* n_out);
+
 /* ----------------------------------------------------- boxes / detection ---- */
 
 /* utils/box_utils.py:184-202 `decode(loc, priors, variances)`, batched over images:
@@ -599,6 +635,16 @@ int ct_postprocess_batched_soft(const float* boxes, const float* scores, int bat
                                 float score_threshold, int max_per_image, int out_cap, float* out_dets,
                                 int* out_count, int* out_index, int* overflow,
                                 void* workspace, size_t workspace_bytes, ct_stream_t stream);
+/* The same with Matrix NMS (ct_matrix_nms_batched_dev's method / sigma / score_threshold / pre_top) in place of hard NMS:
+ * every candidate is selected and sorted, the first pre_top of each segment are decayed, each segment emits at most
+ * max_per_image rows (plus ties with the last one), then the same top-k rule and gather.  Same outputs, same overflow
+ * rule; rows carry their decayed scores.  conf_thresh >= 0 and score_threshold >= 0 as for the soft entry. */
+size_t ct_postprocess_matrix_workspace_bytes(int batch, int num_priors, int num_fg);
+int ct_postprocess_batched_matrix(const float* boxes, const float* scores, int batch, int num_priors,
+                                  int num_fg, float conf_thresh, int method, float sigma,
+                                  float score_threshold, int pre_top, int max_per_image, int out_cap,
+                                  float* out_dets, int* out_count, int* out_index, int* overflow,
+                                  void* workspace, size_t workspace_bytes, ct_stream_t stream);
 
 /* ------------------------- flip test-time augmentation and box voting ---- */
 
