@@ -38,6 +38,7 @@ SOURCES = {
     'ct_pool.hip': [],
     'ct_preproc.hip': ['-ffp-contract=off'],
     'ct_aug_plan.hip': ['-ffp-contract=off'],
+    'ct_affine.hip': ['-ffp-contract=off'],
     'ct_attn.hip': [],
     'ct_attn_bwd.hip': [],
     'ct_train.hip': [],

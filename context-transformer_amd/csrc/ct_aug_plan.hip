@@ -12,9 +12,12 @@
 // All decision arithmetic is fp64 with +, -, *, /, sqrt, comparisons and truncation only (compiled with contraction
 // off), the sequence ctdet/aug_plan_ref.py evaluates in numpy: both give the same bytes.
 #include "ct_common.h"
+#include "ct_aug_draw.h"
 #include <algorithm>
 
 namespace {
+
+using namespace ctdet::aug;                 // philox, the draw rules, block_scan
 
 using AugPlan = ct_aug_plan_record;         // one image's decisions (include/ctdet.h)
 
@@ -24,29 +27,6 @@ struct Fill3 { float v[3]; };
 constexpr int SLOT_MISC = 0, SLOT_CROP = 0x100, SLOT_EXPAND = 0x200;
 constexpr int LANE_COINS = 0, LANE_PARAMS = 1, LANE_MISC = 2, LANE_MODE = 63;
 constexpr int CROP_TRIALS = 50, CROP_ROUNDS = 256, EXPAND_ROUNDS = 64;
-constexpr int PACK_THREADS = 1024;
-
-struct Words { unsigned w[4]; };
-
-__device__ inline Words philox(unsigned long long seed, unsigned long long sample_id, unsigned slot, unsigned lane)
-{
-    unsigned c0 = (unsigned)sample_id, c1 = (unsigned)(sample_id >> 32), c2 = slot, c3 = lane;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)c0 * 0xD2511F53u, p1 = (unsigned long long)c2 * 0xCD9E8D57u;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0; c1 = (unsigned)p1; c2 = n2; c3 = (unsigned)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    Words o;
-    o.w[0] = c0; o.w[1] = c1; o.w[2] = c2; o.w[3] = c3;
-    return o;
-}
-
-__device__ __forceinline__ double unit(unsigned w) { return (double)w * 2.3283064365386962890625e-10; }   // w * 2^-32
-__device__ __forceinline__ double uniform(double a, double b, unsigned w) { return a + (b - a) * unit(w); }
-__device__ __forceinline__ int randrange(int n, unsigned w) { return (int)(((unsigned long long)w * (unsigned)n) >> 32); }
 
 __device__ __forceinline__ void identity_plan(AugPlan& p, int H, int W)
 {
@@ -241,23 +221,6 @@ __global__ __launch_bounds__(64) void aug_plan_kernel(const ct_aug_sample* __res
         plans[s] = plan;
         counts[s] = at;
     }
-}
-
-// inclusive scan over the workgroup's PACK_THREADS values (Hillis-Steele in LDS); IS_MAX: running maximum, else sum
-template <bool IS_MAX>
-__device__ inline int block_scan(int v, int* sh)
-{
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < PACK_THREADS; d <<= 1) {
-        const int o = tid >= d ? sh[tid - d] : (IS_MAX ? -1 : 0);
-        __syncthreads();
-        v = IS_MAX ? max(v, o) : v + o;
-        sh[tid] = v;
-        __syncthreads();
-    }
-    return v;
 }
 
 // One workgroup: a thread owns one sample of the current chunk of PACK_THREADS.  Rows of refused samples are

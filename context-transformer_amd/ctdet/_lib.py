@@ -6,7 +6,7 @@ FAILS LOUDLY -- there is no PyTorch / CPU fallback for the device path.
 import ctypes as C
 import os
 
-from .aug_records import ResizeTap     # noqa: F401  (ct_resize_tap, with the other input-pipeline records)
+from .aug_records import AffineParamsRecord, ResizeTap     # noqa: F401  (with the other input-pipeline records)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CTDET_LIB') or os.path.join(os.path.dirname(_HERE), 'lib', 'libctdet.so')
@@ -338,6 +338,10 @@ SIGNATURES = {
     'ct_aug_plan_mosaic': (_I, [_P, _I, _P, _I, _I, C.c_ulonglong, _F, C.POINTER(_I), C.POINTER(_F), _I, _I, _P, _P, _P,
                                 _I, _P, _P, _P, _Z, _P]),
     'ct_preproc_augment_mosaic': (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    'ct_aug_affine_plan_workspace_bytes': (_Z, [_I, _I]),
+    'ct_aug_affine_plan': (_I, [_P, _P, _P, _I, _I, _I, C.c_ulonglong, C.POINTER(AffineParamsRecord), _P, _P, _P, _P, _P,
+                                _Z, _P]),
+    'ct_preproc_warp_affine': (_I, [_P, _P, _I, _I, C.POINTER(_F), _P, _P]),
     'ct_ctx_pool_fwd': (_I, [_P, _LL, _P, _LL, _I, _I, _I, _I, _I, _P]),
     'ct_ctx_attention_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     'ct_ctx_attention_piece_products': (_I, []),

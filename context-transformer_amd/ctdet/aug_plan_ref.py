@@ -16,14 +16,18 @@ coin = w >> 31.
     0x100 + r      0..49    scale U(.3,1)      ratio u           left rr(W - w)      top rr(H - h)
     0x200 + r      0..63    scale U(1,4)       ratio u           left rr(w - cw + 1) top rr(h - ch + 1)
     0x300 (mosaic) 0        cx margin+rr(S-2m+1) cy likewise     (of a group's first sample; `mosaic_batch` below)
+    0x400 (affine) 0        t U(-rot,rot)      s U(lo,hi)        kx U(-shear,shear)  ky likewise   (`affine_batch` below)
+    0x400          1        tx U(.5-tr,.5+tr)*S ty likewise      gate u (> p: no)
 
 Crop rounds r = 0..255, expand rounds r = 0..63; the lowest passing lane of the first round with one wins.
 """
 import collections
+import math
 
 import numpy as np
 
-from .aug_records import PLAN_DTYPE, SAMPLE_DTYPE, TILE_DTYPE, plan_dict, plan_records     # noqa: F401
+from .aug_records import (AFFINE_DTYPE, PLAN_DTYPE, SAMPLE_DTYPE, TILE_DTYPE, AffineParamsRecord,     # noqa: F401
+                          plan_dict, plan_records)
 
 PHILOX_M = (0xD2511F53, 0xCD9E8D57)
 PHILOX_W = (0x9E3779B9, 0xBB67AE85)
@@ -337,3 +341,192 @@ def mosaic_batch(samples, boxes, num_images, max_gt, seed, p_expand, interp_of_d
     status = np.array([(STATUS_BAD_SAMPLE if bad else 0) | (STATUS_ROWS_DROPPED if dropped else 0), bad, dropped, n_rows],
                       dtype=np.int32)
     return MosaicResult(plans, tiles, all_rows[:cap], gt_off, status, rows_of, fallback, info)
+
+
+# ---------------------------------------------------------------------------------------------------- random affine
+SLOT_AFFINE = 0x400
+AFFINE_APPLIED, AFFINE_FALLBACK, AFFINE_IDENTITY = 1, 2, 4
+STATUS_BAD_IMAGE = 1
+
+AffineResult = collections.namedtuple('AffineResult', 'records truths gt_off status image_rows fallback')
+
+
+class AffineParams(object):
+    """The validated parameters of the random affine stage (include/ctdet.h ct_affine_params), built from degrees:
+    a rotation of at most `degrees`, an isotropic scale in `scale` = (lo, hi), a shear of at most `shear` degrees per
+    axis, a shift of at most `translate` * S, applied with probability `p`; rows are kept when min(w, h) > min_side
+    and at least `min_visible` of their area stays inside.  The two tangents are computed here, once, on the host:
+    the draw is uniform in tan(angle / 2), neither side evaluates a sine or a cosine."""
+    FIELDS = ('rot_half_tan', 'scale_lo', 'scale_hi', 'shear_tan', 'translate', 'p', 'min_side', 'min_visible')
+
+    def __init__(self, degrees=10.0, scale=(0.5, 1.5), shear=2.0, translate=0.1, p=1.0, min_side=0.01, min_visible=0.3):
+        vals = dict(degrees=degrees, scale_lo=scale[0], scale_hi=scale[1], shear=shear, translate=translate, p=p,
+                    min_side=min_side, min_visible=min_visible)
+        for k, v in vals.items():
+            if not math.isfinite(float(v)):
+                raise ValueError('AffineParams: %s=%r is not finite' % (k, v))
+        if not 0 <= degrees <= 90:
+            raise ValueError('AffineParams: degrees=%r outside 0..90' % (degrees,))
+        if not 0 < scale[0] <= scale[1] <= 4:
+            raise ValueError('AffineParams: scale=%r, not 0 < lo <= hi <= 4' % (tuple(scale),))
+        if not 0 <= shear <= math.degrees(math.atan(0.5)):
+            raise ValueError('AffineParams: shear=%r outside 0..atan(0.5) = 26.56 degrees' % (shear,))
+        if not 0 <= translate <= 0.5:
+            raise ValueError('AffineParams: translate=%r outside 0..0.5' % (translate,))
+        for k in ('p', 'min_side', 'min_visible'):
+            if not 0 <= vals[k] <= 1:
+                raise ValueError('AffineParams: %s=%r outside 0..1' % (k, vals[k]))
+        self.degrees, self.shear = float(degrees), float(shear)
+        self.rot_half_tan = min(math.tan(math.radians(float(degrees)) / 2), 1.0)
+        self.scale_lo, self.scale_hi = float(scale[0]), float(scale[1])
+        self.shear_tan = min(math.tan(math.radians(float(shear))), 0.5)
+        self.translate = float(translate)
+        # the C struct holds these three as float: both sides compare against the float's value
+        self.p, self.min_side, self.min_visible = (float(np.float32(v)) for v in (p, min_side, min_visible))
+
+    def struct(self):
+        """-> aug_records.AffineParamsRecord, the host struct ct_aug_affine_plan reads."""
+        return AffineParamsRecord(*[getattr(self, k) for k in self.FIELDS])
+
+    def __repr__(self):
+        return 'AffineParams(%s)' % ', '.join('%s=%r' % (k, getattr(self, k)) for k in self.FIELDS)
+
+
+def affine_identity(flags=AFFINE_IDENTITY):
+    r = np.zeros((), dtype=AFFINE_DTYPE)
+    r['fwd'] = r['inv'] = (1, 0, 0, 0, 1, 0)
+    r['flags'] = flags
+    return r
+
+
+def affine_draws(seed, image_id, size, params):
+    """-> dict(t, s, kx, ky, tx, ty, applied): the seven draws of one image (include/ctdet.h RANDOM AFFINE)."""
+    d = draws(seed, image_id, SLOT_AFFINE, np.arange(2))
+    P, S = params, np.float64(size)
+    return dict(t=uniform(-P.rot_half_tan, P.rot_half_tan, d[0, 0]), s=uniform(P.scale_lo, P.scale_hi, d[0, 1]),
+                kx=uniform(-P.shear_tan, P.shear_tan, d[0, 2]), ky=uniform(-P.shear_tan, P.shear_tan, d[0, 3]),
+                tx=uniform(0.5 - P.translate, 0.5 + P.translate, d[1, 0]) * S,
+                ty=uniform(0.5 - P.translate, 0.5 + P.translate, d[1, 1]) * S,
+                applied=not (float(unit(d[1, 2])) > P.p))
+
+
+def affine_matrix(seed, image_id, size, params):
+    """The record one image draws, gate applied (flags 1, or the identity with flags 4), before its rows are looked
+    at -> AFFINE_DTYPE scalar.  fp64, one rounding per operation, in the header's order."""
+    w = affine_draws(seed, image_id, size, params)
+    if not w['applied']:
+        return affine_identity()
+    t, s, kx, ky, tx, ty = (np.float64(w[k]) for k in ('t', 's', 'kx', 'ky', 'tx', 'ty'))
+    one = np.float64(1.0)
+    tt = t * t
+    q = one + tt
+    c, n = (one - tt) / q, (t + t) / q
+    a, b = s * c, s * n
+    l00, l01, l10, l11 = a - kx * b, b + kx * a, ky * a - b, ky * b + a
+    h = np.float64(size) * np.float64(0.5)
+    f2, f5 = tx - (l00 * h + l01 * h), ty - (l10 * h + l11 * h)
+    det = l00 * l11 - l01 * l10
+    i00, i01, i10, i11 = l11 / det, -l01 / det, -l10 / det, l00 / det
+    r = np.zeros((), dtype=AFFINE_DTYPE)
+    r['fwd'] = (l00, l01, f2, l10, l11, f5)
+    r['inv'] = (i00, i01, -(i00 * f2 + i01 * f5), i10, i11, -(i10 * f2 + i11 * f5))
+    r['flags'] = AFFINE_APPLIED
+    return r
+
+
+def affine_rows(rows, fwd, size, min_side, min_visible):
+    """float32 rows [k,6] normalised to the image -> (float32 rows after the map, keep [k])."""
+    r = np.asarray(rows, dtype=np.float32).reshape(-1, 6)
+    S = np.float64(size)
+    f = np.asarray(fwd, dtype=np.float64)
+    u1, v1, u2, v2 = (r[:, k].astype(np.float64) * S for k in range(4))
+    xs, ys = [], []
+    for u, v in ((u1, v1), (u2, v1), (u1, v2), (u2, v2)):
+        xs.append((f[0] * u + f[1] * v) + f[2])
+        ys.append((f[3] * u + f[4] * v) + f[5])
+    X1, X2 = np.fmin(np.fmin(np.fmin(xs[0], xs[1]), xs[2]), xs[3]), np.fmax(np.fmax(np.fmax(xs[0], xs[1]), xs[2]), xs[3])
+    Y1, Y2 = np.fmin(np.fmin(np.fmin(ys[0], ys[1]), ys[2]), ys[3]), np.fmax(np.fmax(np.fmax(ys[0], ys[1]), ys[2]), ys[3])
+    A0 = (X2 - X1) * (Y2 - Y1)
+    X1, Y1, X2, Y2 = (np.fmin(np.fmax(v, 0.0), S) for v in (X1, Y1, X2, Y2))
+    w, h = X2 - X1, Y2 - Y1
+    A1 = w * h
+    keep = (np.fmin(w, h) / S > np.float64(min_side)) & (A1 >= np.float64(min_visible) * A0)
+    out = r.copy()
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3] = X1 / S, Y1 / S, X2 / S, Y2 / S
+    return out, keep
+
+
+def affine_batch(truths, gt_off, image_ids, size, seed, params, truths_rows=None):
+    """What `ct_aug_affine_plan` computes, safety rule included.  truths float32 [rows,6] and gt_off int32 [B+1] as the
+    planners pack them, image_ids [B] 64-bit, truths_rows the capacity the offsets are clamped to (default: the rows
+    of `truths`).  -> AffineResult: records (AFFINE_DTYPE [B]), truths float32 [rows out, 6], gt_off int32 [B+1],
+    status int32 [4] = (bits, refused images, fallback images, rows out), each image's rows, fallback [B]."""
+    truths = np.ascontiguousarray(truths, dtype=np.float32).reshape(-1, 6)
+    gt_off = np.asarray(gt_off, dtype=np.int64).reshape(-1)
+    B, size = len(gt_off) - 1, int(size)
+    cap = len(truths) if truths_rows is None else int(truths_rows)
+    if B < 1 or len(image_ids) != B or size < 2 or cap < 0 or cap > len(truths):
+        raise ValueError('affine_batch: %d offsets, %d ids, size %d, truths_rows %d of %d'
+                         % (len(gt_off), len(image_ids), size, cap, len(truths)))
+    off = np.clip(gt_off, 0, cap)
+    records = np.zeros(B, dtype=AFFINE_DTYPE)
+    fallback = np.zeros(B, dtype=bool)
+    image_rows, bad, prev = [], 0, 0
+    for i in range(B):
+        b, e = int(off[i]), int(off[i + 1])
+        refused = b > e or b < prev             # prev: the largest clamped end of the images before this one
+        if i >= 1:
+            prev = max(prev, b)                 # this image's begin is the end of the one before it
+        if refused:
+            records[i] = affine_identity()
+            image_rows.append(np.zeros((0, 6), dtype=np.float32))
+            bad += 1
+            continue
+        rows = truths[b:e]
+        rec = affine_matrix(seed, image_ids[i], size, params)
+        if rec['flags'] & AFFINE_APPLIED:
+            mapped, keep = affine_rows(rows, rec['fwd'], size, params.min_side, params.min_visible)
+            if len(rows) and not keep.any():
+                fallback[i] = True
+                rec = affine_identity(AFFINE_FALLBACK | AFFINE_IDENTITY)
+            else:
+                rows = mapped[keep]
+        records[i] = rec
+        image_rows.append(rows.copy())
+    all_rows = np.concatenate(image_rows, 0)
+    out_off = np.concatenate([[0], np.cumsum([len(r) for r in image_rows])]).astype(np.int32)
+    status = np.array([STATUS_BAD_IMAGE if bad else 0, bad, int(fallback.sum()), len(all_rows)], dtype=np.int32)
+    return AffineResult(records, all_rows, out_off, status, image_rows, fallback)
+
+
+def warp_affine(x, records, border3):
+    """What `ct_preproc_warp_affine` computes: x float32 [B,3,S,S], records AFFINE_DTYPE [B], border3 three floats ->
+    float32 [B,3,S,S].  Coordinates in float64, the blend in float32, one rounding per operation: bit-comparable to
+    the device.  A record with flag 4 copies; any other table, NaN and infinities included, is evaluated by the rule."""
+    x = np.asarray(x, dtype=np.float32)
+    B, _, S, _ = x.shape
+    bd = np.asarray(border3, dtype=np.float32).reshape(3)
+    out = np.empty_like(x)
+    yy, xx = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64), indexing='ij')
+    Sd = np.float64(S)
+    for n in range(B):
+        if int(records[n]['flags']) & AFFINE_IDENTITY:
+            out[n] = x[n]
+            continue
+        v = np.asarray(records[n]['inv'], dtype=np.float64)
+        with np.errstate(invalid='ignore', over='ignore'):
+            X, Y = (v[0] * xx + v[1] * yy) + v[2], (v[3] * xx + v[4] * yy) + v[5]
+            inside = (-1.0 < X) & (X < Sd) & (-1.0 < Y) & (Y < Sd)
+        X, Y = np.where(inside, X, 0.0), np.where(inside, Y, 0.0)
+        flx, fly = np.floor(X), np.floor(Y)
+        fx, fy = (X - flx).astype(np.float32), (Y - fly).astype(np.float32)
+        ix, iy = flx.astype(np.int64), fly.astype(np.int64)
+        x0, x1, y0, y1 = ix >= 0, ix + 1 < S, iy >= 0, iy + 1 < S
+        cx0, cx1, cy0, cy1 = np.maximum(ix, 0), np.minimum(ix + 1, S - 1), np.maximum(iy, 0), np.minimum(iy + 1, S - 1)
+        for c in range(3):
+            p, bc = x[n, c], bd[c]
+            a, b = np.where(x0 & y0, p[cy0, cx0], bc), np.where(x1 & y0, p[cy0, cx1], bc)
+            cc, d = np.where(x0 & y1, p[cy1, cx0], bc), np.where(x1 & y1, p[cy1, cx1], bc)
+            top, bot = a + fx * (b - a), cc + fx * (d - cc)
+            out[n, c] = np.where(inside, top + fy * (bot - top), bc)
+    return out

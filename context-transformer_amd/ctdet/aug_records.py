@@ -1,7 +1,8 @@
-"""The four records of the device input pipeline (include/ctdet.h), each laid out once for Python: the numpy dtypes
+"""The records of the device input pipeline (include/ctdet.h), each laid out once for Python: the numpy dtypes
 host code fills and reads, the ctypes twins callers fill by field name, and their sizes.  numpy and ctypes only: the
 host twin (ctdet/aug_plan_ref.py) imports this without torch or the library.  tests/test_aug_records_cpu.py compiles
-the header and compares every offset, so a layout edited in one place fails at import, at compile time or there."""
+the header and compares every offset (tests/test_affine_cpu.py does for the two affine structs), so a layout edited
+in one place fails at import, at compile time or there."""
 import ctypes as C
 
 import numpy as np
@@ -22,6 +23,18 @@ class ResizeTap(C.Structure):
     _fields_ = [('first', C.c_int), ('c', C.c_short * 8)]
 
 
+class AffineRecord(C.Structure):
+    """ct_affine_record: one image's random affine map, both directions."""
+    _fields_ = [('fwd', C.c_double * 6), ('inv', C.c_double * 6), ('flags', C.c_int), ('pad', C.c_int)]
+
+
+class AffineParamsRecord(C.Structure):
+    """ct_affine_params: the host struct ct_aug_affine_plan takes (ctdet/aug_plan_ref.py AffineParams fills it)."""
+    _fields_ = [('rot_half_tan', C.c_double), ('scale_lo', C.c_double), ('scale_hi', C.c_double),
+                ('shear_tan', C.c_double), ('translate', C.c_double), ('p', C.c_float), ('min_side', C.c_float),
+                ('min_visible', C.c_float)]
+
+
 # ct_aug_plan_record with the field names of the plan dict ops.Augmenter takes: crop = (l, t, w, h), exp = (w, h, left, top)
 PLAN_DTYPE = np.dtype([('src_off', '<i8'), ('H', '<i4'), ('W', '<i4'), ('crop', '<i4', (4,)), ('exp', '<i4', (4,)),
                        ('mirror', '<i4'), ('interp', '<i4'), ('flags', '<i4'), ('hue', '<i4'), ('beta', '<f4'),
@@ -30,9 +43,11 @@ SAMPLE_DTYPE = np.dtype([('src_off', '<i8'), ('sample_id', '<u8'), ('H', '<i4'),
                          ('box_end', '<i4'), ('image', '<i4'), ('cls', '<i4'), ('weight', '<f4'), ('flags', '<i4')])    # ct_aug_sample
 TILE_DTYPE = np.dtype([('x0', '<i4'), ('y0', '<i4'), ('w', '<i4'), ('h', '<i4')])       # ct_mosaic_tile
 TAP_DTYPE = np.dtype([('first', '<i4'), ('c', '<i2', (8,))])                            # ct_resize_tap
+AFFINE_DTYPE = np.dtype([('fwd', '<f8', (6,)), ('inv', '<f8', (6,)), ('flags', '<i4'), ('pad', '<i4')])   # ct_affine_record
 
 PLAN_BYTES, SAMPLE_BYTES = PLAN_DTYPE.itemsize, SAMPLE_DTYPE.itemsize
 TILE_BYTES, TAP_BYTES = TILE_DTYPE.itemsize, TAP_DTYPE.itemsize
+AFFINE_BYTES = AFFINE_DTYPE.itemsize
 
 
 def scalars(dtype):
@@ -54,7 +69,7 @@ def _same_layout(struct, dtype):
             and all(at.get(dtype.fields[n][1], '').startswith(n) for n in dtype.names))
 
 
-assert _same_layout(AugPlan, PLAN_DTYPE) and _same_layout(ResizeTap, TAP_DTYPE)
+assert _same_layout(AugPlan, PLAN_DTYPE) and _same_layout(ResizeTap, TAP_DTYPE) and _same_layout(AffineRecord, AFFINE_DTYPE)
 
 PLAN_KEYS = ('H', 'W', 'crop', 'exp', 'mirror', 'interp', 'flags', 'hue', 'beta', 'alpha', 'sat')
 

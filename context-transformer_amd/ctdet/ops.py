@@ -16,6 +16,8 @@ from . import _lib
 from ._lib import check, lib
 from .aug_records import (PLAN_BYTES, PLAN_DTYPE, SAMPLE_BYTES, SAMPLE_DTYPE as AUG_SAMPLE_DTYPE, TAP_BYTES, TAP_DTYPE,
                           TILE_BYTES, AugPlan, plan_records)   # noqa: F401  (AugPlan: callers of the C ABI fill it by name)
+from .aug_records import AFFINE_BYTES, AFFINE_DTYPE, AffineRecord     # noqa: F401
+from .aug_plan_ref import AffineParams
 
 
 def _stream():
@@ -1230,6 +1232,77 @@ class AugPlanner:
         if st[0]:
             raise _lib.CtdetError('ct_aug_plan: status %d (%d samples refused, %d rows dropped of %d)'
                                   % (st[0], st[1], st[2], st[3]))
+        return st
+
+
+def affine_params(params):
+    """An AffineParams, or the dict of its keyword arguments (degrees, scale, shear, translate, p, min_side,
+    min_visible) -> AffineParams."""
+    if isinstance(params, AffineParams):
+        return params
+    if isinstance(params, dict):
+        return AffineParams(**params)
+    raise ValueError('affine parameters: an AffineParams or a dict of its arguments, not %r' % (params,))
+
+
+class AffineWarp:
+    """The random affine post-stage on a rendered batch (include/ctdet.h RANDOM AFFINE): `plan` draws one record per
+    image and carries the packed rows along (ct_aug_affine_plan, two launches), `warp` resamples the pixels
+    (ct_preproc_warp_affine, one launch).  Everything stays on the device; no host synchronisation unless `check()`
+    is called."""
+
+    def __init__(self, device, seed, params):
+        self.device, self.seed = torch.device(device), int(seed) & (2 ** 64 - 1)
+        self.params = affine_params(params)
+        self._struct = self.params.struct()
+        self.status = None                  # int32 [4] on the device, of the last plan
+
+    def plan(self, packed, image_ids, n, size):
+        """packed: PackedTargets normalised to the size x size image; image_ids: n 64-bit ids ->
+        (records uint8 [n*AFFINE_BYTES] on the device, PackedTargets).  The ids go up as one small non-blocking copy."""
+        n, size = int(n), int(size)
+        truths, gt_off = packed.truths, packed.gt_off
+        if n < 1 or len(image_ids) != n or gt_off.numel() < n + 1 or truths.dim() != 2 or truths.shape[1] != 6:
+            raise ValueError('AffineWarp.plan: %d images, %d ids, %d offsets, truths %s'
+                             % (n, len(image_ids), gt_off.numel(), tuple(truths.shape)))
+        ids = np.array([int(v) % 2 ** 64 for v in image_ids], dtype=np.uint64).view(np.int64)
+        ids_d = torch.from_numpy(ids).to(self.device, non_blocking=True)
+        rows = truths.shape[0]
+        dev, u8, i32 = self.device, torch.uint8, torch.int32
+        records = torch.empty(n * AFFINE_BYTES, dtype=u8, device=dev)
+        truths_out = torch.empty(max(rows, 1), 6, dtype=torch.float32, device=dev)
+        gt_off_out = torch.empty(n + 1, dtype=i32, device=dev)
+        self.status = torch.empty(4, dtype=i32, device=dev)
+        ws_bytes = lib().ct_aug_affine_plan_workspace_bytes(n, rows)
+        ws = torch.empty(ws_bytes, dtype=u8, device=dev)
+        check(lib().ct_aug_affine_plan(_dev(truths, 'truths'), _dev(gt_off, 'gt_off', i32), _dev(ids_d, 'image_ids', torch.int64),
+                                       n, rows, size, self.seed, C.byref(self._struct), _dev(records, 'records', u8),
+                                       _dev(truths_out, 'truths_out'), _dev(gt_off_out, 'gt_off_out', i32),
+                                       _dev(self.status, 'status', i32), _dev(ws, 'workspace', u8), ws_bytes, _stream()),
+              'ct_aug_affine_plan')
+        return records, PackedTargets(truths_out, gt_off_out, packed.max_gt)
+
+    def warp(self, x, records_d, border3, out=None):
+        """x float32 [n,3,S,S] on the device, records_d what `plan` returned, border3 what lies outside the image (three
+        floats) -> float32 [n,3,S,S]; `out` must not be x."""
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or records_d.numel() < x.shape[0] * AFFINE_BYTES:
+            raise ValueError('AffineWarp.warp: x %s, %d record bytes' % (tuple(x.shape), records_d.numel()))
+        if out is None:
+            out = torch.empty_like(x)
+        border = (C.c_float * 3)(*[float(v) for v in border3])
+        check(lib().ct_preproc_warp_affine(_dev(x, 'x'), _dev(records_d, 'records', torch.uint8), x.shape[0], x.shape[2],
+                                           border, _dev(out, 'out'), _stream()), 'ct_preproc_warp_affine')
+        return out
+
+    def __call__(self, x, packed, image_ids, border3, out=None):
+        records, packed = self.plan(packed, image_ids, x.shape[0], x.shape[2])
+        return self.warp(x, records, border3, out), packed
+
+    def check(self):
+        """Read the status words of the last plan (a host synchronisation) and raise when an image was refused."""
+        st = self.status.cpu().numpy()
+        if st[0]:
+            raise _lib.CtdetError('ct_aug_affine_plan: status %d (%d images refused)' % (st[0], st[1]))
         return st
 
 

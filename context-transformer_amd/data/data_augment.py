@@ -12,7 +12,8 @@ expanded intermediates.  `filters='cv2'` (or CTDET_AUG_FILTERS=cv2) adds the bic
 reference also draws (`ct_preproc_augment_taps`); the default maps those two draws onto linear.
 `preproc.batch(images, targets)` is the batched entry that keeps 8 GPUs fed; `mixup_targets` / `mixup_images` are the mixup of data/voc0712.py:240-275.
 With `decisions='device'`, `preproc.batch_device` draws the decisions on the device too and `preproc.mosaic_device`
-composes four samples into each output image (`ct_aug_plan_mosaic`, `ct_preproc_augment_mosaic`).
+composes four samples into each output image (`ct_aug_plan_mosaic`, `ct_preproc_augment_mosaic`); `affine=` appends
+the random affine stage to both (`ct_aug_affine_plan`, `ct_preproc_warp_affine`).
 """
 import math
 import os
@@ -78,11 +79,14 @@ def _pack_samples(images, targets, offs, sample_ids, image_of, weights, cls):
 
 class preproc(object):
     def __init__(self, resize, rgb_means, p, device='cuda', max_batch=32, rng=None, filters=None, decisions='host',
-                 seed=None):
+                 seed=None, affine=None):
         """filters: 'fast' or 'cv2' (INTERP_FILTERS); None reads CTDET_AUG_FILTERS, default 'fast'.  Either way the
         random draws are the same in number and order.
         decisions: 'host' (the default) draws from `random` in the reference's order; 'device' adds `batch_device`,
-        which draws them on the device from the counter-based generator keyed by `seed` (ctdet/aug_plan_ref.py)."""
+        which draws them on the device from the counter-based generator keyed by `seed` (ctdet/aug_plan_ref.py).
+        affine: None, or an ops.AffineParams (or the dict of its arguments): `batch_device` and `mosaic_device` then
+        end with the random affine stage -- rotation, scale, shear, shift, rows carried along (ops.AffineWarp).  It
+        needs decisions='device'."""
         if filters is None:
             filters = os.environ.get('CTDET_AUG_FILTERS', 'fast')
         if filters not in INTERP_FILTERS:
@@ -99,6 +103,10 @@ class preproc(object):
                              "the canvas size, which decisions='device' never brings to the host")
         self.decisions, self.seed = decisions, 0 if seed is None else int(seed)
         self._planner = self._aug_dev = None
+        if affine is not None and decisions != 'device':
+            raise ValueError("preproc: affine= needs decisions='device': the stage runs behind batch_device / mosaic_device")
+        self.affine = None if affine is None else ops.affine_params(affine)
+        self._affine = None
 
     # ------------------------------------------------------------------ decisions (host scalars, no pixels)
     def _crop(self, width, height, boxes, labels, cls):
@@ -226,12 +234,23 @@ class preproc(object):
             self._planner = ops.AugPlanner(self.device, self.seed, self.p, self.interp_of_draw, self.means,
                                            per_image * self.max_batch)
 
+    def _affine_stage(self, x, packed, image_ids):
+        """The random affine post-stage on a rendered batch and its packed rows, when `affine` was given; image i draws
+        with image_ids[i].  Outside the image lies the renderers' canvas fill, (float)(int)mean - mean."""
+        if self.affine is None:
+            return x, packed
+        if self._affine is None:
+            self._affine = ops.AffineWarp(self.device, self.seed, self.affine)
+        border = [float(np.float32(int(m)) - np.float32(m)) for m in self.means]
+        return self._affine(x, packed, image_ids, border)
+
     def batch_device(self, images, targets, sample_ids, cls=None, mix=None):
         """decisions='device': lists of uint8 HxWx3 images and [G,5] pixel targets, one 64-bit sample id per image ->
         (float32 [n,3,S,S], ops.PackedTargets(truths, gt_off, max_gt)), all on the device; no per-sample host work
         beyond packing the inputs.  mix = (second images, second targets, lambdas): image i is blended with its
         second image by lambdas[i] (data/voc0712.py:240-275); a lambda >= 1 means the first sample alone with weight
-        1.  A second sample draws with id sample_ids[i] + 2**63."""
+        1.  A second sample draws with id sample_ids[i] + 2**63.  With `affine`, the (blended) image and its merged
+        rows are then warped; the warp draws with sample_ids[i]."""
         if self.decisions != 'device':
             raise ValueError("preproc.batch_device needs preproc(..., decisions='device')")
         n = len(images)
@@ -256,11 +275,12 @@ class preproc(object):
                                                [r[0] for r in rec], [r[2] for r in rec], cls)
         plans, packed = self._planner(samples, boxes, n, max_gt)
         if mix is None:
-            return self._aug_dev.render(plans, n), packed
+            return self._affine_stage(self._aug_dev.render(plans, n), packed, sample_ids)
         # the plans of the first samples, then of the second ones (a lambda >= 1 blends an image with itself)
         order = torch.tensor(first + second, dtype=torch.int64).to(self.device, non_blocking=True)
         x = self._aug_dev.render(plans.view(m, ops.PLAN_BYTES).index_select(0, order).reshape(-1), 2 * n)
-        return ops.mixup_blend(x[:n], x[n:], torch.tensor(lam, dtype=torch.float32).clamp(max=1.0).to(self.device)), packed
+        x = ops.mixup_blend(x[:n], x[n:], torch.tensor(lam, dtype=torch.float32).clamp(max=1.0).to(self.device))
+        return self._affine_stage(x, packed, sample_ids)
 
     def mosaic_device(self, images, targets, sample_ids, cls=None, margin=None):
         """decisions='device': four-image mosaic.  4n uint8 HxWx3 images and [G,5] pixel targets, group-major (sample
@@ -269,7 +289,8 @@ class preproc(object):
         (sample_ids[i] + k * 2**61) mod 2**64 (distinct from mixup's + 2**63); the tiles meet at a point drawn per
         image at least `margin` (default S // 4) pixels from every edge (include/ctdet.h MOSAIC).  Every sample is
         cropped / distorted / expanded / mirrored as in `batch_device`, then resized into its tile; the rows are in
-        units of the composed image."""
+        units of the composed image.  With `affine`, the composed image and its rows are then warped; the warp draws
+        with sample_ids[i], the id of the group's first sample."""
         if self.decisions != 'device':
             raise ValueError("preproc.mosaic_device needs preproc(..., decisions='device')")
         n = len(sample_ids)
@@ -285,7 +306,7 @@ class preproc(object):
         samples, boxes, max_gt = _pack_samples(images, targets, self._aug_dev.upload(images), ids,
                                                [s // 4 for s in range(4 * n)], [1.0] * (4 * n), cls)
         plans, tiles, packed = self._planner.mosaic(samples, boxes, n, max_gt, S, margin)
-        return self._aug_dev.render_mosaic(plans, tiles, n), packed
+        return self._affine_stage(self._aug_dev.render_mosaic(plans, tiles, n), packed, sample_ids)
 
 
 def mixup_targets(target1, target2, lambd, ignore_minus1=False):

@@ -1581,6 +1581,88 @@ int ct_aug_plan_mosaic(const ct_aug_sample* samples /* dev [4*num_images] */, in
 int ct_preproc_augment_mosaic(const unsigned char* src, const void* plans, const ct_mosaic_tile* tiles,
                               int num_images, int size, const float* means3, float* out, ct_stream_t stream);
 
+/* RANDOM AFFINE: a rotation, an isotropic scale, a shear and a shift of a rendered batch, with its rows carried along
+ * (csrc/ct_affine.hip; host twin ctdet/aug_plan_ref.py affine_batch / warp_affine).  A post-stage on what the
+ * renderers above produce -- float32 [B,3,S,S], mean-subtracted, and the packed rows normalised to that image -- so
+ * it composes with the plain path, the tap filters, mixup and mosaic, none of whose entries it touches.  Opt-in.
+ *
+ * NO TRIGONOMETRY  host and device round sin / cos differently (see ct_preproc_augment_taps), so the rotation is drawn
+ *   as t = tan(angle / 2), uniform in [-rot_half_tan, rot_half_tan], and the shear as its tangent; the caller computes
+ *   the two bounds once.  cos = (1 - t^2) / (1 + t^2), sin = 2t / (1 + t^2): + - * / only.
+ * GENERATOR  Philox4x32-10 and the draw rules of ct_aug_plan; key = seed, counter = (image id lo, image id hi, slot
+ *   0x400, lane): a slot outside the draw table and the mosaic's 0x300.  uniform(a,b) = a + (b - a) * (w * 2^-32).
+ *   lane 0   w0 t = uniform(-rot_half_tan, rot_half_tan)    w1 s = uniform(scale_lo, scale_hi)
+ *            w2 kx = uniform(-shear_tan, shear_tan)         w3 ky likewise
+ *   lane 1   w0 tx = uniform(0.5 - translate, 0.5 + translate) * S    w1 ty likewise
+ *            w2 gate: w2 * 2^-32 > (double)p means the image is not warped
+ * MATRIX  fp64, every operation rounded separately (contraction off), in this order:
+ *     q = 1 + t*t;  c = (1 - t*t)/q;  n = (t + t)/q;  a = s*c;  b = s*n
+ *     l00 = a - kx*b;  l01 = b + kx*a;  l10 = ky*a - b;  l11 = ky*b + a             shear . (rotation . scale)
+ *     h = S*0.5
+ *     fwd = {l00, l01, tx - (l00*h + l01*h),  l10, l11, ty - (l10*h + l11*h)}       about the centre, then the shift
+ *     det = l00*l11 - l01*l10                     = s^2 (1 - kx ky) >= 0.75 s^2 by the bounds of the parameters
+ *     i00 = l11/det;  i01 = -l01/det;  i10 = -l10/det;  i11 = l00/det
+ *     inv = {i00, i01, -(i00*fwd2 + i01*fwd5),  i10, i11, -(i10*fwd2 + i11*fwd5)}
+ * ROWS (ct_aug_affine_plan)  each row of the image, fp64: the corners (x1,y1) (x2,y1) (x1,y2) (x2,y2), each float32
+ *   coordinate widened and multiplied by S; each corner through fwd as X = (fwd0*u + fwd1*v) + fwd2, Y = (fwd3*u +
+ *   fwd4*v) + fwd5; the axis-aligned bounds by fmin / fmax in corner order; A0 = (X2 - X1)*(Y2 - Y1); every bound
+ *   clipped as fmin(fmax(., 0), S); w = X2 - X1, h = Y2 - Y1 and A1 = w*h of the clipped bounds.  A row is kept when
+ *   fmin(w, h)/S > (double)min_side && A1 >= (double)min_visible * A0, and is then float32 [X1/S, Y1/S, X2/S, Y2/S,
+ *   label, weight]; label and weight pass through.  The box of a rotated box is its bounding box: targets grow with
+ *   the angle (by a factor of at most |cos| + |sin| per side).
+ *   GATE  an image the gate leaves alone gets the identity record, flags 4, and its rows unchanged, byte for byte.
+ *   FALLBACK (the mosaic's rule)  an image that has rows of which none is kept is not warped: the identity record,
+ *   flags 2|4, and its rows unchanged.  An applied image has flags 1.  The identity record is exactly fwd = inv =
+ *   {1,0,0, 0,1,0}.
+ *   Rows keep image order and input order within an image; they never outnumber the input's, so truths_rows, the
+ *   capacity of BOTH row buffers, always suffices.  status = {bits, refused images, fallback images, rows out}.
+ * SAFETY RULE (this entry cannot inspect device tables)  every gt_off_in value is clamped to [0, truths_rows].  An image
+ *   whose clamped begin exceeds its clamped end, or lies below the clamped end of an image before it, is refused: the
+ *   identity record (flags 4), no rows, status bit 1.  The images that remain read disjoint row ranges.  Nothing is
+ *   written outside the given sizes.
+ * INDEPENDENCE  an image's record and rows depend on (seed, its id, S, the parameters, its rows) and nothing else.
+ * CT_ERR_INVALID before any device work: null pointers, batch < 1 or > 65535, size < 2 or > 16384, truths_rows < 0,
+ *   a parameter that is not finite or outside the range its comment gives, row buffers that overlap, a workspace that
+ *   is too small or not 16-byte aligned.  Two launches, no allocation, no host synchronisation, capturable.
+ * PIXELS (ct_preproc_warp_affine)  output pixel (x, y) of image n, every channel c:
+ *     X = ((double)inv0*x + (double)inv1*y) + inv2;  Y = ((double)inv3*x + (double)inv4*y) + inv5      fp64, op by op
+ *     unless -1 < X && X < S && -1 < Y && Y < S (false for NaN) the pixel is border3[c] and no index is formed
+ *     ix = floor(X); fx = (float)(X - ix);  iy, fy likewise
+ *     tap(jx, jy) = in[n][c][jy][jx] when 0 <= jx < S and 0 <= jy < S, else border3[c]         constant border, blended
+ *     a = tap(ix, iy), b = tap(ix+1, iy), cc = tap(ix, iy+1), d = tap(ix+1, iy+1)
+ *     top = a + fx*(b - a);  bot = cc + fx*(d - cc);  pixel = top + fy*(bot - top)             fp32, op by op, no fma
+ *   A record with flag 4 copies its image; the rule above gives the same bits for the identity matrix (fx = fy = 0),
+ *   so the copy is a shortcut and not a second definition.  The outside rule and the per-tap test make ANY record table
+ *   memory-safe: NaN, infinite or huge matrices yield border pixels.  `in` and `out` must not overlap
+ *   (CT_ERR_INVALID).  One launch: a 32x8 output tile per 256-thread workgroup, one thread per pixel for the three
+ *   channels; no allocation, no host synchronisation, capturable. */
+typedef struct {
+    double fwd[6];   /* source pixel (u,v) -> output pixel: x = fwd0*u + fwd1*v + fwd2, y = fwd3*u + fwd4*v + fwd5 */
+    double inv[6];   /* output pixel -> source pixel */
+    int flags;       /* 1 drawn and applied; 2 fallback (rows would all have been lost); 4 identity: the warp copies */
+    int pad;
+} ct_affine_record;  /* 104 bytes */
+
+typedef struct {
+    double rot_half_tan;       /* tan(max angle / 2), 0..1 */
+    double scale_lo, scale_hi; /* 0 < lo <= hi <= 4 */
+    double shear_tan;          /* tan(max shear), 0..0.5 */
+    double translate;          /* fraction of S, 0..0.5 */
+    float p;                   /* probability that an image is warped, 0..1 */
+    float min_side;            /* rows kept when min(w,h) > min_side (normalised; the pipeline's 0.01), 0..1 */
+    float min_visible;         /* and when clipped area >= min_visible * unclipped area, 0..1 */
+} ct_affine_params;            /* host struct */
+
+size_t ct_aug_affine_plan_workspace_bytes(int batch, int truths_rows);
+int ct_aug_affine_plan(const float* truths_in /* dev [truths_rows,6] */, const int* gt_off_in /* dev [batch+1] */,
+                       const unsigned long long* image_ids /* dev [batch] */, int batch, int truths_rows, int size,
+                       unsigned long long seed, const ct_affine_params* params /* host */,
+                       ct_affine_record* records_out /* dev [batch] */, float* truths_out /* dev [truths_rows,6] */,
+                       int* gt_off_out /* dev [batch+1] */, int* status /* dev [4] */, void* workspace,
+                       size_t workspace_bytes, ct_stream_t stream);
+int ct_preproc_warp_affine(const float* in /* dev [batch,3,size,size] */, const ct_affine_record* records /* dev [batch] */,
+                           int batch, int size, const float* border3 /* host */, float* out, ct_stream_t stream);
+
 /* torch.nn.MaxPool2d of models/RFB_Net_vgg.py:328-330,338 (2x2 s2 [ceil], 3x3 s1 p1) on an NCHW
  * buffer: planes = batch*channels; windows are clipped to the input (ceil_mode semantics are
  * encoded in oh/ow by the caller). */
