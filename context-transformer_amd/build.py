@@ -46,6 +46,8 @@ SOURCES = {
     'ct_wgrad_h2.hip': [],
     'ct_box.hip': ['-ffp-contract=off'],
     'ct_atss.hip': ['-ffp-contract=off'],
+    # the task-aligned matcher's sqrtf and IoU division are part of its contract, as AdamW's are below
+    'ct_tal.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
     'ct_loss.hip': ['-ffp-contract=off'],
     'ct_optim.hip': ['-ffp-contract=off'],
     'ct_ema.hip': ['-ffp-contract=off'],

@@ -6,6 +6,7 @@
 // Compiled with -ffp-contract=off like ct_box.hip: distances, IoUs and the float64 statistics round operation by operation.
 #include "ct_common.h"
 #include "ct_box_math.h"
+#include "ct_claims.h"
 #include <cmath>
 #include <cstdint>
 
@@ -13,8 +14,8 @@
 
 namespace {
 
-using ctdet::encode_box;
 using ctdet::iou_plain;
+using ctdet::pack_claim;         // ordered by rule 7
 using ctdet::point_form;
 
 constexpr int kMaxLevels = 8;
@@ -27,14 +28,6 @@ struct Levels {                                          // level_off travels in
     int n;
     int off[kMaxLevels + 1];
 };
-
-// A claim on a prior, ordered by rule 7 under atomicMax: forced over ordinary, then the larger IoU (a non-negative float's
-// bits order like its value), then the lower box index.  Never 0, which stands for "no claim".
-__device__ __forceinline__ unsigned long long pack_claim(bool forced, float iou, int g)
-{
-    return ((unsigned long long)(forced ? 1u : 0u) << 63) | ((unsigned long long)(__float_as_uint(iou) & 0x7FFFFFFFu) << 32) |
-           (unsigned long long)(0xFFFFFFFFu - (unsigned)g);
-}
 
 __device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
 {
@@ -169,25 +162,8 @@ __global__ __launch_bounds__(256) void atss_assign(const float* __restrict__ tru
                                                    float4* __restrict__ loc_t, float2* __restrict__ conf_t,
                                                    uint8_t* __restrict__ obj_t, float* __restrict__ overlap)
 {
-    const int b = blockIdx.y;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    const size_t o = (size_t)b * P + p;
-    const unsigned long long claim = claims[o];
-    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
-    float label = 0.f, weight = 1.f, ov = 0.f;
-    if (claim != 0ull) {
-        const int g = (int)(0xFFFFFFFFu - (unsigned)(claim & 0xFFFFFFFFull));
-        const float* t = truths + (size_t)(gt_off[b] + g) * 6;
-        ov = __uint_as_float((unsigned)(claim >> 32) & 0x7FFFFFFFu);
-        label = t[4];
-        weight = t[5];
-        out = encode_box(make_float4(t[0], t[1], t[2], t[3]), priors[p], v0, v1);
-    }
-    loc_t[o] = out;
-    conf_t[o] = make_float2(label, weight);
-    obj_t[o] = label != 0.f ? 1 : 0;
-    if (overlap) overlap[o] = ov;
+    if (p < P) ctdet::assign_claim(truths, gt_off, priors, P, blockIdx.y, p, claims, v0, v1, loc_t, conf_t, obj_t, overlap);
 }
 
 }  // namespace

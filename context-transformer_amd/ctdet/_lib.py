@@ -17,7 +17,9 @@ LOC_LOSSES = ('smooth_l1', 'iou', 'giou', 'diou', 'ciou')
 # CT_CONF_*: the classification terms of ct_multibox_loss_fwd_terms / _bwd_terms, by position
 CONF_LOSSES = ('ce', 'focal')
 # the target assignment of MultiBoxLoss: ct_match_batched (the reference's fixed IoU rule) or ct_atss_match_batched
+# (these two need no predictions) or, from the network's current predictions, ct_tal_match_batched
 MATCHERS = ('ssd', 'atss')
+PRED_MATCHERS = ('tal',)
 
 
 class CtdetError(RuntimeError):
@@ -159,6 +161,9 @@ SIGNATURES = {
     'ct_match_batched': (_I, [_P, _P, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_atss_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_atss_match_batched': (_I, [_P, _P, _I, _I, _P, _I, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'ct_tal_lds_keys': (_I, []),
+    'ct_tal_workspace_bytes': (_Z, [_I, _I, _I]),
+    'ct_tal_match_batched': (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_multibox_loss_workspace_bytes': (_Z, [_I, _I, _I]),
     'ct_multibox_loss_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ct_multibox_loss_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),

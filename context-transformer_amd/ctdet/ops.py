@@ -209,6 +209,79 @@ def atss_match_packed(truths, gt_off, batch, max_gt, priors, level_offsets, topk
     return _atss_call(truths, gt_off, B, max_gt, priors, level_offsets, topk, variances, want_overlap, want_stats)
 
 
+def check_tal(topk, alpha, beta):
+    """The rules of include/ctdet.h (ct_tal_match_batched) on the host -> (topk, alpha2 = 2 * alpha, beta) as ints; ValueError."""
+    def whole(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and int(v) == v
+    if not whole(topk) or not 1 <= int(topk) <= 16:
+        raise ValueError('tal_topk must be an integer in 1..16, got %r' % (topk,))
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)) or alpha not in (0, 0.5, 1, 1.5, 2):
+        raise ValueError('tal_alpha must be one of 0, 0.5, 1, 1.5, 2, got %r' % (alpha,))
+    if not whole(beta) or not 0 <= int(beta) <= 8:
+        raise ValueError('tal_beta must be an integer in 0..8, got %r' % (beta,))
+    return int(topk), int(2 * alpha), int(beta)
+
+
+def _tal_call(truths, gt_off, B, max_gt, priors, pred_boxes, pred_scores, topk, alpha, beta, variances, want_overlap,
+              want_stats):
+    dev = priors.device
+    P = priors.shape[0]
+    topk, alpha2, beta = check_tal(topk, alpha, beta)
+    if tuple(pred_boxes.shape) != (B, P, 4):
+        raise _lib.CtdetError('pred_boxes must be [%d,%d,4], got %s' % (B, P, tuple(pred_boxes.shape)))
+    if pred_scores.dim() != 3 or tuple(pred_scores.shape[:2]) != (B, P):
+        raise _lib.CtdetError('pred_scores must be [%d,%d,score_cols], got %s' % (B, P, tuple(pred_scores.shape)))
+    loc_t = torch.empty(B, P, 4, device=dev)
+    conf_t = torch.empty(B, P, 2, device=dev)
+    obj_t = torch.empty(B, P, device=dev, dtype=torch.uint8)
+    overlap = torch.empty(B, P, device=dev) if want_overlap else None
+    stats = torch.empty(B, max_gt, 4, device=dev) if want_stats else None
+    ws_bytes = lib().ct_tal_workspace_bytes(B, P, max_gt)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    check(lib().ct_tal_match_batched(_dev(truths, 'truths'), _dev(gt_off, 'gt_off', torch.int32), B, max_gt,
+                                     _dev(priors, 'priors'), P, _dev(pred_boxes, 'pred_boxes'),
+                                     _dev(pred_scores, 'pred_scores'), int(pred_scores.shape[2]), topk, alpha2, beta,
+                                     float(variances[0]), float(variances[1]), _dev(loc_t, 'loc_t'), _dev(conf_t, 'conf_t'),
+                                     _dev(obj_t, 'obj_t', torch.uint8), _opt(overlap, 'overlap'), _opt(stats, 'gt_stats'),
+                                     _dev(ws, 'ws', torch.uint8), ws_bytes, _stream()), 'ct_tal_match_batched')
+    out = (loc_t, conf_t, obj_t.bool())
+    if want_overlap:
+        out += (overlap,)
+    if want_stats:
+        out += (stats,)
+    return out
+
+
+def tal_match_batched(targets, priors, pred_boxes, pred_scores, topk, alpha, beta, variances, want_overlap=False,
+                      want_stats=False):
+    """match_batched with the task-aligned rule (include/ctdet.h, ct_tal_match_batched): the priors inside a box are ranked by
+    score^alpha * IoU(predicted box, box)^beta and the best topk are its positives.  targets: list of [G,6] tensors;
+    pred_boxes [B,P,4] and pred_scores [B,P,1+num_fg]: what detect_fused(apply_softmax=True) returns for the current
+    predictions -> loc_t, conf_t, obj_t[, overlap][, gt_stats [B,max_gt,4]]."""
+    dev = priors.device
+    B = len(targets)
+    counts = [int(t.shape[0]) for t in targets]
+    max_gt = max(max(counts), 1)
+    off = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32).to(dev)
+    if sum(counts) > 0:
+        truths = torch.cat([t.reshape(-1, 6) for t in targets], 0).to(dev, torch.float32).contiguous()
+    else:
+        truths = torch.zeros(1, 6, device=dev)
+    return _tal_call(truths, off, B, max_gt, priors, pred_boxes, pred_scores, topk, alpha, beta, variances, want_overlap,
+                     want_stats)
+
+
+def tal_match_packed(truths, gt_off, batch, max_gt, priors, pred_boxes, pred_scores, topk, alpha, beta, variances,
+                     want_overlap=False, want_stats=False):
+    """tal_match_batched on device-resident inputs, as match_packed is to match_batched: no host-built offset table and no
+    copy.  An image with more than max_gt rows is matched against its first max_gt rows."""
+    B, max_gt = int(batch), max(int(max_gt), 1)
+    if gt_off.numel() < B + 1:
+        raise ValueError('tal_match_packed: gt_off has %d entries, batch %d needs %d' % (gt_off.numel(), B, B + 1))
+    return _tal_call(truths, gt_off, B, max_gt, priors, pred_boxes, pred_scores, topk, alpha, beta, variances, want_overlap,
+                     want_stats)
+
+
 # ------------------------------------------------------------------ loss
 def _u8(t, name):
     """The matcher's ignore mask: uint8 as ct_match_batched writes it, or the bool view match_batched returns."""

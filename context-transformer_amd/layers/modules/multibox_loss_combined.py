@@ -12,7 +12,9 @@ The classification terms are the reference's two cross-entropies over the 3:1 mi
 'focal'` / CTDET_CONF_LOSS -- focal terms over every prior that is not ignored, with no mining (defined in include/ctdet.h
 at ct_multibox_loss_fwd_terms), in both forms; focal_prior_init() below sets the objectness biases such a run starts from.
 The assignment itself is the reference's fixed IoU rule (the default) or -- `matcher='atss'` / CTDET_MATCHER -- adaptive
-training sample selection (defined in include/ctdet.h at ct_atss_match_batched), one library call either way.
+training sample selection (defined in include/ctdet.h at ct_atss_match_batched), one library call either way; or --
+`matcher='tal'` -- task-aligned assignment from the network's current predictions (ct_tal_match_batched), which costs one
+ct_detect_fused pass over the detached predictions before the matching call.
 targets: list of [G,6] tensors = [x1,y1,x2,y2,label,mixup_weight], or an ops.PackedTargets holding the same rows on
 the device (what preproc(decisions='device').batch_device returns).
 """
@@ -57,7 +59,8 @@ class FusedMultiBoxLoss(torch.autograd.Function):
 
 LOC_LOSSES = _lib.LOC_LOSSES        # 'smooth_l1' and the four IoU kinds
 CONF_LOSSES = _lib.CONF_LOSSES      # 'ce' and 'focal'
-MATCHERS = _lib.MATCHERS            # 'ssd' and 'atss'
+MATCHERS = _lib.MATCHERS            # 'ssd' and 'atss': they read the ground truth and the priors only
+PRED_MATCHERS = _lib.PRED_MATCHERS  # 'tal': it reads the current predictions too
 
 
 class _ScaleGrad(torch.autograd.Function):
@@ -145,6 +148,14 @@ def focal_prior_init(net, pi=0.01):
     return net
 
 
+def _env_int(name, default):
+    text = os.environ.get(name, '')
+    try:
+        return int(text) if text else default
+    except ValueError:
+        raise ValueError('%s must be an integer, got %r' % (name, text))
+
+
 def _env_float(name, default):
     text = os.environ.get(name, '')
     try:
@@ -156,7 +167,8 @@ def _env_float(name, default):
 class MultiBoxLoss_combined(nn.Module):
     def __init__(self, num_classes, overlap_thresh, prior_for_matching, bkg_label, neg_mining, neg_pos,
                  neg_overlap, encode_target, fused=None, loc_loss=None, loc_weight=1.0, conf_loss=None, focal_gamma=None,
-                 focal_alpha=None, matcher=None, atss_topk=None, level_offsets=None):
+                 focal_alpha=None, matcher=None, atss_topk=None, level_offsets=None, tal_topk=None, tal_alpha=None,
+                 tal_beta=None):
         super().__init__()
         # fused: the HIP loss kernels instead of the torch ops below; None reads CTDET_LOSS_FUSED (default off)
         self.fused = os.environ.get('CTDET_LOSS_FUSED', '0') == '1' if fused is None else bool(fused)
@@ -189,8 +201,8 @@ class MultiBoxLoss_combined(nn.Module):
         # offsets of the levels (PriorBox.level_offsets()), which match() checks against the priors it is given
         if matcher is None:
             matcher = os.environ.get('CTDET_MATCHER', '') or 'ssd'
-        if matcher not in MATCHERS:
-            raise ValueError('matcher must be one of %s, got %r' % (', '.join(MATCHERS), matcher))
+        if matcher not in MATCHERS + PRED_MATCHERS:
+            raise ValueError('matcher must be one of %s, got %r' % (', '.join(MATCHERS + PRED_MATCHERS), matcher))
         self.matcher = matcher
         if atss_topk is None:
             text = os.environ.get('CTDET_ATSS_TOPK', '')
@@ -202,16 +214,27 @@ class MultiBoxLoss_combined(nn.Module):
             raise ValueError('atss_topk must be an integer in 1..16, got %r' % (atss_topk,))
         self.atss_topk = int(atss_topk)
         self.level_offsets = None if level_offsets is None else [int(o) for o in level_offsets]
+        # 'tal' (include/ctdet.h, ct_tal_match_batched) reads neither overlap_thresh nor level_offsets but the predictions:
+        # the tal_topk priors inside a box with the largest score^tal_alpha * IoU(predicted box, box)^tal_beta are its
+        # positives.  None reads CTDET_TAL_TOPK / CTDET_TAL_ALPHA / CTDET_TAL_BETA (unset or empty: 13 / 1.0 / 6, TOOD's)
+        topk, alpha2, beta = ops.check_tal(_env_int('CTDET_TAL_TOPK', 13) if tal_topk is None else tal_topk,
+                                           _env_float('CTDET_TAL_ALPHA', 1.0) if tal_alpha is None else tal_alpha,
+                                           _env_int('CTDET_TAL_BETA', 6) if tal_beta is None else tal_beta)
+        self.tal_topk, self.tal_alpha, self.tal_beta = topk, alpha2 / 2.0, beta
         self.sync_normalizer = False      # set True under multi-process data parallelism
 
     @torch.no_grad()
-    def match(self, priors, targets, device=None, out=None):
-        """The target assignment of :60-76 alone (it depends on the ground truth and the priors only): -> MatchedTargets,
-        which forward() accepts in place of the raw target list.  `out`: a MatchedTargets of the same batch to overwrite
-        in place -- a training step captured as a hipGraph (bench.py --train) reads the same three tensors at every
-        replay, the matching itself (a host-built offset table, an H2D copy) stays outside the graph."""
+    def match(self, priors, targets, device=None, out=None, predictions=None):
+        """The target assignment of :60-76 alone (under 'ssd' and 'atss' it depends on the ground truth and the priors
+        only): -> MatchedTargets, which forward() accepts in place of the raw target list.  `out`: a MatchedTargets of the
+        same batch to overwrite in place -- a training step captured as a hipGraph (bench.py --train) reads the same three
+        tensors at every replay, the matching itself (a host-built offset table, an H2D copy) stays outside the graph.
+        `predictions`: the (loc, conf, obj) the network just produced, read by matcher='tal' alone, which cannot match
+        without them; they are detached, no gradient flows through the assignment."""
         dev = torch.device(device) if device is not None else priors.device
-        if self.matcher == 'atss':
+        if self.matcher == 'tal':
+            loc_t, conf_t, obj_t = self._match_tal(priors, targets, dev, predictions)
+        elif self.matcher == 'atss':
             loc_t, conf_t, obj_t = self._match_atss(priors, targets, dev)
         elif isinstance(targets, ops.PackedTargets):      # device-resident truths / gt_off (ops.AugPlanner): no host table
             loc_t, conf_t, obj_t = ops.match_packed(targets.truths, targets.gt_off, targets.gt_off.numel() - 1,
@@ -233,12 +256,26 @@ class MultiBoxLoss_combined(nn.Module):
                                          topk, self.variance)
         return ops.atss_match_batched([t.to(dev) for t in targets], pri, off, topk, self.variance)
 
+    def _match_tal(self, priors, targets, dev, predictions):
+        if predictions is None:
+            raise ValueError("matcher='tal' assigns targets from the current predictions: match() needs predictions=(loc, "
+                             "conf, obj); matching ahead of the forward pass is for matcher='ssd' and 'atss'")
+        pri = priors.to(dev).float().contiguous()
+        loc, conf, obj = (p.detach().to(dev).float().contiguous() for p in predictions)
+        boxes, scores = ops.detect_fused(loc, conf, obj, pri, self.variance, apply_softmax=True)
+        tal = (pri, boxes, scores, self.tal_topk, self.tal_alpha, self.tal_beta, self.variance)
+        if isinstance(targets, ops.PackedTargets):
+            return ops.tal_match_packed(targets.truths, targets.gt_off, targets.gt_off.numel() - 1, targets.max_gt, *tal)
+        return ops.tal_match_batched([t.to(dev) for t in targets], *tal)
+
     def forward(self, predictions, priors, targets):
         loc_data, conf_data, obj_data = predictions
         dev = loc_data.device
         num, num_priors = loc_data.size(0), priors.size(0)
         if isinstance(targets, MatchedTargets):
             loc_t, conf_t, obj_t = targets
+        elif self.matcher in PRED_MATCHERS:
+            loc_t, conf_t, obj_t = self.match(priors, targets, dev, predictions=predictions)
         else:
             loc_t, conf_t, obj_t = self.match(priors, targets, dev)
         if self.fused:

@@ -269,6 +269,57 @@ int ct_atss_match_batched(const float* truths, const int* gt_off, int batch, int
                           float* overlap, float* gt_stats, void* workspace, size_t workspace_bytes,
                           ct_stream_t stream);
 
+/* TASK-ALIGNED ASSIGNMENT (TAL; Feng et al., TOOD, ICCV 2021; the family of SimOTA): the prediction-aware matcher.  Where
+ * ct_match_batched and ct_atss_match_batched read the ground truth and the priors only, this one ranks the priors inside a
+ * box by how well the network currently classifies and localises from them, m = score^alpha * IoU(predicted box, box)^beta,
+ * and trains the best topk.  The outputs have the layout of the other two, so the loss entries below read any matcher's result.
+ *
+ * truths, gt_off, priors, max_gt (truncation contract included), loc_t, conf_t, obj_t and overlap are those of
+ * ct_atss_match_batched.  pred_boxes dev [B,P,4] (point form) and pred_scores dev [B,P,score_cols] are in the layout
+ * ct_detect_fused writes: column 0 is the background / objectness-negative probability, column c >= 1 is foreground class c,
+ * score_cols = 1 + num_fg.  alpha2 = 2 * alpha (0..4, so alpha is 0, 0.5, 1, 1.5 or 2); beta is an integer 0..8.
+ * All fp32 arithmetic is rounded operation by operation (no FMA contraction; IEEE division and square root).
+ *
+ * For every image b, every box g < min(G_b, max_gt) is handled independently of the others.
+ *  1. DEGENERATE BOXES.  A box with !(x2 > x1 && y2 > y1) is skipped: it has no candidates and no positives.
+ *  2. CANDIDATES.  The priors whose centre lies strictly inside the box: x1 < pcx < x2 && y1 < pcy < y2, on the fp32 values as
+ *     they are.
+ *  3. METRIC.  For a candidate p: u = the IoU expression of ct_jaccard of the box and pred_boxes[b,p], and u = 0 if !(u > 0)
+ *     (NaN and Inf-born boxes included).  s = pred_scores[b,p,L] if the box's label L is an integer in 1..score_cols-1;
+ *     otherwise (label -1, 0 or out of range) s = 1.f - pred_scores[b,p,0]; s = 0 if !(s > 0).  m = s^(alpha2/2) * u^beta in
+ *     fp32, in this order: start from 1.f, multiply by sqrtf(s) if alpha2 is odd, then by s alpha2/2 times, then by u beta
+ *     times.  Finally m = 0 if !(m >= FLT_MIN): the result is the same whether or not fp32 subnormals are flushed (products
+ *     of values <= 1 only shrink).  A candidate is ELIGIBLE if m > 0.
+ *  4. POSITIVES.  The min(topk, eligible) eligible candidates with the largest m.  Ties go to the lower prior index.
+ *  5. FORCED POSITIVE.  A non-degenerate box with no eligible candidate (no centre inside, or every metric 0) takes one forced
+ *     positive: the prior with the largest IoU of the box and the prior in point form, over ALL priors, lowest index on a
+ *     tie.  Its claim carries that IoU.  As in ATSS, every box trains at least one prior unless rule 6 takes it away.
+ *  6. CONFLICTS.  A prior claimed by several boxes goes to the claim that wins this order: a forced claim over an ordinary
+ *     one, then the larger u (for a forced claim, its prior IoU), then the lower box index.
+ *  7. OUTPUTS.  An assigned prior gets loc_t = the encode expression of ct_encode, conf_t = (label, weight) of its box and
+ *     obj_t = label != 0.  Every other prior gets loc_t = 0, conf_t = (0, 1) and obj_t = 0, exactly.  overlap may be NULL: it
+ *     holds the winning claim's u, else 0.  gt_stats may be NULL: it is [B, max_gt, 4] floats = (eligible count, number of
+ *     positives before conflicts with the forced one counted, m of the last positive chosen or 0 if forced, forced ? 1 : 0);
+ *     rows of skipped or absent boxes are zeros.
+ * An image's result never depends on its batch mates, and the same inputs give the same bits on every run.  The entry makes
+ * no allocation, does no host synchronisation and makes no H2D copy.  One memset and two launches on `stream`.  The selection
+ * kernel evaluates a candidate (its predicted box, score and metric) once while it scans and once more if it is chosen; its
+ * LDS key buffer holds ct_tal_lds_keys() keys whatever P is, and is reduced to the topk best whenever it could overflow.
+ * workspace: ct_tal_workspace_bytes(batch, num_priors, max_gt) bytes, 8-byte aligned.
+ * CT_ERR_INVALID before any HIP call: NULL tensors (overlap and gt_stats excepted); batch, num_priors or max_gt < 1;
+ * num_priors above 2^30 or batch above 65535; score_cols < 2; topk outside 1..16; alpha2 outside 0..4; beta outside 0..8; a
+ * variance that is not positive and finite; a workspace that is too small or not 8-byte aligned. */
+int ct_tal_lds_keys(void);
+size_t ct_tal_workspace_bytes(int batch, int num_priors, int max_gt);
+int ct_tal_match_batched(const float* truths, const int* gt_off, int batch, int max_gt,
+                         const float* priors, int num_priors,
+                         const float* pred_boxes  /* dev [B,P,4] point form */,
+                         const float* pred_scores /* dev [B,P,score_cols] */, int score_cols,
+                         int topk, int alpha2, int beta, float var0, float var1,
+                         float* loc_t, float* conf_t, uint8_t* obj_t,
+                         float* overlap /* or NULL */, float* gt_stats /* or NULL */,
+                         void* workspace, size_t workspace_bytes, ct_stream_t stream);
+
 /* layers/modules/multibox_loss_combined.py:76-122 (`MultiBoxLoss_combined.forward` after the matching): the loss
  * arithmetic, fused.  Forward = three launches, backward = one; no allocation, no host synchronisation, capturable.
  *   loc dev [B,P,4], conf dev [B,P,C-1], obj dev [B,P,2]      the network's raw outputs (C = num_classes >= 2)

@@ -2,7 +2,7 @@
 """One-GPU training-step timing: RFBNet forward (batch-stat BN) + MultiBoxLoss + HIP backward + SGD.
    python tools/train_bench.py [--size 300 --batch 32 --classes 20 --steps 5] [--fused-sgd] [--per-tensor-groups] [--wgrad-h2]
                                [--optimizer sgd|adamw] [--clip-norm X] [--ema DECAY] [--deterministic] [--loc-loss NAME] [--loc-weight X]
-                               [--conf-loss focal [--focal-gamma X --focal-alpha X]] [--matcher ssd|atss [--atss-topk K]] [--json]
+                               [--conf-loss focal [--focal-gamma X --focal-alpha X]] [--matcher ssd|atss|tal [--atss-topk K] [--tal-topk K --tal-alpha A --tal-beta B]] [--json]
                                [--sync-bn]
    --classes: classes of the conf head; default 20, with --phase 2 the width of the Context-Transformer block (60 for 'transfer',
    15 for 'incre': the head feeds the block);
@@ -26,6 +26,8 @@
    focal_prior_init(net) (objectness prior 0.01); all three are reported on the JSON line, which is then always printed;
    --matcher NAME [--atss-topk K]: the criterion's target assignment (ssd, atss; default: what CTDET_MATCHER says, else ssd) and the
    ATSS candidates per level (default: CTDET_ATSS_TOPK, else 9); both are reported on the JSON line, which is then always printed;
+   --matcher tal [--tal-topk K --tal-alpha A --tal-beta B]: task-aligned assignment from the step's own predictions (one more
+   ct_detect_fused pass inside the loss time; defaults: CTDET_TAL_TOPK / _ALPHA / _BETA, else 13 / 1.0 / 6), reported likewise;
    --sync-bn: under torchrun, TrainRuntime.enable_bn_sync(): BatchNorm statistics over the global batch (two small all-reduces per
    BatchNorm stage and step); the JSON line (then always printed) carries `sync_bn`: the global batch, the
    stages and the collectives per step;
@@ -50,6 +52,8 @@ ap.add_argument('--loc-loss', default=None); ap.add_argument('--loc-weight', typ
 ap.add_argument('--conf-loss', default=None); ap.add_argument('--focal-gamma', type=float, default=None)
 ap.add_argument('--focal-alpha', type=float, default=None)
 ap.add_argument('--matcher', default=None); ap.add_argument('--atss-topk', type=int, default=None)
+ap.add_argument('--tal-topk', type=int, default=None); ap.add_argument('--tal-alpha', type=float, default=None)
+ap.add_argument('--tal-beta', type=int, default=None)
 ap.add_argument('--sync-bn', action='store_true')
 a = ap.parse_args()
 if a.clip_norm is not None or a.ema is not None:
@@ -77,7 +81,8 @@ priors = prior_box.forward().cuda()
 nout = a.classes if a.phase == 1 else net.OBJ_Target.weight.shape[0] + (a.classes if a.setting == 'incre' else 0)
 crit = MultiBoxLoss_combined(nout + 1, 0.5, True, 0, True, 3, 0.5, False, loc_loss=a.loc_loss, loc_weight=a.loc_weight,
                              conf_loss=a.conf_loss, focal_gamma=a.focal_gamma, focal_alpha=a.focal_alpha, matcher=a.matcher,
-                             atss_topk=a.atss_topk, level_offsets=prior_box.level_offsets())
+                             atss_topk=a.atss_topk, level_offsets=prior_box.level_offsets(), tal_topk=a.tal_topk,
+                             tal_alpha=a.tal_alpha, tal_beta=a.tal_beta)
 if crit.conf_loss == 'focal':
     focal_prior_init(net)       # every prior starts at objectness 0.01 instead of 0.5 (the biases; set before the runtime is built)
 crit.sync_normalizer = world > 1
@@ -142,7 +147,8 @@ if rank == 0:
                'fwd_ms': round(tf / n, 3), 'loss_ms': round(tl / n, 3), 'bwd_ms': round(tb / n, 3), 'opt_ms': round(to / n, 3),
                'clip_norm': a.clip_norm, 'loss': float(loss), 'loc_loss': crit.loc_loss, 'loc_weight': crit.loc_weight,
                'loss_fused': crit.fused, 'conf_loss': crit.conf_loss, 'focal_gamma': crit.focal_gamma,
-               'focal_alpha': crit.focal_alpha, 'matcher': crit.matcher, 'atss_topk': crit.atss_topk}
+               'focal_alpha': crit.focal_alpha, 'matcher': crit.matcher, 'atss_topk': crit.atss_topk, 'tal_topk': crit.tal_topk,
+               'tal_alpha': crit.tal_alpha, 'tal_beta': crit.tal_beta}
         if a.clip_norm is not None:
             row.update(opt.clip_info())                 # norm, coef, finite, nonfinite of the last step
         if a.ema is not None:
